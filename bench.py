@@ -9,8 +9,16 @@ run/distill.py:149-150 does); plus the per-point open-vocabulary query time.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
+A plain run sets up, warms up, times the --steps steps and prints the line; every other measurement below (the untimed
+per-kernel survey and roofline, the CPU baseline, the query / inference / voxeliser / loader phases, the other workloads
+and precisions, the one-GPU batch of N scenes) runs only with --full.  --dump-outputs DIR writes what the last timed step
+computed as .npy files (see dump_outputs()); the inputs depend on the arguments alone, so two builds can be compared.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+
 Rank 0 prints ONE JSON line (contract in the task statement):
   value      = voxels processed by ALL ranks in the timed region / max-over-ranks time
+  ms_per_step = milliseconds of one timed step (max over ranks)
   roofline   = dominant spconv kernel instance: ALGORITHMIC bytes per launch / mean launch
                duration from HIP events recorded inside the timed region on the launch stream
   cpu_baseline = the CPU oracle (`oracle/`, kind "port": per-offset gather -> BLAS mm ->
@@ -566,6 +574,41 @@ def write_detail(detail, path=None):
     return written
 
 
+DUMP_ROWS = 4096               # output rows kept by --dump-outputs (fixed seeded sample)
+DUMP_ELEMS = 1 << 20           # parameter / gradient elements kept by --dump-outputs (fixed seeded sample)
+
+
+def dump_outputs(out_dir, loss, out, model, seed=0):
+    """--dump-outputs: what the last timed step handed its caller, as float .npy files (~21 MB in all):
+      loss.npy      the step's loss, float64 [1]
+      output.npy    the step's output rows (the supervised rows, or every voxel with the full head): DUMP_ROWS of them, a seeded
+                    sample in row order, float32 [rows, D]
+      params.npy    the parameters after the optimizer step, flattened in model.parameters() order: DUMP_ELEMS elements at
+                    seeded positions in increasing order, float32
+      grads.npy     the step's gradients at the same positions, float32
+      bn_stats.npy  every batch-norm running mean and variance after the step, concatenated in state_dict order, float32
+    The sample positions depend on the shapes alone, so two builds' files compare element for element."""
+    os.makedirs(out_dir, exist_ok=True)
+    g = torch.Generator().manual_seed(seed)
+
+    def sample(n, k):
+        return torch.randperm(n, generator=g)[:k].sort().values if n > k else torch.arange(n)
+
+    params = list(model.parameters())
+    flat_p = torch.cat([p.detach().reshape(-1) for p in params])
+    flat_g = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1) for p in params])
+    pick = sample(flat_p.numel(), DUMP_ELEMS).to(flat_p.device)
+    rows = sample(out.shape[0], DUMP_ROWS).to(out.device)
+    stats = [b.detach().reshape(-1) for n, b in model.named_buffers() if n.endswith(("running_mean", "running_var"))]
+    arrays = {"loss": np.array([float(loss.detach())], dtype=np.float64),
+              "output": out.index_select(0, rows).float().cpu().numpy(),
+              "params": flat_p.index_select(0, pick).float().cpu().numpy(),
+              "grads": flat_g.index_select(0, pick).float().cpu().numpy(),
+              "bn_stats": torch.cat(stats).float().cpu().numpy()}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def _num(x, nd=4):
     if isinstance(x, float):
         return float("%.*g" % (nd + 2, x))
@@ -743,11 +786,18 @@ def main():
     ap.add_argument("--no-kernel-events", action="store_true")
     ap.add_argument("--train-only", action="store_true", help="skip the query / inference / voxeliser / loader phases "
                     "(for rocprofv3 runs: every traced kernel then belongs to the training steps)")
+    ap.add_argument("--full", action="store_true", help="also run every measurement beyond the timed steps: kernel survey and "
+                    "roofline, CPU baseline, query / inference / voxeliser / loader phases, other workloads and precisions, the "
+                    "one-GPU batch of N scenes (--train-only, --no-cpu-baseline and --no-kernel-events trim it)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR", help="after the timed steps, write what the last one computed "
+                    "(loss, output rows, parameters, gradients, batch-norm statistics) as DIR/<name>.npy")
     ap.add_argument("--cpu-baseline-only", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--spawn-self-test", action="store_true", help=argparse.SUPPRESS)
     ap.add_argument("--detail", default=None, help="where the full record goes (default: bench_detail.json next to bench.py, "
                     "and gpurun_out/ when present); stdout carries only the < 6 KB headline line")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     global LOSS_HIP
     LOSS_HIP = not args.torch_loss
     if args.cpu_baseline_only:
@@ -876,7 +926,7 @@ def main():
         gpu_marks.append((name, ev))
         return t
 
-    def step():
+    def step(keep=None):
         # `out[mask]` with a bool mask makes torch read the selected-row count back in the MIDDLE of the step
         # (host stalls until the forward has drained, then refills an empty queue).  The row indices of the mask
         # are batch data (openscene_amd.loader hands them out): resolve them here, next to the size read-backs
@@ -894,6 +944,8 @@ def main():
         t_ = seg("take", t_)
         rows_head = not args.full_head and not (dist_on and args.ddp)
         out = net(sinput, rows=sel) if rows_head else net(sinput)
+        if keep is not None:
+            keep["out"] = out.detach()                             # --dump-outputs: the last timed step's output rows
         t_ = seg("forward", t_)
         # (1 - cos(out[mask], feat_3d)).mean(), run/distill.py:322-326: one fused forward and one fused backward launch
         # (openscene_amd.losses, csrc/loss.hip); --torch-loss keeps torch's own ~25-launch chain
@@ -920,14 +972,16 @@ def main():
             dist.barrier()
             torch.cuda.synchronize(device)
 
-    pair_counts, sizes = all_pair_counts(coords0)
+    pair_counts, sizes = all_pair_counts(coords0) if args.full else ({}, None)
     last = {}                                   # the coordinate manager of the most recent step (survey bookkeeping)
     for _ in range(args.warmup):
         step()
     from openscene_amd import executor as _ex
     ex = _ex.for_model(model.net3d) if _ex.ENABLED else None
-    prof = ExecProfiler(ex) if (ex is not None and not args.no_kernel_events) else None
-    legacy = LaunchProfiler() if (ex is None and not args.no_kernel_events) else None
+    # the per-kernel survey (untimed steps of its own) and the event brackets in the timed region feed the roofline: --full only
+    events_on = args.full and not args.no_kernel_events
+    prof = ExecProfiler(ex) if (ex is not None and events_on) else None
+    legacy = LaunchProfiler() if (ex is None and events_on) else None
     survey_groups, survey_shapes, dom_key, dom_tags = {}, {}, None, []
     dom_fwd_only = False
     stages = None
@@ -1005,12 +1059,16 @@ def main():
     sync()
     host_t.clear()
     del gpu_marks[:]
+    kept = {}
     t0 = time.perf_counter()
-    for _ in range(args.steps):
-        loss = step()
+    for i in range(args.steps):
+        loss = step(kept if i == args.steps - 1 else None)
     t_issue = time.perf_counter() - t0
     sync()
     dt = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, kept["out"], model)
+    del kept
     if host_on and rank == 0:
         gt = {}
         for (n0, e0), (n1, e1) in zip(gpu_marks[:-1], gpu_marks[1:]):
@@ -1060,7 +1118,7 @@ def main():
     extra = None
     # the side phases (query, voxeliser, inference, the other workloads) are single-GPU measurements: at N > 1 every rank
     # goes straight to the teardown, so that no rank leaves the process group a minute before rank 0 does
-    if rank == 0 and not args.train_only and world == 1:
+    if rank == 0 and args.full and not args.train_only and world == 1:
         model.eval()
         with torch.no_grad():
             pred = model(SparseTensor(feats, coords0))
@@ -1354,7 +1412,7 @@ def main():
             dist.destroy_process_group()
         return
 
-    step_bytes, step_flops = step_algorithmic_bytes(model, sizes, pair_counts)
+    step_bytes, step_flops = step_algorithmic_bytes(model, sizes, pair_counts) if args.full else (None, None)
     ms_per_step = dt_max * 1e3 / args.steps
     # The OTHER scaling definition.  The line's `value` is weak scaling: one S100k-shaped scene per rank.  The
     # reference splits a FIXED batch (run/distill.py:146 `batch_size //= ngpus`; config/scannet/ours_openseg.yaml: batch_size 8):
@@ -1362,7 +1420,7 @@ def main():
     # scenes (untimed region, after the other ranks have left) and the line carries  speedup_vs_same_batch_on_one_gpu =
     # t(N scenes on 1 GPU) / t(1 scene on each of N GPUs).  No multi-GPU number exists in this repository until SCALE runs.
     scaling_ref = None
-    if world > 1 and not args.dist_single and os.environ.get("OSN_BENCH_SCALING_REF", "1") != "0":
+    if args.full and world > 1 and not args.dist_single and os.environ.get("OSN_BENCH_SCALING_REF", "1") != "0":
         try:
             from openscene_amd import synthetic as syn
             rooms_n = [syn.shuffled(syn.grid_voxels(syn.room_points(sd, n_pts=args.scene_points), 0.02), sd) for sd in range(world)]
@@ -1443,7 +1501,7 @@ def main():
             roofline["avg_launch_us_fwd"] = us_f
             roofline["frac_fwd"] = per_f / (us_f * 1e-6) / (1e12 if roofline["bound"] == "mfma" else 1e9) / roofline["peak"]
     cpu = None
-    if world == 1 and not args.no_cpu_baseline:
+    if world == 1 and args.full and not args.no_cpu_baseline:
         # separate process (own thread pool, no GPU context) with a hard time bound
         import subprocess
         try:
@@ -1465,9 +1523,7 @@ def main():
         "config": {"workload": "ScanNet distillation step (configs[2]): %s, %d-d head, 1 synthetic S100k scene/GPU "
                                "(%d voxels on rank 0, 2 cm), training-mode BN; timed = coordinate+kernel maps, "
                                "forward, cosine loss, backward, gradient all-reduce, Adam step" % (args.arch, out_dim, n_vox),
-                   "arch": args.arch, "feature_dim": out_dim, "voxels_rank0": n_vox,
-                   "level_sizes": sizes, "parallelism": "dp%d" % world,
-                   "step_algorithmic_GB": step_bytes / 1e9, "step_GFLOP": step_flops / 1e9},
+                   "arch": args.arch, "feature_dim": out_dim, "voxels_rank0": n_vox, "parallelism": "dp%d" % world},
         "query": qres, "voxelizer": vox_res, "phases": extra, "roofline": roofline, "cpu_baseline": cpu, "comm": comm,
         "kernels": kernels, "stages": stages, "loss": float(loss.detach()), "scaling_reference": scaling_ref,
         "host_path": "network executor (one C call per forward / backward pass)" if ex is not None else "per-module (Python autograd)",
@@ -1480,6 +1536,8 @@ def main():
                            "coordinate pyramid (+ mask rows) of step i+1 queued on a side stream during step i; kernel maps inside the step"
                            if prefetch else "pyramid and maps inside the step"),
     }
+    if args.full:               # the step's algorithmic cost model (a map build of its own), beside the roofline
+        detail["config"].update(level_sizes=sizes, step_algorithmic_GB=step_bytes / 1e9, step_GFLOP=step_flops / 1e9)
     detail_path = write_detail(detail, args.detail)
     line = headline(detail, detail_path)
     emit_line(json.dumps(line, separators=(",", ":")))

@@ -118,3 +118,28 @@ def test_library_chatter_on_fd1_does_not_reach_the_callers_stdout():
     assert r.returncode == 0, r.stderr[-2000:]
     assert r.stdout == '{"a":1}\n'
     assert "RCCL version" in r.stderr and "python chatter" in r.stderr
+
+
+def test_dump_outputs_are_float_bounded_and_repeatable(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, under 64 MB in all, sampled at positions that depend on the shapes alone."""
+    import numpy as np
+    import torch
+    b = _bench()
+    torch.manual_seed(0)
+    model = torch.nn.Sequential(torch.nn.Linear(3, 2000), torch.nn.BatchNorm1d(2000), torch.nn.Linear(2000, 768))
+    out = model(torch.randn(30000, 3))
+    loss = out.square().mean()
+    loss.backward()
+    for d in ("a", "b"):
+        b.dump_outputs(str(tmp_path / d), loss, out.detach(), model)
+    names = sorted(os.listdir(tmp_path / "a"))
+    assert names == ["bn_stats.npy", "grads.npy", "loss.npy", "output.npy", "params.npy"]
+    total = 0
+    for n in names:
+        a = np.load(str(tmp_path / "a" / n))
+        assert a.dtype in (np.float32, np.float64), n
+        assert np.array_equal(a, np.load(str(tmp_path / "b" / n))), n
+        total += os.path.getsize(str(tmp_path / "a" / n))
+    assert total <= 64 * 2 ** 20
+    assert np.load(str(tmp_path / "a" / "output.npy")).shape == (b.DUMP_ROWS, 768)
+    assert float(np.load(str(tmp_path / "a" / "loss.npy"))[0]) == float(loss)

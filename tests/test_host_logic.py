@@ -13,8 +13,6 @@ from oracle import sparse_ops as so
 
 import cpu_backend
 
-REFERENCE = "/root/reference"
-
 
 def cloud(seed=0, n=260, extent=11, batch=2):
     rng = np.random.default_rng(seed)
@@ -160,39 +158,34 @@ def test_no_cpu_fallback_in_product():
         ops.coords_unique(torch.zeros((3, 4), dtype=torch.int32))
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE), reason="reference tree not present on this machine")
-def test_reference_model_file_runs_unchanged(cpu_ops, monkeypatch):
-    """The reference's own models/mink_unet.py + models/disnet.py import `MinkowskiEngine`, get
-    openscene_amd.minkowski through the alias, and produce the same numbers as our mirror."""
+def test_reference_model_file_runs_unchanged(cpu_ops, monkeypatch, golden_dir):
+    """The reference's own models/mink_unet.py imports `MinkowskiEngine`, gets openscene_amd.minkowski through the alias, and
+    produced tests/golden/reference_model_file.npz (tests/golden/make_golden_model_file.py): our mirror has its state_dict
+    layout, draws the same parameters from the same seed, and produces the same numbers in eval and train mode."""
     import openscene_amd
     from openscene_amd.mink_unet import mink_unet as mine
     from openscene_amd.sparse import SparseTensor
-    for name in [m for m in sys.modules if m == "MinkowskiEngine" or m.startswith("MinkowskiEngine.")
-                 or m == "models" or m.startswith("models.")]:
+    g = np.load(os.path.join(golden_dir, "reference_model_file.npz"))
+    for name in [m for m in sys.modules if m == "MinkowskiEngine" or m.startswith("MinkowskiEngine.")]:
         monkeypatch.delitem(sys.modules, name)
     openscene_amd.install_minkowski_alias()
-    monkeypatch.syspath_prepend(REFERENCE)
-    from models.mink_unet import mink_unet as theirs            # noqa: E402  (reference file, unmodified)
     import MinkowskiEngine as ME
     assert ME.__openscene_amd__
     torch.manual_seed(0)
-    ref_model = theirs(3, 10, 3, "MinkUNet14A").double().eval()
     my_model = mine(3, 10, 3, "MinkUNet14A").double().eval()
-    assert list(ref_model.state_dict().keys()) == list(my_model.state_dict().keys())
-    assert [tuple(v.shape) for v in ref_model.state_dict().values()] == \
-           [tuple(v.shape) for v in my_model.state_dict().values()]
-    my_model.load_state_dict(ref_model.state_dict(), strict=True)
-    coords = cloud(5)
-    feats = torch.rand(coords.shape[0], 3, dtype=torch.float64)
-    a = ref_model(ME.SparseTensor(feats, coords))
+    sd = my_model.state_dict()
+    assert list(sd.keys()) == g["keys"].tolist()
+    assert [str(tuple(v.shape)) for v in sd.values()] == g["shapes"].tolist()
+    assert np.allclose([float(v.double().sum()) for v in sd.values()], g["init_sum"], rtol=1e-12, atol=1e-12)
+    assert np.allclose([float(v.double().square().sum()) for v in sd.values()], g["init_sq"], rtol=1e-12, atol=1e-12)
+    coords = torch.from_numpy(g["coords"])
+    feats = torch.from_numpy(g["feats"])
     b = my_model(SparseTensor(feats, coords))
-    assert torch.allclose(a, b, atol=1e-10)
-    ref_model.train(); my_model.train()
-    a = ref_model(ME.SparseTensor(feats, coords))
+    assert torch.allclose(torch.from_numpy(g["out_eval"]), b, atol=1e-10)
+    my_model.train()
     b = my_model(SparseTensor(feats, coords))
-    assert torch.allclose(a, b, atol=1e-9)
-    for name in [m for m in sys.modules if m == "MinkowskiEngine" or m.startswith("MinkowskiEngine.")
-                 or m == "models" or m.startswith("models.")]:
+    assert torch.allclose(torch.from_numpy(g["out_train"]), b, atol=1e-9)
+    for name in [m for m in sys.modules if m == "MinkowskiEngine" or m.startswith("MinkowskiEngine.")]:
         monkeypatch.delitem(sys.modules, name)
 
 

@@ -5,16 +5,14 @@ own main() (tests/ref_loops.py, tests/golden/make_golden_loops.py): one distilla
 reference's loaders, Adam, poly learning rate, validate(), save_checkpoint, then evaluate() in the 'distill' and 'ensemble'
 modes with test_repeats = 2 on the checkpoint it wrote.
 
-  * here (reference tree present): the files are run again and must reproduce the fixture -- this is the test that fails when a
-    symbol those files touch is missing from the MinkowskiEngine alias or shaped differently (run/distill.py:18-27,113-150,
-    295-447; run/evaluate.py:18-23,164-222,224-425);
+  * where the reference tree exists, `python tests/golden/make_golden_loops.py --check REFERENCE_ROOT` runs the files again and
+    they must reproduce the fixture -- the check that fails when a symbol those files touch is missing from the MinkowskiEngine
+    alias or shaped differently (run/distill.py:18-27,113-150, 295-447; run/evaluate.py:18-23,164-222,224-425);
   * everywhere: the same operations replayed through openscene_amd's own DisNet / SparseTensor on the recorded batches -- on
     the CPU test backend bit for bit (the fixture's own replay), on the GPU box through the HIP library within the stated
     tolerances (losses 2e-4, validation loss 5e-3 relative, metrics 5e-3, the two Adam steps' update within 5 %, predicted
     labels equal on every point whose top-2 margin is above 2 % of the largest score, mIoU 5e-3).
 """
-import contextlib
-import io
 import os
 
 import numpy as np
@@ -30,38 +28,14 @@ def gold(golden_dir):
     return g, {k[len("replay:"):]: v for k, v in g.items() if k.startswith("replay:")}
 
 
-@pytest.mark.skipif(not os.path.isdir(RL.REFERENCE), reason="reference tree not present on this machine")
-def test_reference_loops_run_unmodified_and_reproduce_the_fixture(gold, tmp_path, monkeypatch):
-    g, margins = gold
-    with contextlib.redirect_stdout(io.StringIO()):
-        got = RL.run_reference(str(tmp_path), monkeypatch)
-    # the loops' own outputs: losses per iteration, the learning-rate schedule, the epoch mean, validate()'s four numbers
-    assert np.allclose(got["train_loss_batch"], g["train_loss_batch"], rtol=0, atol=1e-6)
-    assert np.allclose(got["train_loss_epoch"], g["train_loss_epoch"], rtol=0, atol=1e-6)
-    assert np.array_equal(got["train_lr"], g["train_lr"])
-    assert np.allclose(got["val"], g["val"], rtol=1e-5, atol=1e-6)
-    # the batches its loaders produced (voxeliser + augmentation + collate under the run's own seeds) and the in-loop shift
-    for k in g:
-        if k.endswith(("_coords", "_mask", "_labels", "_code", "_inds")):
-            assert np.array_equal(got[k], g[k]), k
-    # the checkpoint it wrote: epoch, the full key list of models/mink_unet.py through the alias, two Adam steps
-    assert int(got["ckpt_epoch"]) == 1 and float(got["optimizer_steps"]) == 2.0
-    assert got["ckpt_keys"].tolist() == g["ckpt_keys"].tolist()
-    from openscene_amd.disnet import DisNet
+def test_the_reference_checkpoint_has_the_mirrors_key_list(gold):
+    """The checkpoint the reference's loop wrote (models/mink_unet.py through the alias) has exactly our DisNet's state_dict keys."""
     import types
+    from openscene_amd.disnet import DisNet
+    g, _ = gold
     mine = DisNet(types.SimpleNamespace(arch_3d=RL.ARCH, feature_2d_extractor="openseg"))
+    assert int(g["ckpt_epoch"]) == 1 and float(g["optimizer_steps"]) == 2.0
     assert list(mine.state_dict().keys()) == g["ckpt_keys"].tolist()
-    for k in g:
-        if k.startswith("ckpt:"):
-            assert np.allclose(got[k], g[k], rtol=1e-6, atol=1e-8), k
-    # evaluate(): predictions and mean IoU of both modes and both repeats
-    for mode in ("distill", "ensemble"):
-        assert int(got["eval_%s_reps" % mode]) == 2
-        for rep in range(2):
-            k = "eval_%s_rep%d_" % (mode, rep)
-            assert np.array_equal(got[k + "gt"], g[k + "gt"])
-            assert float((got[k + "pred"] == g[k + "pred"]).mean()) >= 0.9999, k
-            assert abs(float(got[k + "miou"]) - float(g[k + "miou"])) <= 1e-6, k
 
 
 def test_replay_through_openscene_amd_on_the_cpu_backend(gold, monkeypatch):

@@ -24,7 +24,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 def build_dry_lib():
     from openscene_amd import build as b
     b.build(verbose=False)
-    out = "/tmp/osn_dry"
+    out = os.path.join(os.path.dirname(b.LIB), "dry")            # next to the real library, inside this checkout
     os.makedirs(out, exist_ok=True)
     obj = os.path.join(out, "hip_null.o")
     so = os.path.join(out, "libosn_dry.so")

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Round-end evidence in one call: full GPU tests + smoke, the default bench line (with the CPU baseline), the same bench command
+# Round-end evidence in one call: full GPU tests + smoke, the bench line with --full (with the CPU baseline), the same bench command
 # under rocprofv3 (whole-run kernel stats + the dominant kernel's dispatch durations), per-step kernel stats of the training
 # step, and the PMC traffic passes of the tile-list kernels.   usage: gpu_final.sh <tag>
 R=${GRAFT_REPO_ROOT:-$(pwd)}
@@ -10,9 +10,9 @@ export TMPDIR=/tmp
 t0=$(date +%s)
 if [ "${SKIP_TESTS:-0}" != "1" ]; then timeout 1500 python -m pytest tests -m gpu -x -q -p no:cacheprovider > $O/pytest_gpu.log 2>&1; echo "pytest exit $? in $(( $(date +%s) - t0 )) s"; tail -2 $O/pytest_gpu.log; fi
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke exit $?"; tail -1 $O/smoke.log
-if [ "${SKIP_BENCH:-0}" != "1" ]; then timeout 900 python bench.py > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; cp bench_detail.json $O/bench_detail.json 2>/dev/null; fi
+if [ "${SKIP_BENCH:-0}" != "1" ]; then timeout 900 python bench.py --full > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; cp bench_detail.json $O/bench_detail.json 2>/dev/null; fi
 cd /tmp
-timeout 900 rocprofv3 --kernel-trace --stats -d $O/whole -o trace -- python $R/bench.py --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
+timeout 900 rocprofv3 --kernel-trace --stats -d $O/whole -o trace -- python $R/bench.py --full --no-cpu-baseline > $O/bench_under_rocprof.json 2> $O/bench_under_rocprof.err
 python $R/tools/rocpd_stats.py $O/whole/trace_results.db > $O/kernel_stats_whole_run.csv
 python $R/tools/rocpd_stats.py $O/whole/trace_results.db --dispatches spconv_tl_kernel 400 > $O/tl_dispatches.txt
 rm -rf $O/whole

@@ -17,11 +17,11 @@ fi
 echo "== smoke"
 timeout 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.log 2>&1; echo "smoke exit $?" >> $O/smoke.log; tail -n 5 $O/smoke.log
 echo "== bench"
-timeout 600 python bench.py --steps ${BENCH_STEPS:-10} --warmup 3 > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -c 3000 $O/bench.json; tail -n 20 $O/bench.err
+timeout 600 python bench.py --full --steps ${BENCH_STEPS:-10} --warmup 3 > $O/bench.json 2> $O/bench.err; echo "bench exit $?"; tail -c 3000 $O/bench.json; tail -n 20 $O/bench.err
 if [ "${SKIP_PROF:-0}" != "1" ]; then
   echo "== rocprofv3"
   cd /tmp
-  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r01 -- python $R/bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-kernel-events > $O/prof_bench.json 2> $O/prof.err
+  timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o r01 -- python $R/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-kernel-events > $O/prof_bench.json 2> $O/prof.err
   echo "rocprof exit $?"
   ls -R $O/prof | head -20
   f=$(find $O/prof -name '*kernel_stats.csv' | head -1)
