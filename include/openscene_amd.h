@@ -432,6 +432,44 @@ int osn_distill_loss_check(const void* state, int64_t n, int64_t n_sel, osn_stre
 int osn_adam_step(float* params, const float* grads, float* exp_avg, float* exp_avg_sq, int64_t n, int64_t step, float lr,
                   float beta1, float beta2, float eps, float weight_decay, osn_stream_t stream);
 
+/* SGD with momentum over the same flat layout.  Replaces optimizer.step() of torch.optim.SGD(model.parameters(), lr,
+ * momentum, weight_decay) (run/train_mink.py:147-148 builds it, :283 steps it; its lr is set per iteration, :303-306).
+ * torch's update rule (maximize = False):  d = g + weight_decay p;  momentum_buf = first ? d : momentum momentum_buf +
+ * (1 - dampening) d;  d = nesterov ? d + momentum momentum_buf : momentum_buf;  p -= lr d.  `first` = the buffer does not
+ * exist yet (torch's `momentum_buffer is None`); with momentum == 0 there is no buffer and momentum_buf may be null.
+ * n % 4 == 0, 16-byte aligned arrays: one launch, 20 bytes per parameter (12 without momentum).                      */
+int osn_sgd_step(float* params, const float* grads, float* momentum_buf, int64_t n, float lr, float momentum, float dampening,
+                 float weight_decay, int nesterov, int first, osn_stream_t stream);
+
+/* ---- supervised segmentation head: cross-entropy, argmax, confusion matrix, test-repeat votes -------------- *
+ * Replaces the supervised baseline's per-iteration head (run/train_mink.py:160,279-290,367-372):
+ *     loss = nn.CrossEntropyLoss(ignore_index=255)(output, label)
+ *     output = output.detach().max(1)[1]
+ *     intersection, union, target = intersectionAndUnionGPU(output, label, classes, 255)   (util/util.py:132-145)
+ * the numpy confusion matrix of util/metric.py:9-25 and the vote over test repeats of run/eval_mink.py:184-216.
+ *   logits     float [n, c]  (1 <= c <= 256, any c: rows need no alignment)
+ *   rows       int64 [n_lab] or null: row j of the head reads logits[rows[j]] (output[inds_reverse]); null: n_lab == n
+ *   labels     int64 [n_lab]; rows whose label == ignore_index (255, or torch's -100) count in neither loss nor confusion
+ *   loss       float [1] (device, nullable) = sum over labelled rows of (logsumexp(x) - x[y]) / n_valid; NaN if n_valid == 0.
+ *              A fixed-order two-level sum (per-workgroup fp64 partials, then a one-workgroup launch): bitwise reproducible
+ *   pred       int64 [n_lab] (nullable) = torch.max(x, 1)[1] (lowest column on a tie)
+ *   confusion  int64 [c, c] (nullable), ACCUMULATED: confusion[pred * c + label] += 1 over the labelled rows.  diag =
+ *              intersection, row sums = output, column sums = target of intersectionAndUnionGPU
+ *   state      osn_seg_loss_state_bytes(n_lab, c) bytes kept by the caller from the forward to the backward call
+ * osn_seg_loss_bwd (rows == null only): glogits [n, c] = gloss (softmax(x) - onehot(y)) / n_valid on labelled rows, zeros
+ * on the others (gloss float [1] on the device, null = 1).  osn_seg_loss_check synchronises the stream and reports a label
+ * outside [0, c) that is not ignore_index, or a rows entry outside [0, n) (OSN_E_ARG); the kernels never read or write out of
+ * bounds (such a row counts as ignored).  osn_seg_vote: votes [n_pts, c] += logits[rows ? rows[p] : p] (a rows entry outside
+ * [0, n) adds nothing); the vote's argmax and confusion then come from osn_seg_loss_fwd on `votes` with loss = null.     */
+size_t osn_seg_loss_state_bytes(int64_t n_lab, int c);
+int osn_seg_loss_fwd(const float* logits, const int64_t* rows, const int64_t* labels, int64_t n, int64_t n_lab, int c,
+                     int64_t ignore_index, float* loss, int64_t* pred, int64_t* confusion, void* state, size_t state_bytes,
+                     osn_stream_t stream);
+int osn_seg_loss_bwd(const float* logits, const int64_t* labels, const float* gloss, int64_t n, int c, int64_t ignore_index,
+                     float* glogits, const void* state, size_t state_bytes, osn_stream_t stream);
+int osn_seg_loss_check(const void* state, int64_t n, int64_t n_lab, int c, osn_stream_t stream);
+int osn_seg_vote(const float* logits, const int64_t* rows, int64_t n, int64_t n_pts, int c, float* votes, osn_stream_t stream);
+
 /* ---- row-aligned elementwise pieces --------------------------------------- *
  * Replaces the stand-alone [ME] MinkowskiReLU (models/mink_unet.py:114, used un-fused by the reference's own module
  * chain), the BasicBlock residual `out += residual` when it is not fused into a batch norm, and ME.cat of two tensors

@@ -67,6 +67,12 @@ PROTOTYPES = {
     "osn_dense_fwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i32, _vp]),
     "osn_rows_argmax": (_i32, [_vp, _i64, _i32, _vp, _i64, _i64, _vp, _vp]),
     "osn_adam_step": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _f32, _f32, _f32, _f32, _f32, _vp]),
+    "osn_sgd_step": (_i32, [_vp, _vp, _vp, _i64, _f32, _f32, _f32, _f32, _i32, _i32, _vp]),
+    "osn_seg_loss_state_bytes": (_sz, [_i64, _i32]),
+    "osn_seg_loss_fwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i64, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "osn_seg_loss_bwd": (_i32, [_vp, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _sz, _vp]),
+    "osn_seg_loss_check": (_i32, [_vp, _i64, _i64, _i32, _vp]),
+    "osn_seg_vote": (_i32, [_vp, _vp, _i64, _i64, _i32, _vp, _vp]),
     "osn_spconv_fwd_ws_ws_bytes": (_sz, [_i64, _i32, _i32, _i32]),
     "osn_spconv_fwd_ws": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _sz, _vp]),
     "osn_spconv_wgrad_tl_partial": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),

@@ -96,3 +96,77 @@ def distill_loss(output, sel, target, loss_type="cosine", validate=False):
     if sel.dtype == torch.bool:
         sel = sel.nonzero(as_tuple=False).squeeze(1)
     return _DistillLoss.apply(output, sel, target, KINDS[loss_type], bool(validate))
+
+
+# ---- supervised segmentation (the MinkowskiNet baseline, run/train_mink.py)
+class _SegLoss(Function):
+    @staticmethod
+    def forward(ctx, logits, labels, rows, ignore_index, want_pred, confusion, validate):
+        loss, pred, state = ops.seg_loss_fwd(logits, labels, ignore_index, rows=rows, want_pred=want_pred, confusion=confusion,
+                                             validate=validate)
+        if pred is None:
+            pred = torch.empty(0, dtype=torch.int64, device=logits.device)
+        ctx.mark_non_differentiable(pred)
+        ctx.save_for_backward(logits, labels, state)
+        ctx.ignore_index = ignore_index
+        return loss, pred
+
+    @staticmethod
+    def backward(ctx, gloss, _gpred):
+        logits, labels, state = ctx.saved_tensors
+        return ops.seg_loss_bwd(logits, labels, state, ctx.ignore_index, gloss), None, None, None, None, None, None
+
+
+def segmentation_loss(logits, labels, ignore_index=255, rows=None, pred=False, meter=None, validate=False):
+    """``nn.CrossEntropyLoss(ignore_index=ignore_index)(logits[rows], labels)`` (run/train_mink.py:160,279,368) in one launch
+    pair, with what the supervised loop computes next from the same rows folded into the same pass:
+
+      pred=True   also return ``logits[rows].max(1)[1]`` (run/train_mink.py:285): ``(loss, pred)``
+      meter       a metrics.SegmentationMeter: its confusion matrix takes this batch's (pred, label) counts
+                  (intersectionAndUnionGPU, run/train_mink.py:286-290), on the device, without a host synchronisation
+      rows        int64 row indices (``inds_reverse``, duplicates allowed): the loss of ``logits[rows]`` without the gather.
+                  Forward only (validation runs under no_grad): NotImplementedError when the logits need a gradient
+      validate    raise on a label outside [0, c) that is not ignore_index or a rows entry outside [0, n) (synchronises;
+                  torch raises in both cases, the kernels count such a row as ignored)
+
+    logits float32 [N, C] (1 <= C <= 256), labels int64 [N] (or [len(rows)]).  The loss is NaN when every label is ignored
+    (as torch's); its gradient is then zero."""
+    if rows is not None and logits.requires_grad and torch.is_grad_enabled():
+        raise NotImplementedError("segmentation_loss: a gathered (rows=...) loss has no backward pass; run it under torch.no_grad()")
+    confusion = None
+    if meter is not None:
+        if meter.num_classes != logits.shape[-1] or meter.ignore_index != ignore_index:
+            raise ValueError("meter counts %d classes with ignore_index %d, the loss sees %d with %d"
+                             % (meter.num_classes, meter.ignore_index, logits.shape[-1], ignore_index))
+        confusion = meter.confusion
+    loss, p = _SegLoss.apply(logits, labels, rows, int(ignore_index), bool(pred), confusion, bool(validate))
+    return (loss, p) if pred else loss
+
+
+class SegmentationLoss(torch.nn.Module):
+    """Replacement for ``nn.CrossEntropyLoss(ignore_index=...)`` (run/train_mink.py:160) on 2-D float32 logits and 1-D int64
+    labels, the form the supervised baseline uses.  Every other form of torch's module (class weights, label smoothing,
+    a reduction other than 'mean', probability targets, extra dimensions) raises NotImplementedError instead of computing
+    something else."""
+
+    def __init__(self, weight=None, size_average=None, ignore_index=-100, reduce=None, reduction="mean", label_smoothing=0.0):
+        super().__init__()
+        if weight is not None:
+            raise NotImplementedError("SegmentationLoss: class weights")
+        if size_average is not None or reduce is not None:
+            raise NotImplementedError("SegmentationLoss: the deprecated size_average / reduce arguments")
+        if reduction != "mean":
+            raise NotImplementedError("SegmentationLoss: reduction=%r (only 'mean')" % (reduction,))
+        if label_smoothing != 0.0:
+            raise NotImplementedError("SegmentationLoss: label smoothing")
+        self.ignore_index = int(ignore_index)
+        self.reduction = reduction
+
+    def forward(self, input, target):
+        if input.dim() != 2 or input.dtype != torch.float32:
+            raise NotImplementedError("SegmentationLoss: logits must be a float32 [N, C] matrix (got %s %s)"
+                                      % (input.dtype, tuple(input.shape)))
+        if target.dim() != 1 or target.dtype != torch.int64:
+            raise NotImplementedError("SegmentationLoss: targets must be an int64 vector of class indices (got %s %s)"
+                                      % (target.dtype, tuple(target.shape)))
+        return segmentation_loss(input, target, self.ignore_index)

@@ -1360,3 +1360,74 @@ def fusion_finish(sum_features, counter):
     with _Dev(dev):
         check(lib.osn_fusion_finish(_p(sum_features), _p(counter), n, D, _p(bank), _stream(dev)), "osn_fusion_finish")
     return bank
+
+
+# ------------------------------------------------- supervised segmentation head: cross-entropy, argmax, confusion, votes
+def _seg_index(t, name, n, dev):
+    if t.dtype != torch.int64 or t.dim() != 1 or t.device != dev or (n is not None and t.shape[0] != n):
+        raise ValueError("%s must be an int64 vector%s on the logits' device" % (name, "" if n is None else " of %d entries" % n))
+    return t.contiguous()
+
+
+def seg_loss_fwd(logits, labels, ignore_index=255, rows=None, want_loss=True, want_pred=False, confusion=None, validate=False):
+    """-> (loss float32 scalar or None, pred int64 [n_lab] or None, state): cross-entropy with ignore_index over the rows
+    `logits[rows]` (all rows when rows is None) against `labels`, their argmax, and `confusion` [c, c] int64 += the counts of
+    (pred, label) over the labelled rows.  validate: raise on a label outside [0, c) that is not ignore_index or a rows entry
+    outside [0, n) (synchronises).  `state` feeds seg_loss_bwd."""
+    dev = logits.device
+    lib = _prep(dev)
+    if logits.dim() != 2:
+        raise ValueError("logits must be a [n, c] matrix")
+    logits = _f32c(logits, "logits")
+    n, c = logits.shape
+    if not 1 <= c <= 256 or n < 1:
+        raise ValueError("logits are %s: the kernels take 1 <= c <= 256 classes and at least one row" % (tuple(logits.shape),))
+    if rows is not None:
+        rows = _seg_index(rows, "rows", None, dev)
+    n_lab = n if rows is None else rows.shape[0]
+    labels = _seg_index(labels, "labels", n_lab, dev)
+    if confusion is not None and (confusion.dtype != torch.int64 or tuple(confusion.shape) != (c, c) or confusion.device != dev
+                                  or not confusion.is_contiguous()):
+        raise ValueError("confusion must be a contiguous int64 [%d, %d] matrix on the logits' device" % (c, c))
+    state = torch.empty(int(_cached("osn_seg_loss_state_bytes", n_lab, c)), dtype=torch.uint8, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev) if want_loss else None
+    pred = torch.empty(n_lab, dtype=torch.int64, device=dev) if want_pred else None
+    with _Dev(dev):
+        check(lib.osn_seg_loss_fwd(_p(logits), _p(rows), _p(labels), n, n_lab, c, int(ignore_index), _p(loss), _p(pred), _p(confusion),
+                                   _p(state), state.numel(), _stream(dev)), "osn_seg_loss_fwd")
+        if validate:
+            check(lib.osn_seg_loss_check(_p(state), n, n_lab, c, _stream(dev)), "osn_seg_loss_check")
+    return loss, pred, state
+
+
+def seg_loss_bwd(logits, labels, state, ignore_index=255, gloss=None):
+    """d loss / d logits [n, c] of seg_loss_fwd (rows = None) times gloss (a float32 device scalar, None = 1)."""
+    dev = logits.device
+    lib = _prep(dev)
+    logits = _f32c(logits, "logits")
+    n, c = logits.shape
+    labels = _seg_index(labels, "labels", n, dev)
+    if gloss is not None:
+        gloss = gloss.to(device=dev, dtype=torch.float32).contiguous()
+    glogits = torch.empty_like(logits)
+    with _Dev(dev):
+        check(lib.osn_seg_loss_bwd(_p(logits), _p(labels), _p(gloss), n, c, int(ignore_index), _p(glogits), _p(state), state.numel(),
+                                   _stream(dev)), "osn_seg_loss_bwd")
+    return glogits
+
+
+def seg_vote(logits, votes, rows=None):
+    """votes [n_pts, c] += logits[rows] (logits itself when rows is None), in place -- run/eval_mink.py:210's `store = pred +
+    store` on the device.  A rows entry outside [0, n) adds nothing."""
+    dev = logits.device
+    lib = _prep(dev)
+    logits = _f32c(logits, "logits")
+    n, c = logits.shape
+    if rows is not None:
+        rows = _seg_index(rows, "rows", None, dev)
+    n_pts = n if rows is None else rows.shape[0]
+    if votes.dtype != torch.float32 or tuple(votes.shape) != (n_pts, c) or votes.device != dev or not votes.is_contiguous():
+        raise ValueError("votes must be a contiguous float32 [%d, %d] matrix on the logits' device" % (n_pts, c))
+    with _Dev(dev):
+        check(lib.osn_seg_vote(_p(logits), _p(rows), n, n_pts, c, _p(votes), _stream(dev)), "osn_seg_vote")
+    return votes
