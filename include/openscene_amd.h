@@ -567,6 +567,23 @@ int osn_fusion_accumulate(const float* feat2d, int D, int H, int W, const int64_
 int osn_fusion_finish(const float* sum_features, const float* counter, int64_t n, int D, float* feat_bank,
                       osn_stream_t stream);
 
+/* ---- elastic distortion: the pre-voxeliser transform of Point3DLoader (dataset/point_loader.py:156) ---------- *
+ * ElasticDistortion.elastic_distortion (dataset/augmentation.py:159-201), bit-identical to numpy / scipy given the
+ * same noise draw; the draw (np.random.randn(*noise_dim, 3).astype(float32)) and np.linspace of the axes stay on the host.
+ * osn_bbox: bbox6 (device, 6 doubles) = per-axis min of xyz float64 [n,3], then per-axis max.  n >= 1.
+ * osn_elastic_blur: in place on noise float32 [nx, ny, nz, 3]: the six scipy.ndimage.convolve passes (3-tap box of
+ *   weight (double)(float)(1/3) along x, y, z, twice; zero boundary; double accumulation, float32 after each pass).
+ * osn_elastic_apply: out = xyz + RegularGridInterpolator(axes, noise, bounds_error=0, fill_value=0)(xyz) * magnitude
+ *   (scipy's linear rule and operation order), and bbox6 = the bounding box of out (sizes the next field).
+ *   axes float64 [nx + ny + nz] (device, ascending, >= 2 nodes each); out must not alias xyz.                    */
+size_t osn_bbox_ws_bytes(int64_t n);
+int osn_bbox(const double* xyz, int64_t n, double* bbox6, void* ws, size_t ws_bytes, osn_stream_t stream);
+size_t osn_elastic_blur_ws_bytes(int nx, int ny, int nz);
+int osn_elastic_blur(float* noise, int nx, int ny, int nz, void* ws, size_t ws_bytes, osn_stream_t stream);
+size_t osn_elastic_apply_ws_bytes(int64_t n);
+int osn_elastic_apply(const double* xyz, int64_t n, const float* noise, int nx, int ny, int nz, const double* axes,
+                      double magnitude, double* out, double* bbox6, void* ws, size_t ws_bytes, osn_stream_t stream);
+
 /* ---- network executor: one call per forward / backward pass of a MinkUNet -------------------------------- *
  * Replaces the Python-level walk of models/mink_unet.py:116-174 (MinkUNetBase.forward: conv0 .. block8, final) and
  * of its autograd graph.  The module tree is compiled ONCE into a linear program of stages

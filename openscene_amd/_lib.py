@@ -121,6 +121,12 @@ PROTOTYPES = {
                                   _c.c_double, _vp, _vp]),
     "osn_fusion_accumulate": (_i32, [_vp, _i32, _i32, _i32, _vp, _i64, _vp, _vp, _vp]),
     "osn_fusion_finish": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
+    "osn_bbox_ws_bytes": (_sz, [_i64]),
+    "osn_bbox": (_i32, [_vp, _i64, _vp, _vp, _sz, _vp]),
+    "osn_elastic_blur_ws_bytes": (_sz, [_i32, _i32, _i32]),
+    "osn_elastic_blur": (_i32, [_vp, _i32, _i32, _i32, _vp, _sz, _vp]),
+    "osn_elastic_apply_ws_bytes": (_sz, [_i64]),
+    "osn_elastic_apply": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _c.c_double, _vp, _vp, _vp, _sz, _vp]),
 }
 
 _lock = threading.Lock()

@@ -26,17 +26,18 @@ def _load(path, map_location="cpu"):
     return torch.load(path, map_location=map_location, weights_only=False)
 
 
-def load_scene(path):
+def load_scene(path, missing_color=0.0):
     """-> (xyz float64 [N,3], colors float64 [N,3] in 0..255, labels uint8 [N]) exactly as the reference's
     loaders hold them after reading (``feature_loader.py:70-79``): -100 -> 255, colours -> (c + 1) * 127.5,
-    a scalar-0 colour entry (lidar clouds) -> zeros."""
+    a scalar-0 colour entry (lidar clouds) -> ``missing_color`` everywhere: 0 as FusedFeatureLoader holds it, 127.5 as
+    Point3DLoader does (``point_loader.py:136-139`` applies the (c + 1) * 127.5 to the zeros as well)."""
     locs, feats, labels = _load(path)
     locs = np.asarray(locs)
     labels = np.asarray(labels).copy()
     labels[labels == -100] = 255
     labels = labels.astype(np.uint8)
     if np.isscalar(feats) and feats == 0:
-        feats = np.zeros_like(locs)
+        feats = np.full_like(locs, missing_color, dtype=np.float64) if missing_color else np.zeros_like(locs)
     else:
         feats = (np.asarray(feats) + 1.0) * 127.5
     return locs, feats, labels

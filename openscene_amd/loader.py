@@ -19,12 +19,16 @@ to the tensors in HBM (float64, numpy's operation order: bit-identical results).
     item  = fused_feature_item(voxelizer, scene, split="train")
     coords, feats, labels, feat_3d, mask = collate([item0, item1, ...])
 """
+import glob
+import os
 import random
 
 import numpy as np
 import torch
 
+from . import io as _io
 from . import ops
+from .voxelizer import Voxelizer
 
 
 class TrainAugmentation:
@@ -53,6 +57,19 @@ class TrainAugmentation:
             for gi, (granularity, magnitude) in enumerate(self.elastic_params):
                 last = gi == len(self.elastic_params) - 1
                 pts = self._elastic(pts, granularity, magnitude, evaluate=not last)
+
+    def prevoxel_apply(self, xyz):
+        """ElasticDistortion.__call__ as Point3DLoader runs it (``point_loader.py:156``): the 0.95 gate, then every field in
+        turn on the distorted cloud, bit-identical to numpy / scipy (``ops.elastic_distort``; each field's grid is sized
+        from the previous field's bounding box, computed in the same kernel).  xyz float64 [N, 3] on the device ->
+        the distorted cloud (a new tensor), or xyz itself when nothing is applied."""
+        if self.elastic_params is None:
+            return xyz
+        if random.random() < 0.95:
+            box = None
+            for granularity, magnitude in self.elastic_params:
+                xyz, box = ops.elastic_distort(xyz, granularity, magnitude, bbox6=box, return_bbox=True)
+        return xyz
 
     @staticmethod
     def _elastic(pts, granularity, magnitude, evaluate):
@@ -245,3 +262,115 @@ def collate(items):
             acc += n
         out.append(torch.cat(rec))
     return tuple(out)
+
+
+# ------------------------------------------------------------------ Point3DLoader (dataset/point_loader.py)
+def point_item(voxelizer, xyz, colors, labels, split="train", eval_all=False, input_color=False, aug=None):
+    """Point3DLoader.__getitem__ (``point_loader.py:137-174``) on device tensors.
+    xyz float64 [N,3], colors float [N,3] in 0..255, labels uint8/int [N] (255 = ignore), as ``io.load_scene`` returns them;
+    aug: a :class:`TrainAugmentation` (the reference's ``aug=True``) or None.  Random draws in the reference's order: the
+    elastic distortion, the voxeliser's matrix, then the flip and chromatic transforms (which with ``input_color=False``
+    only consume their draws).  ``split`` is accepted for symmetry with the reference; it changes nothing here.
+    -> (coords3 int32 [V,3], feats f32 [V,3], labels int64 [V] (or [N] with eval_all)[, inds_reconstruct int64 [N]])."""
+    if xyz.dtype != torch.float64:
+        raise TypeError("xyz must be float64 (the reference voxelises in float64)")
+    n = xyz.shape[0]
+    if labels.shape[0] != n or (colors is not None and colors.shape[0] != n):
+        raise ValueError("per-point arrays disagree on the number of points")
+    if input_color and colors is None:
+        raise ValueError("input_color=True needs per-point colours")
+    locs_in = aug.prevoxel_apply(xyz) if aug is not None else xyz          # :156
+    M_v, M_r = voxelizer.get_transformation_matrix()                        # :157-158, consumes numpy.random
+    T = M_r @ M_v if voxelizer.use_augmentation else M_v
+    grid, vox_ind, inverse = voxelizer.voxelize_tensors(locs_in, T)
+    locs = grid[vox_ind]
+    feats_v = colors[vox_ind].double() if input_color else None
+    if aug is not None:                                                     # :161-162
+        locs, feats_v = aug.after_voxelizer(locs, feats_v)
+    coords3 = locs.to(torch.int32)
+    if input_color:
+        # Division by a TENSOR, as in fused_feature_item: torch turns division by a Python scalar into a multiplication.
+        div = torch.full((1, 1), 127.5, dtype=torch.float32, device=coords3.device)
+        feats = feats_v.float() / div - 1.0
+    else:
+        feats = torch.ones(coords3.shape[0], 3, device=coords3.device)      # :169-170
+    lab = (labels if eval_all else labels[vox_ind]).long()
+    return (coords3, feats, lab, inverse) if eval_all else (coords3, feats, lab)
+
+
+def point_collate(items):
+    """``collation_fn`` / ``collation_fn_eval_all`` (``point_loader.py:22-51``) for :func:`point_item` results: column 0 of
+    the coordinates is the scene's index in the batch; a fourth entry per item (``inds_reconstruct``) is offset by the
+    voxels of the scenes before it.  -> (coords int32 [V,4], feats, labels[, inds_reconstruct])."""
+    if not items:
+        raise ValueError("empty batch")
+    nf = len(items[0])
+    if nf not in (3, 4) or any(len(it) != nf for it in items):
+        raise ValueError("point_collate takes items of 3 or 4 fields (all alike)")
+    dev = items[0][0].device
+    sizes = [it[0].shape[0] for it in items]
+    coords = torch.empty((sum(sizes), 4), dtype=torch.int32, device=dev)
+    off = 0
+    for b, (it, n) in enumerate(zip(items, sizes)):
+        ops.batch_coords(it[0], b, coords[off:off + n])
+        off += n
+    out = [coords, torch.cat([it[1] for it in items]), torch.cat([it[2] for it in items])]
+    if nf == 4:
+        acc, rec = 0, []
+        for it, n in zip(items, sizes):
+            rec.append(it[3] + acc)
+            acc += n
+        out.append(torch.cat(rec))
+    return tuple(out)
+
+
+class PointLoader(torch.utils.data.Dataset):
+    """Point3DLoader (``dataset/point_loader.py:54-177``) with the per-item work on a GPU: same constructor arguments,
+    class constants, file discovery, ``loop`` and index wrap, and the same random draws per item (seed parity with a
+    ``num_workers=0`` reference run).  ``memcache_init`` / ``identifier`` (the shared-memory cache) are accepted and
+    ignored.  Scenes are read with ``io.load_scene`` on every access and uploaded to ``device``.
+
+        ds = PointLoader(datapath_prefix, voxel_size=0.02, split="train", aug=True, device="cuda")
+        DataLoader(ds, batch_size=8, shuffle=True, num_workers=0, pin_memory=False, collate_fn=point_collate)"""
+
+    SCALE_AUGMENTATION_BOUND = (0.9, 1.1)
+    ROTATION_AUGMENTATION_BOUND = ((-np.pi / 64, np.pi / 64), (-np.pi / 64, np.pi / 64), (-np.pi, np.pi))
+    TRANSLATION_AUGMENTATION_RATIO_BOUND = ((-0.2, 0.2), (-0.2, 0.2), (0, 0))
+    ELASTIC_DISTORT_PARAMS = ((0.2, 0.4), (0.8, 1.6))
+    ROTATION_AXIS = "z"
+    LOCFEAT_IDX = 2
+
+    def __init__(self, datapath_prefix="data", voxel_size=0.05, split="train", aug=False, memcache_init=False,
+                 identifier=1233, loop=1, data_aug_color_trans_ratio=0.1, data_aug_color_jitter_std=0.05,
+                 data_aug_hue_max=0.5, data_aug_saturation_max=0.2, eval_all=False, input_color=False, device=None):
+        super().__init__()
+        self.split = split
+        self.identifier = identifier
+        self.data_paths = sorted(glob.glob(os.path.join(datapath_prefix, split if split is not None else "", "*.pth")))
+        if len(self.data_paths) == 0:
+            raise Exception("0 file is loaded in the point loader.")
+        self.input_color, self.voxel_size, self.aug, self.loop, self.eval_all = input_color, voxel_size, aug, loop, eval_all
+        self.dataset_name = datapath_prefix.split("/")[-1]
+        if device is None:
+            if not torch.cuda.is_available():
+                raise RuntimeError("PointLoader needs a HIP device (there is no CPU path)")
+            device = torch.device("cuda", torch.cuda.current_device())
+        self.device = torch.device(device)
+        self.voxelizer = Voxelizer(voxel_size=voxel_size, clip_bound=None, use_augmentation=True,
+                                   scale_augmentation_bound=self.SCALE_AUGMENTATION_BOUND,
+                                   rotation_augmentation_bound=self.ROTATION_AUGMENTATION_BOUND,
+                                   translation_augmentation_ratio_bound=self.TRANSLATION_AUGMENTATION_RATIO_BOUND,
+                                   device=self.device)
+        self.augmentation = TrainAugmentation(self.ELASTIC_DISTORT_PARAMS, data_aug_color_trans_ratio,
+                                              data_aug_color_jitter_std, data_aug_hue_max,
+                                              data_aug_saturation_max) if aug else None
+
+    def __getitem__(self, index_long):
+        index = index_long % len(self.data_paths)
+        xyz, colors, labels = _io.load_scene(self.data_paths[index], missing_color=127.5)
+        t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+        return point_item(self.voxelizer, t(xyz.astype(np.float64)), t(colors), t(labels), split=self.split,
+                          eval_all=self.eval_all, input_color=self.input_color, aug=self.augmentation)
+
+    def __len__(self):
+        return len(self.data_paths) * self.loop

@@ -1431,3 +1431,89 @@ def seg_vote(logits, votes, rows=None):
     with _Dev(dev):
         check(lib.osn_seg_vote(_p(logits), _p(rows), n, n_pts, c, _p(votes), _stream(dev)), "osn_seg_vote")
     return votes
+
+
+# ------------------------------------------------------- elastic distortion (Point3DLoader's pre-voxeliser transform)
+def _xyz64(xyz, name="xyz"):
+    if xyz.dtype != torch.float64:
+        raise TypeError("%s must be float64 (the reference distorts in float64), got %s" % (name, xyz.dtype))
+    if xyz.dim() != 2 or xyz.shape[1] != 3:
+        raise ValueError("%s must be [n, 3], got %s" % (name, tuple(xyz.shape)))
+    if not xyz.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+
+
+def bbox(xyz):
+    """float64 [6] on the device: per-axis min of a float64 [n, 3] cloud, then per-axis max (``coords.min(0)``,
+    ``coords.max(0)``).  An empty cloud raises, as numpy's min does."""
+    dev = xyz.device
+    lib = _prep(dev)
+    _xyz64(xyz)
+    n = xyz.shape[0]
+    out = torch.empty(6, dtype=torch.float64, device=dev)
+    with _Dev(dev):
+        ws = _ws(lib.osn_bbox_ws_bytes(n), dev)
+        check(lib.osn_bbox(_p(xyz), n, _p(out), _p(ws), ws.numel(), _stream(dev)), "osn_bbox")
+    return out
+
+
+def elastic_blur(noise):
+    """The six ``scipy.ndimage.convolve`` box-filter passes of augmentation.py:181-185, in place on a contiguous float32
+    [nx, ny, nz, 3] device grid (bit-identical)."""
+    dev = noise.device
+    lib = _prep(dev)
+    if noise.dtype != torch.float32 or noise.dim() != 4 or noise.shape[3] != 3 or not noise.is_contiguous():
+        raise ValueError("noise must be a contiguous float32 [nx, ny, nz, 3] grid")
+    nx, ny, nz = (int(s) for s in noise.shape[:3])
+    with _Dev(dev):
+        ws = _ws(lib.osn_elastic_blur_ws_bytes(nx, ny, nz), dev)
+        check(lib.osn_elastic_blur(_p(noise), nx, ny, nz, _p(ws), ws.numel(), _stream(dev)), "osn_elastic_blur")
+    return noise
+
+
+def elastic_apply(xyz, noise, axes, magnitude):
+    """xyz + RegularGridInterpolator(axes, noise, bounds_error=0, fill_value=0)(xyz) * magnitude (augmentation.py:188-194,
+    bit-identical), and the bounding box of the result (float64 [6], device).  noise: float32 [nx, ny, nz, 3] device grid;
+    axes: three ascending float64 node arrays (host) of nx, ny, nz >= 2 nodes.  -> (out float64 [n, 3], bbox6)."""
+    import numpy as np
+    dev = xyz.device
+    lib = _prep(dev)
+    _xyz64(xyz)
+    if noise.dtype != torch.float32 or noise.dim() != 4 or noise.shape[3] != 3 or not noise.is_contiguous():
+        raise ValueError("noise must be a contiguous float32 [nx, ny, nz, 3] grid")
+    dims = tuple(int(s) for s in noise.shape[:3])
+    axes = [np.asarray(a, dtype=np.float64) for a in axes]
+    if tuple(a.shape[0] for a in axes) != dims:
+        raise ValueError("axes of %s nodes for a %s grid" % ([a.shape[0] for a in axes], dims))
+    ax = torch.from_numpy(np.concatenate(axes)).to(dev)
+    n = xyz.shape[0]
+    out = torch.empty((n, 3), dtype=torch.float64, device=dev)
+    box = torch.empty(6, dtype=torch.float64, device=dev)
+    with _Dev(dev):
+        ws = _ws(lib.osn_elastic_apply_ws_bytes(n), dev)
+        check(lib.osn_elastic_apply(_p(xyz), n, _p(noise), dims[0], dims[1], dims[2], _p(ax), float(magnitude), _p(out),
+                                    _p(box), _p(ws), ws.numel(), _stream(dev)), "osn_elastic_apply")
+    return out, box
+
+
+def elastic_distort(xyz, granularity, magnitude, bbox6=None, return_bbox=False):
+    """One field of ElasticDistortion.elastic_distortion (augmentation.py:159-194) on a float64 [n, 3] device cloud,
+    bit-identical to numpy / scipy.  The noise is drawn on the host from ``numpy.random`` exactly as the reference draws it
+    (the grid size comes from the cloud's bounding box: its 6 doubles are the one read-back of a field) and the axes come
+    from ``np.linspace`` on the host; the blur and the interpolation run on the device.
+    bbox6: the cloud's bounding box if already known (the previous field's ``return_bbox``), else computed here.
+    -> out float64 [n, 3] (a new tensor), or (out, bbox6 of out) with return_bbox."""
+    import numpy as np
+    _xyz64(xyz)
+    dev = xyz.device
+    if bbox6 is None:
+        bbox6 = bbox(xyz)
+    b = bbox6.cpu().numpy()
+    coords_min, coords_max = b[:3], b[3:]
+    noise_dim = ((coords_max - coords_min) // granularity).astype(int) + 3     # == (coords - coords_min).max(0) // g
+    noise = np.random.randn(*noise_dim, 3).astype(np.float32)
+    axes = [np.linspace(d_min, d_max, d)
+            for d_min, d_max, d in zip(coords_min - granularity, coords_min + granularity * (noise_dim - 2), noise_dim)]
+    grid = elastic_blur(torch.from_numpy(noise).to(dev))
+    out, box = elastic_apply(xyz, grid, axes, magnitude)
+    return (out, box) if return_bbox else out
