@@ -509,6 +509,38 @@ int osn_query_ensemble(const float* X_distill, const int64_t* gather_distill,
                        const float* X_fusion, const int64_t* gather_fusion,
                        const void* text_f16, void* scores_f16, int64_t* argmax, uint8_t* sel,
                        int64_t n, int d, int c, void* ws, size_t ws_bytes, osn_stream_t stream);
+/* Test-repeat votes (run/evaluate.py:390,397,416: `preds.append(pred.cpu())`, `torch.cat`, `store = pred + store` on
+ * CPU fp16 tensors).  The same queries with a vote epilogue: instead of storing the fp16 score of (point p, label l) the
+ * kernel adds it to the caller-owned fp16 matrix,
+ *     votes_f16[p * c + l] = fp16_rne(float(votes_f16[p * c + l]) + float(score_f16))
+ * which is torch's CPU half add (computed in fp32, rounded once).  Each cell has one owner: no atomics, deterministic.
+ * votes_f16 is [n, c], already offset to the scene's first row; 16-byte aligned when c % 8 == 0, else 2-byte aligned.
+ * No score matrix is written; argmax (nullable) is the per-scene label of this repeat's scores, as above.            */
+int osn_cosine_query_vote(const float* X, const int64_t* gather, const void* text_f16,
+                          void* votes_f16, int64_t* argmax, int64_t n, int d, int c,
+                          osn_stream_t stream);
+int osn_query_ensemble_vote(const float* X_distill, const int64_t* gather_distill,
+                            const float* X_fusion, const int64_t* gather_fusion,
+                            const void* text_f16, void* votes_f16, int64_t* argmax, uint8_t* sel,
+                            int64_t n, int d, int c, void* ws, size_t ws_bytes, osn_stream_t stream);
+
+/* ---- open-vocabulary evaluation (csrc/evaluate.hip) ------------------------------------------------------------ *
+ * Replaces run/evaluate.py:397-424 (`store.float().max(1)[1]`, `mapper[...]`, `[~mask] = 256`) and util/metric.py:9-25
+ * (confusion_matrix).  One pass over n points; exactly one prediction source:
+ *   votes_f16  fp16 [n, c_in] (1 <= c_in <= 256): pred = Tensor.max(1)[1] on CPU (first NaN wins, else the lowest column
+ *              among equal maxima), or
+ *   ids        int64 [n]: given predictions (the one-repeat path, run/evaluate.py:387; 256 = no feature).
+ * mapper (nullable) int64 [n_map]: pred = mapper[pred] (nuScenes 43 -> 16); has_feature (nullable) uint8 [n]: 0 -> 256.
+ * labels int64 [n]: 255 is ignored.  confusion int64 [(c_out + 1) * c_out], [pred, gt], ACCUMULATED: rows 0 .. c_out-1 are
+ * metric.confusion_matrix, row c_out counts the no-feature points per gt class.  1 <= c_out <= 254.
+ * err int32 [1] (device) is ORed with: 1 a prediction outside the mapper, 2 a gt outside [0, c_out) that is not 255,
+ * 4 a counted prediction outside [0, c_out) that is not 256; osn_eval_check synchronises and turns it into OSN_E_ARG.
+ * hist: -1 chooses (LDS up to 90 classes), 1 counts in an LDS histogram per workgroup (c_out <= 160), 0 uses int64
+ * atomics on the matrix.                                                                                         */
+int osn_eval_confusion(const void* votes_f16, const int64_t* ids, int64_t n, int c_in, const int64_t* labels,
+                       const int64_t* mapper, int64_t n_map, const uint8_t* has_feature, int c_out,
+                       int64_t* confusion, int32_t* err, int hist, osn_stream_t stream);
+int osn_eval_check(const int32_t* err, osn_stream_t stream);
 
 /* ---- hash voxelisation --------------------------------------------------- *
  * Replaces Voxelizer.voxelize (dataset/voxelizer.py:117-129) +

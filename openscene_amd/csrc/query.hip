@@ -22,9 +22,14 @@ constexpr int Q_BM = 128;   // points per workgroup (4 waves x 32)
 constexpr int Q_DK = 64;    // feature chunk
 constexpr int Q_LD = Q_DK + 8;  // padded LDS row (144 B: 16-B aligned, conflict-free ds_read_b128)
 
+// Test-repeat vote (run/evaluate.py:397,416  `store = pred + store` on CPU fp16 tensors): torch adds two halves in fp32 and
+// rounds the sum to half once (round to nearest even).  Each (point, label) cell has one owner thread: no atomics.
+__device__ inline void vote_add(_Float16& cell, _Float16 s) { cell = (_Float16)((float)cell + (float)s); }
+
 // sources: point p reads row g0[p] of X0 (or p if g0 null); if sel && sel[p], row g1[p] of X1.
 // NBUF chunks of point rows (and of the text) in flight per thread, WGS workgroups per CU (register budget 512 / WGS).
-template <int CT, int NBUF, int WGS>
+// VOTE: `scores` is the caller's fp16 vote matrix and each fp16 score is ADDED to its cell (see vote_add) instead of stored.
+template <int CT, int NBUF, int WGS, bool VOTE = false>
 __global__ __launch_bounds__(256, WGS) void query_kernel(const float* __restrict__ X0, const int64_t* __restrict__ g0,
                                                     const float* __restrict__ X1, const int64_t* __restrict__ g1,
                                                     const uint8_t* __restrict__ sel, const float* __restrict__ rowdiv,
@@ -186,7 +191,10 @@ __global__ __launch_bounds__(256, WGS) void query_kernel(const float* __restrict
                 const _Float16 hv = (_Float16)acc[t][r];
                 const float v = (float)hv;
                 if (col < c) {
-                    if (scores && row < n) scores[row * c + col] = hv;
+                    if (scores && row < n) {
+                        if constexpr (VOTE) vote_add(scores[row * c + col], hv);
+                        else scores[row * c + col] = hv;
+                    }
                     if (v > bestv[r] || (v == bestv[r] && col < besti[r])) { bestv[r] = v; besti[r] = col; }
                 }
             }
@@ -241,7 +249,7 @@ __global__ __launch_bounds__(256, WGS) void query_kernel(const float* __restrict
 // feature dimension in ascending order, one fp16 rounding).
 constexpr int QW_TP = 32;        // points per tile
 
-template <int D, int NCW>
+template <int D, int NCW, bool VOTE = false>
 __global__ __launch_bounds__(512, 1) void query_wide_kernel(const float* __restrict__ X0, const int64_t* __restrict__ g0,
                                                             const float* __restrict__ X1, const int64_t* __restrict__ g1,
                                                             const uint8_t* __restrict__ sel, const float* __restrict__ rowdiv,
@@ -399,13 +407,27 @@ __global__ __launch_bounds__(512, 1) void query_wide_kernel(const float* __restr
                     const int cpr = c >> 3;
                     for (int e = pl; e < QW_TP * cpr; e += NPL) {
                         const int pt = e / cpr, ch = e - pt * cpr;
-                        if (row0 + pt < n)
-                            *reinterpret_cast<uint4*>(scores + (row0 + pt) * c + 8 * ch) = *reinterpret_cast<const uint4*>(src + pt * LS + 8 * ch);
+                        if (row0 + pt < n) {
+                            if constexpr (VOTE) {
+                                typedef _Float16 h8v __attribute__((ext_vector_type(8)));
+                                uint4* dst = reinterpret_cast<uint4*>(scores + (row0 + pt) * c + 8 * ch);
+                                h8v acc = __builtin_bit_cast(h8v, *dst);
+                                const h8v add = __builtin_bit_cast(h8v, *reinterpret_cast<const uint4*>(src + pt * LS + 8 * ch));
+#pragma unroll
+                                for (int k = 0; k < 8; ++k) acc[k] = (_Float16)((float)acc[k] + (float)add[k]);
+                                *dst = __builtin_bit_cast(uint4, acc);
+                            } else {
+                                *reinterpret_cast<uint4*>(scores + (row0 + pt) * c + 8 * ch) = *reinterpret_cast<const uint4*>(src + pt * LS + 8 * ch);
+                            }
+                        }
                     }
                 } else {
                     for (int e = pl; e < QW_TP * c; e += NPL) {
                         const int pt = e / c, col = e - pt * c;
-                        if (row0 + pt < n) scores[(row0 + pt) * c + col] = src[pt * LS + col];
+                        if (row0 + pt < n) {
+                            if constexpr (VOTE) vote_add(scores[(row0 + pt) * c + col], src[pt * LS + col]);
+                            else scores[(row0 + pt) * c + col] = src[pt * LS + col];
+                        }
                     }
                 }
             }
@@ -507,6 +529,8 @@ __global__ __launch_bounds__(256) void rows_argmax_kernel(const float* __restric
     if (lane == 0) labels[p] = bi == 0x7fffffff ? 0 : bi;
 }
 
+// VOTE: `scores` is the vote matrix the fp16 scores are added into (query_kernel / query_wide_kernel)
+template <bool VOTE>
 static int launch_query(hipStream_t st, const float* X0, const int64_t* g0, const float* X1, const int64_t* g1,
                         const uint8_t* sel, const float* rowdiv, const _Float16* T, _Float16* scores, int64_t* argmax,
                         float* rowmax, int64_t n, int d, int c) {
@@ -532,7 +556,7 @@ static int launch_query(hipStream_t st, const float* X0, const int64_t* g0, cons
         const bool dev_slot_ok = dev_id >= 0 && dev_id < 64;
 #define OSN_QW(D_, W_)                                                                                                      \
     do {                                                                                                                   \
-        auto kern = query_wide_kernel<D_, W_>;                                                                             \
+        auto kern = query_wide_kernel<D_, W_, VOTE>;                                                                             \
         static std::atomic<signed char> attr_state[64];          /* 0 unknown, 1 set, -1 refused */                        \
         signed char stt = dev_slot_ok ? attr_state[dev_id].load(std::memory_order_relaxed) : 0;                            \
         if (stt == 0) {                                                                                                    \
@@ -561,7 +585,7 @@ static int launch_query(hipStream_t st, const float* X0, const int64_t* g0, cons
     }
     const dim3 grid(cdiv(n, Q_BM)), block(256);
     const int ct = int(cdiv(c, 32));
-#define OSN_Q(CT, NB, WG) hipLaunchKernelGGL((query_kernel<CT, NB, WG>), grid, block, 0, st, X0, g0, X1, g1, sel, rowdiv, T, scores, argmax, rowmax, n, d, c)
+#define OSN_Q(CT, NB, WG) hipLaunchKernelGGL((query_kernel<CT, NB, WG, VOTE>), grid, block, 0, st, X0, g0, X1, g1, sel, rowdiv, T, scores, argmax, rowmax, n, d, c)
     // one chunk in flight per thread; three workgroups per CU where the registers allow it (<= 64 labels).  Measured
     // alternatives (profiles/r02_s6_query_variants.txt): deeper register pipelines (2-4 chunks, also with one 512-register
     // workgroup per CU) and a column-split kernel with the text read straight from L2 are all slower.
@@ -586,8 +610,26 @@ extern "C" int osn_cosine_query(const float* X, const int64_t* gather, const voi
     if (n == 0) return OSN_OK;
     OSN_REQUIRE(X && text_f16 && (argmax || scores_f16), OSN_E_ARG, "osn_cosine_query: null pointer");
     OSN_REQUIRE(aligned16(X) && aligned16(text_f16), OSN_E_ARG, "osn_cosine_query: X and text must be 16-byte aligned");
-    return launch_query(st, X, gather, nullptr, nullptr, nullptr, nullptr, static_cast<const _Float16*>(text_f16),
-                        static_cast<_Float16*>(scores_f16), argmax, nullptr, n, d, c);
+    return launch_query<false>(st, X, gather, nullptr, nullptr, nullptr, nullptr, static_cast<const _Float16*>(text_f16),
+                               static_cast<_Float16*>(scores_f16), argmax, nullptr, n, d, c);
+}
+
+// the vote matrix takes 16-byte accesses when a row is a whole number of them (c % 8 == 0), 2-byte ones otherwise
+static bool votes_aligned(const void* votes, int c) {
+    return (c & 7) == 0 ? aligned16(votes) : (reinterpret_cast<uintptr_t>(votes) & 1u) == 0;
+}
+
+extern "C" int osn_cosine_query_vote(const float* X, const int64_t* gather, const void* text_f16, void* votes_f16,
+                                     int64_t* argmax, int64_t n, int d, int c, osn_stream_t stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    OSN_REQUIRE(n >= 0 && d >= 8 && (d & 7) == 0 && c >= 1, OSN_E_ARG,
+                "osn_cosine_query_vote: need d %% 8 == 0 and c >= 1 (d=%d c=%d)", d, c);
+    if (n == 0) return OSN_OK;
+    OSN_REQUIRE(X && text_f16 && votes_f16, OSN_E_ARG, "osn_cosine_query_vote: null pointer");
+    OSN_REQUIRE(aligned16(X) && aligned16(text_f16) && votes_aligned(votes_f16, c), OSN_E_ARG,
+                "osn_cosine_query_vote: X and text must be 16-byte aligned, the votes too when c %% 8 == 0");
+    return launch_query<true>(st, X, gather, nullptr, nullptr, nullptr, nullptr, static_cast<const _Float16*>(text_f16),
+                              static_cast<_Float16*>(votes_f16), argmax, nullptr, n, d, c);
 }
 
 extern "C" int osn_rows_argmax(const float* scores, int64_t ld, int c, const int64_t* gather, int64_t n_pts, int64_t n_rows,
@@ -607,17 +649,11 @@ extern "C" size_t osn_query_ensemble_ws_bytes(int64_t n) {
     return 4 * align_up(m * 4, 256) + align_up(m, 256);
 }
 
-extern "C" int osn_query_ensemble(const float* X_distill, const int64_t* gather_distill, const float* X_fusion,
-                                  const int64_t* gather_fusion, const void* text_f16, void* scores_f16,
-                                  int64_t* argmax, uint8_t* sel_out, int64_t n, int d, int c, void* ws, size_t ws_bytes,
-                                  osn_stream_t stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    OSN_REQUIRE(n >= 0 && d >= 8 && (d & 7) == 0 && c >= 1, OSN_E_ARG, "osn_query_ensemble: need d %% 8 == 0 and c >= 1");
-    if (n == 0) return OSN_OK;
-    OSN_REQUIRE(X_distill && X_fusion && text_f16 && (argmax || scores_f16), OSN_E_ARG, "osn_query_ensemble: null pointer");
-    OSN_REQUIRE(aligned16(X_distill) && aligned16(X_fusion) && aligned16(text_f16), OSN_E_ARG,
-                "osn_query_ensemble: feature and text pointers must be 16-byte aligned");
-    OSN_REQUIRE(ws && ws_bytes >= osn_query_ensemble_ws_bytes(n), OSN_E_WS, "osn_query_ensemble: workspace too small");
+// the three queries of the ensemble; the last one stores (or, VOTE, adds) the scores of the selected source
+template <bool VOTE>
+static int query_ensemble(hipStream_t st, const float* X_distill, const int64_t* gather_distill, const float* X_fusion,
+                          const int64_t* gather_fusion, const void* text_f16, void* scores_f16, int64_t* argmax,
+                          uint8_t* sel_out, int64_t n, int d, int c, void* ws, size_t ws_bytes) {
     char* p = static_cast<char*>(ws);
     const size_t fsz = align_up(size_t(n) * 4, 256);
     float* den_d = reinterpret_cast<float*>(p);
@@ -630,12 +666,42 @@ extern "C" int osn_query_ensemble(const float* X_distill, const int64_t* gather_
     hipLaunchKernelGGL(row_norm_kernel, ngrid, block, 0, st, X_distill, gather_distill, n, d, 1e-5f, den_d);
     hipLaunchKernelGGL(row_norm_kernel, ngrid, block, 0, st, X_fusion, gather_fusion, n, d, 1e-5f, den_f);
     OSN_LAUNCH_CHECK();
-    int rc = launch_query(st, X_distill, gather_distill, nullptr, nullptr, nullptr, den_d, T, nullptr, nullptr, max_d, n, d, c);
+    int rc = launch_query<false>(st, X_distill, gather_distill, nullptr, nullptr, nullptr, den_d, T, nullptr, nullptr, max_d, n, d, c);
     if (rc) return rc;
-    rc = launch_query(st, X_fusion, gather_fusion, nullptr, nullptr, nullptr, den_f, T, nullptr, nullptr, max_f, n, d, c);
+    rc = launch_query<false>(st, X_fusion, gather_fusion, nullptr, nullptr, nullptr, den_f, T, nullptr, nullptr, max_f, n, d, c);
     if (rc) return rc;
     hipLaunchKernelGGL(ensemble_select_kernel, dim3(cdiv(n, 256)), block, 0, st, max_d, max_f, n, sel);
     OSN_LAUNCH_CHECK();
-    return launch_query(st, X_distill, gather_distill, X_fusion, gather_fusion, sel, nullptr, T,
-                        static_cast<_Float16*>(scores_f16), argmax, nullptr, n, d, c);
+    return launch_query<VOTE>(st, X_distill, gather_distill, X_fusion, gather_fusion, sel, nullptr, T,
+                              static_cast<_Float16*>(scores_f16), argmax, nullptr, n, d, c);
+}
+
+extern "C" int osn_query_ensemble(const float* X_distill, const int64_t* gather_distill, const float* X_fusion,
+                                  const int64_t* gather_fusion, const void* text_f16, void* scores_f16,
+                                  int64_t* argmax, uint8_t* sel_out, int64_t n, int d, int c, void* ws, size_t ws_bytes,
+                                  osn_stream_t stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    OSN_REQUIRE(n >= 0 && d >= 8 && (d & 7) == 0 && c >= 1, OSN_E_ARG, "osn_query_ensemble: need d %% 8 == 0 and c >= 1");
+    if (n == 0) return OSN_OK;
+    OSN_REQUIRE(X_distill && X_fusion && text_f16 && (argmax || scores_f16), OSN_E_ARG, "osn_query_ensemble: null pointer");
+    OSN_REQUIRE(aligned16(X_distill) && aligned16(X_fusion) && aligned16(text_f16), OSN_E_ARG,
+                "osn_query_ensemble: feature and text pointers must be 16-byte aligned");
+    OSN_REQUIRE(ws && ws_bytes >= osn_query_ensemble_ws_bytes(n), OSN_E_WS, "osn_query_ensemble: workspace too small");
+    return query_ensemble<false>(st, X_distill, gather_distill, X_fusion, gather_fusion, text_f16, scores_f16, argmax, sel_out,
+                                 n, d, c, ws, ws_bytes);
+}
+
+extern "C" int osn_query_ensemble_vote(const float* X_distill, const int64_t* gather_distill, const float* X_fusion,
+                                       const int64_t* gather_fusion, const void* text_f16, void* votes_f16,
+                                       int64_t* argmax, uint8_t* sel_out, int64_t n, int d, int c, void* ws, size_t ws_bytes,
+                                       osn_stream_t stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    OSN_REQUIRE(n >= 0 && d >= 8 && (d & 7) == 0 && c >= 1, OSN_E_ARG, "osn_query_ensemble_vote: need d %% 8 == 0 and c >= 1");
+    if (n == 0) return OSN_OK;
+    OSN_REQUIRE(X_distill && X_fusion && text_f16 && votes_f16, OSN_E_ARG, "osn_query_ensemble_vote: null pointer");
+    OSN_REQUIRE(aligned16(X_distill) && aligned16(X_fusion) && aligned16(text_f16) && votes_aligned(votes_f16, c), OSN_E_ARG,
+                "osn_query_ensemble_vote: feature and text pointers must be 16-byte aligned, the votes too when c %% 8 == 0");
+    OSN_REQUIRE(ws && ws_bytes >= osn_query_ensemble_ws_bytes(n), OSN_E_WS, "osn_query_ensemble_vote: workspace too small");
+    return query_ensemble<true>(st, X_distill, gather_distill, X_fusion, gather_fusion, text_f16, votes_f16, argmax, sel_out,
+                                n, d, c, ws, ws_bytes);
 }

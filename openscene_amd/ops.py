@@ -1214,6 +1214,123 @@ def query_ensemble(feat_distill, feat_fusion, text_half, gather_distill=None, ga
     return scores, amax, sel.bool()
 
 
+def _vote_matrix(votes, n, c, dev):
+    if (votes.dtype != torch.float16 or votes.dim() != 2 or tuple(votes.shape) != (n, c) or votes.device != dev
+            or not votes.is_contiguous()):
+        raise ValueError("votes must be a contiguous float16 [%d, %d] matrix on the features' device" % (n, c))
+    if votes.data_ptr() % (16 if c % 8 == 0 else 2):
+        raise ValueError("votes must start 16-byte aligned when the label count is a multiple of 8")
+
+
+def cosine_query_vote(feats, text_half, votes, gather=None, want_labels=False):
+    """votes [n, C] (fp16, in place) += feats[gather].half() @ text.t() with torch's CPU half rounding (fp32 add, one
+    rounding): run/evaluate.py:397,416 `store = pred + store` fused into the query.  -> argmax int64 [n] of this call's
+    scores, or None."""
+    dev = feats.device
+    lib = _prep(dev)
+    feats = _query_feats(feats, "features")
+    if text_half.dtype != torch.float16:
+        raise TypeError("text features must be float16 (util/util.py:41-44 produces fp16)")
+    text_half = text_half.contiguous()
+    c, d = text_half.shape
+    if feats.shape[1] != d:
+        raise ValueError("feature dim %d != text dim %d" % (feats.shape[1], d))
+    if gather is not None:
+        gather = (gather if gather.dtype == torch.int64 else gather.long()).contiguous()
+    n = gather.shape[0] if gather is not None else feats.shape[0]
+    _vote_matrix(votes, n, c, dev)
+    amax = torch.empty(n, dtype=torch.int64, device=dev) if want_labels else None
+    with _Dev(dev):
+        check(lib.osn_cosine_query_vote(_p(feats), _p(gather), _p(text_half), _p(votes), _p(amax), n, d, c, _stream(dev)),
+              "osn_cosine_query_vote")
+    return amax
+
+
+def query_ensemble_vote(feat_distill, feat_fusion, text_half, votes, gather_distill=None, gather_fusion=None, want_labels=False):
+    """query_ensemble with the vote epilogue: votes [n, C] += the selected source's fp16 scores.  -> (argmax or None,
+    used_fusion bool [n])."""
+    dev = feat_distill.device
+    lib = _prep(dev)
+    fd = _query_feats(feat_distill, "distill features")
+    ff = _query_feats(feat_fusion, "fusion features")
+    if text_half.dtype != torch.float16:
+        raise TypeError("text features must be float16 (util/util.py:41-44 produces fp16)")
+    text_half = text_half.contiguous()
+    c, d = text_half.shape
+
+    def _g(g):
+        if g is None:
+            return None
+        return (g if g.dtype == torch.int64 else g.long()).contiguous()
+
+    gd, gf = _g(gather_distill), _g(gather_fusion)
+    n = gd.shape[0] if gd is not None else fd.shape[0]
+    nf = gf.shape[0] if gf is not None else ff.shape[0]
+    if n != nf:
+        raise ValueError("the two feature sources address %d vs %d points" % (n, nf))
+    _vote_matrix(votes, n, c, dev)
+    amax = torch.empty(n, dtype=torch.int64, device=dev) if want_labels else None
+    sel = torch.empty(n, dtype=torch.uint8, device=dev)
+    ws = _ws(lib.osn_query_ensemble_ws_bytes(n), dev)
+    with _Dev(dev):
+        check(lib.osn_query_ensemble_vote(_p(fd), _p(gd), _p(ff), _p(gf), _p(text_half), _p(votes), _p(amax), _p(sel), n,
+                                          d, c, _p(ws), ws.numel(), _stream(dev)), "osn_query_ensemble_vote")
+    return amax, sel.bool()
+
+
+def eval_confusion(labels, confusion, err, votes=None, ids=None, mapper=None, has_feature=None, hist=-1):
+    """confusion int64 [C + 1, C] += the counts of (prediction, gt) over the points whose gt is not 255: prediction =
+    Tensor.max(1)[1] of the fp16 `votes` [n, c_in] (or the int64 `ids` [n]), then mapper[prediction], then 256 where
+    has_feature is False; row C counts the no-feature points.  `err` (int32 [1], device) collects bad mapper ids, gt and
+    predictions without a synchronisation; eval_check raises on them.  hist: -1 auto (LDS up to 90 classes), 1 LDS histogram
+    (up to 160 classes), 0 global atomics."""
+    dev = labels.device
+    lib = _prep(dev)
+    if (votes is None) == (ids is None):
+        raise ValueError("give exactly one of votes and ids")
+    if labels.dtype != torch.int64 or labels.dim() != 1:
+        raise ValueError("labels must be an int64 vector")
+    labels = labels.contiguous()
+    n = labels.shape[0]
+    c_in = 0
+    if votes is not None:
+        if votes.dtype != torch.float16 or votes.dim() != 2 or votes.shape[0] != n or votes.device != dev:
+            raise ValueError("votes must be a float16 [%d, c] matrix on the labels' device" % n)
+        votes = votes.contiguous()
+        c_in = votes.shape[1]
+    else:
+        if ids.dtype != torch.int64 or tuple(ids.shape) != (n,) or ids.device != dev:
+            raise ValueError("ids must be an int64 vector of %d entries on the labels' device" % n)
+        ids = ids.contiguous()
+    n_map = 0
+    if mapper is not None:
+        if mapper.dtype != torch.int64 or mapper.dim() != 1 or mapper.device != dev:
+            raise ValueError("mapper must be an int64 vector on the labels' device")
+        mapper = mapper.contiguous()
+        n_map = mapper.shape[0]
+    if has_feature is not None:
+        if has_feature.dim() != 1 or has_feature.shape[0] != n or has_feature.device != dev:
+            raise ValueError("has_feature must be a vector of %d entries on the labels' device" % n)
+        has_feature = has_feature.to(torch.uint8).contiguous()
+    if (confusion.dtype != torch.int64 or confusion.dim() != 2 or confusion.shape[0] != confusion.shape[1] + 1
+            or confusion.device != dev or not confusion.is_contiguous()):
+        raise ValueError("confusion must be a contiguous int64 [C + 1, C] matrix on the labels' device")
+    if err.dtype != torch.int32 or err.numel() != 1 or err.device != dev:
+        raise ValueError("err must be an int32 [1] tensor on the labels' device")
+    with _Dev(dev):
+        check(lib.osn_eval_confusion(_p(votes), _p(ids), n, c_in, _p(labels), _p(mapper), n_map, _p(has_feature),
+                                     confusion.shape[1], _p(confusion), _p(err), int(hist), _stream(dev)), "osn_eval_confusion")
+    return confusion
+
+
+def eval_check(err):
+    """Raise on what eval_confusion recorded in `err` (synchronises)."""
+    dev = err.device
+    lib = _prep(dev)
+    with _Dev(dev):
+        check(lib.osn_eval_check(_p(err), _stream(dev)), "osn_eval_check")
+
+
 # ------------------------------------------------------------------- voxelizer
 def voxelize_fnv(xyz, T):
     """xyz float64 [N,3] (device), T 4x4 float64 (host, numpy or tensor) ->
