@@ -542,6 +542,41 @@ int osn_eval_confusion(const void* votes_f16, const int64_t* ids, int64_t n, int
                        int64_t* confusion, int32_t* err, int hist, osn_stream_t stream);
 int osn_eval_check(const int32_t* err, osn_stream_t stream);
 
+/* ---- text search over a bank of scenes (csrc/search.hip) -------------------------------------------------------- *
+ * The second half of the open-vocabulary query (README "Applications": scene exploration, rare object search in a 3D
+ * scene database): heat-maps for arbitrary queries and the k best points of every scene, over a bank of per-point fp16
+ * features -- the rows run/evaluate.py:232-235,328-330 saves as <scene>_openscene_feat_<feature_type>.npy.
+ *
+ * The append: bank_f16[row0 + i, :] = fp16_rne(X[gather ? gather[i] : i, :]) for i < n -- X[inds_reverse].half() of
+ * run/evaluate.py:290 without the float32 [n, d] intermediate.  X float32 [n_rows, d]; gather (nullable) int64 [n];
+ * d % 8 == 0.  A gather entry outside [0, n_rows) reads and writes nothing for that row and ORs bit 1 into the device
+ * word err (int32 [1]).
+ * The check synchronises and turns the bits of err into OSN_E_ARG: 1 a bad gather index, 2 scene offsets that do
+ * not start at 0, ascend and end within the bank, 4 a scene longer than max_scene_rows.
+ *
+ * The search: bank fp16 [n, d]; scene_offsets int64 [n_scenes + 1] (device), ascending from 0, empty scenes allowed;
+ *   max_scene_rows >= the longest scene (sizes the grid); queries fp16 [q, d], L2-normalised by the caller
+ *   (util/util.py:41-44); 1 <= q <= 1024; 1 <= k <= 128; thresholds (nullable) float32 [q].
+ *   score(p, j) with h = the stored fp16 row p, hf = h.float():
+ *     normalize = 1   run/evaluate.py:305,310  (hf / (hf.norm(dim=-1, keepdim=True) + 1e-5)).half() @ t.t()
+ *     normalize = 0   run/evaluate.py:291      h @ t.t()
+ *   fp16 MFMA, fp32 accumulate, one rounding to fp16; with normalize the fp32 accumulator is divided by (norm + 1e-5),
+ *   the norm taken from the same chunks that feed the MFMA (the bank is read once) -- within 2^-11 of rounding the
+ *   normalised vector first, for unit-norm queries.
+ *   heat (nullable) fp16 [n, q]; topk_scores fp16 [n_scenes, q, k]; topk_points int64 [n_scenes, q, k] = the row inside
+ *   its scene, ordered by higher score, then lower row; NaN orders below every number (and is stored as NaN in heat);
+ *   a scene with fewer than k points pads with (-inf, -1).  counts (nullable, needs thresholds) int64 [n_scenes, q] =
+ *   the scene's points with score >= thresholds[j].  n_scenes = 0 writes the heat-map only.  Integer atomics only:
+ *   bitwise repeatable.  Offsets are clamped before use (nothing is read out of bounds) and reported through err. */
+int osn_bank_append(const float* X, int64_t n_rows, const int64_t* gather, int64_t n, int d, void* bank_f16,
+                    int64_t row0, int32_t* err, osn_stream_t stream);
+int osn_bank_check(const int32_t* err, osn_stream_t stream);
+size_t osn_bank_search_ws_bytes(int64_t n, int n_scenes, int q, int k, int64_t max_scene_rows);
+int osn_bank_search(const void* bank_f16, int64_t n, int d, const int64_t* scene_offsets, int n_scenes,
+                    int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
+                    const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
+                    int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
+
 /* ---- hash voxelisation --------------------------------------------------- *
  * Replaces Voxelizer.voxelize (dataset/voxelizer.py:117-129) +
  * sparse_quantize / fnv_hash_vec (dataset/voxelization_utils.py:9-22,112-132):

@@ -1,0 +1,585 @@
+// Text search over a bank of scenes on gfx950: per-point heat-maps for arbitrary queries and the k best points of every
+// scene, for a bank of per-point fp16 features (the files run/evaluate.py:232-235,328-330 writes).
+//
+//   osn_bank_append   bank[row0 + i] = X[gather[i]].half()            (run/evaluate.py:290, the rows the query reads)
+//   osn_bank_search   score(p, q) = run/evaluate.py:305,310 (normalize) or :291 (raw) on the stored fp16 row,
+//                     heat [N, Q], and per (scene, query) the k best points / the points over a threshold.
+//
+// Pass 1 (heat_kernel) is the streaming pass: 128 bank rows per workgroup, fp16 rows go HBM -> registers -> LDS with no
+// conversion, v_mfma_f32_32x32x16_f16 against the query chunk, fp32 accumulate.  The sum of squares of a row is taken
+// from the very chunks that feed the MFMA (the bank is read once), the accumulator is divided by (norm + 1e-5) in fp32
+// and rounded to fp16 once.  The scores leave through an LDS tile twice: row-major into the caller's `heat` (optional)
+// and column-major into the workspace (`heatT` [Q][ldT]): a (scene, query) pair is then one contiguous fp16 array.
+//
+// Pass 2 selects on heatT with integer arithmetic only.  The fp16 score becomes a monotone 16-bit key (NaN -> 0, below
+// -inf; -0 -> +0).  A two-round 8-bit radix select over per-(scene, query) 256-bin histograms (LDS per workgroup, integer
+// atomics into the global one) finds the k-th key K exactly.  Everything above K is selected; of the points equal to K the
+// lowest indices are: per-chunk counts of key == K give every chunk its rank offset, a block scan orders the chunk's own.
+// A final rank-by-counting sort of the <= 128 candidates writes (score desc, index asc).  No floating-point atomics:
+// results are bitwise repeatable.
+#include "common.h"
+
+namespace osn {
+
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+typedef _Float16 half8 __attribute__((ext_vector_type(8)));
+typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+
+constexpr int S_BM = 128;          // bank rows per workgroup (4 waves x 32)
+constexpr int S_DK = 128;          // feature chunk (halfs): 256 bytes of a row, 32 KB per workgroup in flight
+constexpr int S_LD = S_DK + 8;     // padded LDS row (272 B: 16-byte aligned, conflict-free 16-byte reads)
+static_assert(S_LD >= S_BM + 8, "the score tile [column][row] reuses the row tile");
+
+constexpr int SEL_T = 256;         // threads of a select workgroup
+constexpr int SEL_IT = 2;          // 8 scores per thread and iteration
+constexpr int SEL_R = SEL_T * 8 * SEL_IT;   // rows of a chunk (4096)
+constexpr int SEL_ST = 16;         // uint32 words of per-(scene, query) select state
+constexpr uint32_t SEL_NONE = 0x10000u;     // K of an empty selection (above every key)
+enum { ST_KK = 0, ST_B1, ST_ABOVE, ST_K, ST_GT, ST_NEED_EQ, ST_EQ_TOTAL, ST_SLOT_GT, ST_SLOT_EQ };
+
+constexpr int BANK_E_GATHER = 1, BANK_E_OFFSETS = 2, BANK_E_LONG = 4;
+
+// ------------------------------------------------------------------------------------------------------ append
+__global__ __launch_bounds__(256) void bank_append_kernel(const float* __restrict__ X, int64_t n_rows, const int64_t* __restrict__ g,
+                                                          int64_t n, int d4, _Float16* __restrict__ out, int32_t* __restrict__ err) {
+    const int64_t total = n * d4;
+    for (int64_t e = int64_t(blockIdx.x) * 256 + threadIdx.x; e < total; e += int64_t(gridDim.x) * 256) {
+        const int64_t p = e / d4;
+        const int c = int(e - p * d4);
+        const int64_t r = g ? g[p] : p;
+        if (r < 0 || r >= n_rows) {                          // nothing is read or written for this row
+            if (c == 0) atomicOr(err, BANK_E_GATHER);
+            continue;
+        }
+        const float4 v = *reinterpret_cast<const float4*>(X + (r * d4 + c) * 4);
+        half4 h;
+        h[0] = (_Float16)v.x; h[1] = (_Float16)v.y; h[2] = (_Float16)v.z; h[3] = (_Float16)v.w;
+        *reinterpret_cast<half4*>(out + (p * d4 + c) * 4) = h;
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------ pass 1
+template <int CT, int WGS>
+__global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restrict__ B, const _Float16* __restrict__ T,
+                                                        _Float16* __restrict__ heat, _Float16* __restrict__ heatT, int64_t ldT,
+                                                        int64_t n, int d, int q, int normalize) {
+    __shared__ __attribute__((aligned(16))) _Float16 Xs[S_BM][S_LD];
+    __shared__ __attribute__((aligned(16))) _Float16 Ts[CT * 32][S_LD];
+    __shared__ float rden[S_BM];
+    _Float16(*Sc)[S_LD] = Xs;                               // score tile [column][row] once the MFMAs are done (CT * 32 <= 128 rows of it)
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t row0 = int64_t(blockIdx.x) * S_BM;
+    const int xq = tid & 15, xr = tid >> 4;                 // 16 lanes x 16 bytes = one row's 256-byte chunk; 16 rows per sweep
+    float ss[S_BM / 16];
+#pragma unroll
+    for (int ps = 0; ps < S_BM / 16; ++ps) ss[ps] = 0.f;
+
+    for (int cg0 = 0; cg0 < q; cg0 += 32 * CT) {
+        const bool sumsq = normalize && cg0 == 0;
+        f32x16 acc[CT];
+#pragma unroll
+        for (int t = 0; t < CT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+        // one chunk in flight in registers while the MFMAs of the previous one run from LDS; all loads unconditional from
+        // clamped addresses (query.hip: a conditional fetch makes the compiler drain the memory counter before every stash)
+        uint4 px[S_BM / 16];
+        uint4 pt[2 * CT];
+        auto fetch = [&](int d0) {
+#pragma unroll
+            for (int j = 0; j < 2 * CT; ++j) {
+                const int f = tid + 256 * j;
+                const int trow = f >> 4, ch = f & 15;
+                const int col = cg0 + trow;
+                const bool ok = col < q && d0 + ch * 8 < d;
+                pt[j] = *reinterpret_cast<const uint4*>(ok ? T + int64_t(col) * d + d0 + ch * 8 : T);
+            }
+#pragma unroll
+            for (int ps = 0; ps < S_BM / 16; ++ps) {
+                const int64_t row = row0 + ps * 16 + xr;
+                const bool ok = row < n && d0 + xq * 8 < d;
+                px[ps] = *reinterpret_cast<const uint4*>(ok ? B + row * d + d0 + xq * 8 : B);
+            }
+        };
+        auto stash = [&](int d0) {
+#pragma unroll
+            for (int ps = 0; ps < S_BM / 16; ++ps) {
+                const int row = ps * 16 + xr;
+                const bool ok = row0 + row < n && d0 + xq * 8 < d;
+                uint4 v = px[ps];
+                if (!ok) v = make_uint4(0, 0, 0, 0);
+                if (sumsq) {
+                    const half8 h = __builtin_bit_cast(half8, v);
+                    float s = 0.f;
+#pragma unroll
+                    for (int k = 0; k < 8; ++k) s += (float)h[k] * (float)h[k];
+                    ss[ps] += s;
+                }
+                *reinterpret_cast<uint4*>(&Xs[row][xq * 8]) = v;
+            }
+#pragma unroll
+            for (int j = 0; j < 2 * CT; ++j) {
+                const int f = tid + 256 * j;
+                const int trow = f >> 4, ch = f & 15;
+                const bool ok = cg0 + trow < q && d0 + ch * 8 < d;
+                uint4 v = pt[j];
+                if (!ok) v = make_uint4(0, 0, 0, 0);
+                *reinterpret_cast<uint4*>(&Ts[trow][ch * 8]) = v;
+            }
+        };
+        // fragments of k-step ks + 1 are read from LDS while the MFMAs of k-step ks run (two register sets, as query.hip)
+        auto mfmas = [&]() {
+            const int arow = wave * 32 + (lane & 31);
+            const int kh = 8 * (lane >> 5);
+            half8 fa[2], fb[2][CT];
+            auto frags = [&](int ks, int w) {
+                fa[w] = *reinterpret_cast<const half8*>(&Xs[arow][ks * 16 + kh]);
+#pragma unroll
+                for (int t = 0; t < CT; ++t)
+                    fb[w][t] = *reinterpret_cast<const half8*>(&Ts[t * 32 + (lane & 31)][ks * 16 + kh]);
+            };
+            frags(0, 0);
+#pragma unroll
+            for (int ks = 0; ks < S_DK / 16; ++ks) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (ks + 1 < S_DK / 16) frags(ks + 1, (ks + 1) & 1);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int t = 0; t < CT; ++t)
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks & 1], fb[ks & 1][t], acc[t], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        fetch(0);
+        stash(0);
+        __syncthreads();
+        for (int d0 = 0; d0 < d; d0 += S_DK) {
+            __builtin_amdgcn_sched_barrier(0);
+            fetch(d0 + S_DK);                               // (past the end: the first 16 bytes of B / T, never staged)
+            __builtin_amdgcn_sched_barrier(0);
+            mfmas();
+            __syncthreads();
+            if (d0 + S_DK < d) stash(d0 + S_DK);
+            __syncthreads();
+        }
+        if (sumsq) {                                        // the 16 lanes that share a row: ||h|| + 1e-5 (run/evaluate.py:305)
+#pragma unroll
+            for (int ps = 0; ps < S_BM / 16; ++ps) {
+                float s = ss[ps];
+#pragma unroll
+                for (int m = 1; m < 16; m <<= 1) s += __shfl_xor(s, m, 64);
+                if (xq == 0) rden[ps * 16 + xr] = sqrtf(s) + 1e-5f;
+            }
+            __syncthreads();
+        }
+        // ---- epilogue: divide the fp32 accumulator, round to fp16 once, tile -> LDS [column][row]
+#pragma unroll
+        for (int t = 0; t < CT; ++t) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int lrow = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                float v = acc[t][r];
+                if (normalize) v /= rden[lrow];
+                Sc[t * 32 + (lane & 31)][lrow] = (_Float16)v;
+            }
+        }
+        __syncthreads();
+        for (int e = tid; e < CT * 32 * (S_BM / 8); e += 256) {       // column-major: 16-byte pieces of a column's 128 rows
+            const int col = e >> 4, v8 = e & 15;
+            const int gc = cg0 + col;
+            if (gc >= q) continue;
+            const int64_t r = row0 + 8 * v8;
+            _Float16* dst = heatT + int64_t(gc) * ldT + r;
+            if (r + 8 <= n) {
+                *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(&Sc[col][8 * v8]);
+            } else {
+                for (int j = 0; j < 8; ++j)
+                    if (r + j < n) dst[j] = Sc[col][8 * v8 + j];
+            }
+        }
+        if (heat) {
+            const int qn = (q - cg0) < 32 * CT ? (q - cg0) : 32 * CT;
+            for (int e = tid; e < S_BM * qn; e += 256) {
+                const int r = e / qn, c = e - r * qn;
+                if (row0 + r < n) heat[(row0 + r) * q + cg0 + c] = Sc[c][r];
+            }
+        }
+        __syncthreads();                                    // the tile is the next column group's row buffer
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------ pass 2
+// monotone key of an fp16 score: NaN -> 0 (below -inf = 0x03FF), -0 -> +0 (equal values tie on the index, as a sort does)
+__device__ inline uint32_t sel_key(uint16_t hb) {
+    if ((hb & 0x7FFFu) > 0x7C00u) return 0u;
+    if (hb == 0x8000u) hb = 0;
+    return (hb & 0x8000u) ? (~uint32_t(hb) & 0xFFFFu) : (uint32_t(hb) | 0x8000u);
+}
+
+// element j of eight packed halfs, as bits (taken with shifts: a bit cast of a vector ELEMENT read element 0 for every j)
+__device__ inline uint16_t half_bits(const uint4& v, int j) {
+    const uint32_t w = j < 2 ? v.x : j < 4 ? v.y : j < 6 ? v.z : v.w;
+    return uint16_t(w >> (16 * (j & 1)));
+}
+
+// rows of a scene, clamped so that nothing is read out of bounds whatever the offsets hold (search_check_kernel reports them)
+struct SceneRange {
+    int64_t o_s, o_e;      // global rows [o_s, o_e)
+    int64_t g0, g1;        // this chunk's 8-aligned global rows [g0, g1)
+};
+__device__ inline SceneRange scene_range(const int64_t* __restrict__ off, int s, int64_t n, int64_t max_rows, int chunk) {
+    SceneRange r;
+    int64_t a = off[s], b = off[s + 1];
+    a = a < 0 ? 0 : (a > n ? n : a);
+    b = b < a ? a : (b > n ? n : b);
+    if (b - a > max_rows) b = a + max_rows;
+    r.o_s = a;
+    r.o_e = b;
+    const int64_t end8 = (b + 7) & ~int64_t(7);
+    r.g0 = (a & ~int64_t(7)) + int64_t(chunk) * SEL_R;
+    r.g1 = r.g0 + SEL_R < end8 ? r.g0 + SEL_R : end8;
+    return r;
+}
+
+__global__ void search_check_kernel(const int64_t* __restrict__ off, int S, int64_t n, int64_t max_rows, int32_t* __restrict__ err) {
+    const int s = blockIdx.x * blockDim.x + threadIdx.x;
+    if (s >= S) return;
+    const int64_t a = off[s], b = off[s + 1];
+    int e = 0;
+    if (a < 0 || b < a || b > n || (s == 0 && a != 0)) e |= BANK_E_OFFSETS;
+    else if (b - a > max_rows) e |= BANK_E_LONG;
+    if (e) atomicOr(err, e);
+}
+
+__device__ inline uint32_t block_sum(uint32_t v, uint32_t* sh4) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    __syncthreads();
+    if ((threadIdx.x & 63) == 0) sh4[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sh4[0] + sh4[1] + sh4[2] + sh4[3];
+}
+
+// PASS 0: histogram of the key's high byte (and the threshold count); PASS 1: of the low byte among keys whose high byte is b1;
+// PASS 2: the chunk's number of keys == K (only where the ties have to be ordered)
+template <int PASS>
+__global__ __launch_bounds__(SEL_T) void select_hist_kernel(const _Float16* __restrict__ heatT, int64_t ldT, const int64_t* __restrict__ off,
+                                                            int64_t n, int64_t max_rows, int Q, int max_chunks,
+                                                            const float* __restrict__ thr, unsigned long long* __restrict__ counts,
+                                                            uint32_t* __restrict__ hist, uint32_t* __restrict__ state,
+                                                            uint32_t* __restrict__ chunk_eq) {
+    __shared__ uint32_t h[256];
+    __shared__ uint32_t sh4[4];
+    const int tid = threadIdx.x;
+    const int chunk = blockIdx.x, s = blockIdx.y, q = blockIdx.z;
+    const int64_t item = int64_t(s) * Q + q;
+    const uint32_t* st = state + item * SEL_ST;
+    uint32_t want = 0;
+    if (PASS == 1) {
+        if (st[ST_K] == SEL_NONE) return;
+        want = st[ST_B1];
+    }
+    if (PASS == 2) {
+        if (st[ST_K] == SEL_NONE || st[ST_EQ_TOTAL] == st[ST_NEED_EQ]) return;
+        want = st[ST_K];
+    }
+    const SceneRange R = scene_range(off, s, n, max_rows, chunk);
+    if (PASS != 2) {
+        if (R.g0 >= R.g1) return;
+        h[tid] = 0;
+        __syncthreads();
+    }
+    const bool do_thr = PASS == 0 && thr != nullptr;
+    const float th = do_thr ? thr[q] : 0.f;
+    uint32_t cnt = 0;
+    const _Float16* col = heatT + int64_t(q) * ldT;
+    for (int it = 0; it < SEL_IT; ++it) {
+        const int64_t g = R.g0 + (int64_t(it) * SEL_T + tid) * 8;
+        if (g >= R.g1) continue;
+        const uint4 v = *reinterpret_cast<const uint4*>(col + g);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const int64_t gi = g + j;
+            if (gi < R.o_s || gi >= R.o_e) continue;
+            const uint16_t hb = half_bits(v, j);
+            const uint32_t key = sel_key(hb);
+            if (PASS == 0) {
+                atomicAdd(&h[key >> 8], 1u);
+                if (do_thr && (float)__builtin_bit_cast(_Float16, hb) >= th) ++cnt;
+            } else if (PASS == 1) {
+                if ((key >> 8) == want) atomicAdd(&h[key & 255u], 1u);
+            } else {
+                if (key == want) ++cnt;
+            }
+        }
+    }
+    if (PASS != 2) {
+        __syncthreads();
+        if (h[tid]) atomicAdd(&hist[item * 256 + tid], h[tid]);
+    }
+    if (do_thr || PASS == 2) {
+        const uint32_t tot = block_sum(cnt, sh4);
+        if (tid == 0) {
+            if (PASS == 2) chunk_eq[(int64_t(s) * max_chunks + chunk) * Q + q] = tot;
+            else if (tot) atomicAdd(&counts[item], (unsigned long long)tot);
+        }
+    }
+}
+
+// one workgroup per (scene, query): the bin in which the kk-th largest key lies; the bins are zeroed for the next round
+template <int PASS>
+__global__ __launch_bounds__(256) void select_pick_kernel(uint32_t* __restrict__ hist, uint32_t* __restrict__ state, int k) {
+    __shared__ uint32_t a[256];
+    const int tid = threadIdx.x;
+    const int64_t item = blockIdx.x;
+    uint32_t* st = state + item * SEL_ST;
+    if (PASS == 1 && st[ST_K] == SEL_NONE) return;
+    const uint32_t own = hist[item * 256 + tid];
+    hist[item * 256 + tid] = 0;
+    a[tid] = own;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {                     // suffix sums: a[t] = sum of the bins >= t
+        const uint32_t v = a[tid] + (tid + o < 256 ? a[tid + o] : 0u);
+        __syncthreads();
+        a[tid] = v;
+        __syncthreads();
+    }
+    const uint32_t total = a[0];
+    if (PASS == 0) {
+        const uint32_t kk = total < uint32_t(k) ? total : uint32_t(k);
+        if (tid < SEL_ST) st[tid] = 0;
+        __syncthreads();
+        if (tid == 0) { st[ST_KK] = kk; if (kk == 0) st[ST_K] = SEL_NONE; }
+        const uint32_t above = tid + 1 < 256 ? a[tid + 1] : 0u;
+        if (kk > 0 && above < kk && kk <= a[tid]) { st[ST_B1] = uint32_t(tid); st[ST_ABOVE] = above; }
+    } else {
+        const uint32_t kk2 = st[ST_KK] - st[ST_ABOVE];      // 1 <= kk2 <= count of bin b1 = total
+        const uint32_t above = tid + 1 < 256 ? a[tid + 1] : 0u;
+        if (above < kk2 && kk2 <= a[tid]) {
+            const uint32_t gt = st[ST_ABOVE] + above;
+            st[ST_K] = (st[ST_B1] << 8) | uint32_t(tid);
+            st[ST_GT] = gt;
+            st[ST_NEED_EQ] = st[ST_KK] - gt;
+            st[ST_EQ_TOTAL] = own;
+        }
+    }
+}
+
+// candidates: keys > K take the next free slot below count_gt (their order is settled by the final sort); keys == K take slot
+// count_gt + rank, rank = their place among the scene's equal keys in index order, as long as rank < need_eq
+__global__ __launch_bounds__(SEL_T) void select_collect_kernel(const _Float16* __restrict__ heatT, int64_t ldT, const int64_t* __restrict__ off,
+                                                               int64_t n, int64_t max_rows, int Q, int max_chunks, int k,
+                                                               uint32_t* __restrict__ state, const uint32_t* __restrict__ chunk_eq,
+                                                               uint2* __restrict__ cand) {
+    __shared__ uint32_t wsum[4];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int chunk = blockIdx.x, s = blockIdx.y, q = blockIdx.z;
+    const int64_t item = int64_t(s) * Q + q;
+    uint32_t* st = state + item * SEL_ST;
+    const uint32_t K = st[ST_K];
+    if (K == SEL_NONE) return;
+    const uint32_t count_gt = st[ST_GT], need_eq = st[ST_NEED_EQ];
+    const bool ordered = st[ST_EQ_TOTAL] != need_eq;
+    const SceneRange R = scene_range(off, s, n, max_rows, chunk);
+    if (R.g0 >= R.g1) return;
+    uint32_t run = 0;                                       // equal keys of the scene before this chunk / this sweep
+    if (ordered)
+        for (int c = 0; c < chunk; ++c) run += chunk_eq[(int64_t(s) * max_chunks + c) * Q + q];
+    uint2* out = cand + item * k;
+    const _Float16* col = heatT + int64_t(q) * ldT;
+    for (int it = 0; it < SEL_IT; ++it) {
+        const int64_t g = R.g0 + (int64_t(it) * SEL_T + tid) * 8;
+        uint32_t keys[8];
+        uint16_t bits[8];
+        uint32_t neq = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) { keys[j] = 0xFFFFFFFFu; bits[j] = 0; }
+        if (g < R.g1) {
+            const uint4 v = *reinterpret_cast<const uint4*>(col + g);
+#pragma unroll
+            for (int j = 0; j < 8; ++j) {
+                const int64_t gi = g + j;
+                bits[j] = half_bits(v, j);
+                const bool in = gi >= R.o_s && gi < R.o_e;
+                keys[j] = in ? sel_key(bits[j]) : 0xFFFFFFFFu;               // (outside the scene: neither > K nor == K below)
+                if (in && keys[j] > K) {
+                    const uint32_t slot = atomicAdd(&st[ST_SLOT_GT], 1u);
+                    if (slot < uint32_t(k)) out[slot] = make_uint2(bits[j], uint32_t(gi - R.o_s));
+                }
+                if (in && keys[j] == K) ++neq;
+            }
+        }
+        if (!ordered) {
+#pragma unroll
+            for (int j = 0; j < 8; ++j)
+                if (keys[j] == K) {
+                    const uint32_t slot = count_gt + atomicAdd(&st[ST_SLOT_EQ], 1u);
+                    if (slot < uint32_t(k)) out[slot] = make_uint2(bits[j], uint32_t(g + j - R.o_s));
+                }
+            continue;
+        }
+        if (run >= need_eq) continue;                       // (uniform over the workgroup; later sweeps still hold keys > K)
+        // exclusive scan of neq over the workgroup's threads (thread order = row order)
+        uint32_t inc = neq;
+#pragma unroll
+        for (int m = 1; m < 64; m <<= 1) {
+            const uint32_t o = __shfl_up(inc, m, 64);
+            if (lane >= m) inc += o;
+        }
+        __syncthreads();
+        if (lane == 63) wsum[wave] = inc;
+        __syncthreads();
+        uint32_t before = run;
+        for (int w = 0; w < wave; ++w) before += wsum[w];
+        uint32_t rank = before + inc - neq;
+#pragma unroll
+        for (int j = 0; j < 8; ++j)
+            if (keys[j] == K) {
+                if (rank < need_eq) out[count_gt + rank] = make_uint2(bits[j], uint32_t(g + j - R.o_s));
+                ++rank;
+            }
+        run += wsum[0] + wsum[1] + wsum[2] + wsum[3];
+    }
+}
+
+// one workgroup per (scene, query): rank the kk candidates by (key desc, index asc), pad with (-inf, -1)
+__global__ __launch_bounds__(128) void select_sort_kernel(const uint32_t* __restrict__ state, const uint2* __restrict__ cand, int k,
+                                                          _Float16* __restrict__ topk_scores, int64_t* __restrict__ topk_points) {
+    __shared__ uint32_t skey[128], sidx[128];
+    const int tid = threadIdx.x;
+    const int64_t item = blockIdx.x;
+    const uint32_t kk = state[item * SEL_ST + ST_KK];
+    uint2 c = make_uint2(0, 0);
+    if (uint32_t(tid) < kk) c = cand[item * k + tid];
+    const uint32_t key = sel_key(uint16_t(c.x));
+    skey[tid] = key;
+    sidx[tid] = c.y;
+    __syncthreads();
+    if (uint32_t(tid) < kk) {
+        uint32_t rank = 0;
+        for (uint32_t j = 0; j < kk; ++j) rank += (skey[j] > key || (skey[j] == key && sidx[j] < c.y)) ? 1u : 0u;
+        topk_scores[item * k + rank] = __builtin_bit_cast(_Float16, uint16_t(c.x));
+        topk_points[item * k + rank] = int64_t(c.y);
+    } else if (tid < k) {
+        topk_scores[item * k + tid] = __builtin_bit_cast(_Float16, uint16_t(0xFC00));
+        topk_points[item * k + tid] = -1;
+    }
+}
+
+static int sel_max_chunks(int64_t max_scene_rows) { return int(cdiv(max_scene_rows + 7, SEL_R)); }
+
+struct SearchWs {
+    size_t heatT, hist, state, chunk_eq, cand, total;
+    int64_t ldT;
+};
+static SearchWs search_ws(int64_t n, int S, int Q, int k, int64_t max_scene_rows) {
+    SearchWs w;
+    const size_t items = size_t(S > 0 ? S : 0) * size_t(Q > 0 ? Q : 1);
+    w.ldT = int64_t(align_up(size_t(n > 0 ? n : 1), 8));
+    size_t o = 0;
+    w.heatT = o; o += align_up(size_t(Q > 0 ? Q : 1) * size_t(w.ldT) * 2, 256);
+    w.hist = o; o += align_up(items * 256 * 4, 256);
+    w.state = o; o += align_up(items * SEL_ST * 4, 256);
+    w.chunk_eq = o; o += align_up(items * size_t(sel_max_chunks(max_scene_rows > 0 ? max_scene_rows : 0)) * 4, 256);
+    w.cand = o; o += align_up(items * size_t(k > 0 ? k : 1) * 8, 256);
+    w.total = o;
+    return w;
+}
+
+}  // namespace osn
+
+using namespace osn;
+
+extern "C" int osn_bank_append(const float* X, int64_t n_rows, const int64_t* gather, int64_t n, int d, void* bank_f16,
+                               int64_t row0, int32_t* err, osn_stream_t stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    OSN_REQUIRE(n >= 0 && n_rows >= 0 && row0 >= 0 && d >= 8 && (d & 7) == 0, OSN_E_ARG,
+                "osn_bank_append: need n, n_rows, row0 >= 0 and d %% 8 == 0 (n=%lld n_rows=%lld row0=%lld d=%d)", (long long)n,
+                (long long)n_rows, (long long)row0, d);
+    OSN_REQUIRE(err, OSN_E_ARG, "osn_bank_append: null err word");
+    OSN_REQUIRE(gather || n <= n_rows, OSN_E_ARG, "osn_bank_append: %lld rows wanted of %lld", (long long)n, (long long)n_rows);
+    if (n == 0) return OSN_OK;
+    OSN_REQUIRE(X && bank_f16, OSN_E_ARG, "osn_bank_append: null pointer");
+    OSN_REQUIRE(aligned16(X) && aligned16(bank_f16), OSN_E_ARG, "osn_bank_append: X and the bank must be 16-byte aligned");
+    _Float16* out = static_cast<_Float16*>(bank_f16) + row0 * int64_t(d);
+    const int64_t blocks = cdiv(n * (d / 4), 256);
+    const unsigned grid = unsigned(blocks < (int64_t(1) << 20) ? blocks : (int64_t(1) << 20));
+    hipLaunchKernelGGL(bank_append_kernel, dim3(grid), dim3(256), 0, st, X, n_rows, gather, n, d / 4, out, err);
+    OSN_LAUNCH_CHECK();
+    return OSN_OK;
+}
+
+// 0 = fine, else OSN_E_ARG with the error bits spelled out (synchronises the stream)
+extern "C" int osn_bank_check(const int32_t* err, osn_stream_t stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    OSN_REQUIRE(err, OSN_E_ARG, "osn_bank_check: null pointer");
+    int32_t h = 0;
+    OSN_HIP(hipMemcpyAsync(&h, err, 4, hipMemcpyDeviceToHost, st));
+    OSN_HIP(hipStreamSynchronize(st));
+    OSN_REQUIRE(!(h & BANK_E_GATHER), OSN_E_ARG, "osn_bank_append: a gather index outside [0, n_rows) (X[gather] raises in the reference)");
+    OSN_REQUIRE(!(h & BANK_E_OFFSETS), OSN_E_ARG, "osn_bank_search: scene_offsets must start at 0, ascend and end within the bank");
+    OSN_REQUIRE(!(h & BANK_E_LONG), OSN_E_ARG, "osn_bank_search: a scene is longer than max_scene_rows");
+    return OSN_OK;
+}
+
+extern "C" size_t osn_bank_search_ws_bytes(int64_t n, int n_scenes, int q, int k, int64_t max_scene_rows) {
+    return search_ws(n, n_scenes, q, k, max_scene_rows).total;
+}
+
+extern "C" int osn_bank_search(const void* bank_f16, int64_t n, int d, const int64_t* scene_offsets, int n_scenes,
+                               int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
+                               const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
+                               int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    OSN_REQUIRE(n >= 0 && d >= 8 && (d & 7) == 0 && q >= 1 && q <= 1024, OSN_E_ARG,
+                "osn_bank_search: need n >= 0, d %% 8 == 0 and 1 <= q <= 1024 (n=%lld d=%d q=%d)", (long long)n, d, q);
+    OSN_REQUIRE(n_scenes >= 0 && n_scenes <= 65535 && max_scene_rows >= 0 && max_scene_rows < (int64_t(1) << 31), OSN_E_ARG,
+                "osn_bank_search: n_scenes=%d (0 .. 65535) max_scene_rows=%lld (< 2^31)", n_scenes, (long long)max_scene_rows);
+    OSN_REQUIRE((normalize == 0 || normalize == 1) && k >= 1 && k <= 128, OSN_E_ARG,
+                "osn_bank_search: normalize=%d (0 or 1) k=%d (1 .. 128)", normalize, k);
+    OSN_REQUIRE(queries_f16 && aligned16(queries_f16), OSN_E_ARG, "osn_bank_search: queries must be non-null and 16-byte aligned");
+    OSN_REQUIRE(n == 0 || (bank_f16 && aligned16(bank_f16)), OSN_E_ARG, "osn_bank_search: the bank must be non-null and 16-byte aligned");
+    OSN_REQUIRE(n_scenes == 0 || (scene_offsets && topk_scores_f16 && topk_points && err), OSN_E_ARG, "osn_bank_search: null pointer");
+    OSN_REQUIRE(!counts || thresholds, OSN_E_ARG, "osn_bank_search: counts need thresholds");
+    const SearchWs w = search_ws(n, n_scenes, q, k, max_scene_rows);
+    OSN_REQUIRE(ws && aligned16(ws) && ws_bytes >= w.total, OSN_E_WS, "osn_bank_search: workspace too small (%zu < %zu)", ws_bytes, w.total);
+    char* p = static_cast<char*>(ws);
+    _Float16* heatT = reinterpret_cast<_Float16*>(p + w.heatT);
+    uint32_t* hist = reinterpret_cast<uint32_t*>(p + w.hist);
+    uint32_t* state = reinterpret_cast<uint32_t*>(p + w.state);
+    uint32_t* chunk_eq = reinterpret_cast<uint32_t*>(p + w.chunk_eq);
+    uint2* cand = reinterpret_cast<uint2*>(p + w.cand);
+    if (n > 0) {
+        const dim3 grid(unsigned(cdiv(n, S_BM))), block(256);
+        const _Float16* B = static_cast<const _Float16*>(bank_f16);
+        const _Float16* T = static_cast<const _Float16*>(queries_f16);
+        _Float16* heat = static_cast<_Float16*>(heat_f16);
+        if (q <= 32) hipLaunchKernelGGL((heat_kernel<1, 3>), grid, block, 0, st, B, T, heat, heatT, w.ldT, n, d, q, normalize);
+        else hipLaunchKernelGGL((heat_kernel<2, 3>), grid, block, 0, st, B, T, heat, heatT, w.ldT, n, d, q, normalize);
+        OSN_LAUNCH_CHECK();
+    }
+    if (n_scenes == 0) return OSN_OK;
+    const size_t items = size_t(n_scenes) * size_t(q);
+    OSN_HIP(hipMemsetAsync(hist, 0, items * 256 * 4, st));
+    if (counts) OSN_HIP(hipMemsetAsync(counts, 0, items * 8, st));
+    hipLaunchKernelGGL(search_check_kernel, dim3(unsigned(cdiv(n_scenes, 256))), dim3(256), 0, st, scene_offsets, n_scenes, n,
+                       max_scene_rows, err);
+    const int mc = sel_max_chunks(max_scene_rows);
+    const dim3 cgrid(unsigned(mc > 0 ? mc : 1), unsigned(n_scenes), unsigned(q));
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
+    _Float16* ts = static_cast<_Float16*>(topk_scores_f16);
+    hipLaunchKernelGGL(select_hist_kernel<0>, cgrid, dim3(SEL_T), 0, st, heatT, w.ldT, scene_offsets, n, max_scene_rows, q, mc,
+                       counts ? thresholds : nullptr, cnt, hist, state, chunk_eq);
+    hipLaunchKernelGGL(select_pick_kernel<0>, dim3(unsigned(items)), dim3(256), 0, st, hist, state, k);
+    hipLaunchKernelGGL(select_hist_kernel<1>, cgrid, dim3(SEL_T), 0, st, heatT, w.ldT, scene_offsets, n, max_scene_rows, q, mc,
+                       nullptr, cnt, hist, state, chunk_eq);
+    hipLaunchKernelGGL(select_pick_kernel<1>, dim3(unsigned(items)), dim3(256), 0, st, hist, state, k);
+    hipLaunchKernelGGL(select_hist_kernel<2>, cgrid, dim3(SEL_T), 0, st, heatT, w.ldT, scene_offsets, n, max_scene_rows, q, mc,
+                       nullptr, cnt, hist, state, chunk_eq);
+    hipLaunchKernelGGL(select_collect_kernel, cgrid, dim3(SEL_T), 0, st, heatT, w.ldT, scene_offsets, n, max_scene_rows, q, mc, k,
+                       state, chunk_eq, cand);
+    hipLaunchKernelGGL(select_sort_kernel, dim3(unsigned(items)), dim3(128), 0, st, state, cand, k, ts, topk_points);
+    OSN_LAUNCH_CHECK();
+    return OSN_OK;
+}

@@ -75,6 +75,39 @@ def save_fused_features(path, feat, mask_full):
     torch.save({"feat": feat, "mask_full": mask_full}, path)
 
 
+POINT_FEATURE_TAG = "_openscene_feat_"
+
+
+def point_feature_path(folder, scene_name, feature_type):
+    """``run/evaluate.py:330``: ``<folder>/<scene>_openscene_feat_<feature_type>.npy``."""
+    return os.path.join(folder, "%s%s%s.npy" % (scene_name, POINT_FEATURE_TAG, feature_type))
+
+
+def save_point_features(folder, scene_name, feature_type, features):
+    """Write one scene's per-point features as ``save_feature_as_numpy`` does (``run/evaluate.py:232-235,328-330``:
+    ``np.save(<scene>_openscene_feat_<feature_type>.npy, predictions.cpu().numpy())``): the array keeps its dtype --
+    float32 for the distilled features, float16 for the fused and the ensemble ones.  -> the path."""
+    os.makedirs(folder, exist_ok=True)
+    if isinstance(features, torch.Tensor):
+        features = features.detach().cpu().numpy()
+    features = np.asarray(features)
+    if features.ndim != 2:
+        raise ValueError("features must be [points, dim] (got shape %s)" % (features.shape,))
+    path = point_feature_path(folder, scene_name, feature_type)
+    np.save(path, features)
+    return path
+
+
+def list_point_features(folder, feature_type):
+    """-> sorted [(scene_name, path)] of the ``<scene>_openscene_feat_<feature_type>.npy`` files of a folder."""
+    tail = "%s%s.npy" % (POINT_FEATURE_TAG, feature_type)
+    out = []
+    for f in sorted(os.listdir(folder)):
+        if f.endswith(tail) and len(f) > len(tail):
+            out.append((f[:-len(tail)], os.path.join(folder, f)))
+    return out
+
+
 def save_checkpoint(state, is_best, save_dir, filename="model_last.pth.tar"):
     """``util/util.py:18-22``: ``state = {"epoch", "state_dict", "optimizer", "best_iou"}``."""
     missing = {"epoch", "state_dict", "optimizer", "best_iou"} - set(state)
