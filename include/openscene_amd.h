@@ -577,6 +577,51 @@ int osn_bank_search(const void* bank_f16, int64_t n, int d, const int64_t* scene
                     const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
                     int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
 
+/* ---- objects in heat-maps (csrc/objects.hip) -------------------------------------------------------------------- *
+ * What the README "Applications" do with a heat-map -- rare object search in a 3D scene database, image-based 3-D object
+ * detection, interactive object search -- needs objects, not points: WHERE the matches are, how many, how large, how
+ * confident.  An object of query j is a connected component (26- or 6-neighbourhood of the 3^3 self-map) of the voxels
+ * that hold at least one HIT: a point with a finite score and float(heat[p, j]) >= thresholds[j].
+ *
+ * Inputs shared by the two calls: heat fp16 [n, q] (osn_bank_search's); thresholds float32 [q]; inverse int32 [n] =
+ *   the voxel row of every point; coords4 int32 [n_voxels, 4] = (scene, x, y, z) rows in the order the self-map was built
+ *   from (osn_coords_unique); scene_offsets int64 [n_scenes + 1], ascending from 0 to n; n < 2^22, q <= 1024,
+ *   q * n_voxels < 2^31.  ws: osn_objects_ws_bytes(n_voxels, n_scenes, q) bytes -- two words per (query, voxel) and two per
+ *   (scene, query); it carries the labels from the first call to the second.
+ *
+ * osn_objects_label (interactive object search: one call labels every query): marks the active (query, voxel) pairs,
+ *   unites them over nbr int32 [27, n_voxels] (osn_kmap_build_self, ksize 3; the 13 offsets below the centre, or the 3
+ *   face offsets among them for connectivity 6) with a lock-free union-find -- larger root under smaller, compare-and-
+ *   swap, path halving; the partition does not depend on scheduling -- flattens, and numbers the components of every
+ *   (scene, query).  Zeroes and uses the device word err (int32 [1]); SYNCHRONISES once to return the number of components
+ *   to the host (*n_components_host) together with err: bad offsets, an inverse / batch / neighbour entry out of range
+ *   (such entries are skipped, never dereferenced) -> OSN_E_ARG.
+ *
+ * osn_objects_find (rare object search / 3-D detection: ranked objects per scene): records = a buffer of
+ *   osn_objects_records_bytes(n_components) bytes (scratch grows with the components, not with q * n_voxels * record).
+ *   Per component, with integer atomics only (bitwise repeatable): n_points, n_voxels, score_sum = sum of score * 2^24
+ *   (exact: every finite fp16 is a multiple of 2^-24), the peak as a packed (score key, ~point) 64-bit max -- the lowest
+ *   row inside the scene among the maxima --, vox_sum int64 [3], and the float32 box of the members' xyz [n, 3] through
+ *   order-preserving integer min / max.  combine = 1 merges the lanes of a wave that target one record before the
+ *   atomic (0: every hit issues its own; for measurements).  Per (scene, query): objects with n_points < min_points are
+ *   dropped, the rest ordered by peak score descending, then peak point ascending; the first max_objects (1 .. 64) are
+ *   written to out_* [n_scenes, q, max_objects] (vox_sum / box_*: [.., 3]); out_n_objects int64 [n_scenes, q] counts the
+ *   objects that passed the filter; padding = (n_points 0, peak_point -1, peak_score -inf, zeros).  point_object
+ *   (nullable) int32 [n, q] = the rank of the kept object a hit belongs to, else -1.  Asynchronous. */
+size_t osn_objects_ws_bytes(int64_t n_voxels, int n_scenes, int q);
+size_t osn_objects_records_bytes(int64_t n_components);
+int osn_objects_label(const void* heat_f16, int64_t n, int q, const float* thresholds, const int32_t* inverse,
+                      const int32_t* coords4, int64_t n_voxels, const int32_t* nbr, int connectivity,
+                      const int64_t* scene_offsets, int n_scenes, int32_t* err, void* ws, size_t ws_bytes,
+                      int64_t* n_components_host, osn_stream_t stream);
+int osn_objects_find(const void* heat_f16, const float* xyz, int64_t n, int q, const float* thresholds,
+                     const int32_t* inverse, const int32_t* coords4, int64_t n_voxels, const int64_t* scene_offsets,
+                     int n_scenes, int64_t n_components, int min_points, int max_objects, int combine,
+                     int64_t* out_n_points, int64_t* out_n_voxels, void* out_peak_score_f16, int64_t* out_peak_point,
+                     int64_t* out_score_sum, int64_t* out_vox_sum, float* out_box_min, float* out_box_max,
+                     int64_t* out_n_objects, int32_t* point_object, const void* ws, size_t ws_bytes, void* records,
+                     size_t records_bytes, osn_stream_t stream);
+
 /* ---- hash voxelisation --------------------------------------------------- *
  * Replaces Voxelizer.voxelize (dataset/voxelizer.py:117-129) +
  * sparse_quantize / fnv_hash_vec (dataset/voxelization_utils.py:9-22,112-132):

@@ -9,6 +9,8 @@ Python surface (mirrors the reference's own, file:line in each module):
     openscene_amd.disnet           models/disnet.py     (DisNet)
     openscene_amd.voxelizer        dataset/voxelizer.py (Voxelizer)
     openscene_amd.query            run/evaluate.py:283-324 (distill / fusion / ensemble query)
+    openscene_amd.search           README "Applications": a bank of scenes searched by text or image embedding
+    openscene_amd.objects          the same, as objects: connected components of a heat-map, ranked per scene
     install_minkowski_alias()      make `import MinkowskiEngine` resolve to openscene_amd.minkowski
 
 There is no CPU fallback: every op raises if libopenscene_amd.so is missing or

@@ -1435,6 +1435,85 @@ def bank_search(bank, scene_offsets, queries, k=16, thresholds=None, normalize=T
     return heat, top_s, top_p, counts
 
 
+# --------------------------------------------------------------------- objects
+OBJECTS_MAX_M = 64
+OBJECTS_MAX_POINTS = 1 << 22          # keeps score_sum inside int64 for raw scores at the fp16 maximum
+
+
+def objects_find(heat, thresholds, xyz, inverse, coords4, nbr, scene_offsets, connectivity=26, min_points=1, max_objects=16,
+                 return_point_ids=False, combine=True):
+    """Objects of a heat-map: connected components of the voxels that hold a hit, ranked per (scene, query).
+    heat fp16 [N, Q]; thresholds float32 [Q]; xyz float32 [N, 3]; inverse int32 [N] (point -> voxel row); coords4 int32
+    [V, 4] (scene, x, y, z) and nbr int32 [27, V] = coords_unique's rows and kmap_build(..., 3, 1, self_map=True) over
+    them; scene_offsets int64 [S + 1].  All on one device, contiguous.
+    -> dict of [S, Q, M] tensors: n_points, n_voxels, peak_point, score_sum int64, peak_score fp16, vox_sum int64 [.., 3],
+       box_min / box_max float32 [.., 3]; n_objects int64 [S, Q]; point_object int32 [N, Q] or None.
+    The number of components is read back to the host once per call (one synchronisation) to size the record scratch."""
+    dev = heat.device
+    lib = _prep(dev)
+    if heat.dtype != torch.float16:
+        raise TypeError("heat must be float16 (got %s)" % heat.dtype)
+    if heat.dim() != 2 or not heat.is_contiguous():
+        raise ValueError("heat must be a contiguous [points, Q] matrix")
+    n, q = heat.shape
+    if not 1 <= q <= BANK_MAX_Q:
+        raise ValueError("1 .. %d queries per call (got %d)" % (BANK_MAX_Q, q))
+    if n >= OBJECTS_MAX_POINTS:
+        raise ValueError("at most 2^22 - 1 points per call (got %d)" % n)
+    if thresholds.dtype != torch.float32 or tuple(thresholds.shape) != (q,) or thresholds.device != dev:
+        raise ValueError("thresholds must be a float32 [%d] vector on the heat-map's device" % q)
+    if xyz.dtype != torch.float32 or tuple(xyz.shape) != (n, 3) or xyz.device != dev or not xyz.is_contiguous():
+        raise ValueError("xyz must be a contiguous float32 [%d, 3] matrix on the heat-map's device" % n)
+    if inverse.dtype != torch.int32 or tuple(inverse.shape) != (n,) or inverse.device != dev or not inverse.is_contiguous():
+        raise ValueError("inverse must be a contiguous int32 [%d] vector on the heat-map's device" % n)
+    if coords4.dtype != torch.int32 or coords4.dim() != 2 or coords4.shape[1] != 4 or coords4.device != dev or not coords4.is_contiguous():
+        raise ValueError("coords4 must be contiguous int32 [V, 4] rows on the heat-map's device")
+    v = coords4.shape[0]
+    if nbr.dtype != torch.int32 or tuple(nbr.shape) != (27, v) or nbr.device != dev or not nbr.is_contiguous():
+        raise ValueError("nbr must be a contiguous int32 [27, %d] table on the heat-map's device" % v)
+    if scene_offsets.dtype != torch.int64 or scene_offsets.dim() != 1 or scene_offsets.shape[0] < 1 or scene_offsets.device != dev:
+        raise ValueError("scene_offsets must be an int64 [S + 1] vector on the heat-map's device")
+    if connectivity not in (6, 26):
+        raise ValueError("connectivity must be 6 or 26 (got %r)" % (connectivity,))
+    min_points, m = int(min_points), int(max_objects)
+    if not 1 <= m <= OBJECTS_MAX_M:
+        raise ValueError("max_objects must be in 1 .. %d (got %d)" % (OBJECTS_MAX_M, m))
+    if min_points < 1:
+        raise ValueError("min_points must be at least 1 (got %d)" % min_points)
+    if q * v >= 1 << 31:
+        raise ValueError("Q * voxels must stay below 2^31 (got %d x %d)" % (q, v))
+    scene_offsets = scene_offsets.contiguous()
+    thresholds = thresholds.contiguous()
+    s = scene_offsets.shape[0] - 1
+    err = torch.empty(1, dtype=torch.int32, device=dev)                  # (zeroed by the call)
+    ws = torch.empty(max(_cached("osn_objects_ws_bytes", v, s, q), 16), dtype=torch.uint8, device=dev)   # own buffer: it lives across two calls
+    out = {
+        "n_points": torch.empty((s, q, m), dtype=torch.int64, device=dev),
+        "n_voxels": torch.empty((s, q, m), dtype=torch.int64, device=dev),
+        "peak_score": torch.empty((s, q, m), dtype=torch.float16, device=dev),
+        "peak_point": torch.empty((s, q, m), dtype=torch.int64, device=dev),
+        "score_sum": torch.empty((s, q, m), dtype=torch.int64, device=dev),
+        "vox_sum": torch.empty((s, q, m, 3), dtype=torch.int64, device=dev),
+        "box_min": torch.empty((s, q, m, 3), dtype=torch.float32, device=dev),
+        "box_max": torch.empty((s, q, m, 3), dtype=torch.float32, device=dev),
+        "n_objects": torch.empty((s, q), dtype=torch.int64, device=dev),
+        "point_object": torch.empty((n, q), dtype=torch.int32, device=dev) if return_point_ids else None,
+    }
+    nc = ctypes.c_int64(0)
+    with _Dev(dev):
+        st = _stream(dev)
+        check(lib.osn_objects_label(_p(heat), n, q, _p(thresholds), _p(inverse), _p(coords4), v, _p(nbr), int(connectivity),
+                                    _p(scene_offsets), s, _p(err), _p(ws), ws.numel(), ctypes.byref(nc), st), "osn_objects_label")
+        c = int(nc.value)
+        rec = _ws(lib.osn_objects_records_bytes(c), dev)
+        check(lib.osn_objects_find(_p(heat), _p(xyz), n, q, _p(thresholds), _p(inverse), _p(coords4), v, _p(scene_offsets), s, c,
+                                   min_points, m, int(bool(combine)), _p(out["n_points"]), _p(out["n_voxels"]), _p(out["peak_score"]),
+                                   _p(out["peak_point"]), _p(out["score_sum"]), _p(out["vox_sum"]), _p(out["box_min"]),
+                                   _p(out["box_max"]), _p(out["n_objects"]), _p(out["point_object"]), _p(ws), ws.numel(), _p(rec),
+                                   rec.numel(), st), "osn_objects_find")
+    return out
+
+
 # ------------------------------------------------------------------- voxelizer
 def voxelize_fnv(xyz, T):
     """xyz float64 [N,3] (device), T 4x4 float64 (host, numpy or tensor) ->

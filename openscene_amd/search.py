@@ -8,7 +8,8 @@ against CLIP text embeddings (``:291``, ``:305,310``) and can save them per scen
     FeatureBank      one growing fp16 matrix of per-point features, many scenes, on the device
     search           heat-map [N, Q] + the k best points of every scene + counts over a threshold: ONE pass over the bank
     heat_map         the one-scene convenience
-    SearchResult     .rank_scenes(q, by=...) orders the scenes for a query
+    SearchResult     .rank_scenes(q, by=...) orders the scenes for a query; .find_objects(grid, thresholds) groups the
+                     heat-map into ranked objects (openscene_amd.objects)
 
 Kernels: csrc/search.hip through ops.bank_append / ops.bank_search; no CPU path.
 """
@@ -204,6 +205,15 @@ class SearchResult:
         order = torch.sort(score, descending=True, stable=True)[1].tolist()
         vals = score.tolist()
         return [(self.names[i], int(vals[i]) if by == "count" else vals[i]) for i in order]
+
+    def find_objects(self, grid, thresholds, **kw):
+        """The objects of this search's heat-map (openscene_amd.objects.find_objects over `grid`, a VoxelGrid of the bank's
+        points): where in every scene the matches are, how many, how large.  Needs a search with return_heat."""
+        if self.heat is None:
+            raise ValueError("the search was run without return_heat")
+        from .objects import find_objects
+        kw.setdefault("names", self.names)
+        return find_objects(grid, self.heat, thresholds, **kw)
 
 
 def _queries(queries, dim, device):
