@@ -53,12 +53,9 @@ static int ws_kernel(const osn_net_desc* net, const osn_net_op& o, int ca, int c
     return 0;
 }
 static bool dense_eligible(int cin, int cout) { return (cin & 3) == 0 && cin >= 8 && (cout & 3) == 0; }
-// functional.rg_kernel: the register-gather kernel for the narrow layers (32 / 64 channels on both sides) that neither the tile-list
+// ops.rg_eligible: the register-gather kernel for the narrow layers (32 / 64 channels on both sides) that neither the tile-list
 // kernel nor a direct weight-stationary launch takes -- before the partial-row weight-stationary kernel and the first-generation one
 static bool rg_eligible(int K, int ca, int cb, int64_t n_src) { return osn_spconv_fwd_rg_ok(n_src > 0 ? n_src : 1, K, ca, cb) != 0; }
-// ... and AHEAD of the tile-list kernel when one side has 32 channels (measured at 101 k rows, tools/micro_rg.py: 32 -> 32 38.8 us against
-// 49.3, 32 -> 64 49.6 / 53.7; 64 -> 64 stays with the tile-list kernel there: 72 against 112)
-static bool rg_first(int K, int ca, int cb, int64_t n_src) { return (ca == 32 || cb == 32) && rg_eligible(K, ca, cb, n_src); }
 static bool x6_eligible(int K, int cin, int cout, int64_t n_out) {
     if ((cin & 3) || cin < 8) return false;
     if (int64_t(3) * K * cout * ((cin + 31) / 32 * 32) >= (int64_t(1) << 30)) return false;
@@ -66,6 +63,47 @@ static bool x6_eligible(int K, int cin, int cout, int64_t n_out) {
     if (osn_spconv_fwd_plan(n_out, K, cin, cout, plan) != OSN_OK) return false;
     const int S = plan[4] > 0 ? plan[4] : 1;
     return (K + S - 1) / S <= 32;
+}
+
+// functional.conv_kernels' helper, THE rule of this path: the kernel of a launch of stage `o` (n_in input rows) that gathers n_src rows
+// of ca channels and writes n_dst rows of cb channels -- the forward launch, or the input gradient with the roles swapped; 0 = none
+// of the executor's kernels.  In order: 1x1; direct weight-stationary; tile-list, unless one side has 32 channels and the
+// register-gather kernel takes the shape (measured at 101 k rows, tools/micro_rg.py: 32 -> 32 38.8 us against 49.3, 32 -> 64 49.6 / 53.7;
+// 64 -> 64 stays with the tile-list kernel there: 72 against 112); register-gather; weight-stationary with partial rows; split-bf16.
+// tests/test_executor.py::test_both_paths_plan_the_same_kernels holds it to the Python twin.
+static int pick_kernel(const osn_net_desc* net, const osn_net_op& o, int64_t n_in, int ca, int cb, int64_t n_src, int64_t n_dst, bool dst_fine) {
+    if (o.K == 1 && dense_eligible(o.cin, o.cout) && dense_eligible(ca, cb)) return OSN_NET_K_DENSE;
+    const bool lists = o.K > 1 && tl_eligible(o.K, o.cin, o.cout, n_in) && tl_eligible(o.K, ca, cb, n_src);
+    const int ws = lists ? ws_kernel(net, o, ca, cb, n_src, n_dst, dst_fine) : 0;
+    if (ws == OSN_NET_K_WS_DIRECT) return ws;
+    const bool rg = rg_eligible(o.K, ca, cb, n_src);
+    if (lists && tl_rows_ok(net, n_dst, o.cin, o.cout) && !(rg && (ca == 32 || cb == 32))) return OSN_NET_K_TL;
+    if (rg) return OSN_NET_K_RG;
+    if (ws) return ws;
+    return x6_eligible(o.K, ca, cb, n_dst) ? OSN_NET_K_X6 : 0;
+}
+// what `kernel` needs to write n_dst rows of cb channels from ca channels: its weight image (the input-gradient one for dgrad) and
+// its workspace bytes
+static uint64_t conv_needs(int kernel, bool dgrad, int K, int ca, int cb, int64_t n_dst, int32_t& images) {
+    if (kernel == OSN_NET_K_STEM) return 0;
+    if (kernel == OSN_NET_K_X6) {
+        images |= dgrad ? OSN_NET_IMG_X6_DGRAD : OSN_NET_IMG_X6_FWD;
+        return osn_spconv_fwd_ws_bytes(n_dst, K, ca, cb);
+    }
+    images |= dgrad ? OSN_NET_IMG_TL_DGRAD : OSN_NET_IMG_TL_FWD;
+    if (kernel == OSN_NET_K_TL) return osn_spconv_fwd_tl_ws_bytes(n_dst, K, cb, osn_tile_rows(n_dst));
+    if (kernel == OSN_NET_K_WS || kernel == OSN_NET_K_WS_DIRECT) return osn_spconv_fwd_ws_ws_bytes(n_dst, K, cb, kernel == OSN_NET_K_WS_DIRECT);
+    return 0;
+}
+// weight gradient: the pair-array kernel on every 3^3 / 2^3 map, and -- identity map -- for the 1x1 shortcut convs up to 256 x 256
+// channels (their partial tiles are summed by the pass's batched reductions; the 96 -> 768 head stays on the table kernel: 188 us
+// against 215 us measured).  Round 6: the limit was 128 x 128, which left the three wide shortcuts of MinkUNet18A (128 -> 256 at 730
+// rows, 256 -> 128 at 3.3 k, 192 -> 128 at 13 k) on the first-generation table kernel: 78 - 85 us each for microseconds of work
+// (profiles/r05_s20_bench_detail.json, ops 20 / 26 / 32).
+static int pick_wgrad(const osn_net_op& o, int64_t n_in) {
+    if (stem_eligible(o.K, o.cin, o.cout)) return OSN_NET_K_WGRAD_STEM;
+    const bool pairs = o.K > 1 || (o.cin <= 256 && o.cout <= 256);
+    return pairs && tl_eligible(o.K, o.cin, o.cout, n_in) ? OSN_NET_K_WGRAD_TL : OSN_NET_K_WGRAD;
 }
 
 // Everything the passes derive from (program, level sizes): kernel per stage, arena offsets, scratch size.
@@ -146,79 +184,26 @@ static int make_layout(const osn_net_desc* net, const int64_t* rows, int trainin
         if (stem_eligible(o.K, o.cin, o.cout)) {
             OSN_REQUIRE(!o.transposed, OSN_E_ARG, "osn_net: op %d: transposed stem", i);
             L.fwd_k[i] = OSN_NET_K_STEM;
-        } else if (o.K == 1 && dense_eligible(o.cin, o.cout)) {
-            L.fwd_k[i] = OSN_NET_K_DENSE;
-            L.images[i] |= OSN_NET_IMG_TL_FWD;
-        } else if (ws_kernel(net, o, o.cin, o.cout, n_in, n_out, o.transposed != 0) == OSN_NET_K_WS_DIRECT) {
-            L.fwd_k[i] = OSN_NET_K_WS_DIRECT;
-            L.images[i] |= OSN_NET_IMG_TL_FWD;
-            need_ws(osn_spconv_fwd_ws_ws_bytes(n_out, o.K, o.cout, 1));
-        } else if (o.K > 1 && tl_eligible(o.K, o.cin, o.cout, n_in) && tl_rows_ok(net, n_out, o.cin, o.cout) && !rg_first(o.K, o.cin, o.cout, n_in)) {
-            L.fwd_k[i] = OSN_NET_K_TL;
-            L.images[i] |= OSN_NET_IMG_TL_FWD;
-            need_ws(osn_spconv_fwd_tl_ws_bytes(n_out, o.K, o.cout, osn_tile_rows(n_out)));
-        } else if (rg_eligible(o.K, o.cin, o.cout, n_in)) {
-            L.fwd_k[i] = OSN_NET_K_RG;
-            L.images[i] |= OSN_NET_IMG_TL_FWD;
-        } else if (ws_kernel(net, o, o.cin, o.cout, n_in, n_out, o.transposed != 0) == OSN_NET_K_WS) {
-            L.fwd_k[i] = OSN_NET_K_WS;
-            L.images[i] |= OSN_NET_IMG_TL_FWD;
-            need_ws(osn_spconv_fwd_ws_ws_bytes(n_out, o.K, o.cout, 0));
-        } else if (x6_eligible(o.K, o.cin, o.cout, n_out)) {
-            L.fwd_k[i] = OSN_NET_K_X6;
-            L.images[i] |= OSN_NET_IMG_X6_FWD;
-            need_ws(osn_spconv_fwd_ws_bytes(n_out, o.K, o.cin, o.cout));
         } else {
-            OSN_REQUIRE(false, OSN_E_ARG, "osn_net: op %d (K=%d, %d -> %d) fits none of the executor's forward kernels", i, o.K, o.cin, o.cout);
+            L.fwd_k[i] = pick_kernel(net, o, n_in, o.cin, o.cout, n_in, n_out, o.transposed != 0);
+            OSN_REQUIRE(L.fwd_k[i], OSN_E_ARG, "osn_net: op %d (K=%d, %d -> %d) fits none of the executor's forward kernels", i, o.K, o.cin, o.cout);
         }
+        need_ws(conv_needs(L.fwd_k[i], false, o.K, o.cin, o.cout, n_out, L.images[i]));
         if (!training) continue;
         // ---- input gradient: a convolution of the output gradient with the transposed weights, [n_in, cin]
         if (o.need_dgrad) {
-            const int wsk = tl_eligible(o.K, o.cin, o.cout, n_in) ? ws_kernel(net, o, o.cout, o.cin, n_out, n_in, o.transposed == 0) : 0;
-            if (o.K == 1 && dense_eligible(o.cin, o.cout) && dense_eligible(o.cout, o.cin)) {
-                L.dgrad_k[i] = OSN_NET_K_DENSE;
-                L.images[i] |= OSN_NET_IMG_TL_DGRAD;
-            } else if (wsk == OSN_NET_K_WS_DIRECT) {
-                L.dgrad_k[i] = OSN_NET_K_WS_DIRECT;
-                L.images[i] |= OSN_NET_IMG_TL_DGRAD;
-                need_ws(osn_spconv_fwd_ws_ws_bytes(n_in, o.K, o.cin, 1));
-            } else if (o.K > 1 && tl_eligible(o.K, o.cout, o.cin, n_out) && tl_eligible(o.K, o.cin, o.cout, n_in) && tl_rows_ok(net, n_in, o.cin, o.cout) &&
-                       !rg_first(o.K, o.cout, o.cin, n_out)) {
-                L.dgrad_k[i] = OSN_NET_K_TL;
-                L.images[i] |= OSN_NET_IMG_TL_DGRAD;
-                need_ws(osn_spconv_fwd_tl_ws_bytes(n_in, o.K, o.cin, osn_tile_rows(n_in)));
-            } else if (rg_eligible(o.K, o.cout, o.cin, n_out)) {
-                L.dgrad_k[i] = OSN_NET_K_RG;
-                L.images[i] |= OSN_NET_IMG_TL_DGRAD;
-            } else if (wsk == OSN_NET_K_WS) {
-                L.dgrad_k[i] = OSN_NET_K_WS;
-                L.images[i] |= OSN_NET_IMG_TL_DGRAD;
-                need_ws(osn_spconv_fwd_ws_ws_bytes(n_in, o.K, o.cin, 0));
-            } else if (x6_eligible(o.K, o.cout, o.cin, n_in)) {
-                L.dgrad_k[i] = OSN_NET_K_X6;
-                L.images[i] |= OSN_NET_IMG_X6_DGRAD;
-                need_ws(osn_spconv_fwd_ws_bytes(n_in, o.K, o.cout, o.cin));
-            } else {
-                OSN_REQUIRE(false, OSN_E_ARG, "osn_net: op %d (K=%d, %d -> %d) fits none of the executor's input-gradient kernels", i, o.K, o.cin, o.cout);
-            }
+            L.dgrad_k[i] = pick_kernel(net, o, n_in, o.cout, o.cin, n_out, n_in, o.transposed == 0);
+            OSN_REQUIRE(L.dgrad_k[i], OSN_E_ARG, "osn_net: op %d (K=%d, %d -> %d) fits none of the executor's input-gradient kernels", i, o.K, o.cin, o.cout);
+            need_ws(conv_needs(L.dgrad_k[i], true, o.K, o.cout, o.cin, n_in, L.images[i]));
         }
         // ---- weight gradient
-        // pair-array kernel on every 3^3 / 2^3 map, and -- identity map -- for the 1x1 shortcut convs up to 256 x 256
-        // channels (their partial tiles are summed by the pass's batched reductions; the 96 -> 768 head stays on the
-        // table kernel: 188 us against 215 us measured).  Round 6: the limit was 128 x 128, which left the three wide shortcuts of
-        // MinkUNet18A (128 -> 256 at 730 rows, 256 -> 128 at 3.3 k, 192 -> 128 at 13 k) on the first-generation table kernel:
-        // 78 - 85 us each for microseconds of work (profiles/r05_s20_bench_detail.json, ops 20 / 26 / 32).
-        const bool wg_tl = (o.K > 1 || (o.cin <= 256 && o.cout <= 256)) && tl_eligible(o.K, o.cin, o.cout, n_in) &&
-                           !stem_eligible(o.K, o.cin, o.cout);
-        if (stem_eligible(o.K, o.cin, o.cout)) {
-            L.wgrad_k[i] = OSN_NET_K_WGRAD_STEM;
+        L.wgrad_k[i] = pick_wgrad(o, n_in);
+        if (L.wgrad_k[i] == OSN_NET_K_WGRAD_STEM) {
             need_ws(osn_stem_conv_wgrad_ws_bytes(o.K, o.cin));
-        } else if (wg_tl) {
-            L.wgrad_k[i] = OSN_NET_K_WGRAD_TL;
+        } else if (L.wgrad_k[i] == OSN_NET_K_WGRAD_TL) {
             // partial sums per work item live in the backward arena until the ONE batched reduction at the end of the pass
             L.gpart_off[i] = b; b += up256(osn_spconv_wgrad_tl_ws_bytes(o.K, o.cin, o.cout));
         } else {
-            L.wgrad_k[i] = OSN_NET_K_WGRAD;
             need_ws(osn_spconv_wgrad_ws_bytes(n_out, o.K, o.cin, o.cout));
         }
     }

@@ -12,12 +12,14 @@ from . import ops
 # Kernels / arithmetic of the forward and input-gradient convolutions:
 #   "tl"     (default) second-generation kernels: forward / input gradient from per-tile compacted pair lists
 #            (weights in registers, output tile in LDS, spconv_tl.hip) on the large maps, weight gradient from
-#            per-offset pair arrays on the bf16 MFMA (wgrad_tl.hip) on every map; smaller maps, 1x1 convs and
-#            the 3-channel stem take the "bf16x6" forward and the fp32-MFMA weight gradient
+#            per-offset pair arrays on the bf16 MFMA (wgrad_tl.hip) on every map; the other families (1x1, weight-stationary,
+#            register-gather, stem) and the order they are tried in: conv_kernels below
 #   "bf16x6" output-stationary kernel over the dense neighbour table, three-way bf16 split of both operands,
 #            six bf16 MFMAs per product block, fp32 accumulate: fp32-level accuracy
 #   "fp32"   the same kernel on v_mfma_f32_32x32x2_f32 (exact fp32 products, 157 TF peak)
 CONV_MODE = os.environ.get("OSN_CONV_MODE", "tl")
+# Tile-list kernel, forward / input gradient: on the tables of at least this many rows (measured: 20-30 % faster on the 100 k-row
+# maps, a tie at 48 k rows, slower below) ...
 TL_FWD_MIN_ROWS = 65536
 # ... and from this many rows on when both channel counts are at least 96 (measured with the per-width channel chunks of
 # round 3, profiles/r03_s8: 48 k rows 96 -> 96 121 us against 134 us, 128 -> 96 143 / 164; 12.9 k rows 128 -> 128 63 / 78,
@@ -56,6 +58,87 @@ def tl_rows_ok(n_rows, c_a, c_b):
 WGRAD_OVERLAP_MAX_ROWS = 0
 
 
+# kernel name -> layout of the weight image it multiplies with (the other kernels read the fp32 weight)
+_IMAGE = {"dense": ops.PREP_TL, "ws_direct": ops.PREP_TL, "tl": ops.PREP_TL, "rg": ops.PREP_TL, "ws": ops.PREP_TL, "x6": ops.PREP_X6}
+
+
+_plans = {}
+
+
+def conv_kernels(K, cin, cout, n_in, n_out, transposed, fine_unique, need_dgrad=True, have_lists_fwd=True, have_lists_bwd=True,
+                 have_pairs=True):
+    """_plan_kernels, remembered per argument set and per state of everything it reads: the thresholds and rules above, which
+    tests and tools set, and the shape predicates of ops, which host-logic tests swap (the per-module path is host-bound, and a
+    step asks the same ~40 questions again)."""
+    key = (K, cin, cout, n_in, n_out, transposed, fine_unique, need_dgrad, have_lists_fwd, have_lists_bwd, have_pairs,
+           CONV_MODE, TL_FWD_MIN_ROWS, TL_MID_MIN_ROWS, WS_MAX_ROWS, ws_kernel, tl_rows_ok,
+           ops.stem_eligible, ops.dense_eligible, ops.tl_eligible, ops.rg_eligible, ops.x6_eligible)
+    plan = _plans.get(key)
+    if plan is None:
+        plan = _plans[key] = _plan_kernels(*key[:11])
+    return plan
+
+
+def _plan_kernels(K, cin, cout, n_in, n_out, transposed, fine_unique, need_dgrad, have_lists_fwd, have_lists_bwd, have_pairs):
+    """(forward, input-gradient, weight-gradient) kernel of a convolution, by the names Executor.kernels() reports; "generic": the
+    table kernel ops.spconv_fwd, which the executor does not have; "none": no input gradient wanted.  have_*: what the map handed in
+    (tile lists per direction, pair arrays).  THE rule of the per-module path; csrc/net.hip:pick_kernel / pick_wgrad are its twins,
+    tests/test_executor.py::test_both_paths_plan_the_same_kernels holds the two together."""
+    tl_mode = CONV_MODE == "tl"
+    lists_mode = tl_mode and K > 1 and ops.tl_eligible(K, cin, cout, n_in)
+
+    def pick(c_src, c_dst, n_src, n_dst, dst_fine, have_lists):
+        """The kernel of a launch that gathers n_src rows of c_src channels and writes n_dst rows of c_dst channels."""
+        if tl_mode and K == 1 and ops.dense_eligible(cin, cout) and ops.dense_eligible(c_src, c_dst):
+            return "dense"                          # 1x1 convs (head, shortcuts): the row-wise matrix-product kernel
+        if lists_mode:
+            both = ops.tl_eligible(K, c_src, c_dst, n_src)
+            ws = ws_kernel(K, c_src, c_dst, n_src, n_dst, fine_unique, dst_fine) if have_pairs else None
+            if ws == "ws_direct":
+                return ws
+            # (a layer with 32 channels on one side goes to the register-gather kernel on ANY map size, measured in csrc/net.hip)
+            rg = ops.rg_eligible(K, c_src, c_dst, n_src)
+            if both and have_lists and tl_rows_ok(n_dst, cin, cout) and not (rg and min(cin, cout) == 32):
+                return "tl"
+            if rg:
+                return "rg"
+            if ws:
+                return ws
+        if CONV_MODE in ("tl", "bf16x6") and ops.x6_eligible(K, c_src, c_dst, n_dst):
+            return "x6"
+        return "generic"
+
+    if CONV_MODE != "fp32" and ops.stem_eligible(K, cin, cout):
+        fwd, wgrad = "stem", "wgrad_stem"
+    else:
+        fwd = pick(cin, cout, n_in, n_out, transposed, have_lists_fwd)
+        # pair-array kernel on every 3^3 / 2^3 map and, on the identity map, for the 1x1 shortcut convs (the 96 -> 768 head stays on
+        # the table kernel: 188 us against 215 us measured)
+        pairs = have_pairs if K > 1 else cin <= 256 and cout <= 256
+        wgrad = "wgrad_tl" if tl_mode and pairs and ops.tl_eligible(K, cin, cout, n_in) else "wgrad"
+    return fwd, pick(cout, cin, n_out, n_in, not transposed, have_lists_bwd) if need_dgrad else "none", wgrad
+
+
+def _launch(name, x, w, n_dst, c_dst, K, nbr, tiles, lists, pairs, swap):
+    """Convolution kernel `name` on x -> [n_dst, c_dst] (the Python twin of run_conv in csrc/net.hip).  w: the weight image _IMAGE
+    names, else the fp32 weight; nbr / tiles / lists: the destination side's table, tile-ordered table and tile lists; pairs, swap:
+    the map's pair arrays and whether this launch walks them the other way."""
+    tbl, rows, gm = (tiles[1], tiles[0], tiles[2]) if tiles is not None else (nbr, None, None)
+    if name == "stem":
+        return ops.stem_conv_fwd(x, w, nbr, n_dst)
+    if name == "dense":
+        return ops.dense_fwd(x, w, c_dst)
+    if name in ("ws", "ws_direct"):
+        return ops.spconv_fwd_ws(x, w, pairs, nbr, n_dst, K, c_dst, swap=swap, direct=name == "ws_direct")
+    if name == "tl":
+        return ops.spconv_fwd_tl(x, w, lists, n_dst, K, c_dst)
+    if name == "rg":
+        return ops.spconv_fwd_rg(x, w, tbl, n_dst, c_dst, out_rows=rows)
+    if name == "x6":
+        return ops.spconv_fwd_x6(x, w, tbl, n_dst, out_rows=rows, gmask=gm)
+    return ops.spconv_fwd(x, w, tbl, n_dst, out_rows=rows, gmask=gm)
+
+
 class SparseConvFunction(Function):
     """out[o] = sum_k feats[nbr_fwd[k, o]] @ kernel[k]  ([ME] MinkowskiConvolutionFunction /
     MinkowskiConvolutionTransposeFunction).  kernel: [K, cin, cout], or [cin, cout] when K == 1."""
@@ -64,113 +147,64 @@ class SparseConvFunction(Function):
     def forward(ctx, feats, kernel, nbr_fwd, nbr_bwd, flip, n_out, tiles_fwd=None, tiles_bwd=None, counts=None,
                 lists_fwd=None, lists_bwd=None, transposed=False, fine_unique=False):
         ctx.save_for_backward(feats, kernel)
-        # weight gradient: the pair arrays of the map (a transposed conv runs on the arrays of the strided conv it
-        # mirrors = its own input-gradient lists, with the operand roles swapped)
-        ctx.wg_lists = (lists_bwd, True) if transposed else (lists_fwd, False)
-        ctx.maps = (nbr_fwd, nbr_bwd, bool(flip), tiles_bwd, counts)
-        ctx.n_in = feats.shape[0]
+        n_in, flip = feats.shape[0], bool(flip)
         K = 1 if kernel.dim() == 2 else kernel.shape[0]
         cin, cout = kernel.shape[-2], kernel.shape[-1]
-        tbl, rows, gm = (tiles_fwd[1], tiles_fwd[0], tiles_fwd[2]) if tiles_fwd is not None else (nbr_fwd, None, None)
-        ctx.wp_dgrad = None
-        ctx.tl_bwd = None
-        ctx.ws_bwd = None
-        ctx.dense_bwd = None
-        ctx.rg_bwd = None
-        # the cached weight images are shared and refreshed in place: remember which version of the kernel the image kept
-        # for the backward pass belongs to (a weight changed through .data between forward and backward bypasses autograd's
-        # own saved-tensor check)
+        # pair arrays of the map: those of the strided / self direction (a transposed conv runs on the arrays of the strided conv it
+        # mirrors = its own input-gradient lists, and walks them the other way)
+        pairs = lists_bwd if transposed else lists_fwd
+        fwd, dgrad, wgrad = conv_kernels(K, cin, cout, n_in, n_out, transposed, fine_unique, ctx.needs_input_grad[0],
+                                         lists_fwd is not None, lists_bwd is not None, pairs is not None)
+
+        def image(name, for_dgrad):
+            # (for_dgrad: transposed, and on a self map the offsets mirrored -- a 1x1 kernel has one offset)
+            return ops.weight_image(kernel, flip and for_dgrad and name != "dense", for_dgrad, _IMAGE[name]) if name in _IMAGE else None
+        # Weight images: parameters are served from ops' per-device cache (one launch per optimizer step for the whole model), so
+        # the input-gradient image is requested here too and is part of that launch.  The cache prepares a model's images in the
+        # order of their first request, and that order stays what it was: the input-gradient image first, but behind the forward
+        # image when it is a tile-list image after a tile-list / weight-stationary forward, or a first-generation image.  The
+        # latter after any other forward kernel (the stem with an input gradient, odd shapes: no layer of the U-Nets) is asked for
+        # in the backward pass.
+        late = dgrad == "x6" or (dgrad == "tl" and fwd in ("tl", "ws", "ws_direct"))
+        wd = None if late else image(dgrad, True)
+        wf = image(fwd, False)
+        if late and (dgrad == "tl" or fwd == "x6"):
+            wd = image(dgrad, True)
+        # the cached images are shared and refreshed in place: remember which version of the kernel the image kept for the backward
+        # pass belongs to (a weight changed through .data between forward and backward bypasses autograd's own saved-tensor check)
         ctx.kver = (kernel._version, kernel.data_ptr())
-        mode = "bf16x6" if CONV_MODE == "tl" else CONV_MODE
-        ctx.stem = CONV_MODE != "fp32" and nbr_fwd is not None and ops.stem_eligible(K, cin, cout)
-        if ctx.stem:
-            return ops.stem_conv_fwd(feats, kernel, nbr_fwd, n_out)
-        if CONV_MODE == "tl" and K == 1 and ops.dense_eligible(cin, cout):
-            # 1x1 convs (head, shortcuts): the row-wise matrix-product kernel, forward and input gradient
-            if ctx.needs_input_grad[0] and ops.dense_eligible(cout, cin):
-                ctx.dense_bwd = ops.weight_image(kernel, False, True, ops.PREP_TL)
-            return ops.dense_fwd(feats, ops.weight_image(kernel, False, False, ops.PREP_TL), cout)
-        if CONV_MODE == "tl" and K > 1 and ops.tl_eligible(K, cin, cout, ctx.n_in):
-            # weight-stationary kernel from the map's pair arrays (those of the strided / self direction: a transposed conv
-            # walks them the other way): forward, and -- decided here, launched in backward -- the input gradient, which on
-            # a self map (flip) keeps the direction and takes the mirrored weight image
-            pl, swap_f = ctx.wg_lists
-            ws_f = ws_kernel(K, cin, cout, ctx.n_in, n_out, fine_unique, transposed) if pl is not None else None
-            ws_b = (ws_kernel(K, cout, cin, n_out, ctx.n_in, fine_unique, not transposed)
-                    if pl is not None and ctx.needs_input_grad[0] and ops.tl_eligible(K, cout, cin, n_out) else None)
-            # forward / input gradient: only on maps of at least TL_FWD_MIN_ROWS rows (measured: 20-30 % faster on the
-            # 100 k-row maps, a tie at 48 k rows, slower below); 1x1 convs stay on the first-generation kernel
-            # (a layer with 32 channels on one side goes to the register-gather kernel on ANY map size: rg_first, same rule as csrc/net.hip)
-            rg_first_f = min(cin, cout) == 32 and ops.rg_eligible(K, cin, cout, ctx.n_in)
-            rg_first_b = min(cin, cout) == 32 and ops.rg_eligible(K, cout, cin, n_out)
-            fwd_ok = lists_fwd is not None and tl_rows_ok(n_out, cin, cout) and ws_f != "ws_direct" and not rg_first_f
-            bwd_ok = (ctx.needs_input_grad[0] and ops.tl_eligible(K, cout, cin, n_out) and lists_bwd is not None
-                      and tl_rows_ok(ctx.n_in, cin, cout) and ws_b != "ws_direct" and not rg_first_b)
-            # narrow layers (32 / 64 channels on both sides): the register-gather kernel where neither the tile-list kernel nor a
-            # direct weight-stationary launch applies (same rule as csrc/net.hip) -- forward here, input gradient decided here
-            rg_f = not fwd_ok and ws_f != "ws_direct" and ops.rg_eligible(K, cin, cout, ctx.n_in)
-            rg_b = (ctx.needs_input_grad[0] and not bwd_ok and ws_b != "ws_direct" and ops.rg_eligible(K, cout, cin, n_out))
-            if rg_b:
-                ctx.rg_bwd = ops.weight_image(kernel, flip, True, ops.PREP_TL)
-                ws_b = None
-            if rg_f:
-                if bwd_ok:
-                    ctx.wp_dgrad, ctx.tl_bwd = ops.weight_image(kernel, flip, True, ops.PREP_TL), lists_bwd
-                elif ws_b is not None:
-                    ctx.ws_bwd = (ops.weight_image(kernel, flip, True, ops.PREP_TL), pl, swap_f if flip else not swap_f, ws_b == "ws_direct")
-                return ops.spconv_fwd_rg(feats, ops.weight_image(kernel, False, False, ops.PREP_TL), tbl, n_out, cout, out_rows=rows)
-            if ws_b is not None and not bwd_ok:
-                ctx.ws_bwd = (ops.weight_image(kernel, flip, True, ops.PREP_TL), pl, swap_f if flip else not swap_f,
-                              ws_b == "ws_direct")
-            if ws_f is not None and not fwd_ok:
-                wf = ops.weight_image(kernel, False, False, ops.PREP_TL)
-                if bwd_ok:
-                    ctx.wp_dgrad, ctx.tl_bwd = ops.weight_image(kernel, flip, True, ops.PREP_TL), lists_bwd
-                return ops.spconv_fwd_ws(feats, wf, pl, nbr_fwd, n_out, K, cout, swap=swap_f, direct=ws_f == "ws_direct")
-            # weight images: parameters are served from ops' per-device cache (one launch per optimizer step for the
-            # whole model); the input-gradient image is requested here too so that it is part of that launch
-            wf = ops.weight_image(kernel, False, False, ops.PREP_TL) if fwd_ok else None
-            if bwd_ok:
-                ctx.wp_dgrad, ctx.tl_bwd = ops.weight_image(kernel, flip, True, ops.PREP_TL), lists_bwd
-            if fwd_ok:
-                return ops.spconv_fwd_tl(feats, wf, lists_fwd, n_out, K, cout)
-        if mode == "bf16x6" and ops.x6_eligible(K, cin, cout, n_out):
-            wp = ops.weight_image(kernel, False, False, ops.PREP_X6)
-            if (ctx.needs_input_grad[0] and ctx.tl_bwd is None and ctx.ws_bwd is None and ctx.rg_bwd is None
-                    and ops.x6_eligible(K, cout, cin, ctx.n_in)):
-                ctx.wp_dgrad = ops.weight_image(kernel, flip, True, ops.PREP_X6)
-            return ops.spconv_fwd_x6(feats, wp, tbl, n_out, out_rows=rows, gmask=gm)
-        return ops.spconv_fwd(feats, kernel, tbl, n_out, out_rows=rows, gmask=gm)
+        # the input gradient is a convolution of the output gradient over the map's other side; on a self map (flip) it keeps the
+        # direction of the pair arrays and takes the mirrored weight image
+        ctx.dgrad = (dgrad, wd, nbr_bwd, tiles_bwd, lists_bwd, pairs, transposed if flip else not transposed)
+        ctx.wgrad = (wgrad, nbr_fwd, counts, transposed, flip)
+        return _launch(fwd, feats, wf if wf is not None else kernel, n_out, cout, K, nbr_fwd, tiles_fwd, lists_fwd, pairs, transposed)
 
     @staticmethod
     def backward(ctx, gout):
         feats, kernel = ctx.saved_tensors
-        nbr_fwd, nbr_bwd, flip, tiles_bwd, counts = ctx.maps
+        dgrad, wd, nbr_bwd, tiles_bwd, lists_bwd, pairs, swap_b = ctx.dgrad
+        wgrad, nbr_fwd, counts, swap, flip = ctx.wgrad
         gout = gout.contiguous()
         gin = gk = None
         K = 1 if kernel.dim() == 2 else kernel.shape[0]
-        if (ctx.wp_dgrad is not None or ctx.ws_bwd is not None or ctx.dense_bwd is not None or ctx.rg_bwd is not None) and ctx.kver != (kernel._version, kernel.data_ptr()):
+        n_in, cin = feats.shape
+        if wd is not None and ctx.kver != (kernel._version, kernel.data_ptr()):
             raise RuntimeError("a convolution kernel changed between its forward and its backward pass (version %d -> %d): "
                                "the input-gradient weight image kept from the forward is stale" % (ctx.kver[0], kernel._version))
 
         def weight_grad():
-            cin, cout = kernel.shape[-2], kernel.shape[-1]
-            tl, swap = ctx.wg_lists
-            if ctx.stem:
-                return ops.stem_conv_wgrad(feats, gout, nbr_fwd, K).reshape(kernel.shape)
-            if CONV_MODE == "tl" and ops.tl_eligible(K, cin, cout, ctx.n_in):
-                if K > 1 and tl is not None:
-                    return ops.spconv_wgrad_tl(feats, gout, tl, K, swap=swap).reshape(kernel.shape)
-                if K == 1 and cin <= 256 and cout <= 256:
-                    # 1x1 shortcut convs: the pair-array kernel on the identity map (the 96 -> 768 head stays on the table
-                    # kernel: 188 us against 215 us measured); same rule as the network executor (csrc/net.hip)
-                    return ops.spconv_wgrad_tl(feats, gout, None, 1).reshape(kernel.shape)
-            return ops.spconv_wgrad(feats, gout, nbr_fwd, K, counts).reshape(kernel.shape)
+            if wgrad == "wgrad_stem":
+                gw = ops.stem_conv_wgrad(feats, gout, nbr_fwd, K)
+            elif wgrad == "wgrad_tl":
+                gw = ops.spconv_wgrad_tl(feats, gout, pairs, K, swap=swap) if K > 1 else ops.spconv_wgrad_tl(feats, gout, None, 1)
+            else:
+                gw = ops.spconv_wgrad(feats, gout, nbr_fwd, K, counts)
+            return gw.reshape(kernel.shape)
 
         side = None
         if ctx.needs_input_grad[1]:
             if (ctx.needs_input_grad[0] and gout.is_cuda
-                    and max(ctx.n_in, gout.shape[0]) <= WGRAD_OVERLAP_MAX_ROWS):
+                    and max(n_in, gout.shape[0]) <= WGRAD_OVERLAP_MAX_ROWS):
                 main = torch.cuda.current_stream(gout.device)
                 side = ops.side_stream(gout.device)
                 side.wait_stream(main)                    # fork: gout (and everything before it) is ready
@@ -179,29 +213,9 @@ class SparseConvFunction(Function):
             else:
                 gk = weight_grad()
         if ctx.needs_input_grad[0]:
-            cin, cout = kernel.shape[-2], kernel.shape[-1]
-            tbl, rows, gm = (tiles_bwd[1], tiles_bwd[0], tiles_bwd[2]) if tiles_bwd is not None else (nbr_bwd, None, None)
-            mode = "bf16x6" if CONV_MODE == "tl" else CONV_MODE
-            if ctx.dense_bwd is not None:
-                gin = ops.dense_fwd(gout, ctx.dense_bwd, cin)
-                ctx.dense_bwd = None
-            elif ctx.rg_bwd is not None:
-                gin = ops.spconv_fwd_rg(gout, ctx.rg_bwd, tbl, ctx.n_in, cin, out_rows=rows)
-                ctx.rg_bwd = None
-            elif ctx.tl_bwd is not None:
-                gin = ops.spconv_fwd_tl(gout, ctx.wp_dgrad, ctx.tl_bwd, ctx.n_in, K, cin)
-                ctx.wp_dgrad = ctx.tl_bwd = None
-            elif ctx.ws_bwd is not None:
-                wb, pl, swap_b, direct = ctx.ws_bwd
-                gin = ops.spconv_fwd_ws(gout, wb, pl, nbr_bwd, ctx.n_in, K, cin, swap=swap_b, direct=direct)
-                ctx.ws_bwd = None
-            elif mode == "bf16x6" and ops.x6_eligible(K, cout, cin, ctx.n_in):
-                # (reached only when the forward pass planned this kernel: rg_bwd / tl_bwd / ws_bwd are set otherwise)
-                wp = ctx.wp_dgrad if ctx.wp_dgrad is not None else ops.weight_image(kernel, flip, True, ops.PREP_X6)
-                ctx.wp_dgrad = None
-                gin = ops.spconv_fwd_x6(gout, wp, tbl, ctx.n_in, out_rows=rows, gmask=gm)
-            else:
-                gin = ops.spconv_fwd(gout, ops.weight_transpose(kernel, flip), tbl, ctx.n_in, out_rows=rows, gmask=gm)
+            if wd is None:
+                wd = ops.weight_image(kernel, flip, True, ops.PREP_X6) if dgrad == "x6" else ops.weight_transpose(kernel, flip)
+            gin = _launch(dgrad, gout, wd, n_in, cin, K, nbr_bwd, tiles_bwd, lists_bwd, pairs, swap_b)
         if side is not None:
             main.wait_stream(side)                        # join: later work on this stream sees the weight gradient
         return gin, gk, None, None, None, None, None, None, None, None, None, None, None

@@ -60,7 +60,7 @@ def test_planned_kernels_are_the_per_module_choice():
     direct mode for every launch that writes the fine side of a 2^3 stride-2 map; tile-list kernels from TL_FWD_MIN_ROWS
     table rows on (TL_MID_MIN_ROWS for >= 96 channels); the weight-stationary kernel with partial rows for launches writing
     at most WS_MAX_ROWS rows; the split-bf16 output-stationary kernel for the rest; pair-array weight gradient on every
-    3^3 / 2^3 map and (identity map) for the 1x1 shortcuts up to 128 channels, the table weight gradient for the stem
+    3^3 / 2^3 map and (identity map) for the 1x1 shortcuts up to 256 channels, the table weight gradient for the stem
     and the 96 -> 768 head."""
     from openscene_amd import executor as E
     from openscene_amd import functional as F_
@@ -101,6 +101,38 @@ def test_planned_kernels_are_the_per_module_choice():
     assert sum(k[1] == "rg" for k in ks) == 4 + 4 + 3 and sum(k[2] == "rg" for k in ks) == 4 + 4
     assert not any(k[1] == "x6" or k[2] == "x6" for k in ks), "MinkUNet18A no longer launches the first-generation kernel"
     assert not any(k[1] == "x6" and o["K"] > 1 and S100K[o["lvl_out"]] <= 4096 for k, o in zip(ks, ex.program.ops))
+
+
+@pytest.mark.parametrize("arch", ["MinkUNet14A", "MinkUNet18A", "MinkUNet18D", "MinkUNet34A", "MinkUNet34C"])
+def test_both_paths_plan_the_same_kernels(arch, monkeypatch):
+    """The rule is written once per path -- functional.conv_kernels (per-module path) and pick_kernel / pick_wgrad in csrc/net.hip
+    (executor) -- and the two must agree stage by stage on all three kernels, the stem included: on the S100k sizes, on a small
+    scene, with a level exactly at and one row past every row threshold, and under the threshold settings the GPU tests force."""
+    import itertools
+    from openscene_amd import executor as E
+    from openscene_amd import functional as F_
+    from openscene_amd.mink_unet import mink_unet
+    ex = E.for_model(mink_unet(3, 768, 3, arch))
+
+    def compare(rows):
+        ks = ex.kernels(rows, training=True)
+        assert len(ks) == len(ex.program.ops)
+        for (i, kf, kd, kw), o in zip(ks, ex.program.ops):
+            mine = F_.conv_kernels(o["K"], o["cin"], o["cout"], rows[o["lvl_in"]], rows[o["lvl_out"]], bool(o["transposed"]),
+                                   bool(o["fine_unique"]), need_dgrad=bool(o["need_dgrad"]))
+            assert (kf, kd, kw) == mine, (rows, i, o)
+    assert (F_.TL_FWD_MIN_ROWS, F_.TL_MID_MIN_ROWS, F_.WS_MAX_ROWS) == (65536, 8192, 8192)     # what the edge sizes below stand on
+    compare(S100K)
+    compare([6400, 3100, 1500, 700, 300])
+    for l0, l1, l2 in itertools.product((65535, 65536), (8192, 8193), (8192, 8193)):
+        compare([l0, l1, l2, 3052, 700])
+    monkeypatch.setattr(F_, "TL_FWD_MIN_ROWS", 0)
+    compare(S100K)
+    monkeypatch.setattr(F_, "TL_FWD_MIN_ROWS", 1 << 30)
+    monkeypatch.setattr(F_, "TL_MID_MIN_ROWS", 1 << 30)
+    for ws_max in (0, 1 << 30):
+        monkeypatch.setattr(F_, "WS_MAX_ROWS", ws_max)
+        compare(S100K)
 
 
 def test_executor_is_not_used_outside_its_configuration(monkeypatch):
