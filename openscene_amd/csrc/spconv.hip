@@ -18,6 +18,19 @@
 //   * small maps (deep U-Net levels) use narrower row tiles and split the offset
 //     loop across workgroups (deterministic partial buffers + ordered reduce) so
 //     the launch still covers the 256 CUs.
+//
+// Three forward kernels.  spconv_fwd_kernel is the simple loop (stem-sized cin, scalar
+// tails).  The other two are ONE offset pipeline with two arithmetic back ends:
+//   * offset_prologue  lists the block's active offsets (from gmask in units mode, from a
+//     scan of the table otherwise),
+//   * run_stages       is the software pipeline over (offset, channel chunk) stages, with
+//     the two-deep row-index prefetch,
+//   * store_part       picks the destination of the block's part and stores the accumulators;
+//   spconv_fwd_pipe_kernel (fp32 MFMA, OSN_CONV_MODE=fp32) and spconv_fwd_x6_kernel
+//   (split-bf16, six MFMAs per product) supply only their LDS tiles, fetch / stash and the
+//   MFMA block of a stage.
+// The host side mirrors it: table_workspace carves the workspace, for_tile turns the
+// plan's (cfg, tn) into compile-time tile parameters, table_tail runs the fix-up / reduce.
 #include "common.h"
 #include "weight_prep.h"
 #include <stdlib.h>
@@ -25,6 +38,26 @@
 namespace osn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
+
+// C layout of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
+// `out_rows` (nullable) maps tile rows to tensor rows.
+template <int TN>
+__device__ __forceinline__ void store_acc(float* __restrict__ dst, const int32_t* __restrict__ out_rows, int row0, int n0,
+                                          int wm, int wn, int n_out, int cout, const f32x16 (&acc)[TN]) {
+    const int lane = threadIdx.x & 63;
+#pragma unroll
+    for (int t = 0; t < TN; ++t) {
+        const int col = n0 + (wn * TN + t) * 32 + (lane & 31);
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = row0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            if (row < n_out && col < cout) {
+                const int orow = out_rows ? out_rows[row] : row;
+                dst[int64_t(orow) * cout + col] = acc[t][r];
+            }
+        }
+    }
+}
 
 template <int WM, int WN, int TN, int BK>
 __global__ __launch_bounds__(256) void spconv_fwd_kernel(const float* __restrict__ in, const float* __restrict__ W,
@@ -140,21 +173,9 @@ __global__ __launch_bounds__(256) void spconv_fwd_kernel(const float* __restrict
         }
     }
 
-    // ---- epilogue: C layout col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5)
-    float* dst = out;
-    if (to_partial) dst = out + int64_t(blockIdx.z) * n_out * cout;
-#pragma unroll
-    for (int t = 0; t < TN; ++t) {
-        const int col = n0 + (wn * TN + t) * 32 + (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = row0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (row < n_out && col < cout) {
-                const int orow = (!to_partial && out_rows) ? out_rows[row] : row;
-                dst[int64_t(orow) * cout + col] = acc[t][r];
-            }
-        }
-    }
+    // a partial keeps the tile's row order; the reduce pass applies out_rows
+    store_acc<TN>(to_partial ? out + int64_t(blockIdx.z) * n_out * cout : out, to_partial ? nullptr : out_rows, row0, n0, wm,
+                  wn, n_out, cout, acc);
 }
 
 // ---------------------------------------------------------------------------------------
@@ -163,7 +184,153 @@ __global__ __launch_bounds__(256) void spconv_fwd_kernel(const float* __restrict
 // with their row indices, and the (offset, channel-chunk) stages then run as a software
 // pipeline: the gather + weight loads of stage s+1 are issued into registers before the MFMAs
 // of stage s and written to LDS after them (one barrier pair per stage, global-load latency
-// hidden behind 48-64 MFMAs per wave).
+// hidden behind 48-64 MFMAs per wave).  The prologue, the stage loop and the store below are
+// shared by the fp32 kernel and the split-bf16 kernel.
+constexpr int PIPE_BK = 32;                      // input channels per stage
+constexpr int PIPE_KC = 32;                      // offsets per block (k_per_split <= PIPE_KC)
+
+template <int BM>
+struct OffsetLds {                               // a kernel declares one of these in shared memory
+    int ridx[2][BM];                             // row indices of the next two stages (by stage parity)
+    unsigned char gbits[PIPE_KC][2];
+    int klist[PIPE_KC];                          // active offsets of this block, relative to k_begin ...
+    int kgm[PIPE_KC];                            // ... and which 32-row groups of the tile use each
+    int nact;
+    uint32_t gm[4];
+};
+
+// Two ways to cut the offset loop across blockIdx.z (= part):
+//  * units mode (gmask given): part z takes the z-th group of `unit_k` ACTIVE offsets of this tile
+//    (work per block is bounded and even; parts > 0 go to `extra`, summed in order by a fix-up pass);
+//  * uniform mode: part z takes offsets [z*k_per_split, (z+1)*k_per_split) (small maps).
+// Fills klist / kgm / nact (and tile_parts[blockIdx.x] in units mode), sets k_begin; false = nothing to do.
+// (my_row, row_ok): the table row of thread tid < BM and whether it exists.
+template <int WM>
+__device__ __forceinline__ bool offset_prologue(OffsetLds<32 * WM>& sh, const uint32_t* __restrict__ gmask,
+                                                const int32_t* __restrict__ nbr, int32_t* __restrict__ tile_parts,
+                                                int n_out, int K, int part, int k_per_split, int unit_k, int my_row,
+                                                bool row_ok, int& k_begin) {
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const bool units = gmask != nullptr;
+    k_begin = units ? 0 : part * k_per_split;
+    const int nk = units ? K : min(K, k_begin + k_per_split) - k_begin;     // <= PIPE_KC
+    if (units) {
+        // ---- from the precomputed 32-row group masks: no table scan
+        if (tid < 4) {
+            const int64_t g = int64_t(blockIdx.x) * WM + tid;
+            sh.gm[tid] = (tid < WM && g * 32 < n_out) ? gmask[g] : 0u;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const uint32_t tm = sh.gm[0] | sh.gm[1] | sh.gm[2] | sh.gm[3];
+            int i = 0, n = 0;
+            for (int kk = 0; kk < nk; ++kk) {
+                if (!((tm >> kk) & 1u)) continue;
+                if (i >= part * unit_k && i < (part + 1) * unit_k) {
+                    sh.klist[n] = kk;
+                    sh.kgm[n] = int((sh.gm[0] >> kk) & 1u) | (int((sh.gm[1] >> kk) & 1u) << 1) |
+                                (int((sh.gm[2] >> kk) & 1u) << 2) | (int((sh.gm[3] >> kk) & 1u) << 3);
+                    ++n;
+                }
+                ++i;
+            }
+            sh.nact = n;
+            if (part == 0 && blockIdx.y == 0) tile_parts[blockIdx.x] = (i + unit_k - 1) / unit_k;
+        }
+        __syncthreads();
+        return !(part > 0 && sh.nact == 0);      // false: this tile has no offsets left for part z
+    }
+    // ---- scan: which offsets does this tile use, and which of its 32-row groups
+    for (int kk0 = 0; kk0 < nk; kk0 += 8) {
+        int idx[8];
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            idx[j] = -1;
+            if (row_ok && kk0 + j < nk) idx[j] = nbr ? nbr[int64_t(k_begin + kk0 + j) * n_out + my_row] : my_row;
+        }
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {
+            const unsigned long long b = __ballot(idx[j] >= 0);
+            if (lane == 0 && wave < 2 && kk0 + j < nk)
+                sh.gbits[kk0 + j][wave] = (unsigned char)(((b & 0xFFFFFFFFull) != 0 ? 1 : 0) | ((b >> 32) != 0 ? 2 : 0));
+        }
+    }
+    __syncthreads();
+    if (tid == 0) {
+        int n = 0;
+        for (int kk = 0; kk < nk; ++kk) {
+            const int gm = int(sh.gbits[kk][0]) | (int(sh.gbits[kk][1]) << 2);
+            if (gm) { sh.klist[n] = kk; sh.kgm[n] = gm; ++n; }
+        }
+        sh.nact = n;
+    }
+    __syncthreads();
+    return true;
+}
+
+// The stages of a block: stage s = (slot of klist, channel chunk).  `fetch(slot, c0, parity)` issues the
+// gather + weight loads of a stage into registers (row indices from ridx[parity]), `stash(slot)` writes them to
+// LDS, `mfma()` consumes the LDS tiles.  Rows + weights are fetched one stage ahead; the row indices of
+// stage s+2 are fetched during stage s.  That index load is issued through inline asm: hipcc's waitcnt pass
+// otherwise drains every load in flight around a loop-carried load destination (vmcnt is in-order), which
+// serialises the prefetch.  The value is consumed in the same iteration, after an explicit vmcnt(0).
+template <int BM, class Fetch, class Stash, class Mfma>
+__device__ __forceinline__ void run_stages(OffsetLds<BM>& sh, const int32_t* __restrict__ nbr, int n_out, int k_begin,
+                                           int nchunk, int wm, int my_row, bool row_ok, Fetch fetch, Stash stash, Mfma mfma) {
+    const int tid = threadIdx.x;
+    const int nstage = sh.nact * nchunk;
+    if (nstage > 0) {
+        auto advance = [&](int& sl, int& c) { if (++c == nchunk) { c = 0; ++sl; } };
+        int slot = 0;
+        int slot1 = 0, ch1 = 0; advance(slot1, ch1);
+        int slot2 = slot1, ch2 = ch1; advance(slot2, ch2);
+        auto idx_ptr = [&](int sl) -> const int32_t* {
+            return nbr + (row_ok ? int64_t(k_begin + sh.klist[sl]) * n_out + my_row : 0);
+        };
+        if (tid < BM) sh.ridx[0][tid] = row_ok ? (nbr ? *idx_ptr(0) : my_row) : -1;
+        __syncthreads();
+        fetch(0, 0, 0);
+        const int i1 = nbr ? *idx_ptr(nstage > 1 ? slot1 : 0) : my_row;
+        stash(0);
+        if (tid < BM) sh.ridx[1][tid] = row_ok ? i1 : -1;
+        __syncthreads();
+        for (int s = 0; s < nstage; ++s) {
+            const bool more = s + 1 < nstage, more2 = s + 2 < nstage;
+            if (more) fetch(slot1, ch1 * PIPE_BK, (s + 1) & 1);           // loads in flight during the MFMAs
+            int i2 = my_row;
+            if (nbr) {
+                const int32_t* p2 = idx_ptr(more2 ? slot2 : slot);
+                asm volatile("global_load_dword %0, %1, off" : "=v"(i2) : "v"(p2) : "memory");
+            }
+            if ((sh.kgm[slot] >> wm) & 1) mfma();          // the wave's 32 rows use this offset
+            __syncthreads();                  // stage s consumed; ridx[s&1] is free (its fetch ran an iteration ago)
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // covers the asm index load above
+            if (more) stash(slot1);
+            if (more2 && tid < BM) sh.ridx[s & 1][tid] = row_ok ? i2 : -1;        // stage s+2 reuses stage s' slot
+            __syncthreads();
+            slot = slot1;
+            slot1 = slot2; ch1 = ch2;
+            advance(slot2, ch2);
+        }
+    }
+}
+
+// Where the block's part goes: in units mode part 0 straight to its final rows (through out_rows) and parts > 0 to
+// `extra`; in uniform mode to its partial when the offsets are split, else to its final rows.
+template <int TN>
+__device__ __forceinline__ void store_part(float* __restrict__ out, float* __restrict__ extra,
+                                           const int32_t* __restrict__ out_rows, bool units, int part, int to_partial,
+                                           int row0, int n0, int wm, int wn, int n_out, int cout, const f32x16 (&acc)[TN]) {
+    float* dst = out;
+    bool direct = !to_partial;                   // rows go to their final place (through out_rows)
+    if (units) {
+        if (part > 0) { dst = extra + int64_t(part - 1) * n_out * cout; direct = false; }
+    } else if (to_partial) {
+        dst = out + int64_t(part) * n_out * cout;
+    }
+    store_acc<TN>(dst, direct ? out_rows : nullptr, row0, n0, wm, wn, n_out, cout, acc);
+}
+
 template <int WM, int WN, int TN>
 __global__ __launch_bounds__(256, 2) void spconv_fwd_pipe_kernel(const float* __restrict__ in, const float* __restrict__ W,
                                                               const int32_t* __restrict__ nbr,
@@ -176,90 +343,23 @@ __global__ __launch_bounds__(256, 2) void spconv_fwd_pipe_kernel(const float* __
     static_assert(WM * WN == 4, "four waves per workgroup");
     constexpr int BM = 32 * WM;
     constexpr int BN = 32 * TN * WN;
-    constexpr int BK = 32;
-    constexpr int KC = 32;                       // offsets per block (k_per_split <= KC)
+    constexpr int BK = PIPE_BK;
     constexpr int NA = BM / 32;                  // A float4 per thread per stage
     constexpr int BV = BN / 4;                   // float4 per B row
     constexpr int NB = (BK * BV + 255) / 256;    // B float4 per thread per stage
     __shared__ float As[BM][BK + 1];
     __shared__ __attribute__((aligned(16))) float Bs[BK][BN];
-    __shared__ int ridx[2][BM];                  // row indices of the next two stages (by stage parity)
-    __shared__ unsigned char gbits[KC][2];
-    __shared__ int klist[KC];
-    __shared__ int kgm[KC];
-    __shared__ int nact_s;
+    __shared__ OffsetLds<BM> sh;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
     const int row0 = blockIdx.x * BM;
     const int n0 = blockIdx.y * BN;
-    // Two ways to cut the offset loop across blockIdx.z:
-    //  * units mode (gmask given): part z takes the z-th group of `unit_k` ACTIVE offsets of this tile
-    //    (work per block is bounded and even; parts > 0 go to `extra`, summed in order by a fix-up pass);
-    //  * uniform mode: part z takes offsets [z*k_per_split, (z+1)*k_per_split) (small maps).
-    const bool units = gmask != nullptr;
     const int part = blockIdx.z;
-    const int k_begin = units ? 0 : part * k_per_split;
-    const int nk = units ? K : min(K, k_begin + k_per_split) - k_begin;     // <= KC
     const int my_row = row0 + tid;                               // meaningful for tid < BM
     const bool row_ok = tid < BM && my_row < n_out;
-    __shared__ uint32_t gm_s[4];
-
-    if (units) {
-        // ---- prologue from the precomputed 32-row group masks: no table scan
-        if (tid < 4) {
-            const int64_t g = int64_t(blockIdx.x) * WM + tid;
-            gm_s[tid] = (tid < WM && g * 32 < n_out) ? gmask[g] : 0u;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            const uint32_t tm = gm_s[0] | gm_s[1] | gm_s[2] | gm_s[3];
-            int i = 0, n = 0;
-            for (int kk = 0; kk < nk; ++kk) {
-                if (!((tm >> kk) & 1u)) continue;
-                if (i >= part * unit_k && i < (part + 1) * unit_k) {
-                    klist[n] = kk;
-                    kgm[n] = int((gm_s[0] >> kk) & 1u) | (int((gm_s[1] >> kk) & 1u) << 1) |
-                             (int((gm_s[2] >> kk) & 1u) << 2) | (int((gm_s[3] >> kk) & 1u) << 3);
-                    ++n;
-                }
-                ++i;
-            }
-            nact_s = n;
-            if (part == 0 && blockIdx.y == 0) tile_parts[blockIdx.x] = (i + unit_k - 1) / unit_k;
-        }
-        __syncthreads();
-        if (part > 0 && nact_s == 0) return;     // this tile has no offsets left for part z
-    } else {
-    // ---- prologue: which offsets does this tile use, and which of its 32-row groups
-    for (int kk0 = 0; kk0 < nk; kk0 += 8) {
-        int idx[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            idx[j] = -1;
-            if (row_ok && kk0 + j < nk) idx[j] = nbr ? nbr[int64_t(k_begin + kk0 + j) * n_out + my_row] : my_row;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const unsigned long long b = __ballot(idx[j] >= 0);
-            if (lane == 0 && wave < 2 && kk0 + j < nk)
-                gbits[kk0 + j][wave] = (unsigned char)(((b & 0xFFFFFFFFull) != 0 ? 1 : 0) | ((b >> 32) != 0 ? 2 : 0));
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int n = 0;
-        for (int kk = 0; kk < nk; ++kk) {
-            const int gm = int(gbits[kk][0]) | (int(gbits[kk][1]) << 2);
-            if (gm) { klist[n] = kk; kgm[n] = gm; ++n; }
-        }
-        nact_s = n;
-    }
-    __syncthreads();
-    }   // !units
-    const int nact = nact_s;
-    const int nchunk = (cin + BK - 1) / BK;
-    const int nstage = nact * nchunk;
+    int k_begin;
+    if (!offset_prologue<WM>(sh, gmask, nbr, tile_parts, n_out, K, part, k_per_split, unit_k, my_row, row_ok, k_begin)) return;
 
     f32x16 acc[TN];
 #pragma unroll
@@ -275,12 +375,12 @@ __global__ __launch_bounds__(256, 2) void spconv_fwd_pipe_kernel(const float* __
     // flight across the MFMA block instead of draining them at a control-flow join.
     unsigned pa_ok = 0, pb_ok = 0;
     auto fetch = [&](int slot, int c0, int par) {
-        const int kk = klist[slot], gm = kgm[slot];
+        const int kk = sh.klist[slot], gm = sh.kgm[slot];
         const int c = c0 + a_sub * 4;
         pa_ok = 0;
 #pragma unroll
         for (int p = 0; p < NA; ++p) {
-            const int i = ridx[par][p * 32 + a_r];
+            const int i = sh.ridx[par][p * 32 + a_r];
             const bool ok = ((gm >> p) & 1) && i >= 0 && c < cin;
             pa[p] = *reinterpret_cast<const float4*>(in + (ok ? int64_t(i) * cin + c : 0));
             pa_ok |= (ok ? 1u : 0u) << p;
@@ -298,7 +398,7 @@ __global__ __launch_bounds__(256, 2) void spconv_fwd_pipe_kernel(const float* __
         }
     };
     auto stash = [&](int slot) {
-        const int gm = kgm[slot];
+        const int gm = sh.kgm[slot];
 #pragma unroll
         for (int p = 0; p < NA; ++p) {
             if ((gm >> p) & 1) {
@@ -323,93 +423,37 @@ __global__ __launch_bounds__(256, 2) void spconv_fwd_pipe_kernel(const float* __
         }
     };
 
-    if (nstage > 0) {
-        // stage s = (slot, chunk ch).  Gathered rows + weights are fetched one stage ahead into
-        // registers; the row indices of stage s+2 are fetched during stage s.  That index load is
-        // issued through inline asm: hipcc's waitcnt pass otherwise drains every load in flight
-        // around a loop-carried load destination (vmcnt is in-order), which serialises the prefetch.
-        // The value is consumed in the same iteration, after an explicit vmcnt(0).
-        auto advance = [&](int& sl, int& c) { if (++c == nchunk) { c = 0; ++sl; } };
-        int slot = 0;
-        int slot1 = 0, ch1 = 0; advance(slot1, ch1);
-        int slot2 = slot1, ch2 = ch1; advance(slot2, ch2);
-        auto idx_ptr = [&](int sl) -> const int32_t* {
-            return nbr + (row_ok ? int64_t(k_begin + klist[sl]) * n_out + my_row : 0);
-        };
-        if (tid < BM) ridx[0][tid] = row_ok ? (nbr ? *idx_ptr(0) : my_row) : -1;
-        __syncthreads();
-        fetch(0, 0, 0);
-        const int i1 = nbr ? *idx_ptr(nstage > 1 ? slot1 : 0) : my_row;
-        stash(0);
-        if (tid < BM) ridx[1][tid] = row_ok ? i1 : -1;
-        __syncthreads();
-        for (int s = 0; s < nstage; ++s) {
-            const bool more = s + 1 < nstage, more2 = s + 2 < nstage;
-            if (more) fetch(slot1, ch1 * BK, (s + 1) & 1);            // loads in flight during the MFMAs
-            int i2 = my_row;
-            if (nbr) {
-                const int32_t* p2 = idx_ptr(more2 ? slot2 : slot);
-                asm volatile("global_load_dword %0, %1, off" : "=v"(i2) : "v"(p2) : "memory");
+    auto mfma = [&]() {
+        // operands of step kk+1 are read from LDS while the MFMAs of step kk issue
+        // (rolling two-step register window; the compiler otherwise waits lgkmcnt(0) per MFMA pair)
+        const int arow = wm * 32 + (lane & 31);
+        const int kh = lane >> 5;
+        const int bcol = wn * TN * 32 + (lane & 31);
+        float av[2], bv[2][TN];
+        av[0] = As[arow][kh];
+#pragma unroll
+        for (int t = 0; t < TN; ++t) bv[0][t] = Bs[kh][bcol + t * 32];
+#pragma unroll
+        for (int kk = 0; kk < BK / 2; ++kk) {
+            const int cur = kk & 1, nxt = cur ^ 1;
+            if (kk + 1 < BK / 2) {
+                av[nxt] = As[arow][2 * (kk + 1) + kh];
+#pragma unroll
+                for (int t = 0; t < TN; ++t) bv[nxt][t] = Bs[2 * (kk + 1) + kh][bcol + t * 32];
             }
-            if ((kgm[slot] >> wm) & 1) {
-                // operands of step kk+1 are read from LDS while the MFMAs of step kk issue
-                // (rolling two-step register window; the compiler otherwise waits lgkmcnt(0) per MFMA pair)
-                const int arow = wm * 32 + (lane & 31);
-                const int kh = lane >> 5;
-                const int bcol = wn * TN * 32 + (lane & 31);
-                float av[2], bv[2][TN];
-                av[0] = As[arow][kh];
+            __builtin_amdgcn_sched_barrier(0);       // keep the next step's reads ahead of these MFMAs
 #pragma unroll
-                for (int t = 0; t < TN; ++t) bv[0][t] = Bs[kh][bcol + t * 32];
-#pragma unroll
-                for (int kk = 0; kk < BK / 2; ++kk) {
-                    const int cur = kk & 1, nxt = cur ^ 1;
-                    if (kk + 1 < BK / 2) {
-                        av[nxt] = As[arow][2 * (kk + 1) + kh];
-#pragma unroll
-                        for (int t = 0; t < TN; ++t) bv[nxt][t] = Bs[2 * (kk + 1) + kh][bcol + t * 32];
-                    }
-                    __builtin_amdgcn_sched_barrier(0);       // keep the next step's reads ahead of these MFMAs
-#pragma unroll
-                    for (int t = 0; t < TN; ++t)
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cur], bv[cur][t], acc[t], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                }
-            }
-            __syncthreads();                  // stage s consumed; ridx[s&1] is free (its fetch ran an iteration ago)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // covers the asm index load above
-            if (more) stash(slot1);
-            if (more2 && tid < BM) ridx[s & 1][tid] = row_ok ? i2 : -1;       // stage s+2 reuses stage s' slot
-            __syncthreads();
-            slot = slot1;
-            slot1 = slot2; ch1 = ch2;
-            advance(slot2, ch2);
+            for (int t = 0; t < TN; ++t)
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x2f32(av[cur], bv[cur][t], acc[t], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
         }
-    }
-
-    float* dst = out;
-    bool direct = !to_partial;                   // rows go to their final place (through out_rows)
-    if (units) {
-        if (part > 0) { dst = extra + int64_t(part - 1) * n_out * cout; direct = false; }
-    } else if (to_partial) {
-        dst = out + int64_t(blockIdx.z) * n_out * cout;
-    }
-#pragma unroll
-    for (int t = 0; t < TN; ++t) {
-        const int col = n0 + (wn * TN + t) * 32 + (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = row0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (row < n_out && col < cout) {
-                const int orow = (direct && out_rows) ? out_rows[row] : row;
-                dst[int64_t(orow) * cout + col] = acc[t][r];
-            }
-        }
-    }
+    };
+    run_stages<BM>(sh, nbr, n_out, k_begin, (cin + BK - 1) / BK, wm, my_row, row_ok, fetch, stash, mfma);
+    store_part<TN>(out, extra, out_rows, gmask != nullptr, part, to_partial, row0, n0, wm, wn, n_out, cout, acc);
 }
 
 // ---------------------------------------------------------------------------------------
-// Split-bf16 variant of the pipelined kernel: identical tiling / pipeline / units logic, but the
+// Split-bf16 back end of the same pipeline (same tiling, prologue, stage loop and store): the
 // contraction runs on v_mfma_f32_32x32x16_bf16 (16x the fp32 MFMA rate).  Each fp32 operand is
 // split into three bf16 pieces (x = x1 + x2 + x3) and the six significant cross products are
 // accumulated in fp32 ("bf16x6"): fp32-level accuracy at 2.7x the fp32 MFMA throughput.  The
@@ -429,8 +473,7 @@ __global__ __launch_bounds__(256, 3) void spconv_fwd_x6_kernel(const float* __re
     static_assert(WM * WN == 4, "four waves per workgroup");
     constexpr int BM = 32 * WM;
     constexpr int BN = 32 * TN * WN;
-    constexpr int BK = 32;
-    constexpr int KC = 32;                       // offsets per block (k_per_split <= KC)
+    constexpr int BK = PIPE_BK;
     constexpr int NA = BM / 32;                  // A float4 per thread per stage
     constexpr int NBV = 3 * BN * 4;              // B: 3 planes x BN rows x 4 x (8 bf16 = 16 bytes)
     constexpr int NB = (NBV + 255) / 256;        // B 16-byte pieces per thread per stage
@@ -438,83 +481,17 @@ __global__ __launch_bounds__(256, 3) void spconv_fwd_x6_kernel(const float* __re
     constexpr int LDB = BK + 8;                  // bf16 B rows of 80 B:  aligned + conflict-free ds_read_b128
     __shared__ __attribute__((aligned(16))) float As[BM][LDA];
     __shared__ __attribute__((aligned(16))) __bf16 Bp[3][BN][LDB];
-    __shared__ int ridx[2][BM];                  // row indices of the next two stages (by stage parity)
-    __shared__ unsigned char gbits[KC][2];
-    __shared__ int klist[KC];
-    __shared__ int kgm[KC];
-    __shared__ int nact_s;
+    __shared__ OffsetLds<BM> sh;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave / WN, wn = wave % WN;
     const int row0 = blockIdx.x * BM;
     const int n0 = blockIdx.y * BN;
-    // Two ways to cut the offset loop across blockIdx.z:
-    //  * units mode (gmask given): part z takes the z-th group of `unit_k` ACTIVE offsets of this tile
-    //    (work per block is bounded and even; parts > 0 go to `extra`, summed in order by a fix-up pass);
-    //  * uniform mode: part z takes offsets [z*k_per_split, (z+1)*k_per_split) (small maps).
-    const bool units = gmask != nullptr;
     const int part = blockIdx.z;
-    const int k_begin = units ? 0 : part * k_per_split;
-    const int nk = units ? K : min(K, k_begin + k_per_split) - k_begin;     // <= KC
     const int my_row = row0 + tid;                               // meaningful for tid < BM
     const bool row_ok = tid < BM && my_row < n_out;
-    __shared__ uint32_t gm_s[4];
-
-    if (units) {
-        // ---- prologue from the precomputed 32-row group masks: no table scan
-        if (tid < 4) {
-            const int64_t g = int64_t(blockIdx.x) * WM + tid;
-            gm_s[tid] = (tid < WM && g * 32 < n_out) ? gmask[g] : 0u;
-        }
-        __syncthreads();
-        if (tid == 0) {
-            const uint32_t tm = gm_s[0] | gm_s[1] | gm_s[2] | gm_s[3];
-            int i = 0, n = 0;
-            for (int kk = 0; kk < nk; ++kk) {
-                if (!((tm >> kk) & 1u)) continue;
-                if (i >= part * unit_k && i < (part + 1) * unit_k) {
-                    klist[n] = kk;
-                    kgm[n] = int((gm_s[0] >> kk) & 1u) | (int((gm_s[1] >> kk) & 1u) << 1) |
-                             (int((gm_s[2] >> kk) & 1u) << 2) | (int((gm_s[3] >> kk) & 1u) << 3);
-                    ++n;
-                }
-                ++i;
-            }
-            nact_s = n;
-            if (part == 0 && blockIdx.y == 0) tile_parts[blockIdx.x] = (i + unit_k - 1) / unit_k;
-        }
-        __syncthreads();
-        if (part > 0 && nact_s == 0) return;     // this tile has no offsets left for part z
-    } else {
-    // ---- prologue: which offsets does this tile use, and which of its 32-row groups
-    for (int kk0 = 0; kk0 < nk; kk0 += 8) {
-        int idx[8];
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            idx[j] = -1;
-            if (row_ok && kk0 + j < nk) idx[j] = nbr ? nbr[int64_t(k_begin + kk0 + j) * n_out + my_row] : my_row;
-        }
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {
-            const unsigned long long b = __ballot(idx[j] >= 0);
-            if (lane == 0 && wave < 2 && kk0 + j < nk)
-                gbits[kk0 + j][wave] = (unsigned char)(((b & 0xFFFFFFFFull) != 0 ? 1 : 0) | ((b >> 32) != 0 ? 2 : 0));
-        }
-    }
-    __syncthreads();
-    if (tid == 0) {
-        int n = 0;
-        for (int kk = 0; kk < nk; ++kk) {
-            const int gm = int(gbits[kk][0]) | (int(gbits[kk][1]) << 2);
-            if (gm) { klist[n] = kk; kgm[n] = gm; ++n; }
-        }
-        nact_s = n;
-    }
-    __syncthreads();
-    }   // !units
-    const int nact = nact_s;
-    const int nchunk = (cin + BK - 1) / BK;
-    const int nstage = nact * nchunk;
+    int k_begin;
+    if (!offset_prologue<WM>(sh, gmask, nbr, tile_parts, n_out, K, part, k_per_split, unit_k, my_row, row_ok, k_begin)) return;
 
     f32x16 acc[TN];
 #pragma unroll
@@ -548,12 +525,12 @@ __global__ __launch_bounds__(256, 3) void spconv_fwd_x6_kernel(const float* __re
     const int w_k_stride = cout * cinp;
     unsigned pa_ok = 0;
     auto fetch = [&](int slot, int c0, int par) {
-        const int kk = __builtin_amdgcn_readfirstlane(klist[slot]), gm = kgm[slot];
+        const int kk = __builtin_amdgcn_readfirstlane(sh.klist[slot]), gm = sh.kgm[slot];
         const int c = c0 + a_sub * 4;
         pa_ok = 0;
         int ri[NA];
 #pragma unroll
-        for (int p = 0; p < NA; ++p) ri[p] = ridx[par][p * 32 + a_r];      // all LDS reads first: one wait
+        for (int p = 0; p < NA; ++p) ri[p] = sh.ridx[par][p * 32 + a_r];      // all LDS reads first: one wait
 #pragma unroll
         for (int p = 0; p < NA; ++p) {
             const bool ok = ((gm >> p) & 1) && ri[p] >= 0 && c < cin;
@@ -571,7 +548,7 @@ __global__ __launch_bounds__(256, 3) void spconv_fwd_x6_kernel(const float* __re
                                                     size_t(2u * (unsigned(b_off[h]) + s_off)));
     };
     auto stash = [&](int slot) {
-        const int gm = kgm[slot];
+        const int gm = sh.kgm[slot];
 #pragma unroll
         for (int p = 0; p < NA; ++p) {
             if ((gm >> p) & 1) {
@@ -591,144 +568,88 @@ __global__ __launch_bounds__(256, 3) void spconv_fwd_x6_kernel(const float* __re
         }
     };
 
-    if (nstage > 0) {
-        // stage s = (slot, chunk ch).  Gathered rows + weights are fetched one stage ahead into
-        // registers; the row indices of stage s+2 are fetched during stage s.  That index load is
-        // issued through inline asm: hipcc's waitcnt pass otherwise drains every load in flight
-        // around a loop-carried load destination (vmcnt is in-order), which serialises the prefetch.
-        // The value is consumed in the same iteration, after an explicit vmcnt(0).
-        auto advance = [&](int& sl, int& c) { if (++c == nchunk) { c = 0; ++sl; } };
-        int slot = 0;
-        int slot1 = 0, ch1 = 0; advance(slot1, ch1);
-        int slot2 = slot1, ch2 = ch1; advance(slot2, ch2);
-        auto idx_ptr = [&](int sl) -> const int32_t* {
-            return nbr + (row_ok ? int64_t(k_begin + klist[sl]) * n_out + my_row : 0);
+    auto mfma = [&]() {
+        // fp32-equivalent product from six bf16 MFMAs: x = x1 + x2 + x3 (8 mantissa bits each),
+        // a*b ~= a1b1 + a1b2 + a2b1 + a1b3 + a2b2 + a3b1  (dropped terms <= 2^-24 relative).
+        // The A rows of BOTH 16-deep k-steps are read up front (the two LDS round trips overlap) and the
+        // VALU split of step 1 is scheduled BETWEEN the MFMAs of step 0 (sched_group_barrier), so the
+        // matrix pipe is fed while the VALU converts instead of idling for ~40 VALU per k-step.
+        const int arow = wm * 32 + (lane & 31);
+        const int kq = 8 * (lane >> 5);
+        const int bcol = wn * TN * 32 + (lane & 31);
+        static_assert(BK == 32, "two k-steps per stage");
+        float fv[2][8];
+#pragma unroll
+        for (int ks = 0; ks < 2; ++ks) {
+            const float4 f0 = *reinterpret_cast<const float4*>(&As[arow][ks * 16 + kq]);
+            const float4 f1 = *reinterpret_cast<const float4*>(&As[arow][ks * 16 + kq + 4]);
+            fv[ks][0] = f0.x; fv[ks][1] = f0.y; fv[ks][2] = f0.z; fv[ks][3] = f0.w;
+            fv[ks][4] = f1.x; fv[ks][5] = f1.y; fv[ks][6] = f1.z; fv[ks][7] = f1.w;
+        }
+        bf16x8 a1[2], a2[2], a3[2];
+        auto split = [&](int ks) {
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                const __bf16 h1 = (__bf16)fv[ks][e];
+                const float r1 = fv[ks][e] - (float)h1;
+                const __bf16 h2 = (__bf16)r1;
+                const float r2 = r1 - (float)h2;
+                a1[ks][e] = h1; a2[ks][e] = h2; a3[ks][e] = (__bf16)r2;
+            }
         };
-        if (tid < BM) ridx[0][tid] = row_ok ? (nbr ? *idx_ptr(0) : my_row) : -1;
-        __syncthreads();
-        fetch(0, 0, 0);
-        const int i1 = nbr ? *idx_ptr(nstage > 1 ? slot1 : 0) : my_row;
-        stash(0);
-        if (tid < BM) ridx[1][tid] = row_ok ? i1 : -1;
-        __syncthreads();
-        for (int s = 0; s < nstage; ++s) {
-            const bool more = s + 1 < nstage, more2 = s + 2 < nstage;
-            if (more) fetch(slot1, ch1 * BK, (s + 1) & 1);            // loads in flight during the MFMAs
-            int i2 = my_row;
-            if (nbr) {
-                const int32_t* p2 = idx_ptr(more2 ? slot2 : slot);
-                asm volatile("global_load_dword %0, %1, off" : "=v"(i2) : "v"(p2) : "memory");
+        auto mfmas = [&](int ks) {
+#pragma unroll
+            for (int t = 0; t < TN; ++t) {
+                const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(&Bp[0][bcol + t * 32][ks * 16 + kq]);
+                const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(&Bp[1][bcol + t * 32][ks * 16 + kq]);
+                const bf16x8 b3 = *reinterpret_cast<const bf16x8*>(&Bp[2][bcol + t * 32][ks * 16 + kq]);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3[ks], b1, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[ks], b2, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[ks], b3, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[ks], b1, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[ks], b2, acc[t], 0, 0, 0);
+                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[ks], b1, acc[t], 0, 0, 0);
             }
-            if ((kgm[slot] >> wm) & 1) {
-                // fp32-equivalent product from six bf16 MFMAs: x = x1 + x2 + x3 (8 mantissa bits each),
-                // a*b ~= a1b1 + a1b2 + a2b1 + a1b3 + a2b2 + a3b1  (dropped terms <= 2^-24 relative).
-                // The A rows of BOTH 16-deep k-steps are read up front (the two LDS round trips overlap) and the
-                // VALU split of step 1 is scheduled BETWEEN the MFMAs of step 0 (sched_group_barrier), so the
-                // matrix pipe is fed while the VALU converts instead of idling for ~40 VALU per k-step.
-                const int arow = wm * 32 + (lane & 31);
-                const int kq = 8 * (lane >> 5);
-                const int bcol = wn * TN * 32 + (lane & 31);
-                static_assert(BK == 32, "two k-steps per stage");
-                float fv[2][8];
+        };
+        split(0);
+        // k-step 0: after the 2nd MFMA of each column block (and once more) convert one PAIR of step-1
+        // elements; sched_barrier pins the order so the VALU issues in the shadow of the running MFMAs
+        auto split_pair = [&](int pr) {
 #pragma unroll
-                for (int ks = 0; ks < 2; ++ks) {
-                    const float4 f0 = *reinterpret_cast<const float4*>(&As[arow][ks * 16 + kq]);
-                    const float4 f1 = *reinterpret_cast<const float4*>(&As[arow][ks * 16 + kq + 4]);
-                    fv[ks][0] = f0.x; fv[ks][1] = f0.y; fv[ks][2] = f0.z; fv[ks][3] = f0.w;
-                    fv[ks][4] = f1.x; fv[ks][5] = f1.y; fv[ks][6] = f1.z; fv[ks][7] = f1.w;
-                }
-                bf16x8 a1[2], a2[2], a3[2];
-                auto split = [&](int ks) {
-#pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const __bf16 h1 = (__bf16)fv[ks][e];
-                        const float r1 = fv[ks][e] - (float)h1;
-                        const __bf16 h2 = (__bf16)r1;
-                        const float r2 = r1 - (float)h2;
-                        a1[ks][e] = h1; a2[ks][e] = h2; a3[ks][e] = (__bf16)r2;
-                    }
-                };
-                auto mfmas = [&](int ks) {
-#pragma unroll
-                    for (int t = 0; t < TN; ++t) {
-                        const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(&Bp[0][bcol + t * 32][ks * 16 + kq]);
-                        const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(&Bp[1][bcol + t * 32][ks * 16 + kq]);
-                        const bf16x8 b3 = *reinterpret_cast<const bf16x8*>(&Bp[2][bcol + t * 32][ks * 16 + kq]);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3[ks], b1, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[ks], b2, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[ks], b3, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[ks], b1, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[ks], b2, acc[t], 0, 0, 0);
-                        acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[ks], b1, acc[t], 0, 0, 0);
-                    }
-                };
-                split(0);
-                // k-step 0: after the 2nd MFMA of each column block (and once more) convert one PAIR of step-1
-                // elements; sched_barrier pins the order so the VALU issues in the shadow of the running MFMAs
-                auto split_pair = [&](int pr) {
-#pragma unroll
-                    for (int e = 2 * pr; e < 2 * pr + 2; ++e) {
-                        const __bf16 h1 = (__bf16)fv[1][e];
-                        const float r1 = fv[1][e] - (float)h1;
-                        const __bf16 h2 = (__bf16)r1;
-                        const float r2 = r1 - (float)h2;
-                        a1[1][e] = h1; a2[1][e] = h2; a3[1][e] = (__bf16)r2;
-                    }
-                };
-                int pr = 0;
-#pragma unroll
-                for (int t = 0; t < TN; ++t) {
-                    const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(&Bp[0][bcol + t * 32][kq]);
-                    const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(&Bp[1][bcol + t * 32][kq]);
-                    const bf16x8 b3 = *reinterpret_cast<const bf16x8*>(&Bp[2][bcol + t * 32][kq]);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3[0], b1, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[0], b2, acc[t], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (pr < 4) split_pair(pr++);
-                    __builtin_amdgcn_sched_barrier(0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b3, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[0], b1, acc[t], 0, 0, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    if (TN < 4 && t < 4 - TN && pr < 4) split_pair(pr++);      // TN < 4: a second pair in the first blocks
-                    __builtin_amdgcn_sched_barrier(0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b2, acc[t], 0, 0, 0);
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b1, acc[t], 0, 0, 0);
-                }
-#pragma unroll
-                for (; pr < 4; ++pr) split_pair(pr);                         // TN = 1 / 2: the rest, not hidden
-                __builtin_amdgcn_sched_barrier(0);
-                mfmas(1);
+            for (int e = 2 * pr; e < 2 * pr + 2; ++e) {
+                const __bf16 h1 = (__bf16)fv[1][e];
+                const float r1 = fv[1][e] - (float)h1;
+                const __bf16 h2 = (__bf16)r1;
+                const float r2 = r1 - (float)h2;
+                a1[1][e] = h1; a2[1][e] = h2; a3[1][e] = (__bf16)r2;
             }
-            __syncthreads();                  // stage s consumed; ridx[s&1] is free (its fetch ran an iteration ago)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");          // covers the asm index load above
-            if (more) stash(slot1);
-            if (more2 && tid < BM) ridx[s & 1][tid] = row_ok ? i2 : -1;       // stage s+2 reuses stage s' slot
-            __syncthreads();
-            slot = slot1;
-            slot1 = slot2; ch1 = ch2;
-            advance(slot2, ch2);
+        };
+        int pr = 0;
+#pragma unroll
+        for (int t = 0; t < TN; ++t) {
+            const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(&Bp[0][bcol + t * 32][kq]);
+            const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(&Bp[1][bcol + t * 32][kq]);
+            const bf16x8 b3 = *reinterpret_cast<const bf16x8*>(&Bp[2][bcol + t * 32][kq]);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3[0], b1, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[0], b2, acc[t], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (pr < 4) split_pair(pr++);
+            __builtin_amdgcn_sched_barrier(0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b3, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[0], b1, acc[t], 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+            if (TN < 4 && t < 4 - TN && pr < 4) split_pair(pr++);      // TN < 4: a second pair in the first blocks
+            __builtin_amdgcn_sched_barrier(0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b2, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b1, acc[t], 0, 0, 0);
         }
-    }
-
-    float* dst = out;
-    bool direct = !to_partial;                   // rows go to their final place (through out_rows)
-    if (units) {
-        if (part > 0) { dst = extra + int64_t(part - 1) * n_out * cout; direct = false; }
-    } else if (to_partial) {
-        dst = out + int64_t(blockIdx.z) * n_out * cout;
-    }
 #pragma unroll
-    for (int t = 0; t < TN; ++t) {
-        const int col = n0 + (wn * TN + t) * 32 + (lane & 31);
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int row = row0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-            if (row < n_out && col < cout) {
-                const int orow = (direct && out_rows) ? out_rows[row] : row;
-                dst[int64_t(orow) * cout + col] = acc[t][r];
-            }
-        }
-    }
+        for (; pr < 4; ++pr) split_pair(pr);                         // TN = 1 / 2: the rest, not hidden
+        __builtin_amdgcn_sched_barrier(0);
+        mfmas(1);
+    };
+    run_stages<BM>(sh, nbr, n_out, k_begin, (cin + BK - 1) / BK, wm, my_row, row_ok, fetch, stash, mfma);
+    store_part<TN>(out, extra, out_rows, gmask != nullptr, part, to_partial, row0, n0, wm, wn, n_out, cout, acc);
 }
 
 __global__ void reduce_partial_rows_kernel(const float* __restrict__ partial, int S, int64_t n_out, int cout,
@@ -1181,31 +1102,68 @@ struct UnitsArgs {
     float* extra;
 };
 
-template <int WM, int WN, int TN>
-static void launch_fwd_pipe(const FwdPlan& p, hipStream_t st, const float* in, const float* W, const int32_t* nbr,
-                            const int32_t* out_rows, float* dst, int n_out, int K, int cin, int cout,
-                            const UnitsArgs& u) {
-    const int gz = u.gmask ? p.unit_parts : p.S;
-    hipLaunchKernelGGL((spconv_fwd_pipe_kernel<WM, WN, TN>), dim3(p.gx, p.gy, gz), dim3(256), 0, st, in, W, nbr,
-                       out_rows, u.gmask, u.tile_parts, dst, u.extra, n_out, K, cin, cout, p.kps,
-                       (!u.gmask && p.S > 1) ? 1 : 0, p.unit_k);
+// How a table kernel's launch uses the workspace: units mode (tile_parts + extra parts), a uniform split
+// (S partials, `dst` = workspace) or neither (`dst` = out).
+struct TableLaunch {
+    float* dst;
+    UnitsArgs ua;
+    bool use_units;
+    int gz, to_partial;
+};
+
+static int table_workspace(const char* fn, const FwdPlan& p, const uint32_t* gmask, const int32_t* nbr, float* out,
+                           int64_t n_out, int cout, void* ws, size_t ws_bytes, bool pipe_ok, TableLaunch& t) {
+    t.dst = out;
+    t.ua = {nullptr, nullptr, nullptr};
+    t.use_units = gmask && nbr && p.unit_parts > 1 && pipe_ok;      // same rule osn_spconv_fwd_ws_bytes sizes for
+    if (t.use_units) {
+        const size_t need = units_ws_bytes(p, n_out, cout);
+        OSN_REQUIRE(ws && ws_bytes >= need, OSN_E_WS, "%s: workspace %zu < %zu", fn, ws_bytes, need);
+        t.ua.gmask = gmask;
+        t.ua.tile_parts = static_cast<int32_t*>(ws);
+        t.ua.extra = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up(size_t(p.gx) * 4, 256));
+    } else if (p.S > 1) {
+        const size_t need = size_t(p.S) * size_t(n_out) * size_t(cout) * 4;
+        OSN_REQUIRE(ws && ws_bytes >= need, OSN_E_WS, "%s: workspace %zu < %zu", fn, ws_bytes, need);
+        t.dst = static_cast<float*>(ws);
+    }
+    t.gz = t.use_units ? p.unit_parts : p.S;
+    t.to_partial = (!t.use_units && p.S > 1) ? 1 : 0;
+    return OSN_OK;
 }
 
-template <int WM, int WN, int TN>
-static void launch_fwd_x6(const FwdPlan& p, hipStream_t st, const float* in, const __bf16* Wp, const int32_t* nbr,
-                          const int32_t* out_rows, float* dst, int n_out, int K, int cin, int cinp, int cout,
-                          const UnitsArgs& u) {
-    const int gz = u.gmask ? p.unit_parts : p.S;
-    hipLaunchKernelGGL((spconv_fwd_x6_kernel<WM, WN, TN>), dim3(p.gx, p.gy, gz), dim3(256), 0, st, in, Wp, nbr,
-                       out_rows, u.gmask, u.tile_parts, dst, u.extra, n_out, K, cin, cinp, cout, p.kps,
-                       (!u.gmask && p.S > 1) ? 1 : 0, p.unit_k);
+// units mode: add parts 1.. of every tile to `out`; uniform split: sum the S partials into `out`
+static int table_tail(const FwdPlan& p, const TableLaunch& t, const int32_t* out_rows, float* out, int64_t n_out, int cout,
+                      hipStream_t st) {
+    if (!t.use_units && p.S <= 1) return OSN_OK;
+    int g = int(cdiv(n_out * cout, 256));
+    if (g > 4096) g = 4096;
+    if (t.use_units)
+        hipLaunchKernelGGL(fixup_units_kernel, dim3(g), dim3(256), 0, st, t.ua.extra, t.ua.tile_parts, p.bm, n_out, cout,
+                           out_rows, out);
+    else
+        hipLaunchKernelGGL(reduce_partial_rows_kernel, dim3(g), dim3(256), 0, st, t.dst, p.S, n_out, cout, out_rows, out);
+    OSN_LAUNCH_CHECK();
+    return OSN_OK;
 }
 
-template <int WM, int WN, int TN, int BK>
-static void launch_fwd(const FwdPlan& p, hipStream_t st, const float* in, const float* W, const int32_t* nbr,
-                       const int32_t* out_rows, float* dst, int n_out, int K, int cin, int cout) {
-    hipLaunchKernelGGL((spconv_fwd_kernel<WM, WN, TN, BK>), dim3(p.gx, p.gy, p.S), dim3(256), 0, st, in, W, nbr,
-                       out_rows, dst, n_out, K, cin, cout, p.kps, p.S > 1 ? 1 : 0);
+// The plan's (cfg, tn) as compile-time tile parameters: f(Tile<WM, WN, TN>{}).
+template <int WM_, int WN_, int TN_>
+struct Tile {
+    static constexpr int WM = WM_, WN = WN_, TN = TN_;
+};
+
+template <class F>
+static void for_tile(const FwdPlan& p, F&& f) {
+    switch (p.cfg * 10 + p.tn) {
+        case 1: f(Tile<4, 1, 1>{}); break;
+        case 2: f(Tile<4, 1, 2>{}); break;
+        case 3: f(Tile<4, 1, 3>{}); break;
+        case 4: f(Tile<4, 1, 4>{}); break;
+        case 11: f(Tile<2, 2, 1>{}); break;
+        case 12: f(Tile<2, 2, 2>{}); break;
+        default: f(Tile<1, 4, 1>{}); break;
+    }
 }
 
 extern "C" int osn_spconv_fwd(const float* in, const float* W, const int32_t* nbr, const int32_t* out_rows,
@@ -1219,71 +1177,26 @@ extern "C" int osn_spconv_fwd(const float* in, const float* W, const int32_t* nb
     OSN_REQUIRE(nbr || K == 1, OSN_E_ARG, "osn_spconv_fwd: nbr may be null only for K == 1 (identity map)");
     OSN_REQUIRE(aligned16(in) && aligned16(W) && aligned16(out), OSN_E_ARG, "osn_spconv_fwd: pointers must be 16-byte aligned");
     FwdPlan p = plan_fwd(n_out, K, cin, cout);
-    float* dst = out;
-    UnitsArgs ua = {nullptr, nullptr, nullptr};
+    // the pipelined kernel needs 16-byte row segments; without it the simple kernel runs and ignores gmask
     const bool pipe_ok = cin > 4 && (cin & 3) == 0 && (cout & 3) == 0 && p.kps <= 32;
-    const bool use_units = gmask && nbr && p.unit_parts > 1 && pipe_ok;
-    if (use_units) {
-        const size_t need = units_ws_bytes(p, n_out, cout);
-        OSN_REQUIRE(ws && ws_bytes >= need, OSN_E_WS, "osn_spconv_fwd: workspace %zu < %zu", ws_bytes, need);
-        ua.gmask = gmask;
-        ua.tile_parts = static_cast<int32_t*>(ws);
-        ua.extra = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up(size_t(p.gx) * 4, 256));
-    } else if (p.S > 1) {
-        const size_t need = size_t(p.S) * size_t(n_out) * size_t(cout) * 4;
-        OSN_REQUIRE(ws && ws_bytes >= need, OSN_E_WS, "osn_spconv_fwd: workspace %zu < %zu", ws_bytes, need);
-        dst = static_cast<float*>(ws);
-    }
+    TableLaunch t;
+    if (int e = table_workspace("osn_spconv_fwd", p, gmask, nbr, out, n_out, cout, ws, ws_bytes, pipe_ok, t)) return e;
     const int n = int(n_out);
-    const bool pipe = pipe_ok;
-    if (pipe) {
-        switch (p.cfg * 10 + p.tn) {
-            case 1: launch_fwd_pipe<4, 1, 1>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout, ua); break;
-            case 2: launch_fwd_pipe<4, 1, 2>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout, ua); break;
-            case 3: launch_fwd_pipe<4, 1, 3>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout, ua); break;
-            case 4: launch_fwd_pipe<4, 1, 4>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout, ua); break;
-            case 11: launch_fwd_pipe<2, 2, 1>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout, ua); break;
-            case 12: launch_fwd_pipe<2, 2, 2>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout, ua); break;
-            default: launch_fwd_pipe<1, 4, 1>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout, ua); break;
-        }
-    } else if (cin <= 4) {
-        // stem convolution (3 -> 32): 4-wide channel chunks
-        switch (p.cfg * 10 + p.tn) {
-            case 1: launch_fwd<4, 1, 1, 4>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-            case 2: launch_fwd<4, 1, 2, 4>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-            case 3: launch_fwd<4, 1, 3, 4>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-            case 4: launch_fwd<4, 1, 4, 4>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-            case 11: launch_fwd<2, 2, 1, 4>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-            case 12: launch_fwd<2, 2, 2, 4>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-            default: launch_fwd<1, 4, 1, 4>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-        }
-    } else {
-        switch (p.cfg * 10 + p.tn) {
-            case 1: launch_fwd<4, 1, 1, 32>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-            case 2: launch_fwd<4, 1, 2, 32>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-            case 3: launch_fwd<4, 1, 3, 32>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-            case 4: launch_fwd<4, 1, 4, 32>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-            case 11: launch_fwd<2, 2, 1, 32>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-            case 12: launch_fwd<2, 2, 2, 32>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-            default: launch_fwd<1, 4, 1, 32>(p, st, in, W, nbr, out_rows, dst, n, K, cin, cout); break;
-        }
-    }
+    const dim3 grid(p.gx, p.gy, t.gz), block(256);
+    for_tile(p, [&](auto tile) {
+        using T = decltype(tile);
+        if (pipe_ok)
+            hipLaunchKernelGGL((spconv_fwd_pipe_kernel<T::WM, T::WN, T::TN>), grid, block, 0, st, in, W, nbr, out_rows,
+                               t.ua.gmask, t.ua.tile_parts, t.dst, t.ua.extra, n, K, cin, cout, p.kps, t.to_partial, p.unit_k);
+        else if (cin <= 4)      // stem convolution (3 -> 32): 4-wide channel chunks
+            hipLaunchKernelGGL((spconv_fwd_kernel<T::WM, T::WN, T::TN, 4>), grid, block, 0, st, in, W, nbr, out_rows, t.dst, n,
+                               K, cin, cout, p.kps, t.to_partial);
+        else
+            hipLaunchKernelGGL((spconv_fwd_kernel<T::WM, T::WN, T::TN, 32>), grid, block, 0, st, in, W, nbr, out_rows, t.dst,
+                               n, K, cin, cout, p.kps, t.to_partial);
+    });
     OSN_LAUNCH_CHECK();
-    if (use_units) {
-        const int64_t total = n_out * cout;
-        int g = int(cdiv(total, 256));
-        if (g > 4096) g = 4096;
-        hipLaunchKernelGGL(fixup_units_kernel, dim3(g), dim3(256), 0, st, ua.extra, ua.tile_parts, p.bm, n_out, cout,
-                           out_rows, out);
-        OSN_LAUNCH_CHECK();
-    } else if (p.S > 1) {
-        const int64_t total = n_out * cout;
-        int g = int(cdiv(total, 256));
-        if (g > 4096) g = 4096;
-        hipLaunchKernelGGL(reduce_partial_rows_kernel, dim3(g), dim3(256), 0, st, dst, p.S, n_out, cout, out_rows, out);
-        OSN_LAUNCH_CHECK();
-    }
-    return OSN_OK;
+    return table_tail(p, t, out_rows, out, n_out, cout, st);
 }
 
 extern "C" size_t osn_weight_prep_x6_bytes(int K, int cin, int cout, int for_dgrad) {
@@ -1336,45 +1249,19 @@ extern "C" int osn_spconv_fwd_x6(const float* in, const void* Wp, const int32_t*
     OSN_REQUIRE(aligned16(in) && aligned16(Wp) && aligned16(out), OSN_E_ARG, "osn_spconv_fwd_x6: pointers must be 16-byte aligned");
     FwdPlan p = plan_fwd(n_out, K, cin, cout);
     OSN_REQUIRE(p.kps <= 32, OSN_E_ARG, "osn_spconv_fwd_x6: more than 32 offsets per block (K=%d)", K);
-    float* dst = out;
-    UnitsArgs ua = {nullptr, nullptr, nullptr};
-    const bool use_units = gmask && nbr && p.unit_parts > 1;        // same rule osn_spconv_fwd_ws_bytes sizes for
-    if (use_units) {
-        const size_t need = units_ws_bytes(p, n_out, cout);
-        OSN_REQUIRE(ws && ws_bytes >= need, OSN_E_WS, "osn_spconv_fwd_x6: workspace %zu < %zu", ws_bytes, need);
-        ua.gmask = gmask;
-        ua.tile_parts = static_cast<int32_t*>(ws);
-        ua.extra = reinterpret_cast<float*>(static_cast<char*>(ws) + align_up(size_t(p.gx) * 4, 256));
-    } else if (p.S > 1) {
-        const size_t need = size_t(p.S) * size_t(n_out) * size_t(cout) * 4;
-        OSN_REQUIRE(ws && ws_bytes >= need, OSN_E_WS, "osn_spconv_fwd_x6: workspace %zu < %zu", ws_bytes, need);
-        dst = static_cast<float*>(ws);
-    }
+    TableLaunch t;
+    if (int e = table_workspace("osn_spconv_fwd_x6", p, gmask, nbr, out, n_out, cout, ws, ws_bytes, true, t)) return e;
     const int n = int(n_out);
     const int cinp = (cin + 31) / 32 * 32;
     const __bf16* wp = static_cast<const __bf16*>(Wp);
-    switch (p.cfg * 10 + p.tn) {
-        case 1: launch_fwd_x6<4, 1, 1>(p, st, in, wp, nbr, out_rows, dst, n, K, cin, cinp, cout, ua); break;
-        case 2: launch_fwd_x6<4, 1, 2>(p, st, in, wp, nbr, out_rows, dst, n, K, cin, cinp, cout, ua); break;
-        case 3: launch_fwd_x6<4, 1, 3>(p, st, in, wp, nbr, out_rows, dst, n, K, cin, cinp, cout, ua); break;
-        case 4: launch_fwd_x6<4, 1, 4>(p, st, in, wp, nbr, out_rows, dst, n, K, cin, cinp, cout, ua); break;
-        case 11: launch_fwd_x6<2, 2, 1>(p, st, in, wp, nbr, out_rows, dst, n, K, cin, cinp, cout, ua); break;
-        case 12: launch_fwd_x6<2, 2, 2>(p, st, in, wp, nbr, out_rows, dst, n, K, cin, cinp, cout, ua); break;
-        default: launch_fwd_x6<1, 4, 1>(p, st, in, wp, nbr, out_rows, dst, n, K, cin, cinp, cout, ua); break;
-    }
+    for_tile(p, [&](auto tile) {
+        using T = decltype(tile);
+        hipLaunchKernelGGL((spconv_fwd_x6_kernel<T::WM, T::WN, T::TN>), dim3(p.gx, p.gy, t.gz), dim3(256), 0, st, in, wp, nbr,
+                           out_rows, t.ua.gmask, t.ua.tile_parts, t.dst, t.ua.extra, n, K, cin, cinp, cout, p.kps, t.to_partial,
+                           p.unit_k);
+    });
     OSN_LAUNCH_CHECK();
-    const int64_t total = n_out * cout;
-    int g = int(cdiv(total, 256));
-    if (g > 4096) g = 4096;
-    if (use_units) {
-        hipLaunchKernelGGL(fixup_units_kernel, dim3(g), dim3(256), 0, st, ua.extra, ua.tile_parts, p.bm, n_out, cout,
-                           out_rows, out);
-        OSN_LAUNCH_CHECK();
-    } else if (p.S > 1) {
-        hipLaunchKernelGGL(reduce_partial_rows_kernel, dim3(g), dim3(256), 0, st, dst, p.S, n_out, cout, out_rows, out);
-        OSN_LAUNCH_CHECK();
-    }
-    return OSN_OK;
+    return table_tail(p, t, out_rows, out, n_out, cout, st);
 }
 
 extern "C" int osn_weight_transpose(const float* W, int K, int cin, int cout, int flip, float* Wt,

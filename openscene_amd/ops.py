@@ -398,16 +398,9 @@ def _w3(weight):
     return weight.unsqueeze(0) if weight.dim() == 2 else weight
 
 
-def spconv_fwd(feats, weight, nbr, n_out, out_rows=None, gmask=None):
-    """out[o] = sum_k feats[nbr[k,o]] @ weight[k].  nbr None <=> K == 1 identity map.
-    (out_rows, gmask) come with a tile-ordered table from kmap_sort."""
+def _table_conv(kind, lib, feats, wptr, nbr, n_out, out_rows, gmask, K, cin, cout):
+    """What both table kernels share: table check, output, workspace, profiler bracket and the call of osn_<kind>."""
     dev = feats.device
-    lib = _prep(dev)
-    feats = _f32c(feats, "features")
-    w = _f32c(_w3(weight), "weight")
-    K, cin, cout = w.shape
-    if feats.shape[1] != cin:
-        raise ValueError("features have %d channels, kernel expects %d" % (feats.shape[1], cin))
     if nbr is not None:
         if nbr.dtype != torch.int32 or nbr.shape != (K, n_out):
             raise ValueError("nbr must be int32 [%d, %d], got %s %s" % (K, n_out, nbr.dtype, tuple(nbr.shape)))
@@ -417,13 +410,25 @@ def spconv_fwd(feats, weight, nbr, n_out, out_rows=None, gmask=None):
     out = torch.empty((n_out, cout), dtype=torch.float32, device=dev)
     wsb = _cached("osn_spconv_fwd_ws_bytes", n_out, K, cin, cout)
     ws = _ws(wsb, dev) if wsb else None
-    tok = _prof_start("spconv_fwd", dev, n_in=feats.shape[0], n_out=n_out, K=K, cin=cin, cout=cout)
+    tok = _prof_start(kind, dev, n_in=feats.shape[0], n_out=n_out, K=K, cin=cin, cout=cout)
     with _Dev(dev):
-        check(lib.osn_spconv_fwd(_p(feats), _p(w), _p(nbr), _p(out_rows), _p(gmask), _p(out), n_out, K, cin, cout,
-                                 _p(ws), int(wsb), _stream(dev)), "osn_spconv_fwd")
+        check(getattr(lib, "osn_" + kind)(_p(feats), wptr, _p(nbr), _p(out_rows), _p(gmask), _p(out), n_out, K, cin, cout,
+                                          _p(ws), int(wsb), _stream(dev)), "osn_" + kind)
     if tok is not None:
         _profiler.stop(tok)
     return out
+
+
+def spconv_fwd(feats, weight, nbr, n_out, out_rows=None, gmask=None):
+    """out[o] = sum_k feats[nbr[k,o]] @ weight[k].  nbr None <=> K == 1 identity map.
+    (out_rows, gmask) come with a tile-ordered table from kmap_sort."""
+    lib = _prep(feats.device)
+    feats = _f32c(feats, "features")
+    w = _f32c(_w3(weight), "weight")
+    K, cin, cout = w.shape
+    if feats.shape[1] != cin:
+        raise ValueError("features have %d channels, kernel expects %d" % (feats.shape[1], cin))
+    return _table_conv("spconv_fwd", lib, feats, _p(w), nbr, n_out, out_rows, gmask, K, cin, cout)
 
 
 def weight_prep_x6(weight, flip=False, for_dgrad=False):
@@ -457,29 +462,13 @@ def weight_prep_x6_pair(weight, flip=False):
 
 def spconv_fwd_x6(feats, wp, nbr, n_out, out_rows=None, gmask=None):
     """Split-bf16 convolution: out[o] = sum_k feats[nbr[k,o]] @ B[k], B given as weight_prep_x6 planes."""
-    dev = feats.device
-    lib = _prep(dev)
+    lib = _prep(feats.device)
     feats = _f32c(feats, "features")
     _three, K, cout, cp = wp.shape
     cin = feats.shape[1]
     if (cin + 31) // 32 * 32 != cp:
         raise ValueError("features have %d channels, prepared weights expect <= %d" % (cin, cp))
-    if nbr is not None:
-        if nbr.dtype != torch.int32 or nbr.shape != (K, n_out):
-            raise ValueError("nbr must be int32 [%d, %d], got %s %s" % (K, n_out, nbr.dtype, tuple(nbr.shape)))
-        nbr = nbr.contiguous()
-    elif K != 1 or feats.shape[0] != n_out:
-        raise ValueError("nbr=None is the identity map and needs K == 1 and n_in == n_out")
-    out = torch.empty((n_out, cout), dtype=torch.float32, device=dev)
-    wsb = _cached("osn_spconv_fwd_ws_bytes", n_out, K, cin, cout)
-    ws = _ws(wsb, dev) if wsb else None
-    tok = _prof_start("spconv_fwd_x6", dev, n_in=feats.shape[0], n_out=n_out, K=K, cin=cin, cout=cout)
-    with _Dev(dev):
-        check(lib.osn_spconv_fwd_x6(_p(feats), _p(wp), _p(nbr), _p(out_rows), _p(gmask), _p(out), n_out, K, cin, cout,
-                                    _p(ws), int(wsb), _stream(dev)), "osn_spconv_fwd_x6")
-    if tok is not None:
-        _profiler.stop(tok)
-    return out
+    return _table_conv("spconv_fwd_x6", lib, feats, _p(wp), nbr, n_out, out_rows, gmask, K, cin, cout)
 
 
 # ------------------------------------------------- second-generation convolution (tile lists)

@@ -258,6 +258,74 @@ def test_out_rows_indirection_and_determinism():
     assert (gc - ga).abs().max().item() <= 1e-5 * ga.abs().max().item()
 
 
+_TABLES = {}
+
+
+def random_table(n_out, K=27):
+    """-> (table on the CPU, on the GPU, its kmap_sort triple): a random int32 [K, n_out] neighbour table over n_out input
+    rows, about 30 % of the entries set; cached per row count and never modified."""
+    if n_out not in _TABLES:
+        from openscene_amd import ops
+        g = torch.Generator().manual_seed(n_out * 31 + K)
+        nbr = torch.randint(0, n_out, (K, n_out), generator=g, dtype=torch.int32)
+        nbr[torch.rand(K, n_out, generator=g) < 0.7] = -1
+        dn = nbr.to(dev())
+        _TABLES[n_out] = (nbr, dn, ops.kmap_sort(dn, ops.kmap_count(dn)))
+    return _TABLES[n_out]
+
+
+# launch mode, n_out, cin, cout, kernels, the plan (WM, WN, TN, BK, S, workgroups) that puts the case where its name says
+TABLE_KERNEL_CASES = [
+    ("units", 49100, 32, 32, "both", (4, 1, 1, 32, 1, 384)),        # 128-row tiles, TN = 1 / 2 / 3: 384 x 1 workgroups
+    ("units", 49100, 32, 64, "both", (4, 1, 2, 32, 1, 384)),
+    ("units", 49100, 32, 96, "both", (4, 1, 3, 32, 1, 384)),
+    ("units", 32768, 32, 256, "both", (4, 1, 4, 32, 1, 512)),       # TN = 4: 256 x 2
+    ("units", 24600, 32, 64, "both", (2, 2, 1, 32, 1, 385)),        # 64-row tiles, TN = 1
+    ("units", 4100, 32, 768, "both", (2, 2, 2, 32, 1, 390)),        # 64-row tiles, TN = 2: 65 x 6
+    ("units", 3100, 32, 512, "both", (1, 4, 1, 32, 1, 388)),        # 32-row tiles: 97 x 4, ragged last tile
+    ("split", 200, 48, 128, "both", (1, 4, 1, 32, 14, 98)),         # uniform split; cin % 32 != 0: chunk tail, padded planes
+    ("split", 1, 32, 32, "both", (4, 1, 1, 32, 14, 14)),            # uniform split of a single row (one column tile => the 128-row instance)
+    ("plain", 49100, 32, 96, "both", (4, 1, 3, 32, 1, 384)),        # the units table without gmask
+    ("plain", 49100, 32, 20, "x6", (4, 1, 1, 32, 1, 384)),          # column tail in the split-bf16 weight staging
+]
+
+
+@pytest.mark.parametrize("mode,n_out,cin,cout,kernels,plan", TABLE_KERNEL_CASES,
+                         ids=["%s-%d-%d-%d" % c[:4] for c in TABLE_KERNEL_CASES])
+def test_table_kernels_in_every_launch_mode_and_tile(mode, n_out, cin, cout, kernels, plan):
+    """The two output-stationary table kernels (fp32 MFMA: ops.spconv_fwd, split-bf16: ops.spconv_fwd_x6) share one offset
+    prologue, stage pipeline and store; here each runs directly, on random 27-offset tables, in units mode (tile-ordered table,
+    gmask, rows back through out_rows), with a uniform offset split and plain, through all seven tile instantiations; against
+    the float64 oracle at the file's bound, and bitwise reproducible.  The planner's answer is asserted first, so a case cannot
+    drift into another mode unnoticed; in units mode the workspace size must say that a tile is cut into 4 parts
+    (27 offsets, 8 active offsets per part)."""
+    from openscene_amd import ops
+    K = 27
+    d = dev()
+    assert ops.spconv_fwd_plan(n_out, K, cin, cout) == plan
+    nbr_cpu, nbr, (order, tbl, gm) = random_table(n_out)
+    if mode == "units":
+        gx = -(-n_out // (32 * plan[0]))
+        wsb = int(ops._cached("osn_spconv_fwd_ws_bytes", n_out, K, cin, cout))
+        assert plan[4] == 1 and plan[5] >= 384 and 1 + (wsb - (gx * 4 + 255) // 256 * 256) // (n_out * cout * 4) == 4
+        args = dict(nbr=tbl, n_out=n_out, out_rows=order, gmask=gm)
+    else:
+        assert (plan[4] > 1) == (mode == "split")
+        args = dict(nbr=nbr, n_out=n_out)
+    g = torch.Generator().manual_seed(n_out + 7 * cin + cout)
+    feats = torch.randn(n_out, cin, generator=g)
+    w = torch.randn(K, cin, cout, generator=g) / np.sqrt(cin * K * 0.3)
+    ref = so.sparse_conv(feats.double(), w.double(), nbr_cpu.numpy())
+    fd, wd = feats.to(d), w.to(d)
+    runs = [("split-bf16", lambda: ops.spconv_fwd_x6(fd, ops.weight_prep_x6(wd), **args))]
+    if kernels == "both":
+        runs.append(("fp32", lambda: ops.spconv_fwd(fd, wd, **args)))
+    for name, run in runs:
+        out = run()
+        close(out, ref, "%s kernel, %s mode" % (name, mode))
+        assert torch.equal(out, run()), "%s kernel, %s mode: not bitwise reproducible" % (name, mode)
+
+
 @pytest.mark.parametrize("kind,key,bm", [("big", (1, 1, 3), None), ("big", (1, 2, 2), 88), ("mid", (1, 1, 3), 36),
                                          ("small", (2, 1, 2), 32), ("mid", (1, 1, 5), 80)])
 def test_tile_lists_match_the_spec(kind, key, bm):
