@@ -577,6 +577,28 @@ int osn_bank_search(const void* bank_f16, int64_t n, int d, const int64_t* scene
                     const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
                     int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
 
+/* The same bank at one byte per element: a row x (X[inds_reverse] of run/evaluate.py:290, float32, or float16 widened
+ * exactly) is stored as d OCP e4m3fn codes and one exponent byte e; its stored value is v_i = float(code_i) * 2^e.
+ *   amax = max |x_i|.  A non-finite element: e = 0 and every code of the row is an e4m3 NaN (code & 0x7F == 0x7F).
+ *   amax == 0: e = 0.  Otherwise e = the smallest integer >= -120 with amax * 2^-e <= 448 (-120 <= e <= 120).
+ *   code_i = e4m3fn(x_i * 2^-e): the scaling is exact in float32, the conversion one round-to-nearest-even that keeps
+ *   the sign of zero and never saturates.
+ * osn_bank_append_fp8: X float32 (x_is_f16 = 0) or float16 (1) [n_rows, d]; d % 16 == 0; codes uint8 [.., d] and exps
+ *   int8 [..] receive rows row0 .. row0 + n; gather and err as osn_bank_append.  One wave per row; rows up to 2048 wide
+ *   are read once, wider rows read their tail twice.
+ * osn_bank_search_fp8: osn_bank_search over (codes, exps) -- the remaining arguments, the workspace
+ *   (osn_bank_search_ws_bytes), selection, padding, counts, NaN order and repeatability are osn_bank_search's.  With c the
+ *   row of code values, t an fp16 query and acc = sum c_i t_i (fp16 MFMA, exact widening of the codes, fp32 accumulate):
+ *     normalize = 1   run/evaluate.py:305,310  acc * 2^e / (sqrt(sum c_i^2) * 2^e + 1e-5), rounded to fp16 once
+ *     normalize = 0   run/evaluate.py:291      acc * 2^e, rounded to fp16 once
+ *   A zero row scores exactly 0, a NaN row NaN for every query.                                                      */
+int osn_bank_append_fp8(const void* X, int x_is_f16, int64_t n_rows, const int64_t* gather, int64_t n, int d,
+                        uint8_t* codes, int8_t* exps, int64_t row0, int32_t* err, osn_stream_t stream);
+int osn_bank_search_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int d, const int64_t* scene_offsets,
+                        int n_scenes, int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
+                        const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
+                        int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
+
 /* ---- objects in heat-maps (csrc/objects.hip) -------------------------------------------------------------------- *
  * What the README "Applications" do with a heat-map -- rare object search in a 3D scene database, image-based 3-D object
  * detection, interactive object search -- needs objects, not points: WHERE the matches are, how many, how large, how

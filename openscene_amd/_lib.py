@@ -118,6 +118,8 @@ PROTOTYPES = {
     "osn_bank_check": (_i32, [_vp, _vp]),
     "osn_bank_search_ws_bytes": (_sz, [_i64, _i32, _i32, _i32, _i64]),
     "osn_bank_search": (_i32, [_vp, _i64, _i32, _vp, _i32, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "osn_bank_append_fp8": (_i32, [_vp, _i32, _i64, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp]),
+    "osn_bank_search_fp8": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "osn_objects_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "osn_objects_records_bytes": (_sz, [_i64]),
     "osn_objects_label": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _sz, _c.POINTER(_i64), _vp]),

@@ -17,6 +17,11 @@
 // lowest indices are: per-chunk counts of key == K give every chunk its rank offset, a block scan orders the chunk's own.
 // A final rank-by-counting sort of the <= 128 candidates writes (score desc, index asc).  No floating-point atomics:
 // results are bitwise repeatable.
+//
+// The fp8 bank (osn_bank_append_fp8 / osn_bank_search_fp8) stores a row as d OCP e4m3fn codes and one exponent byte e:
+// value = code * 2^e, e the smallest integer >= -120 with max|x| * 2^-e <= 448.  The append is one wave per row (the
+// row stays in registers between the max and the conversion); the heat pass streams 16 codes per 16-byte load, widens
+// them to fp16 (exact) on the way into LDS and runs the same MFMA loop; 2^e enters in the epilogue.  Pass 2 is shared.
 #include "common.h"
 
 namespace osn {
@@ -206,6 +211,296 @@ __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restri
             }
         }
         __syncthreads();                                    // the tile is the next column group's row buffer
+    }
+}
+
+// ------------------------------------------------------------------------------------------------------ fp8 bank
+typedef _Float16 half2 __attribute__((ext_vector_type(2)));
+
+constexpr int Q8_RG = 2;           // 16-element groups of a row a lane keeps in registers: rows up to 64 * 16 * Q8_RG = 2048
+                                   // wide are read from HBM once, wider rows read their tail twice (max, then conversion)
+
+template <bool F16>
+__device__ inline void q8_load(const void* __restrict__ X, int64_t at, float (&v)[16]) {
+    if (F16) {
+        const uint4* p = reinterpret_cast<const uint4*>(static_cast<const _Float16*>(X) + at);
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const half8 h = __builtin_bit_cast(half8, p[j]);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) v[8 * j + k] = (float)h[k];
+        }
+    } else {
+        const float4* p = reinterpret_cast<const float4*>(static_cast<const float*>(X) + at);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+            const float4 f = p[j];
+            v[4 * j] = f.x; v[4 * j + 1] = f.y; v[4 * j + 2] = f.z; v[4 * j + 3] = f.w;
+        }
+    }
+}
+
+__device__ inline uint32_t q8_absmax(const float (&v)[16], uint32_t m) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) {                          // |x| as bits: orders as the value does, inf and NaN on top
+        const uint32_t b = __float_as_uint(v[k]) & 0x7FFFFFFFu;
+        m = b > m ? b : m;
+    }
+    return m;
+}
+
+// 16 values * 2^-e -> 16 e4m3fn codes (v_cvt_pk_fp8_f32: round to nearest even, never saturating here: |v * s| <= 448)
+__device__ inline uint4 q8_codes(const float (&v)[16], float s, bool bad) {
+    uint32_t w[4];
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        int c = 0;
+        c = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j] * s, v[4 * j + 1] * s, c, false);
+        c = __builtin_amdgcn_cvt_pk_fp8_f32(v[4 * j + 2] * s, v[4 * j + 3] * s, c, true);
+        w[j] = bad ? 0x7F7F7F7Fu : uint32_t(c);
+    }
+    return make_uint4(w[0], w[1], w[2], w[3]);
+}
+
+// one wave per row: lane l holds the 16-element groups l, l + 64, ... of the row; ng = d / 16 groups
+template <bool F16>
+__global__ __launch_bounds__(256) void bank_append_fp8_kernel(const void* __restrict__ X, int64_t n_rows, const int64_t* __restrict__ g,
+                                                              int64_t n, int ng, uint8_t* __restrict__ codes, int8_t* __restrict__ exps,
+                                                              int32_t* __restrict__ err) {
+    const int lane = threadIdx.x & 63;
+    const int64_t d = int64_t(ng) * 16;
+    for (int64_t p = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6); p < n; p += int64_t(gridDim.x) * 4) {
+        const int64_t r = g ? g[p] : p;
+        if (r < 0 || r >= n_rows) {                          // (the whole wave) nothing is read or written for this row
+            if (lane == 0) atomicOr(err, BANK_E_GATHER);
+            continue;
+        }
+        float v[Q8_RG][16];
+        uint32_t amax = 0;
+#pragma unroll
+        for (int j = 0; j < Q8_RG; ++j) {
+            const int grp = lane + 64 * j;
+            if (grp < ng) {
+                q8_load<F16>(X, r * d + grp * 16, v[j]);
+                amax = q8_absmax(v[j], amax);
+            }
+        }
+        for (int grp = lane + 64 * Q8_RG; grp < ng; grp += 64) {
+            float t[16];
+            q8_load<F16>(X, r * d + grp * 16, t);
+            amax = q8_absmax(t, amax);
+        }
+#pragma unroll
+        for (int m = 32; m >= 1; m >>= 1) {
+            const uint32_t o = __shfl_xor(amax, m, 64);
+            amax = o > amax ? o : amax;
+        }
+        // amax = 1.M * 2^(E - 127) = m * 2^x with m = 1.M / 2 in [0.5, 1), x = E - 126: e = x - 9 if m <= 0.875, else x - 8
+        const bool bad = amax >= 0x7F800000u;
+        const int E = int(amax >> 23);
+        int e = E - 135 + ((amax & 0x7FFFFFu) > 0x600000u ? 1 : 0);
+        if (E == 0 || e < -120) e = -120;                    // (a float32 subnormal maximum lies below 448 * 2^-120)
+        if (amax == 0 || bad) e = 0;
+        const float s = __uint_as_float(uint32_t(127 - e) << 23);          // 2^-e, exact: 7 <= 127 - e <= 247
+#pragma unroll
+        for (int j = 0; j < Q8_RG; ++j) {
+            const int grp = lane + 64 * j;
+            if (grp < ng) *reinterpret_cast<uint4*>(codes + p * d + grp * 16) = q8_codes(v[j], s, bad);
+        }
+        for (int grp = lane + 64 * Q8_RG; grp < ng; grp += 64) {
+            float t[16];
+            q8_load<F16>(X, r * d + grp * 16, t);
+            *reinterpret_cast<uint4*>(codes + p * d + grp * 16) = q8_codes(t, s, bad);
+        }
+        if (lane == 0) exps[p] = int8_t(e);
+    }
+}
+
+// pass 1 over code rows.  A chunk is 128 features = 128 bytes of a row (8 lanes x 16 bytes, 32 rows per sweep); TWO code
+// chunks are in flight in registers, so a workgroup has the 32 KB outstanding that heat_kernel has with its one 256-byte
+// chunk (the query chunk, an L2 hit, stays one ahead).
+// Two workgroups per CU: the second register stage and the conversion need 194 / 250 VGPRs (one / two column tiles); held to
+// the 168 of three workgroups the kernel spills inside the loop and measured 0.81x of the fp16 pass at 8 x 150 k x 768 x 32
+// where this shape measured 0.67x.
+// The LDS tiles, the MFMA loop and the way the scores leave are heat_kernel's.
+template <int CT, int WGS>
+__global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __restrict__ B, const int8_t* __restrict__ E,
+                                                            const _Float16* __restrict__ T, _Float16* __restrict__ heat,
+                                                            _Float16* __restrict__ heatT, int64_t ldT, int64_t n, int d, int q,
+                                                            int normalize) {
+    __shared__ __attribute__((aligned(16))) _Float16 Xs[S_BM][S_LD];
+    __shared__ __attribute__((aligned(16))) _Float16 Ts[CT * 32][S_LD];
+    __shared__ float rden[S_BM];
+    __shared__ float rscale[S_BM];                          // 2^e of the row
+    _Float16(*Sc)[S_LD] = Xs;
+
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int64_t row0 = int64_t(blockIdx.x) * S_BM;
+    const int xq = tid & 7, xr = tid >> 3;                  // 8 lanes x 16 codes = one row's 128-byte chunk; 32 rows per sweep
+    constexpr int NPS = S_BM / 32;
+    float ss[NPS];
+#pragma unroll
+    for (int ps = 0; ps < NPS; ++ps) ss[ps] = 0.f;
+    if (tid < S_BM) {
+        const int64_t row = row0 + tid < n ? row0 + tid : n - 1;
+        rscale[tid] = __uint_as_float(uint32_t(127 + int(E[row])) << 23);
+    }
+
+    for (int cg0 = 0; cg0 < q; cg0 += 32 * CT) {
+        const bool sumsq = normalize && cg0 == 0;
+        f32x16 acc[CT];
+#pragma unroll
+        for (int t = 0; t < CT; ++t)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+        // all loads unconditional from clamped addresses, as in heat_kernel
+        uint4 pxa[NPS], pxb[NPS];                           // code chunks c + 1 and c + 2 while the MFMAs of chunk c run
+        uint4 pt[2 * CT];                                   // the query chunk c + 1 (from L2)
+        auto fetch_t = [&](int d0) {
+#pragma unroll
+            for (int j = 0; j < 2 * CT; ++j) {
+                const int f = tid + 256 * j;
+                const int trow = f >> 4, ch = f & 15;
+                const int col = cg0 + trow;
+                const bool ok = col < q && d0 + ch * 8 < d;
+                pt[j] = *reinterpret_cast<const uint4*>(ok ? T + int64_t(col) * d + d0 + ch * 8 : T);
+            }
+        };
+        auto fetch_x = [&](uint4(&px)[NPS], int d0) {
+#pragma unroll
+            for (int ps = 0; ps < NPS; ++ps) {
+                const int64_t row = row0 + ps * 32 + xr;
+                const bool ok = row < n && d0 + xq * 16 < d;
+                px[ps] = *reinterpret_cast<const uint4*>(ok ? B + row * d + d0 + xq * 16 : B);
+            }
+        };
+        auto stash = [&](const uint4(&px)[NPS], int d0) {
+#pragma unroll
+            for (int ps = 0; ps < NPS; ++ps) {
+                const int row = ps * 32 + xr;
+                const bool ok = row0 + row < n && d0 + xq * 16 < d;
+                uint4 v = px[ps];
+                if (!ok) v = make_uint4(0, 0, 0, 0);
+                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+                half2 h[8];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {               // e4m3 -> fp16 is exact (v_cvt_scalef32_pk_f16_fp8, scale 1)
+                    h[2 * j] = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[j], 1.0f, false);
+                    h[2 * j + 1] = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[j], 1.0f, true);
+                }
+                if (sumsq) {
+                    float s = 0.f;
+#pragma unroll
+                    for (int j = 0; j < 8; ++j) s = __builtin_amdgcn_fdot2(h[j], h[j], s, false);
+                    ss[ps] += s;
+                }
+                uint4 lo, hi;
+                lo.x = __builtin_bit_cast(uint32_t, h[0]); lo.y = __builtin_bit_cast(uint32_t, h[1]);
+                lo.z = __builtin_bit_cast(uint32_t, h[2]); lo.w = __builtin_bit_cast(uint32_t, h[3]);
+                hi.x = __builtin_bit_cast(uint32_t, h[4]); hi.y = __builtin_bit_cast(uint32_t, h[5]);
+                hi.z = __builtin_bit_cast(uint32_t, h[6]); hi.w = __builtin_bit_cast(uint32_t, h[7]);
+                *reinterpret_cast<uint4*>(&Xs[row][xq * 16]) = lo;
+                *reinterpret_cast<uint4*>(&Xs[row][xq * 16 + 8]) = hi;
+            }
+#pragma unroll
+            for (int j = 0; j < 2 * CT; ++j) {
+                const int f = tid + 256 * j;
+                const int trow = f >> 4, ch = f & 15;
+                const bool ok = cg0 + trow < q && d0 + ch * 8 < d;
+                uint4 v = pt[j];
+                if (!ok) v = make_uint4(0, 0, 0, 0);
+                *reinterpret_cast<uint4*>(&Ts[trow][ch * 8]) = v;
+            }
+        };
+        auto mfmas = [&]() {
+            const int arow = wave * 32 + (lane & 31);
+            const int kh = 8 * (lane >> 5);
+            half8 fa[2], fb[2][CT];
+            auto frags = [&](int ks, int w) {
+                fa[w] = *reinterpret_cast<const half8*>(&Xs[arow][ks * 16 + kh]);
+#pragma unroll
+                for (int t = 0; t < CT; ++t)
+                    fb[w][t] = *reinterpret_cast<const half8*>(&Ts[t * 32 + (lane & 31)][ks * 16 + kh]);
+            };
+            frags(0, 0);
+#pragma unroll
+            for (int ks = 0; ks < S_DK / 16; ++ks) {
+                __builtin_amdgcn_sched_barrier(0);
+                if (ks + 1 < S_DK / 16) frags(ks + 1, (ks + 1) & 1);
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int t = 0; t < CT; ++t)
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks & 1], fb[ks & 1][t], acc[t], 0, 0, 0);
+            }
+            __builtin_amdgcn_sched_barrier(0);
+        };
+        fetch_t(0);
+        fetch_x(pxa, 0);
+        fetch_x(pxb, S_DK);                                 // (past the end: the first 16 bytes of B / T, never staged)
+        stash(pxa, 0);
+        __syncthreads();
+        for (int d0 = 0; d0 < d; d0 += 2 * S_DK) {
+            __builtin_amdgcn_sched_barrier(0);
+            fetch_t(d0 + S_DK);
+            fetch_x(pxa, d0 + 2 * S_DK);
+            __builtin_amdgcn_sched_barrier(0);
+            mfmas();
+            __syncthreads();
+            if (d0 + S_DK >= d) break;
+            stash(pxb, d0 + S_DK);
+            __syncthreads();
+            __builtin_amdgcn_sched_barrier(0);
+            fetch_t(d0 + 2 * S_DK);
+            fetch_x(pxb, d0 + 3 * S_DK);
+            __builtin_amdgcn_sched_barrier(0);
+            mfmas();
+            __syncthreads();
+            if (d0 + 2 * S_DK < d) stash(pxa, d0 + 2 * S_DK);
+            __syncthreads();
+        }
+        if (sumsq) {                                        // the 8 lanes that share a row: ||c|| * 2^e + 1e-5
+#pragma unroll
+            for (int ps = 0; ps < NPS; ++ps) {
+                float s = ss[ps];
+#pragma unroll
+                for (int m = 1; m < 8; m <<= 1) s += __shfl_xor(s, m, 64);
+                if (xq == 0) rden[ps * 32 + xr] = sqrtf(s) * rscale[ps * 32 + xr] + 1e-5f;
+            }
+            __syncthreads();
+        }
+        // ---- epilogue: acc * 2^e (exact), divide, round to fp16 once, tile -> LDS [column][row]
+#pragma unroll
+        for (int t = 0; t < CT; ++t) {
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                const int lrow = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                float v = acc[t][r] * rscale[lrow];
+                if (normalize) v /= rden[lrow];
+                Sc[t * 32 + (lane & 31)][lrow] = (_Float16)v;
+            }
+        }
+        __syncthreads();
+        for (int e = tid; e < CT * 32 * (S_BM / 8); e += 256) {
+            const int col = e >> 4, v8 = e & 15;
+            const int gc = cg0 + col;
+            if (gc >= q) continue;
+            const int64_t r = row0 + 8 * v8;
+            _Float16* dst = heatT + int64_t(gc) * ldT + r;
+            if (r + 8 <= n) {
+                *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(&Sc[col][8 * v8]);
+            } else {
+                for (int j = 0; j < 8; ++j)
+                    if (r + j < n) dst[j] = Sc[col][8 * v8 + j];
+            }
+        }
+        if (heat) {
+            const int qn = (q - cg0) < 32 * CT ? (q - cg0) : 32 * CT;
+            for (int e = tid; e < S_BM * qn; e += 256) {
+                const int r = e / qn, c = e - r * qn;
+                if (row0 + r < n) heat[(row0 + r) * q + cg0 + c] = Sc[c][r];
+            }
+        }
+        __syncthreads();
     }
 }
 
@@ -487,6 +782,39 @@ static SearchWs search_ws(int64_t n, int S, int Q, int k, int64_t max_scene_rows
     return w;
 }
 
+// pass 2 on the workspace's heatT (written by either heat kernel): the k best rows of every (scene, query), counts
+static int select_pass(const SearchWs& w, char* p, int64_t n, const int64_t* scene_offsets, int n_scenes, int64_t max_scene_rows,
+                       int q, int k, const float* thresholds, void* topk_scores_f16, int64_t* topk_points, int64_t* counts,
+                       int32_t* err, hipStream_t st) {
+    const _Float16* heatT = reinterpret_cast<const _Float16*>(p + w.heatT);
+    uint32_t* hist = reinterpret_cast<uint32_t*>(p + w.hist);
+    uint32_t* state = reinterpret_cast<uint32_t*>(p + w.state);
+    uint32_t* chunk_eq = reinterpret_cast<uint32_t*>(p + w.chunk_eq);
+    uint2* cand = reinterpret_cast<uint2*>(p + w.cand);
+    const size_t items = size_t(n_scenes) * size_t(q);
+    OSN_HIP(hipMemsetAsync(hist, 0, items * 256 * 4, st));
+    if (counts) OSN_HIP(hipMemsetAsync(counts, 0, items * 8, st));
+    hipLaunchKernelGGL(search_check_kernel, dim3(unsigned(cdiv(n_scenes, 256))), dim3(256), 0, st, scene_offsets, n_scenes, n,
+                       max_scene_rows, err);
+    const int mc = sel_max_chunks(max_scene_rows);
+    const dim3 cgrid(unsigned(mc > 0 ? mc : 1), unsigned(n_scenes), unsigned(q));
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
+    _Float16* ts = static_cast<_Float16*>(topk_scores_f16);
+    hipLaunchKernelGGL(select_hist_kernel<0>, cgrid, dim3(SEL_T), 0, st, heatT, w.ldT, scene_offsets, n, max_scene_rows, q, mc,
+                       counts ? thresholds : nullptr, cnt, hist, state, chunk_eq);
+    hipLaunchKernelGGL(select_pick_kernel<0>, dim3(unsigned(items)), dim3(256), 0, st, hist, state, k);
+    hipLaunchKernelGGL(select_hist_kernel<1>, cgrid, dim3(SEL_T), 0, st, heatT, w.ldT, scene_offsets, n, max_scene_rows, q, mc,
+                       nullptr, cnt, hist, state, chunk_eq);
+    hipLaunchKernelGGL(select_pick_kernel<1>, dim3(unsigned(items)), dim3(256), 0, st, hist, state, k);
+    hipLaunchKernelGGL(select_hist_kernel<2>, cgrid, dim3(SEL_T), 0, st, heatT, w.ldT, scene_offsets, n, max_scene_rows, q, mc,
+                       nullptr, cnt, hist, state, chunk_eq);
+    hipLaunchKernelGGL(select_collect_kernel, cgrid, dim3(SEL_T), 0, st, heatT, w.ldT, scene_offsets, n, max_scene_rows, q, mc, k,
+                       state, chunk_eq, cand);
+    hipLaunchKernelGGL(select_sort_kernel, dim3(unsigned(items)), dim3(128), 0, st, state, cand, k, ts, topk_points);
+    OSN_LAUNCH_CHECK();
+    return OSN_OK;
+}
+
 }  // namespace osn
 
 using namespace osn;
@@ -546,10 +874,6 @@ extern "C" int osn_bank_search(const void* bank_f16, int64_t n, int d, const int
     OSN_REQUIRE(ws && aligned16(ws) && ws_bytes >= w.total, OSN_E_WS, "osn_bank_search: workspace too small (%zu < %zu)", ws_bytes, w.total);
     char* p = static_cast<char*>(ws);
     _Float16* heatT = reinterpret_cast<_Float16*>(p + w.heatT);
-    uint32_t* hist = reinterpret_cast<uint32_t*>(p + w.hist);
-    uint32_t* state = reinterpret_cast<uint32_t*>(p + w.state);
-    uint32_t* chunk_eq = reinterpret_cast<uint32_t*>(p + w.chunk_eq);
-    uint2* cand = reinterpret_cast<uint2*>(p + w.cand);
     if (n > 0) {
         const dim3 grid(unsigned(cdiv(n, S_BM))), block(256);
         const _Float16* B = static_cast<const _Float16*>(bank_f16);
@@ -560,26 +884,58 @@ extern "C" int osn_bank_search(const void* bank_f16, int64_t n, int d, const int
         OSN_LAUNCH_CHECK();
     }
     if (n_scenes == 0) return OSN_OK;
-    const size_t items = size_t(n_scenes) * size_t(q);
-    OSN_HIP(hipMemsetAsync(hist, 0, items * 256 * 4, st));
-    if (counts) OSN_HIP(hipMemsetAsync(counts, 0, items * 8, st));
-    hipLaunchKernelGGL(search_check_kernel, dim3(unsigned(cdiv(n_scenes, 256))), dim3(256), 0, st, scene_offsets, n_scenes, n,
-                       max_scene_rows, err);
-    const int mc = sel_max_chunks(max_scene_rows);
-    const dim3 cgrid(unsigned(mc > 0 ? mc : 1), unsigned(n_scenes), unsigned(q));
-    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
-    _Float16* ts = static_cast<_Float16*>(topk_scores_f16);
-    hipLaunchKernelGGL(select_hist_kernel<0>, cgrid, dim3(SEL_T), 0, st, heatT, w.ldT, scene_offsets, n, max_scene_rows, q, mc,
-                       counts ? thresholds : nullptr, cnt, hist, state, chunk_eq);
-    hipLaunchKernelGGL(select_pick_kernel<0>, dim3(unsigned(items)), dim3(256), 0, st, hist, state, k);
-    hipLaunchKernelGGL(select_hist_kernel<1>, cgrid, dim3(SEL_T), 0, st, heatT, w.ldT, scene_offsets, n, max_scene_rows, q, mc,
-                       nullptr, cnt, hist, state, chunk_eq);
-    hipLaunchKernelGGL(select_pick_kernel<1>, dim3(unsigned(items)), dim3(256), 0, st, hist, state, k);
-    hipLaunchKernelGGL(select_hist_kernel<2>, cgrid, dim3(SEL_T), 0, st, heatT, w.ldT, scene_offsets, n, max_scene_rows, q, mc,
-                       nullptr, cnt, hist, state, chunk_eq);
-    hipLaunchKernelGGL(select_collect_kernel, cgrid, dim3(SEL_T), 0, st, heatT, w.ldT, scene_offsets, n, max_scene_rows, q, mc, k,
-                       state, chunk_eq, cand);
-    hipLaunchKernelGGL(select_sort_kernel, dim3(unsigned(items)), dim3(128), 0, st, state, cand, k, ts, topk_points);
+    return select_pass(w, p, n, scene_offsets, n_scenes, max_scene_rows, q, k, thresholds, topk_scores_f16, topk_points, counts, err, st);
+}
+
+extern "C" int osn_bank_append_fp8(const void* X, int x_is_f16, int64_t n_rows, const int64_t* gather, int64_t n, int d,
+                                   uint8_t* codes, int8_t* exps, int64_t row0, int32_t* err, osn_stream_t stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    OSN_REQUIRE(n >= 0 && n_rows >= 0 && row0 >= 0 && d >= 16 && (d & 15) == 0, OSN_E_ARG,
+                "osn_bank_append_fp8: need n, n_rows, row0 >= 0 and d %% 16 == 0 (n=%lld n_rows=%lld row0=%lld d=%d)", (long long)n,
+                (long long)n_rows, (long long)row0, d);
+    OSN_REQUIRE(x_is_f16 == 0 || x_is_f16 == 1, OSN_E_ARG, "osn_bank_append_fp8: x_is_f16=%d (0 or 1)", x_is_f16);
+    OSN_REQUIRE(err, OSN_E_ARG, "osn_bank_append_fp8: null err word");
+    OSN_REQUIRE(gather || n <= n_rows, OSN_E_ARG, "osn_bank_append_fp8: %lld rows wanted of %lld", (long long)n, (long long)n_rows);
+    if (n == 0) return OSN_OK;
+    OSN_REQUIRE(X && codes && exps, OSN_E_ARG, "osn_bank_append_fp8: null pointer");
+    OSN_REQUIRE(aligned16(X) && aligned16(codes), OSN_E_ARG, "osn_bank_append_fp8: X and the codes must be 16-byte aligned");
+    uint8_t* out = codes + row0 * int64_t(d);
+    const int64_t blocks = cdiv(n, 4);
+    const dim3 grid(unsigned(blocks < (int64_t(1) << 20) ? blocks : (int64_t(1) << 20)));
+    if (x_is_f16) hipLaunchKernelGGL(bank_append_fp8_kernel<true>, grid, dim3(256), 0, st, X, n_rows, gather, n, d / 16, out, exps + row0, err);
+    else hipLaunchKernelGGL(bank_append_fp8_kernel<false>, grid, dim3(256), 0, st, X, n_rows, gather, n, d / 16, out, exps + row0, err);
     OSN_LAUNCH_CHECK();
     return OSN_OK;
+}
+
+extern "C" int osn_bank_search_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int d, const int64_t* scene_offsets,
+                                   int n_scenes, int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
+                                   const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
+                                   int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    OSN_REQUIRE(n >= 0 && d >= 16 && (d & 15) == 0 && q >= 1 && q <= 1024, OSN_E_ARG,
+                "osn_bank_search_fp8: need n >= 0, d %% 16 == 0 and 1 <= q <= 1024 (n=%lld d=%d q=%d)", (long long)n, d, q);
+    OSN_REQUIRE(n_scenes >= 0 && n_scenes <= 65535 && max_scene_rows >= 0 && max_scene_rows < (int64_t(1) << 31), OSN_E_ARG,
+                "osn_bank_search_fp8: n_scenes=%d (0 .. 65535) max_scene_rows=%lld (< 2^31)", n_scenes, (long long)max_scene_rows);
+    OSN_REQUIRE((normalize == 0 || normalize == 1) && k >= 1 && k <= 128, OSN_E_ARG,
+                "osn_bank_search_fp8: normalize=%d (0 or 1) k=%d (1 .. 128)", normalize, k);
+    OSN_REQUIRE(queries_f16 && aligned16(queries_f16), OSN_E_ARG, "osn_bank_search_fp8: queries must be non-null and 16-byte aligned");
+    OSN_REQUIRE(n == 0 || (codes && exps && aligned16(codes)), OSN_E_ARG,
+                "osn_bank_search_fp8: codes and exponents must be non-null, the codes 16-byte aligned");
+    OSN_REQUIRE(n_scenes == 0 || (scene_offsets && topk_scores_f16 && topk_points && err), OSN_E_ARG, "osn_bank_search_fp8: null pointer");
+    OSN_REQUIRE(!counts || thresholds, OSN_E_ARG, "osn_bank_search_fp8: counts need thresholds");
+    const SearchWs w = search_ws(n, n_scenes, q, k, max_scene_rows);
+    OSN_REQUIRE(ws && aligned16(ws) && ws_bytes >= w.total, OSN_E_WS, "osn_bank_search_fp8: workspace too small (%zu < %zu)", ws_bytes, w.total);
+    char* p = static_cast<char*>(ws);
+    _Float16* heatT = reinterpret_cast<_Float16*>(p + w.heatT);
+    if (n > 0) {
+        const dim3 grid(unsigned(cdiv(n, S_BM))), block(256);
+        const _Float16* T = static_cast<const _Float16*>(queries_f16);
+        _Float16* heat = static_cast<_Float16*>(heat_f16);
+        if (q <= 32) hipLaunchKernelGGL((heat_fp8_kernel<1, 2>), grid, block, 0, st, codes, exps, T, heat, heatT, w.ldT, n, d, q, normalize);
+        else hipLaunchKernelGGL((heat_fp8_kernel<2, 2>), grid, block, 0, st, codes, exps, T, heat, heatT, w.ldT, n, d, q, normalize);
+        OSN_LAUNCH_CHECK();
+    }
+    if (n_scenes == 0) return OSN_OK;
+    return select_pass(w, p, n, scene_offsets, n_scenes, max_scene_rows, q, k, thresholds, topk_scores_f16, topk_points, counts, err, st);
 }

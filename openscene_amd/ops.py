@@ -1424,6 +1424,105 @@ def bank_search(bank, scene_offsets, queries, k=16, thresholds=None, normalize=T
     return heat, top_s, top_p, counts
 
 
+def bank_append_fp8(codes, exps, row0, feats, err, gather=None):
+    """Rows row0 : row0 + n of an fp8 bank = feats[gather], quantised: e4m3fn codes (uint8 [rows, d]) and one exponent
+    byte per row (int8 [rows]), value = code * 2^e with e the smallest integer >= -120 that brings the row's largest
+    magnitude to 448 or below (include/openscene_amd.h states the format bit for bit).  feats float32 or float16
+    [rows, d], d % 16 == 0.  gather and err as bank_append.  -> n."""
+    dev = feats.device
+    lib = _prep(dev)
+    if feats.dtype not in (torch.float32, torch.float16):
+        raise TypeError("features must be float32 or float16 (got %s)" % feats.dtype)
+    if feats.dim() != 2:
+        raise ValueError("features must be [rows, dim]")
+    feats = feats.contiguous()
+    d = feats.shape[1]
+    if d < 16 or d % 16:
+        raise ValueError("the feature dim must be a multiple of 16 (got %d)" % d)
+    if (codes.dtype != torch.uint8 or codes.dim() != 2 or codes.device != dev or not codes.is_contiguous()
+            or codes.shape[1] != d):
+        raise ValueError("codes must be a contiguous uint8 [rows, %d] matrix on the features' device" % d)
+    if (exps.dtype != torch.int8 or exps.dim() != 1 or exps.device != dev or not exps.is_contiguous()
+            or exps.shape[0] != codes.shape[0]):
+        raise ValueError("exponents must be a contiguous int8 [%d] vector on the features' device" % codes.shape[0])
+    if gather is not None:
+        if gather.dim() != 1 or gather.device != dev:
+            raise ValueError("gather must be a vector on the features' device")
+        gather = (gather if gather.dtype == torch.int64 else gather.long()).contiguous()
+    n = gather.shape[0] if gather is not None else feats.shape[0]
+    row0 = int(row0)
+    if row0 < 0 or row0 + n > codes.shape[0]:
+        raise ValueError("rows [%d, %d) do not fit a bank of %d rows" % (row0, row0 + n, codes.shape[0]))
+    if err.dtype != torch.int32 or err.numel() != 1 or err.device != dev:
+        raise ValueError("err must be an int32 [1] tensor on the features' device")
+    with _Dev(dev):
+        check(lib.osn_bank_append_fp8(_p(feats), int(feats.dtype == torch.float16), feats.shape[0], _p(gather), n, d, _p(codes),
+                                      _p(exps), row0, _p(err), _stream(dev)), "osn_bank_append_fp8")
+    return n
+
+
+def bank_search_fp8(codes, exps, scene_offsets, queries, k=16, thresholds=None, normalize=True, want_heat=False,
+                    max_scene_rows=None, err=None):
+    """bank_search over an fp8 bank: codes uint8 [N, d] (e4m3fn), exps int8 [N], d % 16 == 0; the score is taken on the
+    stored values code * 2^e.  Everything else -- arguments, results, selection order -- is bank_search's."""
+    dev = codes.device
+    lib = _prep(dev)
+    if codes.dtype != torch.uint8:
+        raise TypeError("codes must be uint8 (got %s)" % codes.dtype)
+    if exps.dtype != torch.int8:
+        raise TypeError("exponents must be int8 (got %s)" % exps.dtype)
+    if queries.dtype != torch.float16:
+        raise TypeError("queries must be float16 (util/util.py:41-44 produces fp16)")
+    if codes.dim() != 2 or not codes.is_contiguous():
+        raise ValueError("codes must be a contiguous [rows, dim] matrix")
+    if exps.dim() != 1 or exps.shape[0] != codes.shape[0] or exps.device != dev or not exps.is_contiguous():
+        raise ValueError("exponents must be a contiguous [%d] vector on the codes' device" % codes.shape[0])
+    if queries.dim() != 2 or queries.shape[1] != codes.shape[1]:
+        raise ValueError("queries must be [Q, %d] (got %s)" % (codes.shape[1], tuple(queries.shape)))
+    if queries.device != dev:
+        raise ValueError("queries must be on the bank's device")
+    queries = queries.contiguous()
+    n, d = codes.shape
+    q = queries.shape[0]
+    k = int(k)
+    if not 1 <= k <= BANK_MAX_K:
+        raise ValueError("k must be in 1 .. %d (got %d)" % (BANK_MAX_K, k))
+    if not 1 <= q <= BANK_MAX_Q:
+        raise ValueError("1 .. %d queries per call (got %d)" % (BANK_MAX_Q, q))
+    if d < 16 or d % 16:
+        raise ValueError("the feature dim must be a multiple of 16 (got %d)" % d)
+    if scene_offsets.dtype != torch.int64 or scene_offsets.dim() != 1 or scene_offsets.shape[0] < 1 or scene_offsets.device != dev:
+        raise ValueError("scene_offsets must be an int64 [S + 1] vector on the bank's device")
+    scene_offsets = scene_offsets.contiguous()
+    s = scene_offsets.shape[0] - 1
+    if thresholds is not None:
+        if thresholds.dtype != torch.float32 or tuple(thresholds.shape) != (q,) or thresholds.device != dev:
+            raise ValueError("thresholds must be a float32 [%d] vector on the bank's device" % q)
+        thresholds = thresholds.contiguous()
+    if max_scene_rows is None:
+        max_scene_rows = int((scene_offsets[1:] - scene_offsets[:-1]).max().item()) if s > 0 else 0
+        max_scene_rows = min(max(max_scene_rows, 0), n)
+    max_scene_rows = int(max_scene_rows)
+    own_err = err is None
+    if own_err:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif err.dtype != torch.int32 or err.numel() != 1 or err.device != dev:
+        raise ValueError("err must be an int32 [1] tensor on the bank's device")
+    heat = torch.empty((n, q), dtype=torch.float16, device=dev) if want_heat else None
+    top_s = torch.empty((s, q, k), dtype=torch.float16, device=dev)
+    top_p = torch.empty((s, q, k), dtype=torch.int64, device=dev)
+    counts = torch.empty((s, q), dtype=torch.int64, device=dev) if thresholds is not None else None
+    wsb = _cached("osn_bank_search_ws_bytes", n, s, q, k, max_scene_rows)
+    ws = _ws(wsb, dev)
+    with _Dev(dev):
+        check(lib.osn_bank_search_fp8(_p(codes), _p(exps), n, d, _p(scene_offsets), s, max_scene_rows, _p(queries), q,
+                                      int(bool(normalize)), k, _p(thresholds), _p(heat), _p(top_s), _p(top_p), _p(counts), _p(err),
+                                      _p(ws), ws.numel(), _stream(dev)), "osn_bank_search_fp8")
+    if own_err and s > 0:
+        bank_check(err)
+    return heat, top_s, top_p, counts
+
+
 # --------------------------------------------------------------------- objects
 OBJECTS_MAX_M = 64
 OBJECTS_MAX_POINTS = 1 << 22          # keeps score_sum inside int64 for raw scores at the fp16 maximum

@@ -5,13 +5,14 @@ The reference forms the features (``run/evaluate.py:290`` distill, ``:285`` fusi
 against CLIP text embeddings (``:291``, ``:305,310``) and can save them per scene (``save_feature_as_numpy``,
 ``:232-235,328-330``: ``<scene>_openscene_feat_<feature_type>.npy``).  Here:
 
-    FeatureBank      one growing fp16 matrix of per-point features, many scenes, on the device
+    FeatureBank      one growing matrix of per-point features, many scenes, on the device: fp16, or fp8 (e4m3fn codes
+                     with one power-of-two exponent per row) at half the bytes
     search           heat-map [N, Q] + the k best points of every scene + counts over a threshold: ONE pass over the bank
     heat_map         the one-scene convenience
     SearchResult     .rank_scenes(q, by=...) orders the scenes for a query; .find_objects(grid, thresholds) groups the
                      heat-map into ranked objects (openscene_amd.objects)
 
-Kernels: csrc/search.hip through ops.bank_append / ops.bank_search; no CPU path.
+Kernels: csrc/search.hip through ops.bank_append / ops.bank_search and their _fp8 twins; no CPU path.
 """
 import numpy as np
 import torch
@@ -21,19 +22,34 @@ from . import ops
 
 
 class FeatureBank:
-    """A growing fp16 [rows, dim] matrix on `device` holding the per-point features of many scenes back to back.
+    """A growing [rows, dim] matrix on `device` holding the per-point features of many scenes back to back.
 
+    dtype    "fp16": the rows as ``run/evaluate.py:291`` scores them (``.half()``), two bytes per element.
+             "fp8": one byte per element -- OCP e4m3fn codes (uint8 [rows, dim]) and one power-of-two exponent per row
+             (int8 [rows]); a stored value is ``code * 2^e`` (include/openscene_amd.h states the format bit for bit).
+             Twice the scenes in the same memory, half the bytes for the search to stream.
     offsets  python list, S + 1 ascending row offsets (scene i is rows offsets[i] : offsets[i + 1])
     names    python list of the S scene names (unique)
     """
 
-    def __init__(self, dim, device, capacity_rows=1 << 16):
+    def __init__(self, dim, device, capacity_rows=1 << 16, dtype="fp16"):
         dim = int(dim)
+        if dtype not in ("fp16", "fp8"):
+            raise ValueError('dtype must be "fp16" or "fp8" (got %r)' % (dtype,))
+        if dtype == "fp8" and (dim < 16 or dim % 16):
+            raise ValueError("dim of an fp8 bank must be a positive multiple of 16 (got %d)" % dim)
         if dim < 8 or dim % 8:
             raise ValueError("dim must be a positive multiple of 8 (got %d)" % dim)
         self.dim = dim
+        self.dtype = dtype
         self.device = torch.device(device)
-        self._data = torch.empty((max(int(capacity_rows), 1), dim), dtype=torch.float16, device=self.device)
+        cap = max(int(capacity_rows), 1)
+        if dtype == "fp16":
+            self._data = torch.empty((cap, dim), dtype=torch.float16, device=self.device)
+        else:
+            self._data = None
+            self._codes = torch.empty((cap, dim), dtype=torch.uint8, device=self.device)
+            self._exps = torch.empty((cap,), dtype=torch.int8, device=self.device)
         self.offsets = [0]
         self.names = []
         self._offsets_dev = None
@@ -49,17 +65,55 @@ class FeatureBank:
 
     @property
     def capacity_rows(self):
-        return self._data.shape[0]
+        return (self._data if self.dtype == "fp16" else self._codes).shape[0]
+
+    @property
+    def nbytes(self):
+        """Bytes of the filled rows."""
+        return self.rows * (2 * self.dim if self.dtype == "fp16" else self.dim + 1)
+
+    def _need(self, dtype, what):
+        if self.dtype != dtype:
+            hint = "; dequantize(which=None) returns its values as float32" if self.dtype == "fp8" else ""
+            raise TypeError("%s is for an %s bank, this one is %s%s" % (what, dtype, self.dtype, hint))
 
     @property
     def features(self):
-        """fp16 [rows, dim]: a view of the filled part."""
+        """fp16 [rows, dim]: a view of the filled part (fp16 bank)."""
+        self._need("fp16", "features")
         return self._data[:self.rows]
 
-    def scene(self, which):
-        """fp16 [n, dim] view of one scene's rows (by name or position)."""
+    @property
+    def codes(self):
+        """uint8 [rows, dim]: the e4m3fn codes of the filled part (fp8 bank)."""
+        self._need("fp8", "codes")
+        return self._codes[:self.rows]
+
+    @property
+    def exponents(self):
+        """int8 [rows]: the row exponents of the filled part (fp8 bank)."""
+        self._need("fp8", "exponents")
+        return self._exps[:self.rows]
+
+    def _span(self, which):
+        if which is None:
+            return 0, self.rows
         i = self.names.index(which) if isinstance(which, str) else int(which)
-        return self._data[self.offsets[i]:self.offsets[i + 1]]
+        return self.offsets[i], self.offsets[i + 1]
+
+    def scene(self, which):
+        """fp16 [n, dim] view of one scene's rows (by name or position; fp16 bank)."""
+        self._need("fp16", "scene()")
+        a, b = self._span(which)
+        return self._data[a:b]
+
+    def dequantize(self, which=None):
+        """float32 [n, dim]: the stored values ``code * 2^e`` of one scene (by name or position) or, with None, of the
+        whole fp8 bank.  Plain torch: for inspection and tests, not for the search."""
+        self._need("fp8", "dequantize()")
+        a, b = self._span(which)
+        table = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).float().to(self.device)
+        return torch.ldexp(table[self._codes[a:b].long()], self._exps[a:b].int()[:, None])
 
     def scene_rows(self):
         return [b - a for a, b in zip(self.offsets[:-1], self.offsets[1:])]
@@ -78,24 +132,44 @@ class FeatureBank:
     # ---- growth
     def _reserve(self, n):
         need = self.rows + n
-        if need <= self._data.shape[0]:
+        if need <= self.capacity_rows:
             return
-        cap = max(need, 2 * self._data.shape[0])
-        data = torch.empty((cap, self.dim), dtype=torch.float16, device=self.device)
-        data[:self.rows].copy_(self._data[:self.rows])
-        self._data = data
+        cap = max(need, 2 * self.capacity_rows)
+        if self.dtype == "fp16":
+            data = torch.empty((cap, self.dim), dtype=torch.float16, device=self.device)
+            data[:self.rows].copy_(self._data[:self.rows])
+            self._data = data
+            return
+        codes = torch.empty((cap, self.dim), dtype=torch.uint8, device=self.device)
+        exps = torch.empty((cap,), dtype=torch.int8, device=self.device)
+        codes[:self.rows].copy_(self._codes[:self.rows])
+        exps[:self.rows].copy_(self._exps[:self.rows])
+        self._codes, self._exps = codes, exps
 
     def _commit(self, name, n):
         self.offsets.append(self.rows + n)
         self.names.append(name)
         self._offsets_dev = None
 
+    def _gather(self, inds_reverse):
+        inds_reverse = torch.as_tensor(inds_reverse).to(self.device)
+        if inds_reverse.dim() != 1 or inds_reverse.dtype.is_floating_point or inds_reverse.dtype == torch.bool:
+            raise TypeError("inds_reverse must be a vector of integer indices")
+        return inds_reverse
+
+    def _checked(self, err):
+        try:
+            ops.bank_check(err)
+        except Exception:
+            err.zero_()                           # rows past `rows` are scratch: the bank is as it was
+            raise
+
     def add_scene(self, name, features, inds_reverse=None):
         """Append one scene.  float32 features on the bank's device -- the network output, with the voxel -> point
         map `inds_reverse`: exactly ``predictions = feat_3d[inds_reverse]`` of ``run/evaluate.py:290``, stored as the
         ``.half()`` of ``:291`` -- go through the fused gather + cast kernel; fp16 features (fused / ensemble features,
-        saved files) are copied as they are.  An index outside the feature matrix raises and leaves the bank as it
-        was.  -> the scene's position."""
+        saved files) are copied as they are.  An fp8 bank sends both kinds through the gather + quantise kernel.  An
+        index outside the feature matrix raises and leaves the bank as it was.  -> the scene's position."""
         name = str(name)
         if name in self.names:
             raise ValueError("the bank already holds a scene named %r" % name)
@@ -103,28 +177,31 @@ class FeatureBank:
             features = torch.from_numpy(features)
         if features.dim() != 2 or features.shape[1] != self.dim:
             raise ValueError("features must be [points, %d] (got %s)" % (self.dim, tuple(features.shape)))
-        if features.dtype == torch.float16:
+        if features.dtype not in (torch.float16, torch.float32):
+            raise TypeError("features must be float32 or float16 (got %s)" % features.dtype)
+        if self.dtype == "fp8":
+            features = features.to(self.device)
+            if inds_reverse is not None:
+                inds_reverse = self._gather(inds_reverse)
+            n = features.shape[0] if inds_reverse is None else inds_reverse.shape[0]
+            self._reserve(n)
+            err = self._err_word()
+            ops.bank_append_fp8(self._codes, self._exps, self.rows, features, err, gather=inds_reverse)
+            self._checked(err)
+        elif features.dtype == torch.float16:
             rows = features if inds_reverse is None else features[torch.as_tensor(inds_reverse).long().to(features.device)]
             n = rows.shape[0]
             self._reserve(n)
             self._data[self.rows:self.rows + n].copy_(rows)
-        elif features.dtype == torch.float32:
+        else:
             features = features.to(self.device)
             if inds_reverse is not None:
-                inds_reverse = torch.as_tensor(inds_reverse).to(self.device)
-                if inds_reverse.dim() != 1 or inds_reverse.dtype.is_floating_point or inds_reverse.dtype == torch.bool:
-                    raise TypeError("inds_reverse must be a vector of integer indices")
+                inds_reverse = self._gather(inds_reverse)
             n = features.shape[0] if inds_reverse is None else inds_reverse.shape[0]
             self._reserve(n)
             err = self._err_word()
             ops.bank_append(self._data, self.rows, features, err, gather=inds_reverse)
-            try:
-                ops.bank_check(err)
-            except Exception:
-                err.zero_()                       # rows past `rows` are scratch: the bank is as it was
-                raise
-        else:
-            raise TypeError("features must be float32 or float16 (got %s)" % features.dtype)
+            self._checked(err)
         self._commit(name, n)
         return len(self.names) - 1
 
@@ -140,20 +217,49 @@ class FeatureBank:
             added.append(name)
         return added
 
+    def to_fp8(self):
+        """The fp8 bank of the same scenes: this fp16 bank's rows through the quantising kernel."""
+        self._need("fp16", "to_fp8()")
+        bank = FeatureBank(self.dim, self.device, capacity_rows=max(self.rows, 1), dtype="fp8")
+        if self.rows:
+            err = bank._err_word()
+            ops.bank_append_fp8(bank._codes, bank._exps, 0, self.features, err)
+            bank._checked(err)
+        bank.offsets = list(self.offsets)
+        bank.names = list(self.names)
+        return bank
+
     # ---- persistence
     def save(self, path):
-        """One file: the filled rows (fp16), the offsets and the names."""
-        torch.save({"dim": self.dim, "offsets": list(self.offsets), "names": list(self.names),
-                    "features": self.features.cpu().clone()}, path)
+        """One file: the filled rows (fp16, or codes and exponents), the offsets and the names."""
+        d = {"dim": self.dim, "offsets": list(self.offsets), "names": list(self.names), "dtype": self.dtype}
+        if self.dtype == "fp16":
+            d["features"] = self.features.cpu().clone()
+        else:
+            d["codes"] = self.codes.cpu().clone()
+            d["exponents"] = self.exponents.cpu().clone()
+        torch.save(d, path)
 
     @classmethod
     def load(cls, path, device):
         d = torch.load(path, map_location="cpu", weights_only=False)
-        feats = d["features"]
-        if feats.dtype != torch.float16 or feats.dim() != 2 or feats.shape[1] != d["dim"] or feats.shape[0] != d["offsets"][-1]:
-            raise ValueError("%s is not a feature bank" % path)
-        bank = cls(d["dim"], device, capacity_rows=max(feats.shape[0], 1))
-        bank._data[:feats.shape[0]].copy_(feats)
+        dtype = d.get("dtype", "fp16")                      # (files written before the fp8 bank hold no "dtype")
+        rows = d["offsets"][-1]
+        if dtype == "fp8":
+            codes, exps = d.get("codes"), d.get("exponents")
+            if (codes is None or exps is None or codes.dtype != torch.uint8 or exps.dtype != torch.int8
+                    or tuple(codes.shape) != (rows, d["dim"]) or tuple(exps.shape) != (rows,)):
+                raise ValueError("%s is not a feature bank" % path)
+            bank = cls(d["dim"], device, capacity_rows=max(rows, 1), dtype="fp8")
+            bank._codes[:rows].copy_(codes)
+            bank._exps[:rows].copy_(exps)
+        else:
+            feats = d.get("features")
+            if (dtype != "fp16" or feats is None or feats.dtype != torch.float16 or feats.dim() != 2
+                    or feats.shape[1] != d["dim"] or feats.shape[0] != rows):
+                raise ValueError("%s is not a feature bank" % path)
+            bank = cls(d["dim"], device, capacity_rows=max(rows, 1))
+            bank._data[:rows].copy_(feats)
         bank.offsets = [int(o) for o in d["offsets"]]
         bank.names = [str(n) for n in d["names"]]
         return bank
@@ -233,8 +339,8 @@ def search(bank, queries, k=16, thresholds=None, normalize=True, return_heat=Fal
 
     queries fp16 [Q, dim], L2-normalised (``util/util.py:41-44``); the score is ``run/evaluate.py:305,310`` (normalize:
     ``(hf / (hf.norm(dim=-1, keepdim=True) + 1e-5)).half() @ t.t()``) or ``:291`` (``h @ t.t()``) on the stored fp16
-    rows.  thresholds: a number or [Q] numbers -> counts.  Selection order: higher score, then lower point index; NaN
-    below every number."""
+    rows (an fp8 bank: on its stored values ``code * 2^e``).  thresholds: a number or [Q] numbers -> counts.  Selection
+    order: higher score, then lower point index; NaN below every number."""
     if not isinstance(bank, FeatureBank):
         raise TypeError("bank must be a FeatureBank")
     queries = _queries(queries, bank.dim, bank.device)
@@ -250,10 +356,12 @@ def search(bank, queries, k=16, thresholds=None, normalize=True, return_heat=Fal
             raise ValueError("%d thresholds for %d queries" % (thresholds.numel(), q))
         thresholds = thresholds.contiguous().to(bank.device)
     rows = bank.scene_rows()
-    heat, top_s, top_p, counts = ops.bank_search(bank.features, bank.offsets_tensor(), queries, k=k, thresholds=thresholds,
-                                                 normalize=bool(normalize), want_heat=bool(return_heat),
-                                                 max_scene_rows=max(rows) if rows else 0,
-                                                 err=bank._err_word())       # (the bank owns its offsets: nothing to check)
+    kw = dict(k=k, thresholds=thresholds, normalize=bool(normalize), want_heat=bool(return_heat),
+              max_scene_rows=max(rows) if rows else 0, err=bank._err_word())       # (the bank owns its offsets: nothing to check)
+    if bank.dtype == "fp8":
+        heat, top_s, top_p, counts = ops.bank_search_fp8(bank.codes, bank.exponents, bank.offsets_tensor(), queries, **kw)
+    else:
+        heat, top_s, top_p, counts = ops.bank_search(bank.features, bank.offsets_tensor(), queries, **kw)
     return SearchResult(bank.names, bank.offsets, top_s, top_p, counts, heat)
 
 

@@ -2,13 +2,18 @@
 the fp16 bank widened to float32, ops.cosine_query(want_scores=True), the norm and the division in torch, torch.topk per
 scene and query.  HIP events around back-to-back calls after a warm-up.
 
-    python tools/micro_search.py [iters]
+    python tools/micro_search.py [iters] [--no-composed]
 
 Prints one JSON object per line:
   kind=search   per shape (scenes x rows x d x Q, k = 16): us of the whole search, of the heat pass alone (a call without
                 scenes) and their difference (the select pass), the select pass's share, the heat pass's fraction of the HBM
                 roof on 2 N d + 2 N Q bytes, and the composed path's us with its parts (widen / query / norm + divide / topk)
-  kind=append   osn_bank_append against X[g].half() in torch"""
+                fp8 bank of the same rows (bank.to_fp8()), timed in the same A B loop: us_search_fp8, us_heat_pass_fp8, the
+                heat pass's fraction of the roof on N (d + 1) + 2 N Q (+ 2 N Q for heatT) bytes, its ratio to the fp16 heat
+                pass, and -- after a parity check of 2048 sampled rows against the float64 formula on the stored values
+                (abs <= 2e-3, or the tool stops) -- the fidelity against the fp16 bank: largest and rms difference of the
+                normalised scores, overlap of the per-scene top-16
+  kind=append   osn_bank_append against X[g].half() in torch; osn_bank_append_fp8 from float32 and from float16 rows"""
 import json
 import os
 import sys
@@ -19,7 +24,9 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 from openscene_amd import ops                                        # noqa: E402
 from openscene_amd.search import FeatureBank, search                 # noqa: E402
 
-ITERS = int(sys.argv[1]) if len(sys.argv) > 1 else 20
+ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
+ITERS = int(ARGS[0]) if ARGS else 20
+COMPOSED = "--no-composed" not in sys.argv
 dev = torch.device("cuda", 0)
 HBM_PEAK = 8.0e12
 K = 16
@@ -78,6 +85,29 @@ def composed(bank, text, offsets, parts=None):
     return heat
 
 
+def fp8_parity(bank8, text, heat8, gen):
+    """2048 sampled rows of the fp8 heat-map against acc * 2^e / (sqrt(sum c^2) * 2^e + 1e-5) in float64 -> max abs deviation."""
+    rows = torch.randint(0, bank8.rows, (2048,), generator=gen, device=dev)
+    table = torch.arange(256, dtype=torch.uint8).view(torch.float8_e4m3fn).double().to(dev)
+    c = table[bank8.codes[rows].long()]
+    s = torch.pow(torch.tensor(2.0, dtype=torch.float64, device=dev), bank8.exponents[rows].double())[:, None]
+    ref = (c @ text.double().t()) * s / (c.square().sum(dim=1, keepdim=True).sqrt() * s + 1e-5)
+    worst = (heat8[rows].double() - ref).abs().max().item()
+    if not worst <= 2e-3:
+        raise SystemExit("fp8 heat-map is off the float64 formula by %.3e" % worst)
+    return worst
+
+
+def fidelity(res, res8):
+    diff = (res8.heat.float() - res.heat.float()).double()
+    same = 0
+    for s in range(res.topk_points.shape[0]):
+        for q in range(res.topk_points.shape[1]):
+            same += len(set(res.topk_points[s, q].tolist()) & set(res8.topk_points[s, q].tolist()))
+    return {"max_abs": diff.abs().max().item(), "rms": diff.square().mean().sqrt().item(),
+            "topk_overlap": same / res.topk_points.numel()}
+
+
 def shapes():
     gen = torch.Generator(device=dev).manual_seed(1)
     for scenes, n, d, q in ((1, 150_000, 768, 1), (1, 150_000, 768, 8), (1, 150_000, 768, 32), (8, 150_000, 768, 32),
@@ -86,20 +116,37 @@ def shapes():
         text = torch.nn.functional.normalize(torch.randn(q, d, generator=gen, device=dev), dim=1).half()
         rows = scenes * n
         empty = torch.zeros(1, dtype=torch.int64, device=dev)
-        r = {"all": [], "heat": [], "composed": []}
+        bank8 = bank.to_fp8()
+        res, res8 = search(bank, text, k=K, return_heat=True), search(bank8, text, k=K, return_heat=True)
+        parity = fp8_parity(bank8, text, res8.heat, gen)
+        fid = fidelity(res, res8)
+        del res, res8
+        r = {"all": [], "heat": [], "composed": [], "all8": [], "heat8": []}
         for _ in range(2):                                            # A B C A B C: shows the spread
             r["all"].append(timed(lambda: search(bank, text, k=K, return_heat=True)))
+            r["all8"].append(timed(lambda: search(bank8, text, k=K, return_heat=True)))
             r["heat"].append(timed(lambda: ops.bank_search(bank.features, empty, text, k=K, want_heat=True, max_scene_rows=0)))
-            r["composed"].append(timed(lambda: composed(bank, text, bank.offsets), iters=max(3, ITERS // 4), warmup=1))
+            r["heat8"].append(timed(lambda: ops.bank_search_fp8(bank8.codes, bank8.exponents, empty, text, k=K, want_heat=True,
+                                                                max_scene_rows=0)))
+            if COMPOSED:
+                r["composed"].append(timed(lambda: composed(bank, text, bank.offsets), iters=max(3, ITERS // 4), warmup=1))
         parts = {}
-        composed(bank, text, bank.offsets, parts)
-        us_all, us_heat, us_comp = min(r["all"]), min(r["heat"]), min(r["composed"])
+        if COMPOSED:
+            composed(bank, text, bank.offsets, parts)
+        us_all, us_heat, us_comp = min(r["all"]), min(r["heat"]), min(r["composed"]) if COMPOSED else None
+        us_all8, us_heat8 = min(r["all8"]), min(r["heat8"])
         nbytes = 2 * rows * d + 2 * rows * q
+        nbytes8 = rows * (d + 1) + 2 * rows * q
         emit(kind="search", scenes=scenes, rows_per_scene=n, d=d, q=q, k=K, us_search=r["all"], us_heat_pass=r["heat"],
              us_select_pass=us_all - us_heat, select_share=(us_all - us_heat) / us_all, bytes=nbytes,
              heat_hbm_share=nbytes / us_heat * 1e6 / HBM_PEAK, search_hbm_share=nbytes / us_all * 1e6 / HBM_PEAK,
-             us_composed=r["composed"], composed_parts_us=parts, speedup=us_comp / us_all)
-        del bank
+             us_composed=r["composed"], composed_parts_us=parts, speedup=us_comp / us_all if COMPOSED else None,
+             us_search_fp8=r["all8"], us_heat_pass_fp8=r["heat8"], bytes_fp8=nbytes8, bytes_fp8_with_heatT=nbytes8 + 2 * rows * q,
+             heat_hbm_share_fp8=nbytes8 / us_heat8 * 1e6 / HBM_PEAK,
+             heat_hbm_share_fp8_with_heatT=(nbytes8 + 2 * rows * q) / us_heat8 * 1e6 / HBM_PEAK,
+             heat_fp8_over_fp16=us_heat8 / us_heat, search_fp8_over_fp16=us_all8 / us_all, fp8_parity_max_abs=parity,
+             fp8_vs_fp16=fid)
+        del bank, bank8
 
 
 def append():
@@ -114,6 +161,14 @@ def append():
         us_torch = timed(lambda: bank.copy_(x[g].half()))
         nbytes = n * d * 6 + n * 8
         emit(kind="append", rows=n, d=d, us=us, us_torch=us_torch, bytes=nbytes, hbm_share=nbytes / us * 1e6 / HBM_PEAK)
+        codes = torch.empty((n, d), dtype=torch.uint8, device=dev)
+        exps = torch.empty((n,), dtype=torch.int8, device=dev)
+        for src, width in ((x, 4), (x.half(), 2)):
+            us8 = timed(lambda: ops.bank_append_fp8(codes, exps, 0, src, err, gather=g))
+            ops.bank_check(err)
+            nbytes8 = n * d * width + n * (d + 1) + n * 8
+            emit(kind="append_fp8", source="float%d" % (8 * width), rows=n, d=d, us=us8, bytes=nbytes8,
+                 hbm_share=nbytes8 / us8 * 1e6 / HBM_PEAK, rows_per_s=n / us8 * 1e6)
 
 
 if __name__ == "__main__":
