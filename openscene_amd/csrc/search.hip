@@ -21,7 +21,9 @@
 // The fp8 bank (osn_bank_append_fp8 / osn_bank_search_fp8) stores a row as d OCP e4m3fn codes and one exponent byte e:
 // value = code * 2^e, e the smallest integer >= -120 with max|x| * 2^-e <= 448.  The append is one wave per row (the
 // row stays in registers between the max and the conversion); the heat pass streams 16 codes per 16-byte load, widens
-// them to fp16 (exact) on the way into LDS and runs the same MFMA loop; 2^e enters in the epilogue.  Pass 2 is shared.
+// them to fp16 (exact) on the way into LDS (heat_fp8_kernel); 2^e enters where the scores leave.  The two heat kernels call
+// one set of __device__ templates for the query staging, the MFMA loop, the row norms and the score output; each has its own
+// row fetch, stash and stage loop.  Pass 2 and the entries' argument checks are shared too.
 #include "common.h"
 
 namespace osn {
@@ -29,6 +31,7 @@ namespace osn {
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
+typedef _Float16 half2 __attribute__((ext_vector_type(2)));
 
 constexpr int S_BM = 128;          // bank rows per workgroup (4 waves x 32)
 constexpr int S_DK = 128;          // feature chunk (halfs): 256 bytes of a row, 32 KB per workgroup in flight
@@ -64,6 +67,124 @@ __global__ __launch_bounds__(256) void bank_append_kernel(const float* __restric
 }
 
 // ------------------------------------------------------------------------------------------------------ pass 1
+// What heat_kernel and heat_fp8_kernel share: the query chunk's way into registers and LDS, the MFMAs of one chunk, the
+// row norms and the way the scores leave.  Each kernel keeps its own row fetch and stash, lane-to-row mapping and stage loop.
+
+// query chunk [d0, d0 + S_DK) of the column group at cg0 -> registers.  All loads unconditional from clamped addresses
+// (query.hip: a conditional fetch makes the compiler drain the memory counter before every stash)
+template <int CT>
+__device__ __forceinline__ void fetch_queries(uint4 (&pt)[2 * CT], const _Float16* __restrict__ T, int cg0, int d0, int d, int q,
+                                              int tid) {
+#pragma unroll
+    for (int j = 0; j < 2 * CT; ++j) {
+        const int f = tid + 256 * j;
+        const int trow = f >> 4, ch = f & 15;
+        const int col = cg0 + trow;
+        const bool ok = col < q && d0 + ch * 8 < d;
+        pt[j] = *reinterpret_cast<const uint4*>(ok ? T + int64_t(col) * d + d0 + ch * 8 : T);
+    }
+}
+
+template <int CT>
+__device__ __forceinline__ void stash_queries(_Float16 (*Ts)[S_LD], const uint4 (&pt)[2 * CT], int cg0, int d0, int d, int q,
+                                              int tid) {
+#pragma unroll
+    for (int j = 0; j < 2 * CT; ++j) {
+        const int f = tid + 256 * j;
+        const int trow = f >> 4, ch = f & 15;
+        const bool ok = cg0 + trow < q && d0 + ch * 8 < d;
+        uint4 v = pt[j];
+        if (!ok) v = make_uint4(0, 0, 0, 0);
+        *reinterpret_cast<uint4*>(&Ts[trow][ch * 8]) = v;
+    }
+}
+
+// the MFMAs of one chunk: fragments of k-step ks + 1 are read from LDS while the MFMAs of k-step ks run (two register sets,
+// as query.hip)
+template <int CT>
+__device__ __forceinline__ void mfma_chunk(f32x16 (&acc)[CT], const _Float16 (*Xs)[S_LD], const _Float16 (*Ts)[S_LD], int wave,
+                                           int lane) {
+    const int arow = wave * 32 + (lane & 31);
+    const int kh = 8 * (lane >> 5);
+    half8 fa[2], fb[2][CT];
+    auto frags = [&](int ks, int w) {
+        fa[w] = *reinterpret_cast<const half8*>(&Xs[arow][ks * 16 + kh]);
+#pragma unroll
+        for (int t = 0; t < CT; ++t)
+            fb[w][t] = *reinterpret_cast<const half8*>(&Ts[t * 32 + (lane & 31)][ks * 16 + kh]);
+    };
+    frags(0, 0);
+#pragma unroll
+    for (int ks = 0; ks < S_DK / 16; ++ks) {
+        __builtin_amdgcn_sched_barrier(0);
+        if (ks + 1 < S_DK / 16) frags(ks + 1, (ks + 1) & 1);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int t = 0; t < CT; ++t)
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks & 1], fb[ks & 1][t], acc[t], 0, 0, 0);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+}
+
+// rden[row] = ||row|| [* rscale[row]] + 1e-5 (run/evaluate.py:305) from the partial sums of squares of the LANES lanes that
+// share a row (lane tid % LANES of row ps * (256 / LANES) + tid / LANES)
+template <int LANES, bool SCALED>
+__device__ __forceinline__ void row_norms(float* rden, const float (&ss)[S_BM * LANES / 256], const float* rscale, int tid) {
+    constexpr int SWEEP = 256 / LANES;
+#pragma unroll
+    for (int ps = 0; ps < S_BM / SWEEP; ++ps) {
+        float s = ss[ps];
+#pragma unroll
+        for (int m = 1; m < LANES; m <<= 1) s += __shfl_xor(s, m, 64);
+        const int row = ps * SWEEP + tid / LANES;
+        if (tid % LANES == 0) rden[row] = SCALED ? sqrtf(s) * rscale[row] + 1e-5f : sqrtf(s) + 1e-5f;
+    }
+    __syncthreads();
+}
+
+// the scores of one column group leave: accumulator [* rscale, exact: a power of two], divided by rden in fp32, rounded to
+// fp16 once into the LDS tile Sc[column][row] (CT * 32 <= 128 rows of the row tile); from there column-major into heatT and,
+// where the caller wants it, row-major into heat
+template <int CT, bool SCALED>
+__device__ __forceinline__ void scores_out(const f32x16 (&acc)[CT], _Float16 (*Sc)[S_LD], const float* rden, const float* rscale,
+                                           _Float16* __restrict__ heat, _Float16* __restrict__ heatT, int64_t ldT, int64_t row0,
+                                           int64_t n, int q, int cg0, int normalize, int tid) {
+    const int lane = tid & 63, wave = tid >> 6;
+#pragma unroll
+    for (int t = 0; t < CT; ++t) {
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int lrow = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            float v = acc[t][r];
+            if (SCALED) v *= rscale[lrow];
+            if (normalize) v /= rden[lrow];
+            Sc[t * 32 + (lane & 31)][lrow] = (_Float16)v;
+        }
+    }
+    __syncthreads();
+    for (int e = tid; e < CT * 32 * (S_BM / 8); e += 256) {       // column-major: 16-byte pieces of a column's 128 rows
+        const int col = e >> 4, v8 = e & 15;
+        const int gc = cg0 + col;
+        if (gc >= q) continue;
+        const int64_t r = row0 + 8 * v8;
+        _Float16* dst = heatT + int64_t(gc) * ldT + r;
+        if (r + 8 <= n) {
+            *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(&Sc[col][8 * v8]);
+        } else {
+            for (int j = 0; j < 8; ++j)
+                if (r + j < n) dst[j] = Sc[col][8 * v8 + j];
+        }
+    }
+    if (heat) {
+        const int qn = (q - cg0) < 32 * CT ? (q - cg0) : 32 * CT;
+        for (int e = tid; e < S_BM * qn; e += 256) {
+            const int r = e / qn, c = e - r * qn;
+            if (row0 + r < n) heat[(row0 + r) * q + cg0 + c] = Sc[c][r];
+        }
+    }
+    __syncthreads();                                        // the tile is the next column group's row buffer
+}
+
 template <int CT, int WGS>
 __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restrict__ B, const _Float16* __restrict__ T,
                                                         _Float16* __restrict__ heat, _Float16* __restrict__ heatT, int64_t ldT,
@@ -71,7 +192,6 @@ __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restri
     __shared__ __attribute__((aligned(16))) _Float16 Xs[S_BM][S_LD];
     __shared__ __attribute__((aligned(16))) _Float16 Ts[CT * 32][S_LD];
     __shared__ float rden[S_BM];
-    _Float16(*Sc)[S_LD] = Xs;                               // score tile [column][row] once the MFMAs are done (CT * 32 <= 128 rows of it)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t row0 = int64_t(blockIdx.x) * S_BM;
@@ -87,19 +207,11 @@ __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restri
         for (int t = 0; t < CT; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-        // one chunk in flight in registers while the MFMAs of the previous one run from LDS; all loads unconditional from
-        // clamped addresses (query.hip: a conditional fetch makes the compiler drain the memory counter before every stash)
+        // one chunk in flight in registers while the MFMAs of the previous one run from LDS (rows fetched as the queries are)
         uint4 px[S_BM / 16];
         uint4 pt[2 * CT];
         auto fetch = [&](int d0) {
-#pragma unroll
-            for (int j = 0; j < 2 * CT; ++j) {
-                const int f = tid + 256 * j;
-                const int trow = f >> 4, ch = f & 15;
-                const int col = cg0 + trow;
-                const bool ok = col < q && d0 + ch * 8 < d;
-                pt[j] = *reinterpret_cast<const uint4*>(ok ? T + int64_t(col) * d + d0 + ch * 8 : T);
-            }
+            fetch_queries<CT>(pt, T, cg0, d0, d, q, tid);
 #pragma unroll
             for (int ps = 0; ps < S_BM / 16; ++ps) {
                 const int64_t row = row0 + ps * 16 + xr;
@@ -123,38 +235,7 @@ __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restri
                 }
                 *reinterpret_cast<uint4*>(&Xs[row][xq * 8]) = v;
             }
-#pragma unroll
-            for (int j = 0; j < 2 * CT; ++j) {
-                const int f = tid + 256 * j;
-                const int trow = f >> 4, ch = f & 15;
-                const bool ok = cg0 + trow < q && d0 + ch * 8 < d;
-                uint4 v = pt[j];
-                if (!ok) v = make_uint4(0, 0, 0, 0);
-                *reinterpret_cast<uint4*>(&Ts[trow][ch * 8]) = v;
-            }
-        };
-        // fragments of k-step ks + 1 are read from LDS while the MFMAs of k-step ks run (two register sets, as query.hip)
-        auto mfmas = [&]() {
-            const int arow = wave * 32 + (lane & 31);
-            const int kh = 8 * (lane >> 5);
-            half8 fa[2], fb[2][CT];
-            auto frags = [&](int ks, int w) {
-                fa[w] = *reinterpret_cast<const half8*>(&Xs[arow][ks * 16 + kh]);
-#pragma unroll
-                for (int t = 0; t < CT; ++t)
-                    fb[w][t] = *reinterpret_cast<const half8*>(&Ts[t * 32 + (lane & 31)][ks * 16 + kh]);
-            };
-            frags(0, 0);
-#pragma unroll
-            for (int ks = 0; ks < S_DK / 16; ++ks) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (ks + 1 < S_DK / 16) frags(ks + 1, (ks + 1) & 1);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int t = 0; t < CT; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks & 1], fb[ks & 1][t], acc[t], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
+            stash_queries<CT>(Ts, pt, cg0, d0, d, q, tid);
         };
         fetch(0);
         stash(0);
@@ -163,60 +244,17 @@ __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restri
             __builtin_amdgcn_sched_barrier(0);
             fetch(d0 + S_DK);                               // (past the end: the first 16 bytes of B / T, never staged)
             __builtin_amdgcn_sched_barrier(0);
-            mfmas();
+            mfma_chunk<CT>(acc, Xs, Ts, wave, lane);
             __syncthreads();
             if (d0 + S_DK < d) stash(d0 + S_DK);
             __syncthreads();
         }
-        if (sumsq) {                                        // the 16 lanes that share a row: ||h|| + 1e-5 (run/evaluate.py:305)
-#pragma unroll
-            for (int ps = 0; ps < S_BM / 16; ++ps) {
-                float s = ss[ps];
-#pragma unroll
-                for (int m = 1; m < 16; m <<= 1) s += __shfl_xor(s, m, 64);
-                if (xq == 0) rden[ps * 16 + xr] = sqrtf(s) + 1e-5f;
-            }
-            __syncthreads();
-        }
-        // ---- epilogue: divide the fp32 accumulator, round to fp16 once, tile -> LDS [column][row]
-#pragma unroll
-        for (int t = 0; t < CT; ++t) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int lrow = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                float v = acc[t][r];
-                if (normalize) v /= rden[lrow];
-                Sc[t * 32 + (lane & 31)][lrow] = (_Float16)v;
-            }
-        }
-        __syncthreads();
-        for (int e = tid; e < CT * 32 * (S_BM / 8); e += 256) {       // column-major: 16-byte pieces of a column's 128 rows
-            const int col = e >> 4, v8 = e & 15;
-            const int gc = cg0 + col;
-            if (gc >= q) continue;
-            const int64_t r = row0 + 8 * v8;
-            _Float16* dst = heatT + int64_t(gc) * ldT + r;
-            if (r + 8 <= n) {
-                *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(&Sc[col][8 * v8]);
-            } else {
-                for (int j = 0; j < 8; ++j)
-                    if (r + j < n) dst[j] = Sc[col][8 * v8 + j];
-            }
-        }
-        if (heat) {
-            const int qn = (q - cg0) < 32 * CT ? (q - cg0) : 32 * CT;
-            for (int e = tid; e < S_BM * qn; e += 256) {
-                const int r = e / qn, c = e - r * qn;
-                if (row0 + r < n) heat[(row0 + r) * q + cg0 + c] = Sc[c][r];
-            }
-        }
-        __syncthreads();                                    // the tile is the next column group's row buffer
+        if (sumsq) row_norms<16, false>(rden, ss, nullptr, tid);
+        scores_out<CT, false>(acc, Xs, rden, nullptr, heat, heatT, ldT, row0, n, q, cg0, normalize, tid);
     }
 }
 
 // ------------------------------------------------------------------------------------------------------ fp8 bank
-typedef _Float16 half2 __attribute__((ext_vector_type(2)));
-
 constexpr int Q8_RG = 2;           // 16-element groups of a row a lane keeps in registers: rows up to 64 * 16 * Q8_RG = 2048
                                    // wide are read from HBM once, wider rows read their tail twice (max, then conversion)
 
@@ -322,7 +360,6 @@ __global__ __launch_bounds__(256) void bank_append_fp8_kernel(const void* __rest
 // Two workgroups per CU: the second register stage and the conversion need 194 / 250 VGPRs (one / two column tiles); held to
 // the 168 of three workgroups the kernel spills inside the loop and measured 0.81x of the fp16 pass at 8 x 150 k x 768 x 32
 // where this shape measured 0.67x.
-// The LDS tiles, the MFMA loop and the way the scores leave are heat_kernel's.
 template <int CT, int WGS>
 __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __restrict__ B, const int8_t* __restrict__ E,
                                                             const _Float16* __restrict__ T, _Float16* __restrict__ heat,
@@ -332,7 +369,6 @@ __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __res
     __shared__ __attribute__((aligned(16))) _Float16 Ts[CT * 32][S_LD];
     __shared__ float rden[S_BM];
     __shared__ float rscale[S_BM];                          // 2^e of the row
-    _Float16(*Sc)[S_LD] = Xs;
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t row0 = int64_t(blockIdx.x) * S_BM;
@@ -353,20 +389,9 @@ __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __res
         for (int t = 0; t < CT; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
-        // all loads unconditional from clamped addresses, as in heat_kernel
         uint4 pxa[NPS], pxb[NPS];                           // code chunks c + 1 and c + 2 while the MFMAs of chunk c run
         uint4 pt[2 * CT];                                   // the query chunk c + 1 (from L2)
-        auto fetch_t = [&](int d0) {
-#pragma unroll
-            for (int j = 0; j < 2 * CT; ++j) {
-                const int f = tid + 256 * j;
-                const int trow = f >> 4, ch = f & 15;
-                const int col = cg0 + trow;
-                const bool ok = col < q && d0 + ch * 8 < d;
-                pt[j] = *reinterpret_cast<const uint4*>(ok ? T + int64_t(col) * d + d0 + ch * 8 : T);
-            }
-        };
-        auto fetch_x = [&](uint4(&px)[NPS], int d0) {
+        auto fetch_x = [&](uint4(&px)[NPS], int d0) {       // (unconditional from clamped addresses, as the queries)
 #pragma unroll
             for (int ps = 0; ps < NPS; ++ps) {
                 const int64_t row = row0 + ps * 32 + xr;
@@ -402,105 +427,34 @@ __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __res
                 *reinterpret_cast<uint4*>(&Xs[row][xq * 16]) = lo;
                 *reinterpret_cast<uint4*>(&Xs[row][xq * 16 + 8]) = hi;
             }
-#pragma unroll
-            for (int j = 0; j < 2 * CT; ++j) {
-                const int f = tid + 256 * j;
-                const int trow = f >> 4, ch = f & 15;
-                const bool ok = cg0 + trow < q && d0 + ch * 8 < d;
-                uint4 v = pt[j];
-                if (!ok) v = make_uint4(0, 0, 0, 0);
-                *reinterpret_cast<uint4*>(&Ts[trow][ch * 8]) = v;
-            }
+            stash_queries<CT>(Ts, pt, cg0, d0, d, q, tid);
         };
-        auto mfmas = [&]() {
-            const int arow = wave * 32 + (lane & 31);
-            const int kh = 8 * (lane >> 5);
-            half8 fa[2], fb[2][CT];
-            auto frags = [&](int ks, int w) {
-                fa[w] = *reinterpret_cast<const half8*>(&Xs[arow][ks * 16 + kh]);
-#pragma unroll
-                for (int t = 0; t < CT; ++t)
-                    fb[w][t] = *reinterpret_cast<const half8*>(&Ts[t * 32 + (lane & 31)][ks * 16 + kh]);
-            };
-            frags(0, 0);
-#pragma unroll
-            for (int ks = 0; ks < S_DK / 16; ++ks) {
-                __builtin_amdgcn_sched_barrier(0);
-                if (ks + 1 < S_DK / 16) frags(ks + 1, (ks + 1) & 1);
-                __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-                for (int t = 0; t < CT; ++t)
-                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[ks & 1], fb[ks & 1][t], acc[t], 0, 0, 0);
-            }
-            __builtin_amdgcn_sched_barrier(0);
-        };
-        fetch_t(0);
+        fetch_queries<CT>(pt, T, cg0, 0, d, q, tid);
         fetch_x(pxa, 0);
         fetch_x(pxb, S_DK);                                 // (past the end: the first 16 bytes of B / T, never staged)
         stash(pxa, 0);
         __syncthreads();
         for (int d0 = 0; d0 < d; d0 += 2 * S_DK) {
             __builtin_amdgcn_sched_barrier(0);
-            fetch_t(d0 + S_DK);
+            fetch_queries<CT>(pt, T, cg0, d0 + S_DK, d, q, tid);
             fetch_x(pxa, d0 + 2 * S_DK);
             __builtin_amdgcn_sched_barrier(0);
-            mfmas();
+            mfma_chunk<CT>(acc, Xs, Ts, wave, lane);
             __syncthreads();
             if (d0 + S_DK >= d) break;
             stash(pxb, d0 + S_DK);
             __syncthreads();
             __builtin_amdgcn_sched_barrier(0);
-            fetch_t(d0 + 2 * S_DK);
+            fetch_queries<CT>(pt, T, cg0, d0 + 2 * S_DK, d, q, tid);
             fetch_x(pxb, d0 + 3 * S_DK);
             __builtin_amdgcn_sched_barrier(0);
-            mfmas();
+            mfma_chunk<CT>(acc, Xs, Ts, wave, lane);
             __syncthreads();
             if (d0 + 2 * S_DK < d) stash(pxa, d0 + 2 * S_DK);
             __syncthreads();
         }
-        if (sumsq) {                                        // the 8 lanes that share a row: ||c|| * 2^e + 1e-5
-#pragma unroll
-            for (int ps = 0; ps < NPS; ++ps) {
-                float s = ss[ps];
-#pragma unroll
-                for (int m = 1; m < 8; m <<= 1) s += __shfl_xor(s, m, 64);
-                if (xq == 0) rden[ps * 32 + xr] = sqrtf(s) * rscale[ps * 32 + xr] + 1e-5f;
-            }
-            __syncthreads();
-        }
-        // ---- epilogue: acc * 2^e (exact), divide, round to fp16 once, tile -> LDS [column][row]
-#pragma unroll
-        for (int t = 0; t < CT; ++t) {
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int lrow = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                float v = acc[t][r] * rscale[lrow];
-                if (normalize) v /= rden[lrow];
-                Sc[t * 32 + (lane & 31)][lrow] = (_Float16)v;
-            }
-        }
-        __syncthreads();
-        for (int e = tid; e < CT * 32 * (S_BM / 8); e += 256) {
-            const int col = e >> 4, v8 = e & 15;
-            const int gc = cg0 + col;
-            if (gc >= q) continue;
-            const int64_t r = row0 + 8 * v8;
-            _Float16* dst = heatT + int64_t(gc) * ldT + r;
-            if (r + 8 <= n) {
-                *reinterpret_cast<uint4*>(dst) = *reinterpret_cast<const uint4*>(&Sc[col][8 * v8]);
-            } else {
-                for (int j = 0; j < 8; ++j)
-                    if (r + j < n) dst[j] = Sc[col][8 * v8 + j];
-            }
-        }
-        if (heat) {
-            const int qn = (q - cg0) < 32 * CT ? (q - cg0) : 32 * CT;
-            for (int e = tid; e < S_BM * qn; e += 256) {
-                const int r = e / qn, c = e - r * qn;
-                if (row0 + r < n) heat[(row0 + r) * q + cg0 + c] = Sc[c][r];
-            }
-        }
-        __syncthreads();
+        if (sumsq) row_norms<8, true>(rden, ss, rscale, tid);       // ||c|| * 2^e + 1e-5
+        scores_out<CT, true>(acc, Xs, rden, rscale, heat, heatT, ldT, row0, n, q, cg0, normalize, tid);
     }
 }
 
@@ -818,22 +772,46 @@ static int select_pass(const SearchWs& w, char* p, int64_t n, const int64_t* sce
 }  // namespace osn
 
 using namespace osn;
+// the checks osn_bank_append and osn_bank_append_fp8 share: `who` names the entry in the messages, a row holds a multiple of
+// `dm` features, `out` is the matrix the rows go to.  n == 0 passes without a look at the pointers: nothing to append.
+static int append_args(const char* who, int dm, const void* X, int64_t n_rows, const int64_t* gather, int64_t n, int d,
+                       const void* out, int64_t row0, const int32_t* err) {
+    OSN_REQUIRE(n >= 0 && n_rows >= 0 && row0 >= 0 && d >= dm && d % dm == 0, OSN_E_ARG,
+                "%s: need n, n_rows, row0 >= 0 and d %% %d == 0 (n=%lld n_rows=%lld row0=%lld d=%d)", who, dm, (long long)n,
+                (long long)n_rows, (long long)row0, d);
+    OSN_REQUIRE(err, OSN_E_ARG, "%s: null err word", who);
+    OSN_REQUIRE(gather || n <= n_rows, OSN_E_ARG, "%s: %lld rows wanted of %lld", who, (long long)n, (long long)n_rows);
+    if (n == 0) return OSN_OK;
+    OSN_REQUIRE(X && out, OSN_E_ARG, "%s: null pointer", who);
+    OSN_REQUIRE(aligned16(X) && aligned16(out), OSN_E_ARG, "%s: X and the bank's rows must be 16-byte aligned", who);
+    return OSN_OK;
+}
 
 extern "C" int osn_bank_append(const float* X, int64_t n_rows, const int64_t* gather, int64_t n, int d, void* bank_f16,
                                int64_t row0, int32_t* err, osn_stream_t stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    OSN_REQUIRE(n >= 0 && n_rows >= 0 && row0 >= 0 && d >= 8 && (d & 7) == 0, OSN_E_ARG,
-                "osn_bank_append: need n, n_rows, row0 >= 0 and d %% 8 == 0 (n=%lld n_rows=%lld row0=%lld d=%d)", (long long)n,
-                (long long)n_rows, (long long)row0, d);
-    OSN_REQUIRE(err, OSN_E_ARG, "osn_bank_append: null err word");
-    OSN_REQUIRE(gather || n <= n_rows, OSN_E_ARG, "osn_bank_append: %lld rows wanted of %lld", (long long)n, (long long)n_rows);
-    if (n == 0) return OSN_OK;
-    OSN_REQUIRE(X && bank_f16, OSN_E_ARG, "osn_bank_append: null pointer");
-    OSN_REQUIRE(aligned16(X) && aligned16(bank_f16), OSN_E_ARG, "osn_bank_append: X and the bank must be 16-byte aligned");
+    const int rc = append_args("osn_bank_append", 8, X, n_rows, gather, n, d, bank_f16, row0, err);
+    if (rc != OSN_OK || n == 0) return rc;
     _Float16* out = static_cast<_Float16*>(bank_f16) + row0 * int64_t(d);
     const int64_t blocks = cdiv(n * (d / 4), 256);
     const unsigned grid = unsigned(blocks < (int64_t(1) << 20) ? blocks : (int64_t(1) << 20));
     hipLaunchKernelGGL(bank_append_kernel, dim3(grid), dim3(256), 0, st, X, n_rows, gather, n, d / 4, out, err);
+    OSN_LAUNCH_CHECK();
+    return OSN_OK;
+}
+
+extern "C" int osn_bank_append_fp8(const void* X, int x_is_f16, int64_t n_rows, const int64_t* gather, int64_t n, int d,
+                                   uint8_t* codes, int8_t* exps, int64_t row0, int32_t* err, osn_stream_t stream) {
+    hipStream_t st = static_cast<hipStream_t>(stream);
+    OSN_REQUIRE(x_is_f16 == 0 || x_is_f16 == 1, OSN_E_ARG, "osn_bank_append_fp8: x_is_f16=%d (0 or 1)", x_is_f16);
+    const int rc = append_args("osn_bank_append_fp8", 16, X, n_rows, gather, n, d, codes, row0, err);
+    if (rc != OSN_OK || n == 0) return rc;
+    OSN_REQUIRE(exps, OSN_E_ARG, "osn_bank_append_fp8: null pointer");
+    uint8_t* out = codes + row0 * int64_t(d);
+    const int64_t blocks = cdiv(n, 4);
+    const dim3 grid(unsigned(blocks < (int64_t(1) << 20) ? blocks : (int64_t(1) << 20)));
+    if (x_is_f16) hipLaunchKernelGGL(bank_append_fp8_kernel<true>, grid, dim3(256), 0, st, X, n_rows, gather, n, d / 16, out, exps + row0, err);
+    else hipLaunchKernelGGL(bank_append_fp8_kernel<false>, grid, dim3(256), 0, st, X, n_rows, gather, n, d / 16, out, exps + row0, err);
     OSN_LAUNCH_CHECK();
     return OSN_OK;
 }
@@ -855,87 +833,61 @@ extern "C" size_t osn_bank_search_ws_bytes(int64_t n, int n_scenes, int q, int k
     return search_ws(n, n_scenes, q, k, max_scene_rows).total;
 }
 
-extern "C" int osn_bank_search(const void* bank_f16, int64_t n, int d, const int64_t* scene_offsets, int n_scenes,
-                               int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
-                               const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
-                               int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream) {
+// both searches: `rows` are fp16 rows or, with `fp8`, e4m3 codes that go with the row exponents `exps`; `who` names the entry
+// in the messages
+static int bank_search_impl(const char* who, bool fp8, const void* rows, const int8_t* exps, int64_t n, int d, const int64_t* scene_offsets,
+                            int n_scenes, int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
+                            const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points, int64_t* counts,
+                            int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
-    OSN_REQUIRE(n >= 0 && d >= 8 && (d & 7) == 0 && q >= 1 && q <= 1024, OSN_E_ARG,
-                "osn_bank_search: need n >= 0, d %% 8 == 0 and 1 <= q <= 1024 (n=%lld d=%d q=%d)", (long long)n, d, q);
+    const int dm = fp8 ? 16 : 8;
+    OSN_REQUIRE(n >= 0 && d >= dm && d % dm == 0 && q >= 1 && q <= 1024, OSN_E_ARG,
+                "%s: need n >= 0, d %% %d == 0 and 1 <= q <= 1024 (n=%lld d=%d q=%d)", who, dm, (long long)n, d, q);
     OSN_REQUIRE(n_scenes >= 0 && n_scenes <= 65535 && max_scene_rows >= 0 && max_scene_rows < (int64_t(1) << 31), OSN_E_ARG,
-                "osn_bank_search: n_scenes=%d (0 .. 65535) max_scene_rows=%lld (< 2^31)", n_scenes, (long long)max_scene_rows);
-    OSN_REQUIRE((normalize == 0 || normalize == 1) && k >= 1 && k <= 128, OSN_E_ARG,
-                "osn_bank_search: normalize=%d (0 or 1) k=%d (1 .. 128)", normalize, k);
-    OSN_REQUIRE(queries_f16 && aligned16(queries_f16), OSN_E_ARG, "osn_bank_search: queries must be non-null and 16-byte aligned");
-    OSN_REQUIRE(n == 0 || (bank_f16 && aligned16(bank_f16)), OSN_E_ARG, "osn_bank_search: the bank must be non-null and 16-byte aligned");
-    OSN_REQUIRE(n_scenes == 0 || (scene_offsets && topk_scores_f16 && topk_points && err), OSN_E_ARG, "osn_bank_search: null pointer");
-    OSN_REQUIRE(!counts || thresholds, OSN_E_ARG, "osn_bank_search: counts need thresholds");
+                "%s: n_scenes=%d (0 .. 65535) max_scene_rows=%lld (< 2^31)", who, n_scenes, (long long)max_scene_rows);
+    OSN_REQUIRE((normalize == 0 || normalize == 1) && k >= 1 && k <= 128, OSN_E_ARG, "%s: normalize=%d (0 or 1) k=%d (1 .. 128)", who,
+                normalize, k);
+    OSN_REQUIRE(queries_f16 && aligned16(queries_f16), OSN_E_ARG, "%s: queries must be non-null and 16-byte aligned", who);
+    OSN_REQUIRE(n == 0 || (rows && aligned16(rows) && (exps || !fp8)), OSN_E_ARG,
+                "%s: the bank's rows%s must be non-null, the rows 16-byte aligned", who, fp8 ? " and exponents" : "");
+    OSN_REQUIRE(n_scenes == 0 || (scene_offsets && topk_scores_f16 && topk_points && err), OSN_E_ARG, "%s: null pointer", who);
+    OSN_REQUIRE(!counts || thresholds, OSN_E_ARG, "%s: counts need thresholds", who);
     const SearchWs w = search_ws(n, n_scenes, q, k, max_scene_rows);
-    OSN_REQUIRE(ws && aligned16(ws) && ws_bytes >= w.total, OSN_E_WS, "osn_bank_search: workspace too small (%zu < %zu)", ws_bytes, w.total);
+    OSN_REQUIRE(ws && aligned16(ws) && ws_bytes >= w.total, OSN_E_WS, "%s: workspace too small (%zu < %zu)", who, ws_bytes, w.total);
     char* p = static_cast<char*>(ws);
     _Float16* heatT = reinterpret_cast<_Float16*>(p + w.heatT);
     if (n > 0) {
         const dim3 grid(unsigned(cdiv(n, S_BM))), block(256);
-        const _Float16* B = static_cast<const _Float16*>(bank_f16);
         const _Float16* T = static_cast<const _Float16*>(queries_f16);
         _Float16* heat = static_cast<_Float16*>(heat_f16);
-        if (q <= 32) hipLaunchKernelGGL((heat_kernel<1, 3>), grid, block, 0, st, B, T, heat, heatT, w.ldT, n, d, q, normalize);
-        else hipLaunchKernelGGL((heat_kernel<2, 3>), grid, block, 0, st, B, T, heat, heatT, w.ldT, n, d, q, normalize);
+        if (fp8) {
+            const uint8_t* B = static_cast<const uint8_t*>(rows);
+            if (q <= 32) hipLaunchKernelGGL((heat_fp8_kernel<1, 2>), grid, block, 0, st, B, exps, T, heat, heatT, w.ldT, n, d, q, normalize);
+            else hipLaunchKernelGGL((heat_fp8_kernel<2, 2>), grid, block, 0, st, B, exps, T, heat, heatT, w.ldT, n, d, q, normalize);
+        } else {
+            const _Float16* B = static_cast<const _Float16*>(rows);
+            if (q <= 32) hipLaunchKernelGGL((heat_kernel<1, 3>), grid, block, 0, st, B, T, heat, heatT, w.ldT, n, d, q, normalize);
+            else hipLaunchKernelGGL((heat_kernel<2, 3>), grid, block, 0, st, B, T, heat, heatT, w.ldT, n, d, q, normalize);
+        }
         OSN_LAUNCH_CHECK();
     }
     if (n_scenes == 0) return OSN_OK;
     return select_pass(w, p, n, scene_offsets, n_scenes, max_scene_rows, q, k, thresholds, topk_scores_f16, topk_points, counts, err, st);
 }
 
-extern "C" int osn_bank_append_fp8(const void* X, int x_is_f16, int64_t n_rows, const int64_t* gather, int64_t n, int d,
-                                   uint8_t* codes, int8_t* exps, int64_t row0, int32_t* err, osn_stream_t stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    OSN_REQUIRE(n >= 0 && n_rows >= 0 && row0 >= 0 && d >= 16 && (d & 15) == 0, OSN_E_ARG,
-                "osn_bank_append_fp8: need n, n_rows, row0 >= 0 and d %% 16 == 0 (n=%lld n_rows=%lld row0=%lld d=%d)", (long long)n,
-                (long long)n_rows, (long long)row0, d);
-    OSN_REQUIRE(x_is_f16 == 0 || x_is_f16 == 1, OSN_E_ARG, "osn_bank_append_fp8: x_is_f16=%d (0 or 1)", x_is_f16);
-    OSN_REQUIRE(err, OSN_E_ARG, "osn_bank_append_fp8: null err word");
-    OSN_REQUIRE(gather || n <= n_rows, OSN_E_ARG, "osn_bank_append_fp8: %lld rows wanted of %lld", (long long)n, (long long)n_rows);
-    if (n == 0) return OSN_OK;
-    OSN_REQUIRE(X && codes && exps, OSN_E_ARG, "osn_bank_append_fp8: null pointer");
-    OSN_REQUIRE(aligned16(X) && aligned16(codes), OSN_E_ARG, "osn_bank_append_fp8: X and the codes must be 16-byte aligned");
-    uint8_t* out = codes + row0 * int64_t(d);
-    const int64_t blocks = cdiv(n, 4);
-    const dim3 grid(unsigned(blocks < (int64_t(1) << 20) ? blocks : (int64_t(1) << 20)));
-    if (x_is_f16) hipLaunchKernelGGL(bank_append_fp8_kernel<true>, grid, dim3(256), 0, st, X, n_rows, gather, n, d / 16, out, exps + row0, err);
-    else hipLaunchKernelGGL(bank_append_fp8_kernel<false>, grid, dim3(256), 0, st, X, n_rows, gather, n, d / 16, out, exps + row0, err);
-    OSN_LAUNCH_CHECK();
-    return OSN_OK;
+extern "C" int osn_bank_search(const void* bank_f16, int64_t n, int d, const int64_t* scene_offsets, int n_scenes,
+                               int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
+                               const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
+                               int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream) {
+    return bank_search_impl("osn_bank_search", false, bank_f16, nullptr, n, d, scene_offsets, n_scenes, max_scene_rows, queries_f16, q,
+                            normalize, k, thresholds, heat_f16, topk_scores_f16, topk_points, counts, err, ws, ws_bytes, stream);
 }
 
 extern "C" int osn_bank_search_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int d, const int64_t* scene_offsets,
                                    int n_scenes, int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
                                    const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
                                    int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream) {
-    hipStream_t st = static_cast<hipStream_t>(stream);
-    OSN_REQUIRE(n >= 0 && d >= 16 && (d & 15) == 0 && q >= 1 && q <= 1024, OSN_E_ARG,
-                "osn_bank_search_fp8: need n >= 0, d %% 16 == 0 and 1 <= q <= 1024 (n=%lld d=%d q=%d)", (long long)n, d, q);
-    OSN_REQUIRE(n_scenes >= 0 && n_scenes <= 65535 && max_scene_rows >= 0 && max_scene_rows < (int64_t(1) << 31), OSN_E_ARG,
-                "osn_bank_search_fp8: n_scenes=%d (0 .. 65535) max_scene_rows=%lld (< 2^31)", n_scenes, (long long)max_scene_rows);
-    OSN_REQUIRE((normalize == 0 || normalize == 1) && k >= 1 && k <= 128, OSN_E_ARG,
-                "osn_bank_search_fp8: normalize=%d (0 or 1) k=%d (1 .. 128)", normalize, k);
-    OSN_REQUIRE(queries_f16 && aligned16(queries_f16), OSN_E_ARG, "osn_bank_search_fp8: queries must be non-null and 16-byte aligned");
-    OSN_REQUIRE(n == 0 || (codes && exps && aligned16(codes)), OSN_E_ARG,
-                "osn_bank_search_fp8: codes and exponents must be non-null, the codes 16-byte aligned");
-    OSN_REQUIRE(n_scenes == 0 || (scene_offsets && topk_scores_f16 && topk_points && err), OSN_E_ARG, "osn_bank_search_fp8: null pointer");
-    OSN_REQUIRE(!counts || thresholds, OSN_E_ARG, "osn_bank_search_fp8: counts need thresholds");
-    const SearchWs w = search_ws(n, n_scenes, q, k, max_scene_rows);
-    OSN_REQUIRE(ws && aligned16(ws) && ws_bytes >= w.total, OSN_E_WS, "osn_bank_search_fp8: workspace too small (%zu < %zu)", ws_bytes, w.total);
-    char* p = static_cast<char*>(ws);
-    _Float16* heatT = reinterpret_cast<_Float16*>(p + w.heatT);
-    if (n > 0) {
-        const dim3 grid(unsigned(cdiv(n, S_BM))), block(256);
-        const _Float16* T = static_cast<const _Float16*>(queries_f16);
-        _Float16* heat = static_cast<_Float16*>(heat_f16);
-        if (q <= 32) hipLaunchKernelGGL((heat_fp8_kernel<1, 2>), grid, block, 0, st, codes, exps, T, heat, heatT, w.ldT, n, d, q, normalize);
-        else hipLaunchKernelGGL((heat_fp8_kernel<2, 2>), grid, block, 0, st, codes, exps, T, heat, heatT, w.ldT, n, d, q, normalize);
-        OSN_LAUNCH_CHECK();
-    }
-    if (n_scenes == 0) return OSN_OK;
-    return select_pass(w, p, n, scene_offsets, n_scenes, max_scene_rows, q, k, thresholds, topk_scores_f16, topk_points, counts, err, st);
+    return bank_search_impl("osn_bank_search_fp8", true, codes, exps, n, d, scene_offsets, n_scenes, max_scene_rows,
+                            queries_f16, q, normalize, k, thresholds, heat_f16, topk_scores_f16, topk_points, counts, err, ws,
+                            ws_bytes, stream);
 }

@@ -1325,6 +1325,22 @@ BANK_MAX_K = 128
 BANK_MAX_Q = 1024
 
 
+def _bank_append_args(feats, rows, row0, err, gather):
+    """What bank_append and bank_append_fp8 check alike; `rows` is the matrix the rows go to.  -> (gather, n, row0)"""
+    dev = feats.device
+    if gather is not None:
+        if gather.dim() != 1 or gather.device != dev:
+            raise ValueError("gather must be a vector on the features' device")
+        gather = (gather if gather.dtype == torch.int64 else gather.long()).contiguous()
+    n = gather.shape[0] if gather is not None else feats.shape[0]
+    row0 = int(row0)
+    if row0 < 0 or row0 + n > rows.shape[0]:
+        raise ValueError("rows [%d, %d) do not fit a bank of %d rows" % (row0, row0 + n, rows.shape[0]))
+    if err.dtype != torch.int32 or err.numel() != 1 or err.device != dev:
+        raise ValueError("err must be an int32 [1] tensor on the features' device")
+    return gather, n, row0
+
+
 def bank_append(bank, row0, feats, err, gather=None):
     """bank[row0 : row0 + n] = feats[gather].half() (fp16 rows of a caller-owned matrix, no float32 intermediate):
     the rows `run/evaluate.py:290` forms.  A gather index outside the feature matrix writes nothing for its row and is
@@ -1337,16 +1353,7 @@ def bank_append(bank, row0, feats, err, gather=None):
     if (bank.dtype != torch.float16 or bank.dim() != 2 or bank.device != dev or not bank.is_contiguous()
             or bank.shape[1] != feats.shape[1]):
         raise ValueError("the bank must be a contiguous float16 [rows, %d] matrix on the features' device" % feats.shape[1])
-    if gather is not None:
-        if gather.dim() != 1 or gather.device != dev:
-            raise ValueError("gather must be a vector on the features' device")
-        gather = (gather if gather.dtype == torch.int64 else gather.long()).contiguous()
-    n = gather.shape[0] if gather is not None else feats.shape[0]
-    row0 = int(row0)
-    if row0 < 0 or row0 + n > bank.shape[0]:
-        raise ValueError("rows [%d, %d) do not fit a bank of %d rows" % (row0, row0 + n, bank.shape[0]))
-    if err.dtype != torch.int32 or err.numel() != 1 or err.device != dev:
-        raise ValueError("err must be an int32 [1] tensor on the features' device")
+    gather, n, row0 = _bank_append_args(feats, bank, row0, err, gather)
     with _Dev(dev):
         check(lib.osn_bank_append(_p(feats), feats.shape[0], _p(gather), n, feats.shape[1], _p(bank), row0, _p(err),
                                   _stream(dev)), "osn_bank_append")
@@ -1361,37 +1368,25 @@ def bank_check(err):
         check(lib.osn_bank_check(_p(err), _stream(dev)), "osn_bank_check")
 
 
-def bank_search(bank, scene_offsets, queries, k=16, thresholds=None, normalize=True, want_heat=False, max_scene_rows=None,
-                err=None):
-    """Scores of every bank row against every query and the k best rows of every scene.
-    bank fp16 [N, d]; scene_offsets int64 [S + 1] on the device (ascending from 0; S = 0 computes the heat-map only);
-    queries fp16 [Q, d], L2-normalised; thresholds float32 [Q] or None.
-    -> (heat fp16 [N, Q] or None, topk_scores fp16 [S, Q, k], topk_points int64 [S, Q, k] (row inside the scene, -1 = padding),
-        counts int64 [S, Q] or None).
-    max_scene_rows: the longest scene, when the caller knows it (saves reading the offsets back).  Bad offsets are recorded
-    in `err` when one is given (bank_check raises), and checked here otherwise."""
-    dev = bank.device
-    lib = _prep(dev)
-    if bank.dtype != torch.float16:
-        raise TypeError("the bank must be float16 (got %s)" % bank.dtype)
+def _bank_search(entry, bank_ptrs, n, d, d_multiple, dev, scene_offsets, queries, k, thresholds, normalize, want_heat,
+                 max_scene_rows, err):
+    """bank_search and bank_search_fp8 behind their own checks of the bank: `entry` is the C entry that takes `bank_ptrs`
+    (the fp16 rows, or the codes and the exponents) ahead of the arguments the two share."""
     if queries.dtype != torch.float16:
         raise TypeError("queries must be float16 (util/util.py:41-44 produces fp16)")
-    if bank.dim() != 2 or not bank.is_contiguous():
-        raise ValueError("the bank must be a contiguous [rows, dim] matrix")
-    if queries.dim() != 2 or queries.shape[1] != bank.shape[1]:
-        raise ValueError("queries must be [Q, %d] (got %s)" % (bank.shape[1], tuple(queries.shape)))
+    if queries.dim() != 2 or queries.shape[1] != d:
+        raise ValueError("queries must be [Q, %d] (got %s)" % (d, tuple(queries.shape)))
     if queries.device != dev:
         raise ValueError("queries must be on the bank's device")
     queries = queries.contiguous()
-    n, d = bank.shape
     q = queries.shape[0]
     k = int(k)
     if not 1 <= k <= BANK_MAX_K:
         raise ValueError("k must be in 1 .. %d (got %d)" % (BANK_MAX_K, k))
     if not 1 <= q <= BANK_MAX_Q:
         raise ValueError("1 .. %d queries per call (got %d)" % (BANK_MAX_Q, q))
-    if d % 8:
-        raise ValueError("the feature dim must be a multiple of 8 (got %d)" % d)
+    if d < d_multiple or d % d_multiple:
+        raise ValueError("the feature dim must be a multiple of %d (got %d)" % (d_multiple, d))
     if scene_offsets.dtype != torch.int64 or scene_offsets.dim() != 1 or scene_offsets.shape[0] < 1 or scene_offsets.device != dev:
         raise ValueError("scene_offsets must be an int64 [S + 1] vector on the bank's device")
     scene_offsets = scene_offsets.contiguous()
@@ -1416,12 +1411,30 @@ def bank_search(bank, scene_offsets, queries, k=16, thresholds=None, normalize=T
     wsb = _cached("osn_bank_search_ws_bytes", n, s, q, k, max_scene_rows)
     ws = _ws(wsb, dev)
     with _Dev(dev):
-        check(lib.osn_bank_search(_p(bank), n, d, _p(scene_offsets), s, max_scene_rows, _p(queries), q, int(bool(normalize)), k,
-                                  _p(thresholds), _p(heat), _p(top_s), _p(top_p), _p(counts), _p(err), _p(ws), ws.numel(),
-                                  _stream(dev)), "osn_bank_search")
+        check(entry(*bank_ptrs, n, d, _p(scene_offsets), s, max_scene_rows, _p(queries), q, int(bool(normalize)), k, _p(thresholds),
+                    _p(heat), _p(top_s), _p(top_p), _p(counts), _p(err), _p(ws), ws.numel(), _stream(dev)), entry.__name__)
     if own_err and s > 0:
         bank_check(err)
     return heat, top_s, top_p, counts
+
+
+def bank_search(bank, scene_offsets, queries, k=16, thresholds=None, normalize=True, want_heat=False, max_scene_rows=None,
+                err=None):
+    """Scores of every bank row against every query and the k best rows of every scene.
+    bank fp16 [N, d]; scene_offsets int64 [S + 1] on the device (ascending from 0; S = 0 computes the heat-map only);
+    queries fp16 [Q, d], L2-normalised; thresholds float32 [Q] or None.
+    -> (heat fp16 [N, Q] or None, topk_scores fp16 [S, Q, k], topk_points int64 [S, Q, k] (row inside the scene, -1 = padding),
+        counts int64 [S, Q] or None).
+    max_scene_rows: the longest scene, when the caller knows it (saves reading the offsets back).  Bad offsets are recorded
+    in `err` when one is given (bank_check raises), and checked here otherwise."""
+    lib = _prep(bank.device)
+    if bank.dtype != torch.float16:
+        raise TypeError("the bank must be float16 (got %s)" % bank.dtype)
+    if bank.dim() != 2 or not bank.is_contiguous():
+        raise ValueError("the bank must be a contiguous [rows, dim] matrix")
+    n, d = bank.shape
+    return _bank_search(lib.osn_bank_search, (_p(bank),), n, d, 8, bank.device, scene_offsets, queries, k, thresholds, normalize,
+                        want_heat, max_scene_rows, err)
 
 
 def bank_append_fp8(codes, exps, row0, feats, err, gather=None):
@@ -1445,16 +1458,7 @@ def bank_append_fp8(codes, exps, row0, feats, err, gather=None):
     if (exps.dtype != torch.int8 or exps.dim() != 1 or exps.device != dev or not exps.is_contiguous()
             or exps.shape[0] != codes.shape[0]):
         raise ValueError("exponents must be a contiguous int8 [%d] vector on the features' device" % codes.shape[0])
-    if gather is not None:
-        if gather.dim() != 1 or gather.device != dev:
-            raise ValueError("gather must be a vector on the features' device")
-        gather = (gather if gather.dtype == torch.int64 else gather.long()).contiguous()
-    n = gather.shape[0] if gather is not None else feats.shape[0]
-    row0 = int(row0)
-    if row0 < 0 or row0 + n > codes.shape[0]:
-        raise ValueError("rows [%d, %d) do not fit a bank of %d rows" % (row0, row0 + n, codes.shape[0]))
-    if err.dtype != torch.int32 or err.numel() != 1 or err.device != dev:
-        raise ValueError("err must be an int32 [1] tensor on the features' device")
+    gather, n, row0 = _bank_append_args(feats, codes, row0, err, gather)
     with _Dev(dev):
         check(lib.osn_bank_append_fp8(_p(feats), int(feats.dtype == torch.float16), feats.shape[0], _p(gather), n, d, _p(codes),
                                       _p(exps), row0, _p(err), _stream(dev)), "osn_bank_append_fp8")
@@ -1471,56 +1475,13 @@ def bank_search_fp8(codes, exps, scene_offsets, queries, k=16, thresholds=None, 
         raise TypeError("codes must be uint8 (got %s)" % codes.dtype)
     if exps.dtype != torch.int8:
         raise TypeError("exponents must be int8 (got %s)" % exps.dtype)
-    if queries.dtype != torch.float16:
-        raise TypeError("queries must be float16 (util/util.py:41-44 produces fp16)")
     if codes.dim() != 2 or not codes.is_contiguous():
         raise ValueError("codes must be a contiguous [rows, dim] matrix")
     if exps.dim() != 1 or exps.shape[0] != codes.shape[0] or exps.device != dev or not exps.is_contiguous():
         raise ValueError("exponents must be a contiguous [%d] vector on the codes' device" % codes.shape[0])
-    if queries.dim() != 2 or queries.shape[1] != codes.shape[1]:
-        raise ValueError("queries must be [Q, %d] (got %s)" % (codes.shape[1], tuple(queries.shape)))
-    if queries.device != dev:
-        raise ValueError("queries must be on the bank's device")
-    queries = queries.contiguous()
     n, d = codes.shape
-    q = queries.shape[0]
-    k = int(k)
-    if not 1 <= k <= BANK_MAX_K:
-        raise ValueError("k must be in 1 .. %d (got %d)" % (BANK_MAX_K, k))
-    if not 1 <= q <= BANK_MAX_Q:
-        raise ValueError("1 .. %d queries per call (got %d)" % (BANK_MAX_Q, q))
-    if d < 16 or d % 16:
-        raise ValueError("the feature dim must be a multiple of 16 (got %d)" % d)
-    if scene_offsets.dtype != torch.int64 or scene_offsets.dim() != 1 or scene_offsets.shape[0] < 1 or scene_offsets.device != dev:
-        raise ValueError("scene_offsets must be an int64 [S + 1] vector on the bank's device")
-    scene_offsets = scene_offsets.contiguous()
-    s = scene_offsets.shape[0] - 1
-    if thresholds is not None:
-        if thresholds.dtype != torch.float32 or tuple(thresholds.shape) != (q,) or thresholds.device != dev:
-            raise ValueError("thresholds must be a float32 [%d] vector on the bank's device" % q)
-        thresholds = thresholds.contiguous()
-    if max_scene_rows is None:
-        max_scene_rows = int((scene_offsets[1:] - scene_offsets[:-1]).max().item()) if s > 0 else 0
-        max_scene_rows = min(max(max_scene_rows, 0), n)
-    max_scene_rows = int(max_scene_rows)
-    own_err = err is None
-    if own_err:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-    elif err.dtype != torch.int32 or err.numel() != 1 or err.device != dev:
-        raise ValueError("err must be an int32 [1] tensor on the bank's device")
-    heat = torch.empty((n, q), dtype=torch.float16, device=dev) if want_heat else None
-    top_s = torch.empty((s, q, k), dtype=torch.float16, device=dev)
-    top_p = torch.empty((s, q, k), dtype=torch.int64, device=dev)
-    counts = torch.empty((s, q), dtype=torch.int64, device=dev) if thresholds is not None else None
-    wsb = _cached("osn_bank_search_ws_bytes", n, s, q, k, max_scene_rows)
-    ws = _ws(wsb, dev)
-    with _Dev(dev):
-        check(lib.osn_bank_search_fp8(_p(codes), _p(exps), n, d, _p(scene_offsets), s, max_scene_rows, _p(queries), q,
-                                      int(bool(normalize)), k, _p(thresholds), _p(heat), _p(top_s), _p(top_p), _p(counts), _p(err),
-                                      _p(ws), ws.numel(), _stream(dev)), "osn_bank_search_fp8")
-    if own_err and s > 0:
-        bank_check(err)
-    return heat, top_s, top_p, counts
+    return _bank_search(lib.osn_bank_search_fp8, (_p(codes), _p(exps)), n, d, 16, dev, scene_offsets, queries, k, thresholds,
+                        normalize, want_heat, max_scene_rows, err)
 
 
 # --------------------------------------------------------------------- objects

@@ -21,6 +21,11 @@ from . import io as _io
 from . import ops
 
 
+# what a bank of each kind stores: (name in the file, dtype, a row is [dim] values (True) or one (False)) per tensor
+_STORAGE = {"fp16": (("features", torch.float16, True),),
+            "fp8": (("codes", torch.uint8, True), ("exponents", torch.int8, False))}
+
+
 class FeatureBank:
     """A growing [rows, dim] matrix on `device` holding the per-point features of many scenes back to back.
 
@@ -43,13 +48,7 @@ class FeatureBank:
         self.dim = dim
         self.dtype = dtype
         self.device = torch.device(device)
-        cap = max(int(capacity_rows), 1)
-        if dtype == "fp16":
-            self._data = torch.empty((cap, dim), dtype=torch.float16, device=self.device)
-        else:
-            self._data = None
-            self._codes = torch.empty((cap, dim), dtype=torch.uint8, device=self.device)
-            self._exps = torch.empty((cap,), dtype=torch.int8, device=self.device)
+        self._store = self._alloc(max(int(capacity_rows), 1))          # (features,) or (codes, exponents), filled and scratch rows
         self.offsets = [0]
         self.names = []
         self._offsets_dev = None
@@ -65,12 +64,12 @@ class FeatureBank:
 
     @property
     def capacity_rows(self):
-        return (self._data if self.dtype == "fp16" else self._codes).shape[0]
+        return self._store[0].shape[0]
 
     @property
     def nbytes(self):
         """Bytes of the filled rows."""
-        return self.rows * (2 * self.dim if self.dtype == "fp16" else self.dim + 1)
+        return self.rows * sum(t.element_size() * t[0].numel() for t in self._store)
 
     def _need(self, dtype, what):
         if self.dtype != dtype:
@@ -81,7 +80,7 @@ class FeatureBank:
     def features(self):
         """fp16 [rows, dim]: a view of the filled part (fp16 bank)."""
         self._need("fp16", "features")
-        return self._data[:self.rows]
+        return self._store[0][:self.rows]
 
     @property
     def codes(self):
@@ -95,6 +94,14 @@ class FeatureBank:
         self._need("fp8", "exponents")
         return self._exps[:self.rows]
 
+    @property
+    def _codes(self):
+        return self._store[0]
+
+    @property
+    def _exps(self):
+        return self._store[1]
+
     def _span(self, which):
         if which is None:
             return 0, self.rows
@@ -105,7 +112,7 @@ class FeatureBank:
         """fp16 [n, dim] view of one scene's rows (by name or position; fp16 bank)."""
         self._need("fp16", "scene()")
         a, b = self._span(which)
-        return self._data[a:b]
+        return self._store[0][a:b]
 
     def dequantize(self, which=None):
         """float32 [n, dim]: the stored values ``code * 2^e`` of one scene (by name or position) or, with None, of the
@@ -130,21 +137,18 @@ class FeatureBank:
         return self._err
 
     # ---- growth
+    def _alloc(self, cap):
+        return tuple(torch.empty((cap, self.dim) if wide else (cap,), dtype=dtype, device=self.device)
+                     for _, dtype, wide in _STORAGE[self.dtype])
+
     def _reserve(self, n):
         need = self.rows + n
         if need <= self.capacity_rows:
             return
-        cap = max(need, 2 * self.capacity_rows)
-        if self.dtype == "fp16":
-            data = torch.empty((cap, self.dim), dtype=torch.float16, device=self.device)
-            data[:self.rows].copy_(self._data[:self.rows])
-            self._data = data
-            return
-        codes = torch.empty((cap, self.dim), dtype=torch.uint8, device=self.device)
-        exps = torch.empty((cap,), dtype=torch.int8, device=self.device)
-        codes[:self.rows].copy_(self._codes[:self.rows])
-        exps[:self.rows].copy_(self._exps[:self.rows])
-        self._codes, self._exps = codes, exps
+        store = self._alloc(max(need, 2 * self.capacity_rows))
+        for new, old in zip(store, self._store):
+            new[:self.rows].copy_(old[:self.rows])
+        self._store = store
 
     def _commit(self, name, n):
         self.offsets.append(self.rows + n)
@@ -164,6 +168,19 @@ class FeatureBank:
             err.zero_()                           # rows past `rows` are scratch: the bank is as it was
             raise
 
+    def _append(self, features, inds_reverse):
+        """features[inds_reverse] through the bank kind's append kernel into the rows after the filled ones.  -> their number"""
+        features = features.to(self.device)
+        if inds_reverse is not None:
+            inds_reverse = self._gather(inds_reverse)
+        n = features.shape[0] if inds_reverse is None else inds_reverse.shape[0]
+        self._reserve(n)
+        err = self._err_word()
+        append = ops.bank_append if self.dtype == "fp16" else ops.bank_append_fp8
+        append(*self._store, self.rows, features, err, gather=inds_reverse)
+        self._checked(err)
+        return n
+
     def add_scene(self, name, features, inds_reverse=None):
         """Append one scene.  float32 features on the bank's device -- the network output, with the voxel -> point
         map `inds_reverse`: exactly ``predictions = feat_3d[inds_reverse]`` of ``run/evaluate.py:290``, stored as the
@@ -179,29 +196,13 @@ class FeatureBank:
             raise ValueError("features must be [points, %d] (got %s)" % (self.dim, tuple(features.shape)))
         if features.dtype not in (torch.float16, torch.float32):
             raise TypeError("features must be float32 or float16 (got %s)" % features.dtype)
-        if self.dtype == "fp8":
-            features = features.to(self.device)
-            if inds_reverse is not None:
-                inds_reverse = self._gather(inds_reverse)
-            n = features.shape[0] if inds_reverse is None else inds_reverse.shape[0]
-            self._reserve(n)
-            err = self._err_word()
-            ops.bank_append_fp8(self._codes, self._exps, self.rows, features, err, gather=inds_reverse)
-            self._checked(err)
-        elif features.dtype == torch.float16:
+        if self.dtype == "fp16" and features.dtype == torch.float16:
             rows = features if inds_reverse is None else features[torch.as_tensor(inds_reverse).long().to(features.device)]
             n = rows.shape[0]
             self._reserve(n)
-            self._data[self.rows:self.rows + n].copy_(rows)
+            self._store[0][self.rows:self.rows + n].copy_(rows)
         else:
-            features = features.to(self.device)
-            if inds_reverse is not None:
-                inds_reverse = self._gather(inds_reverse)
-            n = features.shape[0] if inds_reverse is None else inds_reverse.shape[0]
-            self._reserve(n)
-            err = self._err_word()
-            ops.bank_append(self._data, self.rows, features, err, gather=inds_reverse)
-            self._checked(err)
+            n = self._append(features, inds_reverse)
         self._commit(name, n)
         return len(self.names) - 1
 
@@ -222,9 +223,7 @@ class FeatureBank:
         self._need("fp16", "to_fp8()")
         bank = FeatureBank(self.dim, self.device, capacity_rows=max(self.rows, 1), dtype="fp8")
         if self.rows:
-            err = bank._err_word()
-            ops.bank_append_fp8(bank._codes, bank._exps, 0, self.features, err)
-            bank._checked(err)
+            bank._append(self.features, None)
         bank.offsets = list(self.offsets)
         bank.names = list(self.names)
         return bank
@@ -233,11 +232,8 @@ class FeatureBank:
     def save(self, path):
         """One file: the filled rows (fp16, or codes and exponents), the offsets and the names."""
         d = {"dim": self.dim, "offsets": list(self.offsets), "names": list(self.names), "dtype": self.dtype}
-        if self.dtype == "fp16":
-            d["features"] = self.features.cpu().clone()
-        else:
-            d["codes"] = self.codes.cpu().clone()
-            d["exponents"] = self.exponents.cpu().clone()
+        for (key, _, _), t in zip(_STORAGE[self.dtype], self._store):
+            d[key] = t[:self.rows].cpu().clone()
         torch.save(d, path)
 
     @classmethod
@@ -245,21 +241,14 @@ class FeatureBank:
         d = torch.load(path, map_location="cpu", weights_only=False)
         dtype = d.get("dtype", "fp16")                      # (files written before the fp8 bank hold no "dtype")
         rows = d["offsets"][-1]
-        if dtype == "fp8":
-            codes, exps = d.get("codes"), d.get("exponents")
-            if (codes is None or exps is None or codes.dtype != torch.uint8 or exps.dtype != torch.int8
-                    or tuple(codes.shape) != (rows, d["dim"]) or tuple(exps.shape) != (rows,)):
-                raise ValueError("%s is not a feature bank" % path)
-            bank = cls(d["dim"], device, capacity_rows=max(rows, 1), dtype="fp8")
-            bank._codes[:rows].copy_(codes)
-            bank._exps[:rows].copy_(exps)
-        else:
-            feats = d.get("features")
-            if (dtype != "fp16" or feats is None or feats.dtype != torch.float16 or feats.dim() != 2
-                    or feats.shape[1] != d["dim"] or feats.shape[0] != rows):
-                raise ValueError("%s is not a feature bank" % path)
-            bank = cls(d["dim"], device, capacity_rows=max(rows, 1))
-            bank._data[:rows].copy_(feats)
+        layout = _STORAGE.get(dtype, ())
+        parts = [d.get(key) for key, _, _ in layout]
+        if not parts or any(t is None or t.dtype != dt or tuple(t.shape) != ((rows, d["dim"]) if wide else (rows,))
+                            for t, (_, dt, wide) in zip(parts, layout)):
+            raise ValueError("%s is not a feature bank" % path)
+        bank = cls(d["dim"], device, capacity_rows=max(rows, 1), dtype=dtype)
+        for dst, t in zip(bank._store, parts):
+            dst[:rows].copy_(t)
         bank.offsets = [int(o) for o in d["offsets"]]
         bank.names = [str(n) for n in d["names"]]
         return bank

@@ -50,6 +50,26 @@ def same_bits(a, b):
     return a.shape == b.shape and torch.equal(a.contiguous().view(torch.int16), b.contiguous().view(torch.int16))
 
 
+# ---- inputs and the selection check the GPU search tests share
+def unit_rows(n, d, gen, lo=0.5, hi=2.0):
+    """unit rows scaled over U(lo, hi) (SURVEY.md 8(d)'s query input): |row . unit query| < 2"""
+    x = torch.nn.functional.normalize(torch.randn(n, d, generator=gen), dim=1)
+    return x * (lo + (hi - lo) * torch.rand(n, 1, generator=gen))
+
+
+def text(q, d, gen):
+    return torch.nn.functional.normalize(torch.randn(q, d, generator=gen), dim=1).half()
+
+
+def check_selection(res, heat, offsets, k, thresholds=None):
+    """`res` (a SearchResult) holds exactly the selection of `heat`, the kernel's own heat-map"""
+    top_s, top_p, counts = select(heat, offsets, k, thresholds)
+    assert torch.equal(res.topk_points, top_p)
+    assert same_bits(res.topk_scores, top_s)
+    if thresholds is not None:
+        assert torch.equal(res.counts, counts)
+
+
 # ---- CPU stand-ins for ops.bank_append / ops.bank_check / ops.bank_search (host-logic tests only)
 def bank_append(bank, row0, feats, err, gather=None):
     idx = torch.arange(feats.shape[0]) if gather is None else gather.long()

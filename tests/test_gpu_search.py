@@ -10,6 +10,7 @@ import pytest
 import torch
 
 import search_reference as sr
+from search_reference import check_selection, text, unit_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -20,30 +21,12 @@ def dev():
     return torch.device("cuda", 0)
 
 
-def unit_rows(n, d, gen, lo=0.5, hi=2.0):
-    """unit rows scaled over U(lo, hi) (SURVEY.md 8(d)'s query input): |row . unit query| < 2"""
-    x = torch.nn.functional.normalize(torch.randn(n, d, generator=gen), dim=1)
-    return x * (lo + (hi - lo) * torch.rand(n, 1, generator=gen))
-
-
-def text(q, d, gen):
-    return torch.nn.functional.normalize(torch.randn(q, d, generator=gen), dim=1).half()
-
-
 def make_bank(scenes, d, capacity_rows=1 << 10):
     from openscene_amd.search import FeatureBank
     bank = FeatureBank(d, dev(), capacity_rows=capacity_rows)
     for i, f in enumerate(scenes):
         bank.add_scene("scene%04d" % i, f)
     return bank
-
-
-def check_selection(res, heat, offsets, k, thresholds=None):
-    top_s, top_p, counts = sr.select(heat, offsets, k, thresholds)
-    assert torch.equal(res.topk_points, top_p)
-    assert sr.same_bits(res.topk_scores, top_s)
-    if thresholds is not None:
-        assert torch.equal(res.counts, counts)
 
 
 # ----------------------------------------------------------------------------------------------------------- append
