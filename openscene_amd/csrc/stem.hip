@@ -278,6 +278,9 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
                                                          int64_t n_out, int K, int cin) {
     __shared__ __attribute__((aligned(16))) float A[SW_KB * SW_ROWS * STEM_CMAX];      // [offset][row][channel]
     __shared__ __attribute__((aligned(16))) float G[SW_ROWS * STEM_COUT];
+    // live[o][w]: does row o have a pair among the eight offsets wave w staged?  A gradient row without a pair in this workgroup's 32
+    // offsets is taken as zero: the dense walk would multiply it by the zero row of the absent neighbour, and 0 x inf is not 0
+    __shared__ __attribute__((aligned(16))) int live[SW_ROWS][4];
     const int tid = threadIdx.x, n = tid & 31, kq = tid >> 5;
     const int k0 = blockIdx.y * SW_KB;
     float acc[4][STEM_CMAX];
@@ -310,6 +313,12 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
             }
             *reinterpret_cast<float4*>(&A[e * STEM_CMAX]) = v;
         }
+        {
+            bool any = false;                                          // (e % SW_ROWS = tid & 63: a thread's entries are one row's)
+#pragma unroll
+            for (int u = 0; u < SW_KB * SW_ROWS / 256; ++u) any = any || idx[u] >= 0;
+            live[tid & 63][tid >> 6] = any ? 1 : 0;
+        }
 #pragma unroll
         for (int u = 0; u < SW_ROWS * STEM_COUT / 4 / 256; ++u) {
             const int e = tid + 256 * u;
@@ -320,7 +329,8 @@ __global__ __launch_bounds__(256) void stem_wgrad_kernel(const float* __restrict
         __syncthreads();
 #pragma unroll 4
         for (int o = 0; o < SW_ROWS; ++o) {
-            const float g = G[o * STEM_COUT + n];
+            const int4 lv = *reinterpret_cast<const int4*>(&live[o][0]);                                             // broadcast
+            const float g = (lv.x | lv.y | lv.z | lv.w) ? G[o * STEM_COUT + n] : 0.f;
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float4 a = *reinterpret_cast<const float4*>(&A[((4 * kq + j) * SW_ROWS + o) * STEM_CMAX]);     // broadcast
@@ -382,6 +392,15 @@ __global__ __launch_bounds__(256, 2) void stem_mfma_wgrad_kernel(const float* __
         for (int nb = 0; nb < 2; ++nb)
 #pragma unroll
             for (int e = 0; e < 8; ++e) g[nb][e] = o0 + e < n_out ? gout[(o0 + e) * STEM_COUT + 16 * nb + l15] : 0.f;
+        // a gradient row without a pair among this wave's 32 offsets is taken as zero: every product it enters has the zero row of an
+        // absent neighbour on the other side, and 0 x inf is not 0 (the 16 lanes of a row group hold the 16 offsets of a block)
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const unsigned long long m = __ballot(idx[0][e] >= 0 || idx[1][e] >= 0);
+            const bool row_live = ((m >> (16 * lg)) & 0xFFFFull) != 0ull;
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) g[nb][e] = row_live ? g[nb][e] : 0.f;
+        }
         float x[2][STEM_CMAX][8];
 #pragma unroll
         for (int ob = 0; ob < 2; ++ob)

@@ -1,0 +1,205 @@
+"""Every convolution kernel family against the per-element abs-sum bound of tests/conv_bounds.py, and isolated from the rows its
+table does not name.  Each case calls the ops.* wrapper of the kernel its name says, on hand-made tables (about 30 % occupancy, 12 %
+for the 125-offset stem, one output row without any neighbour, a tenth of the input rows referenced by nothing) or on the oracle's
+2^3 stride-2 map, with the five operand kinds; a second call must be bitwise equal to the first.  test_conv_bounds_cpu.py shows
+that these shapes and operands tell a kernel that loses one of its six cross products from one that keeps them.
+
+Bounds: 2e-6 of the abs-sum for a forward / input-gradient launch, 2e-5 for a weight gradient, and 2e-6 for a weight gradient on
+"piece_aligned" (conv_bounds.PIECE_WGRAD_C: at 2e-5 a lost h2h2 / h1h3 / h3h1 product cannot show).  The stem's exact-fp32 kernels
+take no bound from the CPU chain: the chain meets the project's constants on every kind (figures: test_conv_bounds_cpu.py).
+
+Worst err / lim per family and kind, measured on an MI355X (the assertion message prints the same figure):
+(worst over the family's cases; forward rows against 2e-6, weight-gradient rows against 2e-5, last column against 2e-6)
+    family          row_scales     cancellation   gradient_sized wide_elements  piece_aligned  piece@2e-6     
+    rg fwd          0.14           0.01           0.06           0.19           0.46           -              
+    stem_fp32 fwd   0.23           0.08           0.12           0.27           0.26           -              
+    stem_fp32 wgrad 0.02           0.01           0.01           0.02           0.02           0.17           
+    stem_mfma fwd   0.18           0.09           0.10           0.20           0.28           -              
+    stem_mfma wgrad 0.01           0.00           0.00           0.01           0.01           0.13           
+    ws fwd          0.10           0.01           0.10           0.24           0.32           -              
+    tl fwd          0.24           0.01           0.14           0.42           0.72           -              
+    wgrad_tl wgrad  0.03           0.03           0.01           0.03           0.05           0.51           
+    wgrad1 wgrad    0.03           0.03           0.01           0.05           0.07           0.64           
+    dense fwd       0.12           0.02           0.09           0.30           0.93           -              
+"""
+import numpy as np
+import pytest
+import torch
+
+import conv_bounds as cb
+
+pytestmark = pytest.mark.gpu
+
+
+def dev():
+    return torch.device("cuda", 0)
+
+
+class Launch:
+    """The kernel of a case, ready to run on features (and an output gradient) that live on the device."""
+
+    def __init__(self, case, nbr):
+        from openscene_amd import ops
+        self.ops, self.case, self.nbr_np = ops, case, nbr
+        d = dev()
+        self.nbr = torch.from_numpy(np.ascontiguousarray(nbr)).to(d) if nbr is not None else None
+        self.tl = self.rows = self.counts = None
+        f, o = case.family, case.opt
+        if f == "rg" and o.get("perm"):
+            g = torch.Generator().manual_seed(3)
+            perm = torch.randperm(case.n_out, generator=g)
+            self.nbr, self.rows = self.nbr[:, perm.to(d)].contiguous(), perm.int().to(d)
+        if f == "tl" or (f in ("ws", "wgrad_tl") and not o.get("swap") and not o.get("identity")):
+            self.tl = ops.tile_lists(self.nbr)
+        if o.get("s2"):                                      # the lists of the strided convolution this launch mirrors
+            self.tl = ops.tile_lists(torch.from_numpy(cb.stride2_map(o["s2"])[0]).to(d))
+        if f == "wgrad1" and o.get("counts"):
+            self.counts = ops.kmap_count(self.nbr)
+        if f == "tl":                                        # the case is where its name says: a split launch, or one persistent launch
+            wsb = int(ops._cached("osn_spconv_fwd_tl_ws_bytes", case.n_out, case.K, case.cout, self.tl.bm))
+            assert (wsb > 512) == bool(o["split"]) and (o["split"] or self.tl.n_tiles > 1)
+        if f == "rg":
+            assert ops.rg_eligible(case.K, case.cin, case.cout, case.n_in)
+        if f in ("stem_fp32", "stem_mfma"):
+            assert ops.stem_eligible(case.K, case.cin, case.cout) and (case.n_out >= 32768) == (f == "stem_mfma")
+
+    def image(self, w):
+        """The weight image the launch multiplies with: the forward image of w, or the input-gradient image of the transposed weight
+        (the same matrix per offset, through the other preparation path)."""
+        ops = self.ops
+        if self.case.opt.get("image") == "dgrad":
+            return ops.weight_prep_tl(w.transpose(1, 2).contiguous(), flip=False, want_fwd=False)[1]
+        return ops.weight_prep_tl(w, want_dgrad=False)[0]
+
+    def fwd(self, feats, w, bn_partial=None):
+        ops, c, o = self.ops, self.case, self.case.opt
+        if c.family in ("stem_fp32", "stem_mfma"):
+            return ops.stem_conv_fwd(feats, w, self.nbr, c.n_out)
+        wp = self.image(w)
+        if c.family == "rg":
+            return ops.spconv_fwd_rg(feats, wp, self.nbr, c.n_out, c.cout, out_rows=self.rows)
+        if c.family == "ws":
+            return ops.spconv_fwd_ws(feats, wp, self.tl, None if o["direct"] else self.nbr, c.n_out, c.K, c.cout,
+                                     swap=bool(o["swap"]), direct=bool(o["direct"]))
+        if c.family == "tl":
+            return ops.spconv_fwd_tl(feats, wp, self.tl, c.n_out, c.K, c.cout, bn_partial=bn_partial)
+        assert c.family == "dense" and ops.dense_eligible(c.cin, c.cout)
+        return ops.dense_fwd(feats, wp, c.cout)
+
+    def wgrad(self, feats, gout):
+        ops, c, o = self.ops, self.case, self.case.opt
+        if c.family in ("stem_fp32", "stem_mfma"):
+            return ops.stem_conv_wgrad(feats, gout, self.nbr, c.K)
+        if c.family == "wgrad_tl":
+            return ops.spconv_wgrad_tl(feats, gout, self.tl, c.K, swap=bool(o.get("swap")))
+        assert c.family == "wgrad1"
+        return ops.spconv_wgrad(feats, gout, self.nbr, c.K, self.counts)
+
+
+_LAUNCHES = {}
+
+
+def launch_of(case):
+    if case.id not in _LAUNCHES:
+        rc, nbr = cb.resolve(case)
+        _LAUNCHES[case.id] = (rc, nbr, Launch(rc, nbr))
+    return _LAUNCHES[case.id]
+
+
+def padded(x, d):
+    """x as the leading rows of a larger NaN-filled allocation on the device: a read past the last row does not stay unseen."""
+    big = torch.full((x.shape[0] + 64, x.shape[1]), float("nan"), dtype=torch.float32, device=d)
+    big[:x.shape[0]] = x.to(d)
+    return big[:x.shape[0]]
+
+
+@pytest.mark.parametrize("case", cb.CASES, ids=cb.CASE_IDS)
+def test_per_element_abs_sum_bound(case):
+    case, nbr, run = launch_of(case)
+    d = dev()
+    for kind in cb.KINDS:
+        feats, w, gout = cb.operands(case, kind)
+        ref = cb.reference(case, kind)
+        label = "%s %s" % (case.id, kind)
+        fd = padded(feats, d)
+        if case.op == "wgrad":
+            gd = padded(gout, d)
+            got = run.wgrad(fd, gd)
+            assert got.shape == ref.gw.shape
+            ratio, n_bad = cb.worst_ratio(got, ref.gw, ref.b_gw, cb.WGRAD_C)
+            print("RATIO %s %s %s %.3f" % (case.family, case.id, kind, ratio))
+            if kind == "piece_aligned":
+                print("RATIO %s %s %s@2e-6 %.3f" % (case.family, case.id, kind, cb.worst_ratio(got, ref.gw, ref.b_gw, cb.PIECE_WGRAD_C)[0]))
+            cb.within(got, ref.gw, ref.b_gw, cb.WGRAD_C, label + " weight gradient")
+            if kind == "piece_aligned":
+                cb.within(got, ref.gw, ref.b_gw, cb.PIECE_WGRAD_C, label + " weight gradient at the piece bound")
+            assert torch.equal(got, run.wgrad(fd, gd)), label + ": not bitwise reproducible"
+            continue
+        wd = w.to(d)
+        part = None
+        if case.opt.get("bn"):
+            part = torch.zeros(run.tl.n_tiles, 2, case.cout, dtype=torch.float64, device=d)
+        got = run.fwd(fd, wd, bn_partial=part) if part is not None else run.fwd(fd, wd)
+        assert got.shape == ref.out.shape
+        print("RATIO %s %s %s %.3f" % (case.family, case.id, kind, cb.worst_ratio(got, ref.out, ref.b_out, cb.FWD_C)[0]))
+        cb.within(got, ref.out, ref.b_out, cb.FWD_C, label + " forward")
+        assert torch.equal(got, run.fwd(fd, wd)), label + ": not bitwise reproducible"
+        if nbr is not None and case.n_out > 3 and not case.opt.get("s2"):
+            assert float(got[2].abs().max()) == 0.0, label + ": a row without neighbours is not exactly zero"
+        if part is not None:                    # per-tile batch-norm sums against float64 column sums of the kernel's own output
+            a = got.double()
+            s1, s2 = part[:, 0].sum(0), part[:, 1].sum(0)
+            assert (s1 - a.sum(0)).abs().max().item() <= 1e-9 * a.abs().sum(0).max().item(), label + ": bn_partial sums"
+            assert (s2 - (a ** 2).sum(0)).abs().max().item() <= 1e-9 * (a ** 2).sum(0).max().item(), label + ": bn_partial squares"
+
+
+def _same_bits(a, b):
+    return torch.equal(a.contiguous().view(torch.int32), b.contiguous().view(torch.int32))
+
+
+@pytest.mark.parametrize("case", cb.CASES, ids=cb.CASE_IDS)
+def test_rows_the_table_does_not_name_stay_out(case):
+    """inf / NaN in input rows that no table entry references (and, for a weight gradient, in the gradient rows of output rows without
+    a pair) change no bit of the result; inf / NaN in ONE referenced input row reach exactly the output rows (weight gradient: the
+    offsets) that reference it, and every other element keeps its bits.  All indices stay inside their allocations."""
+    case, nbr, run = launch_of(case)
+    d = dev()
+    feats, w, gout = cb.operands(case, "row_scales")
+    table = nbr if nbr is not None else np.arange(case.n_in, dtype=np.int32)[None]
+    used = np.zeros(case.n_in, dtype=bool)
+    used[table[table >= 0]] = True
+    unref = np.nonzero(~used)[0]
+    if nbr is not None:
+        assert unref.shape[0] >= 0.05 * case.n_in, "%s: only %d of %d input rows are unreferenced" % (case.id, unref.shape[0], case.n_in)
+    no_pair = np.nonzero((table < 0).all(0))[0]
+    wd = w.to(d)
+
+    def result(f, g_):
+        fd = padded(f, d)
+        return run.wgrad(fd, padded(g_, d)) if case.op == "wgrad" else run.fwd(fd, wd)
+
+    clean = result(feats, gout)
+    assert bool(torch.isfinite(clean).all())
+    poison = torch.tensor([float("inf"), float("nan"), float("-inf")])
+    f2, g2 = feats.clone(), gout.clone()
+    if unref.shape[0]:
+        f2[torch.from_numpy(unref)] = poison[torch.arange(unref.shape[0] * case.cin) % 3].reshape(unref.shape[0], case.cin)
+    if case.op == "wgrad" and no_pair.shape[0]:
+        g2[torch.from_numpy(no_pair)] = poison[torch.arange(no_pair.shape[0] * case.cout) % 3].reshape(no_pair.shape[0], case.cout)
+    assert _same_bits(clean, result(f2, g2)), "%s: a row that no table entry names reached the result" % case.id
+
+    r = int(np.nonzero(used)[0][len(np.nonzero(used)[0]) // 2])            # one referenced row
+    f3 = feats.clone()
+    f3[r] = float("inf")
+    got = result(f3, gout).cpu()
+    if case.op == "wgrad":
+        hit = torch.from_numpy((table == r).any(1))                       # offsets under which row r appears
+        assert hit.shape[0] == got.shape[0]
+    else:
+        hit = torch.from_numpy((table == r).any(0))                       # output rows that reference row r
+    flat = got.reshape(got.shape[0], -1)
+    assert bool(hit.any())
+    assert torch.equal(~torch.isfinite(flat).all(1), hit), "%s: the non-finite %s are not those that reference the poisoned row" % (
+        case.id, "offsets" if case.op == "wgrad" else "rows")
+    assert not bool(torch.isfinite(flat[hit]).any()), "%s: finite elements where the poisoned row contributes" % case.id
+    assert _same_bits(flat[~hit], clean.cpu().reshape(got.shape[0], -1)[~hit]), "%s: elements away from the poisoned row changed" % case.id

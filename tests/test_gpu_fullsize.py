@@ -21,6 +21,8 @@ from oracle import query as oq
 from oracle import sparse_ops as so
 from openscene_amd import synthetic as syn
 
+from conv_bounds import FWD_C, WGRAD_C, abs_sum_bounds, adversarial as _adversarial, within      # the contract: tests/conv_bounds.py
+
 pytestmark = pytest.mark.gpu
 
 
@@ -262,19 +264,6 @@ def test_query_at_benchmark_sizes(n_pts, d, c):
 
 
 # ------------------------------------------------------------ adversarial operands for the split-bf16 conv
-def _adversarial(kind, n, cin, g):
-    x = torch.randn(n, cin, generator=g)
-    if kind == "row_scales":           # per-row magnitudes 1e-6 .. 1e6: a tile mixes huge and tiny rows
-        x = x * (10.0 ** (torch.rand(n, 1, generator=g) * 12 - 6))
-    elif kind == "cancellation":       # channel pairs (a, -a(1 + 2^-12)): products cancel to ~2^-12 of their size
-        x[:, 1::2] = -x[:, 0::2] * (1 + 2.0 ** -12)
-    elif kind == "gradient_sized":     # operands of the size of late-training gradients
-        x = x * 1e-8
-    elif kind == "wide_elements":      # element-wise magnitudes over 12 decades inside every row
-        x = x * (10.0 ** (torch.rand(n, cin, generator=g) * 12 - 6))
-    return x
-
-
 class _KindRecorder:
     """ops profiler hook that only notes which C-ABI convolution entry points ran."""
 
@@ -321,19 +310,7 @@ def test_conv_adversarial_operands(kind, mode, monkeypatch):
         w[:, 1::2, :] = w[:, 0::2, :]                                 # equal weights on the cancelling channel pairs
     gout = _adversarial(kind if kind != "cancellation" else "row_scales", n, cout, g)
 
-    f64 = feats.double().requires_grad_(True)
-    w64 = w.double().requires_grad_(True)
-    ref = so.sparse_conv(f64, w64, nbr_np)
-    ref.backward(gout.double())
-    with torch.no_grad():                                             # the abs-sum bounds, same operator on |.|
-        b_out = so.sparse_conv(feats.double().abs(), w.double().abs(), nbr_np)
-        nbr_t = oc.transpose_table(nbr_np, n)
-        b_gin = so.sparse_conv(gout.double().abs(), w.double().abs().transpose(1, 2).contiguous(), nbr_t)
-        fa, ga = feats.double().abs(), gout.double().abs()
-        b_gw = torch.zeros(27, cin, cout, dtype=torch.float64)
-        for k in range(27):
-            o = np.nonzero(nbr_np[k] >= 0)[0]
-            b_gw[k] = fa[nbr_np[k, o]].t() @ ga[o]
+    ref, ref_gin, ref_gw, b_out, b_gin, b_gw = abs_sum_bounds(nbr_np, feats, w, gout)     # float64 values, the same operator on |.|
 
     d = dev()
     nbr = torch.from_numpy(nbr_np).to(d)
@@ -355,19 +332,12 @@ def test_conv_adversarial_operands(kind, mode, monkeypatch):
         out = F_.sparse_conv(fg, wg, (nbr, nbr, True), n)
         out.backward(gout.to(d))
 
-    def within(got, want, bound, what, c):
-        err = (got.detach().double().cpu() - want.detach()).abs()
-        # + the fp32 representation of the result itself (half an ulp) and an absolute floor at the denormal edge
-        lim = c * bound + 6e-8 * want.detach().abs() + 1e-37
-        bad = err > lim
-        assert not bool(bad.any()), "%s/%s %s: %d elements beyond the bound, worst ratio %.2f" % (
-            kind, mode, what, int(bad.sum()), float((err / lim).max()))
-
-    within(out, ref, b_out, "forward", 2e-6)
-    within(fg.grad, f64.grad, b_gin, "input gradient", 2e-6)
+    label = "%s/%s " % (kind, mode)
+    within(out, ref, b_out, FWD_C, label + "forward")
+    within(fg.grad, ref_gin, b_gin, FWD_C, label + "input gradient")
     # the weight gradient contracts over up to ~1e5 pairs in several partial sums: fp32 accumulation error grows
     # with the number of terms (sqrt-like for random signs); 2e-5 of the abs-sum covers the 100 k-term reductions
-    within(wg.grad, w64.grad, b_gw, "weight gradient", 2e-5)
+    within(wg.grad, ref_gw, b_gw, WGRAD_C, label + "weight gradient")
 
 
 @pytest.mark.parametrize("cin,cout", [(96, 768), (768, 96), (128, 96)])
@@ -402,11 +372,5 @@ def test_dense_1x1_adversarial_operands(kind, cin, cout):
         ops.set_profiler(None)
     assert rec.kinds.count("dense_fwd") == 2, rec.kinds          # forward and input gradient
 
-    def within(got, want, bound, what):
-        err = (got.detach().double().cpu() - want.detach()).abs()
-        lim = 2e-6 * bound + 6e-8 * want.detach().abs() + 1e-37
-        bad = err > lim
-        assert not bool(bad.any()), "%s %s: %d elements beyond the bound, worst ratio %.2f" % (
-            kind, what, int(bad.sum()), float((err / lim).max()))
-    within(out, ref, b_out, "forward")
-    within(fg.grad, f64.grad, b_gin, "input gradient")
+    within(out, ref, b_out, FWD_C, kind + " forward")
+    within(fg.grad, f64.grad, b_gin, FWD_C, kind + " input gradient")
