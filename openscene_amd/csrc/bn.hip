@@ -208,7 +208,7 @@ __global__ __launch_bounds__(FIN_COLS * FIN_PARTS) void bn_bwd_finalize_kernel(c
 
 __device__ inline float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
 
-// (bn_val / bn_is: epilogue.h -- one definition shared with the convolution kernels' evaluation-mode epilogues)
+// (bn_val / bn_is / bn_relu: epilogue.h -- one definition shared with the convolution kernels' evaluation-mode epilogues)
 
 __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                        const float* __restrict__ var, const float* __restrict__ gamma,
@@ -230,7 +230,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
             o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
         }
         if (relu) {
-            o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
+            o.x = bn_relu(o.x); o.y = bn_relu(o.y); o.z = bn_relu(o.z); o.w = bn_relu(o.w);
         }
         *reinterpret_cast<float4*>(y + e * 4) = o;
         // second store: the same rows as a column window of a wider matrix (ME.cat written in place by its producers)
@@ -383,7 +383,7 @@ __global__ __launch_bounds__(SB_THREADS) void bn_small_fwd_kernel(const float* _
             o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
         }
         if (relu) {
-            o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
+            o.x = bn_relu(o.x); o.y = bn_relu(o.y); o.z = bn_relu(o.z); o.w = bn_relu(o.w);
         }
         *reinterpret_cast<float4*>(y + int64_t(r) * c + col) = o;
         if (y2) *reinterpret_cast<float4*>(y2 + int64_t(r) * ld2 + col) = o;

@@ -17,6 +17,9 @@ namespace osn {
 // from x instead of reading y (round 4): explicit fma so that every side rounds identically whatever the surrounding code.
 __device__ inline float bn_val(float x, float mu, float is, float ga, float be) { return __fmaf_rn((x - mu) * is, ga, be); }
 __device__ inline float bn_is(float var, float eps) { return 1.f / sqrtf(var + eps); }
+// The ReLU behind a batch norm, ONE definition like bn_val: a NaN propagates as torch.relu does (fmaxf(x, 0.f) returns 0 for a NaN,
+// and a diverged run would go on training on zeros); every finite or infinite x gives the bits fmaxf gave.
+__device__ inline float bn_relu(float x) { return x > 0.f ? x : (x != x ? x : 0.f); }
 
 struct Epi {
     const float* mean;      // nullptr: no epilogue, the plain convolution result is stored
@@ -59,7 +62,7 @@ __device__ inline float4 epi_apply(const Epi& e, const EpiCols& c, float4 x, int
         o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
     }
     if (e.relu) {
-        o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
+        o.x = bn_relu(o.x); o.y = bn_relu(o.y); o.z = bn_relu(o.z); o.w = bn_relu(o.w);
     }
     if (e.y2) *reinterpret_cast<float4*>(e.y2 + row * e.ld2 + col) = o;
     return o;

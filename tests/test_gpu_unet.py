@@ -417,6 +417,33 @@ def test_inference_bn_epilogue_is_bitwise_the_separate_launches(arch, n_pts, vox
     assert got[True][0].abs().max().item() > 0 and torch.isfinite(got[True][0]).all()
 
 
+def test_inference_bn_epilogue_propagates_nan_like_the_separate_launches(monkeypatch):
+    """A NaN in one input row reaches the output as NaN through the epilogues' ReLU exactly as through the separate bn_apply launches
+    (bn_relu, csrc/epilogue.h: torch.relu propagates NaN; a clamp that turned it into 0 would hide a diverged run)."""
+    from openscene_amd import executor
+    from openscene_amd.mink_unet import mink_unet
+    from openscene_amd.sparse import SparseTensor
+    d = dev()
+    coords = torch.from_numpy(scene_coords(61, 3000, 0.05, batch=2)).to(d)
+    feats = torch.rand(coords.shape[0], 3, device=d)
+    torch.manual_seed(11)
+    model = mink_unet(3, 48, 3, "MinkUNet14A").to(d).train()
+    with torch.no_grad():
+        for _ in range(2):
+            model(SparseTensor(feats, coords))              # running statistics away from (0, 1)
+    model.eval()
+    feats[coords.shape[0] // 2] = float("nan")
+    got = {}
+    for on in (False, True):
+        monkeypatch.setattr(executor, "BN_EPILOGUE", on)
+        with torch.no_grad():
+            got[on] = model(SparseTensor(feats, coords)).clone()
+    nan = torch.isnan(got[True])
+    assert bool(nan.any()), "the NaN input row did not reach the output"
+    assert torch.equal(nan, torch.isnan(got[False]))
+    assert torch.equal(torch.nan_to_num(got[True]), torch.nan_to_num(got[False]))
+
+
 def test_executor_with_frozen_and_eval_mode_gradients():
     """A frozen parameter gets no gradient; evaluation-mode BN (running statistics) inside a graph that needs gradients
     back-propagates through the executor like the module path does."""
