@@ -552,7 +552,8 @@ int osn_eval_check(const int32_t* err, osn_stream_t stream);
  * d % 8 == 0.  A gather entry outside [0, n_rows) reads and writes nothing for that row and ORs bit 1 into the device
  * word err (int32 [1]).
  * The check synchronises and turns the bits of err into OSN_E_ARG: 1 a bad gather index, 2 scene offsets that do
- * not start at 0, ascend and end within the bank, 4 a scene longer than max_scene_rows.
+ * not start at 0, ascend and end within the bank, 4 a scene longer than max_scene_rows (8, 16, 32: the
+ * pool's, below.)
  *
  * The search: bank fp16 [n, d]; scene_offsets int64 [n_scenes + 1] (device), ascending from 0, empty scenes allowed;
  *   max_scene_rows >= the longest scene (sizes the grid); queries fp16 [q, d], L2-normalised by the caller
@@ -598,6 +599,38 @@ int osn_bank_search_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int
                         int n_scenes, int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
                         const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
                         int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
+
+/* ---- descriptors of point sets over the bank (csrc/pool.hip) ----------------------------------------------------- *
+ * The way back from points to a feature vector (README "Applications": "retrieve examples based on similarities", room
+ * type, labelling a found object): the sum of the normalised stored rows of every group of a list of bank rows; the mean
+ * of a group is its descriptor.  bank / (codes, exps), n, d: the bank of osn_bank_search / osn_bank_search_fp8,
+ * d <= OSN_BANK_POOL_MAX_DIM.  Groups in CSR form: starts int64 [n_groups + 1] (device), ascending, starts[0] = 0,
+ * starts[n_groups] = n_entries; rows (nullable) int64 [n_entries] = bank rows, null: entry i is bank row i (whole scenes:
+ * starts = the bank's scene offsets); weights (nullable) float32 [n_entries], null: 1.  With v the stored row of an entry
+ * (the fp16 values, or float(code) * 2^e, decoded exactly) and w its weight, the entry's term is
+ *     normalize = 1   run/evaluate.py:305   w * v / (v.norm() + 1e-5)     the norm in fp32 over the stored values
+ *     normalize = 0                         w * v
+ * sum float32 [n_groups, d] = the terms of a group added in fp32; wsum float32 [n_groups] = its weights; count int64
+ * [n_groups] = its entries.  Entry order is accumulation order, duplicate rows are allowed, an empty group gives zeros, a
+ * NaN row makes its own group NaN and no other.
+ * Determinism: no floating-point atomics.  A group is cut into chunks of OSN_BANK_POOL_CHUNK consecutive entries; a
+ * chunk is reduced in a fixed order (wave w of four takes entries w, w + 4, ..., the waves are added in wave order) into an
+ * fp32 partial in ws, a second launch adds a group's partials in ascending chunk order.  The result is a function of
+ * the input arrays alone -- bitwise repeatable -- and a group's bits do not depend on its place in the list.
+ * An entry whose row is outside [0, n) or whose weight is negative or not finite is skipped (its row loads are made from
+ * a clamped address inside the bank and not used; it enters neither sum, wsum nor count) and ORs 8 (row) or 16 (weight)
+ * into the bank's err word; starts that do not ascend from 0 to n_entries are clamped before use and OR 32;
+ * osn_bank_check turns the bits into OSN_E_ARG.
+ * ws: osn_bank_pool_ws_bytes(n_groups, n_entries, d) bytes.  Asynchronous.                                           */
+#define OSN_BANK_POOL_CHUNK 512
+#define OSN_BANK_POOL_MAX_DIM 1024
+size_t osn_bank_pool_ws_bytes(int64_t n_groups, int64_t n_entries, int d);
+int osn_bank_pool(const void* bank_f16, int64_t n, int d, const int64_t* starts, int64_t n_groups, const int64_t* rows,
+                  int64_t n_entries, const float* weights, int normalize, float* sum, float* wsum, int64_t* count,
+                  int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
+int osn_bank_pool_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int d, const int64_t* starts, int64_t n_groups,
+                      const int64_t* rows, int64_t n_entries, const float* weights, int normalize, float* sum, float* wsum,
+                      int64_t* count, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
 
 /* ---- objects in heat-maps (csrc/objects.hip) -------------------------------------------------------------------- *
  * What the README "Applications" do with a heat-map -- rare object search in a 3D scene database, image-based 3-D object

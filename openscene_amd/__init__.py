@@ -11,6 +11,7 @@ Python surface (mirrors the reference's own, file:line in each module):
     openscene_amd.query            run/evaluate.py:283-324 (distill / fusion / ensemble query)
     openscene_amd.search           README "Applications": a bank of scenes searched by text or image embedding
     openscene_amd.objects          the same, as objects: connected components of a heat-map, ranked per scene
+    openscene_amd.descriptors      and back: scenes, objects and regions of the bank as descriptors (the next query)
     install_minkowski_alias()      make `import MinkowskiEngine` resolve to openscene_amd.minkowski
 
 There is no CPU fallback: every op raises if libopenscene_amd.so is missing or
@@ -55,6 +56,18 @@ def accelerate(target):
     reference's own models/mink_unet.py:28 class built on the alias -- or a module containing one (DisNet).  See drop_in.py."""
     from .drop_in import accelerate as f
     return f(target)
+
+
+def pool(bank, groups, weights=None, normalize=True):
+    """Descriptors of point sets over a FeatureBank (openscene_amd.descriptors.pool)."""
+    from .descriptors import pool as f
+    return f(bank, groups, weights=weights, normalize=normalize)
+
+
+def describe_scenes(bank, normalize=True):
+    """One descriptor per scene of a FeatureBank (openscene_amd.descriptors.describe_scenes)."""
+    from .descriptors import describe_scenes as f
+    return f(bank, normalize=normalize)
 
 
 def install_minkowski_alias(force=False, accelerate=True):

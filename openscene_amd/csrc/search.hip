@@ -24,14 +24,12 @@
 // them to fp16 (exact) on the way into LDS (heat_fp8_kernel); 2^e enters where the scores leave.  The two heat kernels call
 // one set of __device__ templates for the query staging, the MFMA loop, the row norms and the score output; each has its own
 // row fetch, stash and stage loop.  Pass 2 and the entries' argument checks are shared too.
-#include "common.h"
+#include "bank.h"
 
 namespace osn {
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2 __attribute__((ext_vector_type(2)));
 
 constexpr int S_BM = 128;          // bank rows per workgroup (4 waves x 32)
 constexpr int S_DK = 128;          // feature chunk (halfs): 256 bytes of a row, 32 KB per workgroup in flight
@@ -44,8 +42,6 @@ constexpr int SEL_R = SEL_T * 8 * SEL_IT;   // rows of a chunk (4096)
 constexpr int SEL_ST = 16;         // uint32 words of per-(scene, query) select state
 constexpr uint32_t SEL_NONE = 0x10000u;     // K of an empty selection (above every key)
 enum { ST_KK = 0, ST_B1, ST_ABOVE, ST_K, ST_GT, ST_NEED_EQ, ST_EQ_TOTAL, ST_SLOT_GT, ST_SLOT_EQ };
-
-constexpr int BANK_E_GATHER = 1, BANK_E_OFFSETS = 2, BANK_E_LONG = 4;
 
 // ------------------------------------------------------------------------------------------------------ append
 __global__ __launch_bounds__(256) void bank_append_kernel(const float* __restrict__ X, int64_t n_rows, const int64_t* __restrict__ g,
@@ -406,13 +402,8 @@ __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __res
                 const bool ok = row0 + row < n && d0 + xq * 16 < d;
                 uint4 v = px[ps];
                 if (!ok) v = make_uint4(0, 0, 0, 0);
-                const uint32_t w[4] = {v.x, v.y, v.z, v.w};
                 half2 h[8];
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {               // e4m3 -> fp16 is exact (v_cvt_scalef32_pk_f16_fp8, scale 1)
-                    h[2 * j] = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[j], 1.0f, false);
-                    h[2 * j + 1] = __builtin_amdgcn_cvt_scalef32_pk_f16_fp8(w[j], 1.0f, true);
-                }
+                q8_widen(v, h);                             // e4m3 -> fp16, exact (bank.h)
                 if (sumsq) {
                     float s = 0.f;
 #pragma unroll
@@ -826,6 +817,9 @@ extern "C" int osn_bank_check(const int32_t* err, osn_stream_t stream) {
     OSN_REQUIRE(!(h & BANK_E_GATHER), OSN_E_ARG, "osn_bank_append: a gather index outside [0, n_rows) (X[gather] raises in the reference)");
     OSN_REQUIRE(!(h & BANK_E_OFFSETS), OSN_E_ARG, "osn_bank_search: scene_offsets must start at 0, ascend and end within the bank");
     OSN_REQUIRE(!(h & BANK_E_LONG), OSN_E_ARG, "osn_bank_search: a scene is longer than max_scene_rows");
+    OSN_REQUIRE(!(h & BANK_E_POOL_ROW), OSN_E_ARG, "osn_bank_pool: a row index outside [0, n) (the entry was skipped)");
+    OSN_REQUIRE(!(h & BANK_E_POOL_WEIGHT), OSN_E_ARG, "osn_bank_pool: a negative or non-finite weight (the entry was skipped)");
+    OSN_REQUIRE(!(h & BANK_E_POOL_STARTS), OSN_E_ARG, "osn_bank_pool: starts must ascend from 0 to the number of entries");
     return OSN_OK;
 }
 

@@ -4,7 +4,7 @@ there are, how large each one is and how confident the match is.  `openscene_amd
 
     VoxelGrid        built once for a set of scenes: voxel rows, point -> voxel map, 3^3 neighbour table
     find_objects     heat-map [N, Q] + thresholds -> per (scene, query) the best M objects, ranked
-    ObjectResult     .objects(scene, q) as plain dicts, .rank_scenes(q, by=...)
+    ObjectResult     .objects(scene, q) as plain dicts, .rank_scenes(q, by=...), .descriptors(bank) (an object as the next query)
 
 An object is a connected component (26- or 6-neighbourhood) of the voxels that hold at least one hit -- a point whose score
 is finite and >= the query's threshold.  Every field is an integer, a selected input value, or derived on the host from
@@ -160,6 +160,13 @@ class ObjectResult:
         order = torch.sort(score, descending=True, stable=True)[1].tolist()
         vals = score.tolist()
         return [(self.names[i], vals[i] if by == "peak" else int(vals[i])) for i in order]
+
+    def descriptors(self, bank, heat=None):
+        """Descriptors [S, Q, M] of the kept objects over `bank`, the bank whose heat-map was searched
+        (openscene_amd.descriptors.describe_objects): the mean normalised feature row of every object's hits, with `heat`
+        weighted by max(score, 0).  Needs find_objects(..., return_point_ids=True)."""
+        from .descriptors import describe_objects
+        return describe_objects(self, bank, heat)
 
 
 def find_objects(grid, heat, thresholds, min_points=1, max_objects=16, return_point_ids=False, names=None):

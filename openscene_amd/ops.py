@@ -1484,6 +1484,97 @@ def bank_search_fp8(codes, exps, scene_offsets, queries, k=16, thresholds=None, 
                         normalize, want_heat, max_scene_rows, err)
 
 
+# ------------------------------------------------------------------------ pool
+BANK_POOL_CHUNK = 512            # OSN_BANK_POOL_CHUNK: the entries of a group that are reduced into one fp32 partial
+BANK_POOL_MAX_DIM = 1024         # OSN_BANK_POOL_MAX_DIM: the widest row a wave keeps in registers
+
+
+def _bank_pool(entry, bank_ptrs, n, d, d_multiple, dev, starts, rows, weights, normalize, n_entries, err):
+    """bank_pool and bank_pool_fp8 behind their own checks of the bank: `entry` is the C entry that takes `bank_ptrs`
+    (the fp16 rows, or the codes and the exponents) ahead of the arguments the two share."""
+    if d < d_multiple or d % d_multiple:
+        raise ValueError("the feature dim must be a multiple of %d (got %d)" % (d_multiple, d))
+    if d > BANK_POOL_MAX_DIM:
+        raise ValueError("the feature dim must be at most %d (got %d)" % (BANK_POOL_MAX_DIM, d))
+    if not isinstance(starts, torch.Tensor) or starts.dtype != torch.int64:
+        raise TypeError("starts must be an int64 tensor")
+    if starts.dim() != 1 or starts.shape[0] < 1 or starts.device != dev:
+        raise ValueError("starts must be an int64 [G + 1] vector on the bank's device")
+    starts = starts.contiguous()
+    g = starts.shape[0] - 1
+    if rows is not None:
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64:
+            raise TypeError("rows must be an int64 tensor (or None: entry i is bank row i)")
+        if rows.dim() != 1 or rows.device != dev:
+            raise ValueError("rows must be an int64 [L] vector on the bank's device")
+        rows = rows.contiguous()
+        if n_entries is not None and int(n_entries) != rows.shape[0]:
+            raise ValueError("n_entries=%d for %d rows" % (int(n_entries), rows.shape[0]))
+        n_entries = rows.shape[0]
+    elif n_entries is None:
+        raise ValueError("without rows, n_entries (= starts[-1]) must be given")
+    n_entries = int(n_entries)
+    if n_entries < 0:
+        raise ValueError("n_entries must not be negative (got %d)" % n_entries)
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32:
+            raise TypeError("weights must be a float32 tensor")
+        if tuple(weights.shape) != (n_entries,) or weights.device != dev:
+            raise ValueError("weights must be a float32 [%d] vector on the bank's device (got %s)" % (n_entries, tuple(weights.shape)))
+        weights = weights.contiguous()
+    own_err = err is None
+    if own_err:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif err.dtype != torch.int32 or err.numel() != 1 or err.device != dev:
+        raise ValueError("err must be an int32 [1] tensor on the bank's device")
+    out = torch.empty((g, d), dtype=torch.float32, device=dev)
+    wsum = torch.empty((g,), dtype=torch.float32, device=dev)
+    count = torch.empty((g,), dtype=torch.int64, device=dev)
+    wsb = _cached("osn_bank_pool_ws_bytes", g, n_entries, d)
+    ws = _ws(wsb, dev)
+    with _Dev(dev):
+        check(entry(*bank_ptrs, n, d, _p(starts), g, _p(rows), n_entries, _p(weights), int(bool(normalize)), _p(out), _p(wsum),
+                    _p(count), _p(err), _p(ws), ws.numel(), _stream(dev)), entry.__name__)
+    if own_err and g > 0:
+        bank_check(err)
+    return out, wsum, count
+
+
+def bank_pool(bank, starts, rows=None, weights=None, normalize=True, n_entries=None, err=None):
+    """Sums of the (normalised, weighted) rows of every group of a CSR list of bank rows: an entry adds
+    ``w * hf / (hf.norm() + 1e-5)`` (`run/evaluate.py:305`; normalize) or ``w * hf`` of its stored fp16 row, in fp32.
+    bank fp16 [N, d], d <= BANK_POOL_MAX_DIM; starts int64 [G + 1] on the device, ascending from 0 to L; rows int64 [L] or
+    None (entry i is bank row i; L = n_entries); weights float32 [L] or None (1).
+    -> (sum float32 [G, d], wsum float32 [G], count int64 [G]).
+    A group is reduced in chunks of BANK_POOL_CHUNK entries in a fixed order: bitwise repeatable.  A row outside the bank
+    and a negative or non-finite weight skip their entry and are recorded in `err` when one is given (bank_check raises),
+    and checked here otherwise."""
+    lib = _prep(bank.device)
+    if bank.dtype != torch.float16:
+        raise TypeError("the bank must be float16 (got %s)" % bank.dtype)
+    if bank.dim() != 2 or not bank.is_contiguous():
+        raise ValueError("the bank must be a contiguous [rows, dim] matrix")
+    n, d = bank.shape
+    return _bank_pool(lib.osn_bank_pool, (_p(bank),), n, d, 8, bank.device, starts, rows, weights, normalize, n_entries, err)
+
+
+def bank_pool_fp8(codes, exps, starts, rows=None, weights=None, normalize=True, n_entries=None, err=None):
+    """bank_pool over an fp8 bank: codes uint8 [N, d] (e4m3fn), exps int8 [N], d % 16 == 0; a row's value is
+    code * 2^e, decoded exactly.  Everything else is bank_pool's."""
+    dev = codes.device
+    lib = _prep(dev)
+    if codes.dtype != torch.uint8:
+        raise TypeError("codes must be uint8 (got %s)" % codes.dtype)
+    if exps.dtype != torch.int8:
+        raise TypeError("exponents must be int8 (got %s)" % exps.dtype)
+    if codes.dim() != 2 or not codes.is_contiguous():
+        raise ValueError("codes must be a contiguous [rows, dim] matrix")
+    if exps.dim() != 1 or exps.shape[0] != codes.shape[0] or exps.device != dev or not exps.is_contiguous():
+        raise ValueError("exponents must be a contiguous [%d] vector on the codes' device" % codes.shape[0])
+    n, d = codes.shape
+    return _bank_pool(lib.osn_bank_pool_fp8, (_p(codes), _p(exps)), n, d, 16, dev, starts, rows, weights, normalize, n_entries, err)
+
+
 # --------------------------------------------------------------------- objects
 OBJECTS_MAX_M = 64
 OBJECTS_MAX_POINTS = 1 << 22          # keeps score_sum inside int64 for raw scores at the fp16 maximum
