@@ -223,6 +223,19 @@ int osn_weight_prep_batch(const osn_prep_job* jobs_dev, int n_jobs, int64_t tota
  * the kernel symbol is spconv_fwd_kernel<WM, WN, TN, BK>.                          */
 int osn_spconv_fwd_plan(int64_t n_out, int K, int cin, int cout, int32_t* plan6);
 
+/* The shapes each convolution kernel family is ROUTED to: 1 or 0, pure host arithmetic (no device, no launch, no error string;
+ * 0 for non-positive sizes).  Each is defined beside its kernel and is the one statement of that kernel's limits: the executor
+ * (csrc/net.hip) and openscene_amd.ops ask these.  An entry point may accept more than its predicate (4 input channels,
+ * K == 1); osn_spconv_fwd_rg_ok, further down, is the fifth.                                                              */
+/* stem.hip: cin <= 4, cout == 32, 1 < K <= 125 */
+int osn_stem_conv_ok(int K, int cin, int cout);
+/* spconv_tl.hip: cin % 4 == 0 in [8, 512] (the step table's four 128-channel chunks), cout % 4 == 0, K <= 128, n_in <= 2^24 (0 allowed) */
+int osn_spconv_fwd_tl_ok(int64_t n_in, int K, int cin, int cout);
+/* dense.hip: cin % 4 == 0, cin >= 8, cout % 4 == 0 */
+int osn_dense_fwd_ok(int cin, int cout);
+/* spconv.hip (split-bf16): cin % 4 == 0, cin >= 8, a weight image within 32-bit offsets, at most 32 offsets per block of the launch plan for n_out rows (<= 0: 1) */
+int osn_spconv_fwd_x6_ok(int64_t n_out, int K, int cin, int cout);
+
 /* Wt[k] = W[flip ? K-1-k : k]^T   ([K, cout, cin]).  The input gradient is
  * osn_spconv_fwd(gout, Wt, table, ...) with table = nbr and flip = 1 for a
  * stride-1 odd kernel (the map is its own mirror), or the transposed table and

@@ -36,6 +36,10 @@ PROTOTYPES = {
     "osn_weight_prep_x6_pair": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp]),
     "osn_spconv_fwd_x6": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _sz, _vp]),
     "osn_spconv_fwd_plan": (_i32, [_i64, _i32, _i32, _i32, _c.POINTER(_i32)]),
+    "osn_stem_conv_ok": (_i32, [_i32, _i32, _i32]),
+    "osn_spconv_fwd_tl_ok": (_i32, [_i64, _i32, _i32, _i32]),
+    "osn_dense_fwd_ok": (_i32, [_i32, _i32]),
+    "osn_spconv_fwd_x6_ok": (_i32, [_i64, _i32, _i32, _i32]),
     "osn_tile_rows": (_i32, [_i64]),
     "osn_tile_lists_bytes": (_sz, [_i64, _i32, _i32]),
     "osn_tile_lists_build": (_i32, [_vp, _i64, _i32, _i32, _vp, _vp]),

@@ -158,6 +158,9 @@ __global__ __launch_bounds__(256, 2) void dense_kernel(const float* __restrict__
 
 using namespace osn;
 
+// routing limit of the 1x1 kernel; narrower than what osn_dense_fwd accepts (cin >= 4)
+extern "C" int osn_dense_fwd_ok(int cin, int cout) { return cin >= 8 && (cin & 3) == 0 && cout >= 4 && (cout & 3) == 0; }
+
 int osn::dense_fwd_epi(const float* in, const void* Wp, float* out, int64_t n, int cin, int cout, const Epi& epi, osn_stream_t stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     OSN_REQUIRE(n >= 0 && n < (int64_t(1) << 31) && cin >= 4 && (cin & 3) == 0 && cout >= 4 && (cout & 3) == 0, OSN_E_ARG,

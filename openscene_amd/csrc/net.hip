@@ -34,10 +34,9 @@ struct Prof {
 
 static inline uint64_t up256(uint64_t x) { return (x + 255) & ~uint64_t(255); }
 
-static bool stem_eligible(int K, int cin, int cout) { return cin <= 4 && cout == 32 && K > 1 && K <= 125; }
-static bool tl_eligible(int K, int cin, int cout, int64_t n_in) {
-    return (cin & 3) == 0 && cin >= 8 && cin <= 512 && (cout & 3) == 0 && K <= 128 && n_in <= (int64_t(1) << 24);
-}
+// The shapes a kernel family takes are stated once, by an export beside the kernel (ops.*_eligible ask the same functions): one line each
+static bool stem_eligible(int K, int cin, int cout) { return osn_stem_conv_ok(K, cin, cout) != 0; }
+static bool tl_eligible(int K, int cin, int cout, int64_t n_in) { return osn_spconv_fwd_tl_ok(n_in, K, cin, cout) != 0; }
 // functional.tl_rows_ok: a table big enough for the tile-list kernel (always from tl_min_rows rows on; from tl_mid_rows on
 // when both channel counts are at least 96)
 static bool tl_rows_ok(const osn_net_desc* net, int64_t rows, int ca, int cb) {
@@ -52,25 +51,19 @@ static int ws_kernel(const osn_net_desc* net, const osn_net_op& o, int ca, int c
     if (net->ws_max_rows > 0 && n_dst <= net->ws_max_rows) return OSN_NET_K_WS;
     return 0;
 }
-static bool dense_eligible(int cin, int cout) { return (cin & 3) == 0 && cin >= 8 && (cout & 3) == 0; }
+static bool dense_eligible(int cin, int cout) { return osn_dense_fwd_ok(cin, cout) != 0; }
 // ops.rg_eligible: the register-gather kernel for the narrow layers (32 / 64 channels on both sides) that neither the tile-list
 // kernel nor a direct weight-stationary launch takes -- before the partial-row weight-stationary kernel and the first-generation one
 static bool rg_eligible(int K, int ca, int cb, int64_t n_src) { return osn_spconv_fwd_rg_ok(n_src > 0 ? n_src : 1, K, ca, cb) != 0; }
-static bool x6_eligible(int K, int cin, int cout, int64_t n_out) {
-    if ((cin & 3) || cin < 8) return false;
-    if (int64_t(3) * K * cout * ((cin + 31) / 32 * 32) >= (int64_t(1) << 30)) return false;
-    int32_t plan[6];
-    if (osn_spconv_fwd_plan(n_out, K, cin, cout, plan) != OSN_OK) return false;
-    const int S = plan[4] > 0 ? plan[4] : 1;
-    return (K + S - 1) / S <= 32;
-}
+static bool x6_eligible(int K, int cin, int cout, int64_t n_out) { return osn_spconv_fwd_x6_ok(n_out, K, cin, cout) != 0; }
 
 // functional.conv_kernels' helper, THE rule of this path: the kernel of a launch of stage `o` (n_in input rows) that gathers n_src rows
 // of ca channels and writes n_dst rows of cb channels -- the forward launch, or the input gradient with the roles swapped; 0 = none
 // of the executor's kernels.  In order: 1x1; direct weight-stationary; tile-list, unless one side has 32 channels and the
 // register-gather kernel takes the shape (measured at 101 k rows, tools/micro_rg.py: 32 -> 32 38.8 us against 49.3, 32 -> 64 49.6 / 53.7;
 // 64 -> 64 stays with the tile-list kernel there: 72 against 112); register-gather; weight-stationary with partial rows; split-bf16.
-// tests/test_executor.py::test_both_paths_plan_the_same_kernels holds it to the Python twin.
+// tests/test_executor.py::test_both_paths_plan_the_same_kernels holds it to the Python twin.  (Only the ORDER has a twin: the shape
+// predicates it asks are the library's own exports on both paths.)
 static int pick_kernel(const osn_net_desc* net, const osn_net_op& o, int64_t n_in, int ca, int cb, int64_t n_src, int64_t n_dst, bool dst_fine) {
     if (o.K == 1 && dense_eligible(o.cin, o.cout) && dense_eligible(ca, cb)) return OSN_NET_K_DENSE;
     const bool lists = o.K > 1 && tl_eligible(o.K, o.cin, o.cout, n_in) && tl_eligible(o.K, ca, cb, n_src);

@@ -1083,6 +1083,19 @@ extern "C" size_t osn_spconv_fwd_ws_bytes(int64_t n_out, int K, int cin, int cou
     return uniform > units ? uniform : units;
 }
 
+// the split-bf16 kernel indexes the prepared weight (3 planes of [K][cout][cin padded to 32] bf16) with 32 bits
+static bool x6_weight_fits(int K, int cin, int cout) {
+    constexpr int64_t lim = int64_t(1) << 30;
+    return K < lim && cin < lim && cout < lim && int64_t(3) * K * cout < lim && int64_t(3) * K * cout * ((cin + 31) / 32 * 32) < lim;
+}
+
+// routing limit of the split-bf16 kernel for a launch that writes n_out rows (<= 0: planned as 1 row).  Narrower than what
+// osn_spconv_fwd_x6 accepts: cin >= 8 where the entry takes 4
+extern "C" int osn_spconv_fwd_x6_ok(int64_t n_out, int K, int cin, int cout) {
+    if (K < 1 || cin < 8 || (cin & 3) || cout < 1 || n_out >= (int64_t(1) << 31) || !x6_weight_fits(K, cin, cout)) return 0;
+    return plan_fwd(n_out > 0 ? n_out : 1, K, cin, cout).kps <= PIPE_KC;
+}
+
 extern "C" int osn_spconv_fwd_plan(int64_t n_out, int K, int cin, int cout, int32_t* plan6) {
     OSN_REQUIRE(plan6 && n_out >= 0 && K >= 1 && cin >= 1 && cout >= 1, OSN_E_ARG, "osn_spconv_fwd_plan: bad arguments");
     FwdPlan p = plan_fwd(n_out > 0 ? n_out : 1, K, cin, cout);
@@ -1241,14 +1254,14 @@ extern "C" int osn_spconv_fwd_x6(const float* in, const void* Wp, const int32_t*
     OSN_REQUIRE(n_out >= 0 && n_out < (int64_t(1) << 31), OSN_E_ARG, "osn_spconv_fwd_x6: n_out out of range");
     OSN_REQUIRE(K >= 1 && cin >= 4 && (cin & 3) == 0 && cout >= 1, OSN_E_ARG,
                 "osn_spconv_fwd_x6: needs cin %% 4 == 0 (K=%d cin=%d cout=%d)", K, cin, cout);
-    OSN_REQUIRE(int64_t(3) * K * cout * ((cin + 31) / 32 * 32) < (int64_t(1) << 30), OSN_E_ARG,
+    OSN_REQUIRE(x6_weight_fits(K, cin, cout), OSN_E_ARG,
                 "osn_spconv_fwd_x6: prepared weight of %d x %d x %d exceeds the kernel's 32-bit offsets", K, cin, cout);
     if (n_out == 0) return OSN_OK;
     OSN_REQUIRE(in && Wp && out, OSN_E_ARG, "osn_spconv_fwd_x6: null pointer");
     OSN_REQUIRE(nbr || K == 1, OSN_E_ARG, "osn_spconv_fwd_x6: nbr may be null only for K == 1");
     OSN_REQUIRE(aligned16(in) && aligned16(Wp) && aligned16(out), OSN_E_ARG, "osn_spconv_fwd_x6: pointers must be 16-byte aligned");
     FwdPlan p = plan_fwd(n_out, K, cin, cout);
-    OSN_REQUIRE(p.kps <= 32, OSN_E_ARG, "osn_spconv_fwd_x6: more than 32 offsets per block (K=%d)", K);
+    OSN_REQUIRE(p.kps <= PIPE_KC, OSN_E_ARG, "osn_spconv_fwd_x6: more than 32 offsets per block (K=%d)", K);
     TableLaunch t;
     if (int e = table_workspace("osn_spconv_fwd_x6", p, gmask, nbr, out, n_out, cout, ws, ws_bytes, true, t)) return e;
     const int n = int(n_out);

@@ -49,6 +49,8 @@ constexpr int TL_BOCC3 = 64;      // rows per tile that osn_tile_rows hands out 
 constexpr int TL_LCAP = 1024;     // packed list entries resident in LDS per batch of offsets
 constexpr int TL_STEPS = TL_LCAP / 32 * 4;   // step-table entries: 32-pair steps of a batch x channel chunks (<= 4: 512 channels)
 constexpr int TL_KMAX = 128;      // kernel offsets a list-mode launch can take (5^3 = 125)
+constexpr int TL_CIN_MAX = TL_STEPS / (TL_LCAP / 32) * 128;   // input channels the step table holds: its chunks of at most 4 x 32 channels
+constexpr int64_t TL_ROWS_MAX = int64_t(1) << 24;             // input rows: a packed list entry keeps the row in 24 bits
 constexpr int TL_SLOTS = 512;     // persistent workgroups per column group (2 per CU)
 constexpr int TL_MAX_DEVICES = 64; // per-device "LDS opt-in done" flags of every kernel instance
 
@@ -678,6 +680,14 @@ __global__ void tl_reduce_parts_kernel(const float4* __restrict__ partial, int S
     }
 }
 
+// routing limit of the tile-list kernel (n_in = 0: a shape asked about before its rows are known).  Narrower than what
+// osn_spconv_fwd_tl accepts: cin >= 8 where the entry takes 4, and the channel limit stated up front where the entry finds it in its
+// step-table check
+extern "C" int osn_spconv_fwd_tl_ok(int64_t n_in, int K, int cin, int cout) {
+    return K >= 1 && K <= TL_KMAX && cin >= 8 && cin <= TL_CIN_MAX && (cin & 3) == 0 && cout >= 4 && (cout & 3) == 0 && n_in >= 0 &&
+           n_in <= TL_ROWS_MAX;
+}
+
 static int spconv_fwd_tl_impl(const float* in, int64_t n_in, const void* Wp, const void* tl, const int32_t* out_rows,
                               float* out, double* bn_partial, int64_t n_out, int K, int cin, int cout, int bm, void* ws,
                               size_t ws_bytes, int32_t* counters, long long* prof, osn_stream_t stream, const Epi& epi = epi_none()) {
@@ -686,7 +696,7 @@ static int spconv_fwd_tl_impl(const float* in, int64_t n_in, const void* Wp, con
     OSN_REQUIRE(K >= 1 && K <= TL_KMAX && cin >= 4 && (cin & 3) == 0 && cout >= 4 && (cout & 3) == 0, OSN_E_ARG,
                 "osn_spconv_fwd_tl: needs K <= %d, cin %% 4 == 0, cout %% 4 == 0 (K=%d cin=%d cout=%d)", TL_KMAX, K, cin, cout);
     OSN_REQUIRE(bm >= 1 && bm <= TL_BMAX, OSN_E_ARG, "osn_spconv_fwd_tl: bm=%d (at most %d rows per tile)", bm, TL_BMAX);
-    OSN_REQUIRE(n_in >= 0 && n_in <= (int64_t(1) << 24), OSN_E_RANGE,
+    OSN_REQUIRE(n_in >= 0 && n_in <= TL_ROWS_MAX, OSN_E_RANGE,
                 "osn_spconv_fwd_tl: %lld input rows (the kernel packs an input row into 24 bits; use osn_spconv_fwd_x6)", (long long)n_in);
     if (n_out == 0) return OSN_OK;
     OSN_REQUIRE(in && Wp && out, OSN_E_ARG, "osn_spconv_fwd_tl: null pointer");

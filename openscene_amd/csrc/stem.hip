@@ -18,6 +18,7 @@
 namespace osn {
 
 constexpr int STEM_CMAX = 4;       // input channels at most
+constexpr int STEM_KMAX = 125;     // kernel offsets at most (5^3)
 constexpr int64_t STEM_MFMA_MIN_ROWS = 32768;   // output rows from which the forward convolution runs on the matrix cores (stem_mfma_fwd_kernel)
 constexpr int STEM_COUT = 32;      // output channels handled per thread
 
@@ -509,6 +510,10 @@ __global__ void stem_wgrad_reduce_kernel(const float* __restrict__ partial, int 
 
 using namespace osn;
 
+// routing limit of the stem kernels (forward and weight gradient): what the entry points below accept, less K == 1 -- a 1x1 convolution
+// is a matrix product and goes to the kernels made for one
+extern "C" int osn_stem_conv_ok(int K, int cin, int cout) { return K > 1 && K <= STEM_KMAX && cin >= 1 && cin <= STEM_CMAX && cout == STEM_COUT; }
+
 extern "C" size_t osn_stem_conv_wgrad_ws_bytes(int K, int cin) {
     return size_t(SWM_PARTS > SW_PARTS ? SWM_PARTS : SW_PARTS) * size_t(K > 0 ? K : 1) * size_t(cin > 0 ? cin : 1) * STEM_COUT * 4;
 }
@@ -517,7 +522,7 @@ extern "C" int osn_stem_conv_wgrad(const float* in, const float* gout, const int
                                    int cin, int cout, void* ws, size_t ws_bytes, osn_stream_t stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     OSN_REQUIRE(n_out >= 0 && n_out < (int64_t(1) << 31), OSN_E_ARG, "osn_stem_conv_wgrad: n_out out of range");
-    OSN_REQUIRE(K >= 1 && K <= 125 && cin >= 1 && cin <= STEM_CMAX && cout == STEM_COUT, OSN_E_ARG,
+    OSN_REQUIRE(K >= 1 && K <= STEM_KMAX && cin >= 1 && cin <= STEM_CMAX && cout == STEM_COUT, OSN_E_ARG,
                 "osn_stem_conv_wgrad: needs K <= 125, cin <= %d, cout == %d (K=%d cin=%d cout=%d)", STEM_CMAX, STEM_COUT, K, cin, cout);
     OSN_REQUIRE(gW, OSN_E_ARG, "osn_stem_conv_wgrad: null gradient pointer");
     const int total = K * cin * STEM_COUT;
@@ -552,7 +557,7 @@ int osn::stem_conv_fwd_epi(const float* in, const float* W, const int32_t* nbr, 
                            const Epi& epi, osn_stream_t stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     OSN_REQUIRE(n_out >= 0 && n_out < (int64_t(1) << 31), OSN_E_ARG, "osn_stem_conv_fwd: n_out out of range");
-    OSN_REQUIRE(K >= 1 && K <= 125 && cin >= 1 && cin <= STEM_CMAX && cout == STEM_COUT, OSN_E_ARG,
+    OSN_REQUIRE(K >= 1 && K <= STEM_KMAX && cin >= 1 && cin <= STEM_CMAX && cout == STEM_COUT, OSN_E_ARG,
                 "osn_stem_conv_fwd: needs K <= 125, cin <= %d, cout == %d (K=%d cin=%d cout=%d)", STEM_CMAX, STEM_COUT, K, cin, cout);
     if (n_out == 0) return OSN_OK;
     OSN_REQUIRE(in && W && nbr && out && aligned16(out), OSN_E_ARG, "osn_stem_conv_fwd: null or unaligned pointer");

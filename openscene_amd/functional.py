@@ -37,7 +37,7 @@ WS_MAX_ROWS = 8192
 
 def ws_kernel(K, c_src, c_dst, n_src, n_dst, fine_unique, dst_fine):
     """"ws_direct" / "ws" / None: the weight-stationary kernel for a launch that gathers n_src rows of c_src channels and
-    writes n_dst rows of c_dst channels (same rule as csrc/net.hip:ws_kernel)."""
+    writes n_dst rows of c_dst channels (same rule as csrc/net.hip:ws_kernel; the shape predicate under both is one C export)."""
     if K <= 1 or not ops.tl_eligible(K, c_src, c_dst, n_src):
         return None
     if fine_unique and dst_fine:
@@ -83,7 +83,8 @@ def _plan_kernels(K, cin, cout, n_in, n_out, transposed, fine_unique, need_dgrad
     """(forward, input-gradient, weight-gradient) kernel of a convolution, by the names Executor.kernels() reports; "generic": the
     table kernel ops.spconv_fwd, which the executor does not have; "none": no input gradient wanted.  have_*: what the map handed in
     (tile lists per direction, pair arrays).  THE rule of the per-module path; csrc/net.hip:pick_kernel / pick_wgrad are its twins,
-    tests/test_executor.py::test_both_paths_plan_the_same_kernels holds the two together."""
+    tests/test_executor.py::test_both_paths_plan_the_same_kernels holds the two together.  The shape predicates are no twins: both
+    paths ask the library's osn_*_ok exports (ops.*_eligible here)."""
     tl_mode = CONV_MODE == "tl"
     lists_mode = tl_mode and K > 1 and ops.tl_eligible(K, cin, cout, n_in)
 

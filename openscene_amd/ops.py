@@ -517,7 +517,7 @@ def tile_lists(nbr, out_rows=None, bm=None):
 def tl_eligible(K, cin, cout, n_in=0):
     """Shapes the tile-list kernel takes (everything of the U-Net but the 3-channel stem; up to 2^24 input rows; up to 512
     input channels = four 128-channel chunks in the kernel's step table: wider 1x1 convs are the dense kernel's)."""
-    return cin % 4 == 0 and 8 <= cin <= 512 and cout % 4 == 0 and K <= 128 and n_in <= (1 << 24)
+    return bool(_cached("osn_spconv_fwd_tl_ok", int(n_in), int(K), int(cin), int(cout)))
 
 
 def weight_prep_tl(weight, flip=False, want_fwd=True, want_dgrad=True):
@@ -776,7 +776,7 @@ def rows_argmax(scores, gather=None):
 
 def dense_eligible(cin, cout):
     """Shapes the 1x1-convolution kernel takes (everything of the U-Net family; odd widths stay on the generic kernel)."""
-    return cin % 4 == 0 and cin >= 8 and cout % 4 == 0
+    return bool(_cached("osn_dense_fwd_ok", int(cin), int(cout)))
 
 
 def dense_fwd(feats, wp, cout):
@@ -872,7 +872,7 @@ def spconv_fwd_rg(feats, wp, nbr, n_out, cout, out_rows=None):
 
 def stem_eligible(K, cin, cout):
     """The dedicated kernels of the U-Net's 3-channel stem conv (any conv with <= 4 input and 32 output channels)."""
-    return cin <= 4 and cout == 32 and 1 < K <= 125
+    return bool(_cached("osn_stem_conv_ok", int(K), int(cin), int(cout)))
 
 
 def stem_conv_fwd(feats, weight, nbr, n_out):
@@ -895,13 +895,7 @@ def stem_conv_fwd(feats, weight, nbr, n_out):
 
 def x6_eligible(K, cin, cout, n_out):
     """The split-bf16 kernel handles every conv of the U-Net except the 3-channel stem."""
-    if cin % 4 or cin < 8:
-        return False
-    if 3 * K * cout * ((cin + 31) // 32 * 32) >= 1 << 30:        # the kernel indexes the prepared weight with 32 bits
-        return False
-    plan = spconv_fwd_plan(n_out, K, cin, cout)
-    S = plan[4]
-    return -(-K // S) <= 32
+    return bool(_cached("osn_spconv_fwd_x6_ok", int(n_out), int(K), int(cin), int(cout)))
 
 
 def weight_transpose(weight, flip):

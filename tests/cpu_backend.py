@@ -153,7 +153,8 @@ def tile_lists(nbr, out_rows=None, bm=None):
 
 
 def tl_eligible(K, cin, cout, n_in=0):
-    return cin % 4 == 0 and cin >= 8 and cout % 4 == 0 and K <= 128 and n_in <= (1 << 24)
+    """Spec of osn_spconv_fwd_tl_ok."""
+    return cin % 4 == 0 and 8 <= cin <= 512 and cout % 4 == 0 and cout >= 4 and 1 <= K <= 128 and 0 <= n_in <= (1 << 24)
 
 
 def weight_prep_tl(weight, flip=False, want_fwd=True, want_dgrad=True):
@@ -267,7 +268,8 @@ def spconv_fwd_rg(feats, wp, nbr, n_out, cout, out_rows=None):
 
 
 def stem_eligible(K, cin, cout):
-    return cin <= 4 and cout == 32 and 1 < K <= 125
+    """Spec of osn_stem_conv_ok."""
+    return 1 <= cin <= 4 and cout == 32 and 1 < K <= 125
 
 
 def stem_conv_fwd(feats, weight, nbr, n_out):
@@ -280,7 +282,8 @@ def rows_argmax(scores, gather=None):
 
 
 def dense_eligible(cin, cout):
-    return cin % 4 == 0 and cin >= 8 and cout % 4 == 0
+    """Spec of osn_dense_fwd_ok."""
+    return cin % 4 == 0 and cin >= 8 and cout % 4 == 0 and cout >= 4
 
 
 def dense_fwd(feats, wp, cout):
@@ -292,7 +295,21 @@ def stem_conv_wgrad(feats, gout, nbr, K):
 
 
 def x6_eligible(K, cin, cout, n_out):
-    return cin % 4 == 0 and cin >= 8
+    """Spec of osn_spconv_fwd_x6_ok: a weight image (three bf16 planes, cin padded to 32) within 32-bit offsets, and at most 32
+    offsets per block once the launch plan has split the offsets of a small map: tiles of 128 / 64 / 32 rows by 32 tn / 64 tn / 128
+    columns, and below 384 blocks as many offset groups as bring the launch to 768 (at most 16, at most K)."""
+    if K < 1 or cin % 4 or cin < 8 or cout < 1 or n_out >= 1 << 31 or 3 * K * cout * (-(-cin // 32) * 32) >= 1 << 30:
+        return False
+    n_out, ct = max(n_out, 1), -(-cout // 32)
+    if n_out >= 32768 or ct == 1:
+        bm, bn = 128, 32 * min(ct, 4)
+    elif n_out >= 4096 or ct == 2:
+        bm, bn = 64, 64 * (2 if ct >= 3 else 1)
+    else:
+        bm, bn = 32, 128
+    blocks = -(-n_out // bm) * -(-cout // bn)
+    S = min(-(-768 // blocks), 16, K) if K > 1 and blocks < 384 else 1
+    return -(-K // S) <= 32
 
 
 def weight_transpose(weight, flip):

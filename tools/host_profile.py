@@ -27,6 +27,18 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 
+# the shape predicates answer as the library does (tests/cpu_backend.py states the same), so that a mocked step makes the calls of a
+# real one; x6 for the one-part plan the mock's osn_spconv_fwd_plan reports.  (int): an int32 argument arrives in a 64-bit register.
+SHAPE_OK = {
+    "osn_stem_conv_ok": "(int)a0 > 1 && (int)a0 <= 125 && (int)a1 >= 1 && (int)a1 <= 4 && (int)a2 == 32",
+    "osn_spconv_fwd_tl_ok": "a0 >= 0 && a0 <= (1 << 24) && (int)a1 >= 1 && (int)a1 <= 128 && (int)a2 % 4 == 0 && (int)a2 >= 8 && "
+                            "(int)a2 <= 512 && (int)a3 % 4 == 0 && (int)a3 >= 4",
+    "osn_dense_fwd_ok": "(int)a0 % 4 == 0 && (int)a0 >= 8 && (int)a1 % 4 == 0 && (int)a1 >= 4",
+    "osn_spconv_fwd_x6_ok": "(int)a1 >= 1 && (int)a1 <= 32 && (int)a2 % 4 == 0 && (int)a2 >= 8 && (int)a3 >= 1 && "
+                            "3ll * (int)a1 * (int)a3 * (((int)a2 + 31) / 32 * 32) < (1ll << 30)",
+}
+
+
 def build_mock():
     from openscene_amd import _lib
     src = ["#include <stdint.h>", "#include <stddef.h>", "static long long calls = 0;",
@@ -40,6 +52,8 @@ def build_mock():
                            for (i, a), p in zip(enumerate(args), params.split(", "))) if args else "void"
         if name == "osn_spconv_fwd_plan":
             body = "int32_t* p = (int32_t*)a4; p[0]=4; p[1]=1; p[2]=3; p[3]=32; p[4]=1; p[5]=1000; return 0;"
+        elif name in SHAPE_OK:
+            body = "return %s;" % SHAPE_OK[name]
         elif name == "osn_last_error":
             body = 'return (long long)(intptr_t)"mock";'
         elif name in ("osn_version", "osn_device_ok"):
