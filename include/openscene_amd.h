@@ -613,6 +613,32 @@ int osn_bank_search_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int
                         const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
                         int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
 
+/* Search with negative queries: the heat-map holds relevancies against the best of m negative phrases ("object", "things",
+ * "stuff", "texture" in the LERF line of work) in place of raw cosines, so that one threshold means the same for every
+ * query.  Inputs beyond osn_bank_search's / osn_bank_search_fp8's: negatives fp16 [m, d], L2-normalised by the caller,
+ * 16-byte aligned, 1 <= m <= 1024; temperature float32, finite and > 0.  With s(p, j) the fp16 score osn_bank_search writes
+ * for query j and g(p, i) the one it writes for negative i as a query (either normalize mode; bit for bit, whichever
+ * column group a column falls in):
+ *     nmax(p)   = max_i float(g(p, i))                          a NaN among them makes nmax NaN
+ *     z(p, j)   = (float(s(p, j)) - nmax(p)) / temperature      fp32, IEEE, as written
+ *     rel(p, j) = fp16_rne(1.0f / (1.0f + expf(-z)))
+ * = min_i softmax([s, g_i] / temperature)[0], the pairwise-softmax relevancy (the sigmoid is monotone).  NaN in gives NaN
+ * out (inf - inf included); saturation to exactly 0 or 1 is expected and leaves large tie groups to the selection's total
+ * order.  heat fp16 [n, q] holds rel; the negatives get no column in heat or in the workspace, which stays
+ * osn_bank_search_ws_bytes(n, n_scenes, q, ...).  topk_*, thresholds and counts act on rel; padding, NaN order, clamped
+ * offsets, the err bits, integer atomics only and bitwise repeatability are osn_bank_search's.  One pass over the bank:
+ * the negatives' column groups run first through the same MFMA loop and leave only a per-row maximum in LDS.          */
+int osn_bank_search_contrast(const void* bank_f16, int64_t n, int d, const int64_t* scene_offsets, int n_scenes,
+                             int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
+                             const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
+                             int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream,
+                             const void* negatives_f16, int m, float temperature);
+int osn_bank_search_contrast_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int d, const int64_t* scene_offsets,
+                                 int n_scenes, int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
+                                 const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
+                                 int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream,
+                                 const void* negatives_f16, int m, float temperature);
+
 /* ---- descriptors of point sets over the bank (csrc/pool.hip) ----------------------------------------------------- *
  * The way back from points to a feature vector (README "Applications": "retrieve examples based on similarities", room
  * type, labelling a found object): the sum of the normalised stored rows of every group of a list of bank rows; the mean

@@ -24,6 +24,10 @@
 // them to fp16 (exact) on the way into LDS (heat_fp8_kernel); 2^e enters where the scores leave.  The two heat kernels call
 // one set of __device__ templates for the query staging, the MFMA loop, the row norms and the score output; each has its own
 // row fetch, stash and stage loop.  Pass 2 and the entries' argument checks are shared too.
+//
+// Negative queries (osn_bank_search_contrast / _fp8): the heat kernels' CONTRAST instances walk the negatives' column groups
+// first -- same loop, each score rounded to fp16, only the row's maximum kept (rneg, LDS) -- and then write, for the queries,
+// fp16(1 / (1 + expf(-(s - rneg) / temperature))) in place of the fp16 score s.  Pass 2 selects on that relevancy unchanged.
 #include "bank.h"
 
 namespace osn {
@@ -140,11 +144,15 @@ __device__ __forceinline__ void row_norms(float* rden, const float (&ss)[S_BM * 
 
 // the scores of one column group leave: accumulator [* rscale, exact: a power of two], divided by rden in fp32, rounded to
 // fp16 once into the LDS tile Sc[column][row] (CT * 32 <= 128 rows of the row tile); from there column-major into heatT and,
-// where the caller wants it, row-major into heat
-template <int CT, bool SCALED>
+// where the caller wants it, row-major into heat.
+// CONTRAST (osn_bank_search_contrast): a group of negatives (`neg`, q = their number) is stored nowhere -- the largest fp16
+// score of a row, NaN if one of them is, is kept in rneg[row]; a group of queries writes, in place of the fp16 score s,
+// fp16(1 / (1 + expf(-(s - rneg[row]) / temperature))), the relevancy against the best negative.
+template <int CT, bool SCALED, bool CONTRAST>
 __device__ __forceinline__ void scores_out(const f32x16 (&acc)[CT], _Float16 (*Sc)[S_LD], const float* rden, const float* rscale,
-                                           _Float16* __restrict__ heat, _Float16* __restrict__ heatT, int64_t ldT, int64_t row0,
-                                           int64_t n, int q, int cg0, int normalize, int tid) {
+                                           float* rneg, bool neg, float temperature, _Float16* __restrict__ heat,
+                                           _Float16* __restrict__ heatT, int64_t ldT, int64_t row0, int64_t n, int q, int cg0,
+                                           int normalize, int tid) {
     const int lane = tid & 63, wave = tid >> 6;
 #pragma unroll
     for (int t = 0; t < CT; ++t) {
@@ -154,10 +162,28 @@ __device__ __forceinline__ void scores_out(const f32x16 (&acc)[CT], _Float16 (*S
             float v = acc[t][r];
             if (SCALED) v *= rscale[lrow];
             if (normalize) v /= rden[lrow];
-            Sc[t * 32 + (lane & 31)][lrow] = (_Float16)v;
+            _Float16 h = (_Float16)v;
+            if (CONTRAST && !neg) {
+                const float z = ((float)h - rneg[lrow]) / temperature;
+                h = (_Float16)(1.0f / (1.0f + expf(-z)));
+            }
+            Sc[t * 32 + (lane & 31)][lrow] = h;
         }
     }
     __syncthreads();
+    if (CONTRAST && neg) {                                  // (uniform over the workgroup)
+        if (tid < S_BM) {
+            const int qn = (q - cg0) < 32 * CT ? (q - cg0) : 32 * CT;
+            float nm = rneg[tid];
+            for (int c = 0; c < qn; ++c) {
+                const float v = (float)Sc[c][tid];
+                nm = (v > nm || v != v) ? v : nm;           // a NaN stays
+            }
+            rneg[tid] = nm;
+        }
+        __syncthreads();                                    // the tile is the next column group's row buffer
+        return;
+    }
     for (int e = tid; e < CT * 32 * (S_BM / 8); e += 256) {       // column-major: 16-byte pieces of a column's 128 rows
         const int col = e >> 4, v8 = e & 15;
         const int gc = cg0 + col;
@@ -181,13 +207,25 @@ __device__ __forceinline__ void scores_out(const f32x16 (&acc)[CT], _Float16 (*S
     __syncthreads();                                        // the tile is the next column group's row buffer
 }
 
-template <int CT, int WGS>
+// The column groups in the order a heat kernel walks them: the queries' groups from cg = 0; with CONTRAST the negatives'
+// groups (Tn [m, d]) come first, from cg < 0.  The row norms are taken during the first group walked, whichever that is.
+template <int CT, bool CONTRAST>
+struct ColumnGroups {
+    int first;             // cg of the first group: -(groups of negatives) * 32 * CT, or 0
+    __device__ __forceinline__ explicit ColumnGroups(int m) : first(CONTRAST ? -((m + 32 * CT - 1) / (32 * CT)) * (32 * CT) : 0) {}
+    __device__ __forceinline__ bool neg(int cg) const { return CONTRAST && cg < 0; }
+    __device__ __forceinline__ int col0(int cg) const { return neg(cg) ? cg - first : cg; }       // first column inside its matrix
+};
+
+template <int CT, int WGS, bool CONTRAST>
 __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restrict__ B, const _Float16* __restrict__ T,
                                                         _Float16* __restrict__ heat, _Float16* __restrict__ heatT, int64_t ldT,
-                                                        int64_t n, int d, int q, int normalize) {
+                                                        int64_t n, int d, int q, int normalize, const _Float16* __restrict__ Tn,
+                                                        int m, float temperature) {
     __shared__ __attribute__((aligned(16))) _Float16 Xs[S_BM][S_LD];
     __shared__ __attribute__((aligned(16))) _Float16 Ts[CT * 32][S_LD];
     __shared__ float rden[S_BM];
+    __shared__ float rneg[S_BM];                            // CONTRAST: the row's best negative score
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t row0 = int64_t(blockIdx.x) * S_BM;
@@ -195,9 +233,15 @@ __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restri
     float ss[S_BM / 16];
 #pragma unroll
     for (int ps = 0; ps < S_BM / 16; ++ps) ss[ps] = 0.f;
+    if (CONTRAST && tid < S_BM) rneg[tid] = -INFINITY;      // (read after the barriers of the first group)
 
-    for (int cg0 = 0; cg0 < q; cg0 += 32 * CT) {
-        const bool sumsq = normalize && cg0 == 0;
+    const ColumnGroups<CT, CONTRAST> groups(m);
+    for (int cg = groups.first; cg < q; cg += 32 * CT) {
+        const bool neg = groups.neg(cg);
+        const int cg0 = groups.col0(cg);
+        const _Float16* __restrict__ Tg = neg ? Tn : T;
+        const int qg = neg ? m : q;
+        const bool sumsq = normalize && cg == groups.first;
         f32x16 acc[CT];
 #pragma unroll
         for (int t = 0; t < CT; ++t)
@@ -207,7 +251,7 @@ __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restri
         uint4 px[S_BM / 16];
         uint4 pt[2 * CT];
         auto fetch = [&](int d0) {
-            fetch_queries<CT>(pt, T, cg0, d0, d, q, tid);
+            fetch_queries<CT>(pt, Tg, cg0, d0, d, qg, tid);
 #pragma unroll
             for (int ps = 0; ps < S_BM / 16; ++ps) {
                 const int64_t row = row0 + ps * 16 + xr;
@@ -231,7 +275,7 @@ __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restri
                 }
                 *reinterpret_cast<uint4*>(&Xs[row][xq * 8]) = v;
             }
-            stash_queries<CT>(Ts, pt, cg0, d0, d, q, tid);
+            stash_queries<CT>(Ts, pt, cg0, d0, d, qg, tid);
         };
         fetch(0);
         stash(0);
@@ -246,7 +290,8 @@ __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restri
             __syncthreads();
         }
         if (sumsq) row_norms<16, false>(rden, ss, nullptr, tid);
-        scores_out<CT, false>(acc, Xs, rden, nullptr, heat, heatT, ldT, row0, n, q, cg0, normalize, tid);
+        scores_out<CT, false, CONTRAST>(acc, Xs, rden, nullptr, rneg, neg, temperature, heat, heatT, ldT, row0, n, qg, cg0,
+                                        normalize, tid);
     }
 }
 
@@ -356,15 +401,17 @@ __global__ __launch_bounds__(256) void bank_append_fp8_kernel(const void* __rest
 // Two workgroups per CU: the second register stage and the conversion need 194 / 250 VGPRs (one / two column tiles); held to
 // the 168 of three workgroups the kernel spills inside the loop and measured 0.81x of the fp16 pass at 8 x 150 k x 768 x 32
 // where this shape measured 0.67x.
-template <int CT, int WGS>
+template <int CT, int WGS, bool CONTRAST>
 __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __restrict__ B, const int8_t* __restrict__ E,
                                                             const _Float16* __restrict__ T, _Float16* __restrict__ heat,
                                                             _Float16* __restrict__ heatT, int64_t ldT, int64_t n, int d, int q,
-                                                            int normalize) {
+                                                            int normalize, const _Float16* __restrict__ Tn, int m,
+                                                            float temperature) {
     __shared__ __attribute__((aligned(16))) _Float16 Xs[S_BM][S_LD];
     __shared__ __attribute__((aligned(16))) _Float16 Ts[CT * 32][S_LD];
     __shared__ float rden[S_BM];
     __shared__ float rscale[S_BM];                          // 2^e of the row
+    __shared__ float rneg[S_BM];                            // CONTRAST: the row's best negative score
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t row0 = int64_t(blockIdx.x) * S_BM;
@@ -376,10 +423,16 @@ __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __res
     if (tid < S_BM) {
         const int64_t row = row0 + tid < n ? row0 + tid : n - 1;
         rscale[tid] = __uint_as_float(uint32_t(127 + int(E[row])) << 23);
+        if (CONTRAST) rneg[tid] = -INFINITY;
     }
 
-    for (int cg0 = 0; cg0 < q; cg0 += 32 * CT) {
-        const bool sumsq = normalize && cg0 == 0;
+    const ColumnGroups<CT, CONTRAST> groups(m);
+    for (int cg = groups.first; cg < q; cg += 32 * CT) {
+        const bool neg = groups.neg(cg);
+        const int cg0 = groups.col0(cg);
+        const _Float16* __restrict__ Tg = neg ? Tn : T;
+        const int qg = neg ? m : q;
+        const bool sumsq = normalize && cg == groups.first;
         f32x16 acc[CT];
 #pragma unroll
         for (int t = 0; t < CT; ++t)
@@ -418,16 +471,16 @@ __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __res
                 *reinterpret_cast<uint4*>(&Xs[row][xq * 16]) = lo;
                 *reinterpret_cast<uint4*>(&Xs[row][xq * 16 + 8]) = hi;
             }
-            stash_queries<CT>(Ts, pt, cg0, d0, d, q, tid);
+            stash_queries<CT>(Ts, pt, cg0, d0, d, qg, tid);
         };
-        fetch_queries<CT>(pt, T, cg0, 0, d, q, tid);
+        fetch_queries<CT>(pt, Tg, cg0, 0, d, qg, tid);
         fetch_x(pxa, 0);
         fetch_x(pxb, S_DK);                                 // (past the end: the first 16 bytes of B / T, never staged)
         stash(pxa, 0);
         __syncthreads();
         for (int d0 = 0; d0 < d; d0 += 2 * S_DK) {
             __builtin_amdgcn_sched_barrier(0);
-            fetch_queries<CT>(pt, T, cg0, d0 + S_DK, d, q, tid);
+            fetch_queries<CT>(pt, Tg, cg0, d0 + S_DK, d, qg, tid);
             fetch_x(pxa, d0 + 2 * S_DK);
             __builtin_amdgcn_sched_barrier(0);
             mfma_chunk<CT>(acc, Xs, Ts, wave, lane);
@@ -436,7 +489,7 @@ __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __res
             stash(pxb, d0 + S_DK);
             __syncthreads();
             __builtin_amdgcn_sched_barrier(0);
-            fetch_queries<CT>(pt, T, cg0, d0 + 2 * S_DK, d, q, tid);
+            fetch_queries<CT>(pt, Tg, cg0, d0 + 2 * S_DK, d, qg, tid);
             fetch_x(pxb, d0 + 3 * S_DK);
             __builtin_amdgcn_sched_barrier(0);
             mfma_chunk<CT>(acc, Xs, Ts, wave, lane);
@@ -445,7 +498,8 @@ __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __res
             __syncthreads();
         }
         if (sumsq) row_norms<8, true>(rden, ss, rscale, tid);       // ||c|| * 2^e + 1e-5
-        scores_out<CT, true>(acc, Xs, rden, rscale, heat, heatT, ldT, row0, n, q, cg0, normalize, tid);
+        scores_out<CT, true, CONTRAST>(acc, Xs, rden, rscale, rneg, neg, temperature, heat, heatT, ldT, row0, n, qg, cg0,
+                                       normalize, tid);
     }
 }
 
@@ -827,12 +881,39 @@ extern "C" size_t osn_bank_search_ws_bytes(int64_t n, int n_scenes, int q, int k
     return search_ws(n, n_scenes, q, k, max_scene_rows).total;
 }
 
-// both searches: `rows` are fp16 rows or, with `fp8`, e4m3 codes that go with the row exponents `exps`; `who` names the entry
-// in the messages
+// pass 1 of every search: one or two column tiles (32 or 64 columns a group); three workgroups per CU over fp16 rows, two over
+// codes (heat_fp8_kernel).  The CONTRAST instances keep these bounds: the relevancy adds no register that lives across the
+// chunk loop and 512 bytes of LDS (3 x 53248 B with two column tiles, of 160 KB).
+template <bool CONTRAST>
+static void heat_launch(bool fp8, const void* rows, const int8_t* exps, const _Float16* T, _Float16* heat, _Float16* heatT,
+                        int64_t ldT, int64_t n, int d, int q, int normalize, const _Float16* Tn, int m, float temperature,
+                        hipStream_t st) {
+    const dim3 grid(unsigned(cdiv(n, S_BM))), block(256);
+    const bool one = q <= 32 && m <= 32;                    // (m = 0 without negatives)
+    if (fp8) {
+        const uint8_t* B = static_cast<const uint8_t*>(rows);
+        if (one) hipLaunchKernelGGL((heat_fp8_kernel<1, 2, CONTRAST>), grid, block, 0, st, B, exps, T, heat, heatT, ldT, n, d, q, normalize, Tn, m, temperature);
+        else hipLaunchKernelGGL((heat_fp8_kernel<2, 2, CONTRAST>), grid, block, 0, st, B, exps, T, heat, heatT, ldT, n, d, q, normalize, Tn, m, temperature);
+    } else {
+        const _Float16* B = static_cast<const _Float16*>(rows);
+        if (one) hipLaunchKernelGGL((heat_kernel<1, 3, CONTRAST>), grid, block, 0, st, B, T, heat, heatT, ldT, n, d, q, normalize, Tn, m, temperature);
+        else hipLaunchKernelGGL((heat_kernel<2, 3, CONTRAST>), grid, block, 0, st, B, T, heat, heatT, ldT, n, d, q, normalize, Tn, m, temperature);
+    }
+}
+
+// the negatives of a contrast search (osn_bank_search_contrast): null for the plain entries
+struct Contrast {
+    const void* negatives_f16;
+    int m;
+    float temperature;
+};
+
+// every search: `rows` are fp16 rows or, with `fp8`, e4m3 codes that go with the row exponents `exps`; `who` names the entry
+// in the messages; `contrast` (nullable) turns the scores into relevancies
 static int bank_search_impl(const char* who, bool fp8, const void* rows, const int8_t* exps, int64_t n, int d, const int64_t* scene_offsets,
                             int n_scenes, int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
                             const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points, int64_t* counts,
-                            int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream) {
+                            int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream, const Contrast* contrast = nullptr) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int dm = fp8 ? 16 : 8;
     OSN_REQUIRE(n >= 0 && d >= dm && d % dm == 0 && q >= 1 && q <= 1024, OSN_E_ARG,
@@ -846,23 +927,24 @@ static int bank_search_impl(const char* who, bool fp8, const void* rows, const i
                 "%s: the bank's rows%s must be non-null, the rows 16-byte aligned", who, fp8 ? " and exponents" : "");
     OSN_REQUIRE(n_scenes == 0 || (scene_offsets && topk_scores_f16 && topk_points && err), OSN_E_ARG, "%s: null pointer", who);
     OSN_REQUIRE(!counts || thresholds, OSN_E_ARG, "%s: counts need thresholds", who);
+    if (contrast) {
+        OSN_REQUIRE(contrast->m >= 1 && contrast->m <= 1024, OSN_E_ARG, "%s: need 1 <= m <= 1024 negatives (m=%d)", who, contrast->m);
+        OSN_REQUIRE(contrast->temperature > 0.f && contrast->temperature < INFINITY, OSN_E_ARG,
+                    "%s: the temperature must be finite and > 0 (%g)", who, double(contrast->temperature));
+        OSN_REQUIRE(contrast->negatives_f16 && aligned16(contrast->negatives_f16), OSN_E_ARG,
+                    "%s: negatives must be non-null and 16-byte aligned", who);
+    }
     const SearchWs w = search_ws(n, n_scenes, q, k, max_scene_rows);
     OSN_REQUIRE(ws && aligned16(ws) && ws_bytes >= w.total, OSN_E_WS, "%s: workspace too small (%zu < %zu)", who, ws_bytes, w.total);
     char* p = static_cast<char*>(ws);
     _Float16* heatT = reinterpret_cast<_Float16*>(p + w.heatT);
     if (n > 0) {
-        const dim3 grid(unsigned(cdiv(n, S_BM))), block(256);
         const _Float16* T = static_cast<const _Float16*>(queries_f16);
         _Float16* heat = static_cast<_Float16*>(heat_f16);
-        if (fp8) {
-            const uint8_t* B = static_cast<const uint8_t*>(rows);
-            if (q <= 32) hipLaunchKernelGGL((heat_fp8_kernel<1, 2>), grid, block, 0, st, B, exps, T, heat, heatT, w.ldT, n, d, q, normalize);
-            else hipLaunchKernelGGL((heat_fp8_kernel<2, 2>), grid, block, 0, st, B, exps, T, heat, heatT, w.ldT, n, d, q, normalize);
-        } else {
-            const _Float16* B = static_cast<const _Float16*>(rows);
-            if (q <= 32) hipLaunchKernelGGL((heat_kernel<1, 3>), grid, block, 0, st, B, T, heat, heatT, w.ldT, n, d, q, normalize);
-            else hipLaunchKernelGGL((heat_kernel<2, 3>), grid, block, 0, st, B, T, heat, heatT, w.ldT, n, d, q, normalize);
-        }
+        if (contrast)
+            heat_launch<true>(fp8, rows, exps, T, heat, heatT, w.ldT, n, d, q, normalize,
+                              static_cast<const _Float16*>(contrast->negatives_f16), contrast->m, contrast->temperature, st);
+        else heat_launch<false>(fp8, rows, exps, T, heat, heatT, w.ldT, n, d, q, normalize, nullptr, 0, 0.f, st);
         OSN_LAUNCH_CHECK();
     }
     if (n_scenes == 0) return OSN_OK;
@@ -884,4 +966,26 @@ extern "C" int osn_bank_search_fp8(const uint8_t* codes, const int8_t* exps, int
     return bank_search_impl("osn_bank_search_fp8", true, codes, exps, n, d, scene_offsets, n_scenes, max_scene_rows,
                             queries_f16, q, normalize, k, thresholds, heat_f16, topk_scores_f16, topk_points, counts, err, ws,
                             ws_bytes, stream);
+}
+
+extern "C" int osn_bank_search_contrast(const void* bank_f16, int64_t n, int d, const int64_t* scene_offsets, int n_scenes,
+                                        int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
+                                        const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
+                                        int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream,
+                                        const void* negatives_f16, int m, float temperature) {
+    const Contrast c = {negatives_f16, m, temperature};
+    return bank_search_impl("osn_bank_search_contrast", false, bank_f16, nullptr, n, d, scene_offsets, n_scenes, max_scene_rows,
+                            queries_f16, q, normalize, k, thresholds, heat_f16, topk_scores_f16, topk_points, counts, err, ws,
+                            ws_bytes, stream, &c);
+}
+
+extern "C" int osn_bank_search_contrast_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int d, const int64_t* scene_offsets,
+                                            int n_scenes, int64_t max_scene_rows, const void* queries_f16, int q, int normalize,
+                                            int k, const float* thresholds, void* heat_f16, void* topk_scores_f16,
+                                            int64_t* topk_points, int64_t* counts, int32_t* err, void* ws, size_t ws_bytes,
+                                            osn_stream_t stream, const void* negatives_f16, int m, float temperature) {
+    const Contrast c = {negatives_f16, m, temperature};
+    return bank_search_impl("osn_bank_search_contrast_fp8", true, codes, exps, n, d, scene_offsets, n_scenes, max_scene_rows,
+                            queries_f16, q, normalize, k, thresholds, heat_f16, topk_scores_f16, topk_points, counts, err, ws,
+                            ws_bytes, stream, &c);
 }

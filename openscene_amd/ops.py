@@ -1362,10 +1362,26 @@ def bank_check(err):
         check(lib.osn_bank_check(_p(err), _stream(dev)), "osn_bank_check")
 
 
-def _bank_search(entry, bank_ptrs, n, d, d_multiple, dev, scene_offsets, queries, k, thresholds, normalize, want_heat,
-                 max_scene_rows, err):
-    """bank_search and bank_search_fp8 behind their own checks of the bank: `entry` is the C entry that takes `bank_ptrs`
-    (the fp16 rows, or the codes and the exponents) ahead of the arguments the two share."""
+def _bank_search(entries, bank_ptrs, n, d, d_multiple, dev, scene_offsets, queries, k, thresholds, normalize, want_heat,
+                 max_scene_rows, err, negatives=None, temperature=0.1):
+    """bank_search and bank_search_fp8 behind their own checks of the bank: `entries` are the C entries (plain, contrast)
+    that take `bank_ptrs` (the fp16 rows, or the codes and the exponents) ahead of the arguments the two share; the
+    contrast entry is called when `negatives` are given."""
+    entry, tail = entries[0], ()
+    if negatives is not None:
+        if not isinstance(negatives, torch.Tensor) or negatives.dtype != torch.float16:
+            raise TypeError("negatives must be a float16 tensor")
+        if negatives.dim() != 2 or negatives.shape[1] != d:
+            raise ValueError("negatives must be [M, %d] (got %s)" % (d, tuple(negatives.shape)))
+        if negatives.device != dev:
+            raise ValueError("negatives must be on the bank's device")
+        if not 1 <= negatives.shape[0] <= BANK_MAX_Q:
+            raise ValueError("1 .. %d negatives per call (got %d)" % (BANK_MAX_Q, negatives.shape[0]))
+        temperature = float(temperature)
+        if not 0.0 < temperature < float("inf"):
+            raise ValueError("the temperature must be finite and > 0 (got %r)" % (temperature,))
+        negatives = negatives.contiguous()
+        entry, tail = entries[1], (_p(negatives), negatives.shape[0], temperature)
     if queries.dtype != torch.float16:
         raise TypeError("queries must be float16 (util/util.py:41-44 produces fp16)")
     if queries.dim() != 2 or queries.shape[1] != d:
@@ -1406,29 +1422,31 @@ def _bank_search(entry, bank_ptrs, n, d, d_multiple, dev, scene_offsets, queries
     ws = _ws(wsb, dev)
     with _Dev(dev):
         check(entry(*bank_ptrs, n, d, _p(scene_offsets), s, max_scene_rows, _p(queries), q, int(bool(normalize)), k, _p(thresholds),
-                    _p(heat), _p(top_s), _p(top_p), _p(counts), _p(err), _p(ws), ws.numel(), _stream(dev)), entry.__name__)
+                    _p(heat), _p(top_s), _p(top_p), _p(counts), _p(err), _p(ws), ws.numel(), _stream(dev), *tail), entry.__name__)
     if own_err and s > 0:
         bank_check(err)
     return heat, top_s, top_p, counts
 
 
 def bank_search(bank, scene_offsets, queries, k=16, thresholds=None, normalize=True, want_heat=False, max_scene_rows=None,
-                err=None):
+                err=None, negatives=None, temperature=0.1):
     """Scores of every bank row against every query and the k best rows of every scene.
     bank fp16 [N, d]; scene_offsets int64 [S + 1] on the device (ascending from 0; S = 0 computes the heat-map only);
     queries fp16 [Q, d], L2-normalised; thresholds float32 [Q] or None.
     -> (heat fp16 [N, Q] or None, topk_scores fp16 [S, Q, k], topk_points int64 [S, Q, k] (row inside the scene, -1 = padding),
         counts int64 [S, Q] or None).
     max_scene_rows: the longest scene, when the caller knows it (saves reading the offsets back).  Bad offsets are recorded
-    in `err` when one is given (bank_check raises), and checked here otherwise."""
+    in `err` when one is given (bank_check raises), and checked here otherwise.
+    negatives fp16 [M, d], L2-normalised (osn_bank_search_contrast): heat, the selection and the counts then hold the
+    relevancy sigmoid((score - the row's best negative score) / temperature) in place of the score."""
     lib = _prep(bank.device)
     if bank.dtype != torch.float16:
         raise TypeError("the bank must be float16 (got %s)" % bank.dtype)
     if bank.dim() != 2 or not bank.is_contiguous():
         raise ValueError("the bank must be a contiguous [rows, dim] matrix")
     n, d = bank.shape
-    return _bank_search(lib.osn_bank_search, (_p(bank),), n, d, 8, bank.device, scene_offsets, queries, k, thresholds, normalize,
-                        want_heat, max_scene_rows, err)
+    return _bank_search((lib.osn_bank_search, lib.osn_bank_search_contrast), (_p(bank),), n, d, 8, bank.device, scene_offsets, queries,
+                        k, thresholds, normalize, want_heat, max_scene_rows, err, negatives, temperature)
 
 
 def bank_append_fp8(codes, exps, row0, feats, err, gather=None):
@@ -1460,9 +1478,9 @@ def bank_append_fp8(codes, exps, row0, feats, err, gather=None):
 
 
 def bank_search_fp8(codes, exps, scene_offsets, queries, k=16, thresholds=None, normalize=True, want_heat=False,
-                    max_scene_rows=None, err=None):
+                    max_scene_rows=None, err=None, negatives=None, temperature=0.1):
     """bank_search over an fp8 bank: codes uint8 [N, d] (e4m3fn), exps int8 [N], d % 16 == 0; the score is taken on the
-    stored values code * 2^e.  Everything else -- arguments, results, selection order -- is bank_search's."""
+    stored values code * 2^e.  Everything else -- arguments, results, selection order, negatives -- is bank_search's."""
     dev = codes.device
     lib = _prep(dev)
     if codes.dtype != torch.uint8:
@@ -1474,8 +1492,8 @@ def bank_search_fp8(codes, exps, scene_offsets, queries, k=16, thresholds=None, 
     if exps.dim() != 1 or exps.shape[0] != codes.shape[0] or exps.device != dev or not exps.is_contiguous():
         raise ValueError("exponents must be a contiguous [%d] vector on the codes' device" % codes.shape[0])
     n, d = codes.shape
-    return _bank_search(lib.osn_bank_search_fp8, (_p(codes), _p(exps)), n, d, 16, dev, scene_offsets, queries, k, thresholds,
-                        normalize, want_heat, max_scene_rows, err)
+    return _bank_search((lib.osn_bank_search_fp8, lib.osn_bank_search_contrast_fp8), (_p(codes), _p(exps)), n, d, 16, dev,
+                        scene_offsets, queries, k, thresholds, normalize, want_heat, max_scene_rows, err, negatives, temperature)
 
 
 # ------------------------------------------------------------------------ pool

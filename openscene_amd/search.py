@@ -7,12 +7,14 @@ against CLIP text embeddings (``:291``, ``:305,310``) and can save them per scen
 
     FeatureBank      one growing matrix of per-point features, many scenes, on the device: fp16, or fp8 (e4m3fn codes
                      with one power-of-two exponent per row) at half the bytes
-    search           heat-map [N, Q] + the k best points of every scene + counts over a threshold: ONE pass over the bank
+    search           heat-map [N, Q] + the k best points of every scene + counts over a threshold: ONE pass over the bank;
+                     with negative queries the scores are relevancies against the best negative (same pass)
     heat_map         the one-scene convenience
     SearchResult     .rank_scenes(q, by=...) orders the scenes for a query; .find_objects(grid, thresholds) groups the
                      heat-map into ranked objects (openscene_amd.objects)
 
-Kernels: csrc/search.hip through ops.bank_append / ops.bank_search and their _fp8 twins; no CPU path.
+Kernels: csrc/search.hip through ops.bank_append / ops.bank_search and their _fp8 twins (osn_bank_search_contrast[_fp8]
+when negatives are given); no CPU path.
 """
 import numpy as np
 import torch
@@ -257,15 +259,19 @@ class FeatureBank:
 class SearchResult:
     """topk_scores fp16 [S, Q, k], topk_points int64 [S, Q, k] (row inside its scene; -1 with score -inf pads a scene
     of fewer than k points), counts int64 [S, Q] or None (points with score >= the query's threshold), heat fp16 [N, Q]
-    or None, names (the bank's scene names), offsets."""
+    or None, names (the bank's scene names), offsets.  relevancy: the search was given negatives -- every score (heat,
+    topk_scores, what thresholds and counts compare) is then the relevancy in [0, 1] against the best negative at
+    `temperature` (None for a plain search), and 0.5 means "as likely as the best negative"."""
 
-    def __init__(self, names, offsets, topk_scores, topk_points, counts, heat):
+    def __init__(self, names, offsets, topk_scores, topk_points, counts, heat, relevancy=False, temperature=None):
         self.names = list(names)
         self.offsets = list(offsets)
         self.topk_scores = topk_scores
         self.topk_points = topk_points
         self.counts = counts
         self.heat = heat
+        self.relevancy = bool(relevancy)
+        self.temperature = temperature
 
     def scene_heat(self, which):
         """fp16 [n, Q] view of one scene's rows of the heat-map."""
@@ -303,7 +309,8 @@ class SearchResult:
 
     def find_objects(self, grid, thresholds, **kw):
         """The objects of this search's heat-map (openscene_amd.objects.find_objects over `grid`, a VoxelGrid of the bank's
-        points): where in every scene the matches are, how many, how large.  Needs a search with return_heat."""
+        points): where in every scene the matches are, how many, how large.  Needs a search with return_heat.  After a
+        search with negatives the thresholds are relevancies: 0.5 means "as likely as the best negative", for every query."""
         if self.heat is None:
             raise ValueError("the search was run without return_heat")
         from .objects import find_objects
@@ -311,28 +318,41 @@ class SearchResult:
         return find_objects(grid, self.heat, thresholds, **kw)
 
 
-def _queries(queries, dim, device):
+def _queries(queries, dim, device, what="queries", letter="Q"):
     if not isinstance(queries, torch.Tensor):
-        raise TypeError("queries must be a float16 tensor")
+        raise TypeError("%s must be a float16 tensor" % what)
     if queries.dtype != torch.float16:
-        raise TypeError("queries must be float16 (util/util.py:41-44 produces fp16); got %s" % queries.dtype)
+        raise TypeError("%s must be float16 (util/util.py:41-44 produces fp16); got %s" % (what, queries.dtype))
     if queries.dim() != 2 or queries.shape[1] != dim:
-        raise ValueError("queries must be [Q, %d] (got %s)" % (dim, tuple(queries.shape)))
+        raise ValueError("%s must be [%s, %d] (got %s)" % (what, letter, dim, tuple(queries.shape)))
     if queries.shape[0] < 1:
-        raise ValueError("no query given")
+        raise ValueError("no %s given" % what)
     return queries.to(device)
 
 
-def search(bank, queries, k=16, thresholds=None, normalize=True, return_heat=False):
+def search(bank, queries, k=16, thresholds=None, normalize=True, return_heat=False, negatives=None, temperature=0.1):
     """Score every point of the bank against every query and select per scene.
 
     queries fp16 [Q, dim], L2-normalised (``util/util.py:41-44``); the score is ``run/evaluate.py:305,310`` (normalize:
     ``(hf / (hf.norm(dim=-1, keepdim=True) + 1e-5)).half() @ t.t()``) or ``:291`` (``h @ t.t()``) on the stored fp16
     rows (an fp8 bank: on its stored values ``code * 2^e``).  thresholds: a number or [Q] numbers -> counts.  Selection
-    order: higher score, then lower point index; NaN below every number."""
+    order: higher score, then lower point index; NaN below every number.
+
+    negatives fp16 [M, dim], L2-normalised like the queries ("object", "things", "stuff", "texture" are the usual ones):
+    every score becomes the relevancy ``sigmoid((score - best negative score of the point) / temperature)`` -- the
+    smallest pairwise softmax of the query against a negative -- in the same pass over the bank; the heat-map, the
+    top-k, thresholds and counts are all taken on it, and a threshold of 0.5 means "as likely as the best negative"
+    for every query.  The negatives get no column of their own.  temperature: finite and > 0; the default 0.1 is an
+    interface default, not a tuned value."""
     if not isinstance(bank, FeatureBank):
         raise TypeError("bank must be a FeatureBank")
     queries = _queries(queries, bank.dim, bank.device)
+    contrast = {}
+    if negatives is not None:
+        temperature = float(temperature)
+        if not 0.0 < temperature < float("inf"):                 # (NaN fails both comparisons)
+            raise ValueError("temperature must be finite and > 0 (got %r)" % (temperature,))
+        contrast = dict(negatives=_queries(negatives, bank.dim, bank.device, "negatives", "M"), temperature=temperature)
     k = int(k)
     if not 1 <= k <= ops.BANK_MAX_K:
         raise ValueError("k must be in 1 .. %d (got %d)" % (ops.BANK_MAX_K, k))
@@ -348,14 +368,15 @@ def search(bank, queries, k=16, thresholds=None, normalize=True, return_heat=Fal
     kw = dict(k=k, thresholds=thresholds, normalize=bool(normalize), want_heat=bool(return_heat),
               max_scene_rows=max(rows) if rows else 0, err=bank._err_word())       # (the bank owns its offsets: nothing to check)
     if bank.dtype == "fp8":
-        heat, top_s, top_p, counts = ops.bank_search_fp8(bank.codes, bank.exponents, bank.offsets_tensor(), queries, **kw)
+        heat, top_s, top_p, counts = ops.bank_search_fp8(bank.codes, bank.exponents, bank.offsets_tensor(), queries, **kw, **contrast)
     else:
-        heat, top_s, top_p, counts = ops.bank_search(bank.features, bank.offsets_tensor(), queries, **kw)
-    return SearchResult(bank.names, bank.offsets, top_s, top_p, counts, heat)
+        heat, top_s, top_p, counts = ops.bank_search(bank.features, bank.offsets_tensor(), queries, **kw, **contrast)
+    return SearchResult(bank.names, bank.offsets, top_s, top_p, counts, heat, relevancy=bool(contrast),
+                        temperature=contrast.get("temperature"))
 
 
-def heat_map(features, queries, inds_reverse=None, normalize=True):
-    """fp16 [points, Q]: one scene's similarity heat-map (a bank of one scene)."""
+def heat_map(features, queries, inds_reverse=None, normalize=True, negatives=None, temperature=0.1):
+    """fp16 [points, Q]: one scene's similarity heat-map (a bank of one scene); with negatives, its relevancy map (search)."""
     bank = FeatureBank(features.shape[1], features.device, capacity_rows=(inds_reverse if inds_reverse is not None else features).shape[0])
     bank.add_scene("scene", features, inds_reverse)
-    return search(bank, queries, k=1, normalize=normalize, return_heat=True).heat
+    return search(bank, queries, k=1, normalize=normalize, return_heat=True, negatives=negatives, temperature=temperature).heat

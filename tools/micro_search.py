@@ -2,7 +2,7 @@
 the fp16 bank widened to float32, ops.cosine_query(want_scores=True), the norm and the division in torch, torch.topk per
 scene and query.  HIP events around back-to-back calls after a warm-up.
 
-    python tools/micro_search.py [iters] [--no-composed]
+    python tools/micro_search.py [iters] [--no-composed] [--contrast-only]
 
 Prints one JSON object per line:
   kind=search   per shape (scenes x rows x d x Q, k = 16): us of the whole search, of the heat pass alone (a call without
@@ -13,7 +13,14 @@ Prints one JSON object per line:
                 pass, and -- after a parity check of 2048 sampled rows against the float64 formula on the stored values
                 (abs <= 2e-3, or the tool stops) -- the fidelity against the fp16 bank: largest and rms difference of the
                 normalised scores, overlap of the per-scene top-16
-  kind=append   osn_bank_append against X[g].half() in torch; osn_bank_append_fp8 from float32 and from float16 rows"""
+  kind=append   osn_bank_append against X[g].half() in torch; osn_bank_append_fp8 from float32 and from float16 rows
+  kind=contrast search with negatives (8 scenes x 150 k x 768, 32 queries + 4 negatives, k = 16, heat returned; fp16 and fp8
+                bank) against two routes on the same build, the three timed in turn for ROUNDS rounds: plain36 = the plain
+                search with the 36 rows as queries (the same MFMA work and bank traffic, four more heat columns written);
+                torch_route = that plain search, then the relevancy formula in torch on the [N, 36] heat-map and torch.topk
+                per scene.  Per route every round's us, the minimum and the spread (max - min) / min; the ratios of the
+                minima.  Before timing, the relevancy map is held to 1 fp16 ulp of the float64 formula on the plain36
+                heat-map (or the tool stops)."""
 import json
 import os
 import sys
@@ -27,6 +34,8 @@ from openscene_amd.search import FeatureBank, search                 # noqa: E40
 ARGS = [a for a in sys.argv[1:] if not a.startswith("--")]
 ITERS = int(ARGS[0]) if ARGS else 20
 COMPOSED = "--no-composed" not in sys.argv
+CONTRAST_ONLY = "--contrast-only" in sys.argv
+ROUNDS = 5
 dev = torch.device("cuda", 0)
 HBM_PEAK = 8.0e12
 K = 16
@@ -171,6 +180,45 @@ def append():
                  hbm_share=nbytes8 / us8 * 1e6 / HBM_PEAK, rows_per_s=n / us8 * 1e6)
 
 
+def contrast():
+    scenes, n, d, q, m, tau = 8, 150_000, 768, 32, 4, 0.1
+    gen = torch.Generator(device=dev).manual_seed(3)
+    bank16 = make_bank(scenes, n, d, gen)
+    rows = torch.nn.functional.normalize(torch.randn(q + m, d, generator=gen, device=dev), dim=1).half()
+    text, neg = rows[:q].contiguous(), rows[q:].contiguous()
+    for kind, bank in (("fp16", bank16), ("fp8", bank16.to_fp8())):
+        def ours():
+            return search(bank, text, k=K, return_heat=True, negatives=neg, temperature=tau)
+
+        def plain36():
+            return search(bank, rows, k=K, return_heat=True)
+
+        def torch_route():
+            heat = plain36().heat.float()
+            rel = torch.sigmoid((heat[:, :q] - heat[:, q:].max(dim=1, keepdim=True)[0]) / tau).half()
+            return rel, [torch.topk(rel[a:b].t().float(), min(K, b - a), dim=1) for a, b in zip(bank.offsets[:-1], bank.offsets[1:])]
+        heat = plain36().heat[::97].double()                   # parity on every 97th row
+        z = (heat[:, :q] - heat[:, q:].max(dim=1, keepdim=True)[0]) / float(torch.tensor(tau, dtype=torch.float32))
+        want = (1.0 / (1.0 + torch.exp(-z))).cpu().numpy().astype("float16")
+        got = ours().heat[::97].cpu().numpy()
+        ok = (got == got) == (want == want)
+        ulps = abs(got.view("int16").astype("int64") - want.view("int16").astype("int64"))[got == got]
+        if not ok.all() or ulps.max() > 1:
+            raise SystemExit("relevancy map is off the float64 formula by %d ulp" % ulps.max())
+        us = {"contrast": [], "plain36": [], "torch_route": []}
+        for _ in range(ROUNDS):                                # A B C A B C: shows the spread
+            us["contrast"].append(timed(ours))
+            us["plain36"].append(timed(plain36))
+            us["torch_route"].append(timed(torch_route, iters=max(3, ITERS // 4), warmup=1))
+        lo = {k_: min(v) for k_, v in us.items()}
+        emit(kind="contrast", bank=kind, scenes=scenes, rows_per_scene=n, d=d, q=q, m=m, k=K, temperature=tau, iters=ITERS,
+             us=us, us_min=lo, spread={k_: (max(v) - min(v)) / min(v) for k_, v in us.items()},
+             contrast_over_plain36=lo["contrast"] / lo["plain36"], torch_route_over_contrast=lo["torch_route"] / lo["contrast"],
+             parity_max_ulp=int(ulps.max()), parity_share_differing=float((ulps != 0).mean()))
+
+
 if __name__ == "__main__":
-    shapes()
-    append()
+    if not CONTRAST_ONLY:
+        shapes()
+        append()
+    contrast()
