@@ -502,7 +502,16 @@ int osn_cat2_bwd(const float* gout, float* ga, int ca, float* gb, int cb, int64_
  *   pred = feats[inds_reverse].half() @ text.t();  label = argmax(pred, 1)
  * X float32 [n_rows_x, d]; gather (nullable) int64 [n]; text fp16 [c, d];
  * scores (nullable) fp16 [n, c]; argmax int64 [n].  fp16 MFMA, fp32 accumulate,
- * one rounding to fp16; argmax over the rounded scores, lowest index on ties.    */
+ * one rounding to fp16.  The contract (tests/query_bounds.py holds every kernel to it):
+ *   Scores.  xh = fp16_rne(x) is the reference's .half() (overflow becomes +-inf);
+ *   S = sum_k xh_k t_k and A = sum_k |xh_k| |t_k| in float64.  Every fp16 score satisfies
+ *       fp16_rne(S - c A)  <=  score  <=  fp16_rne(S + c A),      c = 2e-6,
+ *   float64 rounded to fp16 in one step; where the two ends are +-inf or NaN the score
+ *   is that value.
+ *   Labels.  label = torch.max(scores, 1)[1] of the kernel's OWN fp16 scores on every
+ *   row: the first NaN wins, otherwise the lowest column among equal maxima
+ *   (-0.0 == +0.0); the same label with and without the score matrix.
+ * osn_rows_argmax obeys the same label rule on its float32 scores.                   */
 int osn_cosine_query(const float* X, const int64_t* gather, const void* text_f16,
                      void* scores_f16, int64_t* argmax, int64_t n, int d, int c,
                      osn_stream_t stream);
@@ -513,7 +522,7 @@ int osn_cosine_query(const float* X, const int64_t* gather, const void* text_f16
  * voxel features with inds_reverse while the fused features are already per point.
  * sel (nullable) uint8 [n] = 1 where the fusion feature was selected.            */
 /* labels[p] = argmax over the first c columns of row (gather ? gather[p] : p) of a float32 score matrix with row stride ld
- * (first maximum wins): `torch.max(pred, 1)[1]` of run/evaluate.py:292 fused with the point -> voxel gather `[inds_reverse]`,
+ * (the first NaN wins, otherwise the first maximum): `torch.max(pred, 1)[1]` of run/evaluate.py:292 fused with the point -> voxel gather `[inds_reverse]`,
  * for scores that exist per VOXEL (the fused-head query).  Indices outside [0, n_rows) read row 0.  */
 int osn_rows_argmax(const float* scores, int64_t ld, int c, const int64_t* gather, int64_t n_pts, int64_t n_rows,
                     int64_t* labels, osn_stream_t stream);

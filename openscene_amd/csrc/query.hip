@@ -8,6 +8,17 @@
 // matrix (<= 246 KB) stays L2-resident.  MFMA is used because this IS a dense
 // contraction: v_mfma_f32_32x32x16_f16, A = 32 point rows x 16 k, B = text rows
 // (text is [C, D] row-major = the K-contiguous B operand, no transpose needed).
+//
+// The contract (tests/query_bounds.py; include/openscene_amd.h beside osn_cosine_query), the same for query_kernel and
+// query_wide_kernel, with and without the gather, the ensemble's source selection and the vote epilogue:
+//   Scores.  xh = fp16_rne(x) is the reference's .half() (overflow becomes +-inf); S = sum_k xh_k t_k and
+//   A = sum_k |xh_k| |t_k| in float64.  Every fp16 score the kernel writes satisfies
+//       fp16_rne(S - c A)  <=  score  <=  fp16_rne(S + c A),      c = 2e-6,
+//   float64 rounded to fp16 in one step; where the interval's two ends are +-inf or NaN the score is that value.
+//   Labels.  label = torch.max(scores, 1)[1] applied to the kernel's OWN fp16 scores, on every row: the first NaN wins,
+//   otherwise the lowest column among equal maxima (-0.0 == +0.0).  A labels-only call returns the same labels.
+//   rows_argmax_kernel obeys the same label rule on fp32 scores.  (A NaN score is not exotic: a feature above 65504 is inf
+//   as fp16, and against a text row of mixed sign the fp32 accumulation yields inf - inf.)
 #include "common.h"
 #include <atomic>
 #include <type_traits>
@@ -25,6 +36,14 @@ constexpr int Q_LD = Q_DK + 8;  // padded LDS row (144 B: 16-B aligned, conflict
 // Test-repeat vote (run/evaluate.py:397,416  `store = pred + store` on CPU fp16 tensors): torch adds two halves in fp32 and
 // rounds the sum to half once (round to nearest even).  Each (point, label) cell has one owner thread: no atomics.
 __device__ inline void vote_add(_Float16& cell, _Float16 s) { cell = (_Float16)((float)cell + (float)s); }
+
+// The label rule (torch.max(scores, 1)[1] on the CPU, the header above): the first NaN wins; otherwise the largest value, the
+// lowest column among equal ones (-0.0 == +0.0).  Does (v, column i) beat the running best (bv, bi)?
+__device__ inline bool q_better(float v, int i, float bv, int bi) {
+    const bool vn = v != v, bn = bv != bv;
+    if (vn || bn) return vn && (!bn || i < bi);
+    return v > bv || (v == bv && i < bi);
+}
 
 // sources: point p reads row g0[p] of X0 (or p if g0 null); if sel && sel[p], row g1[p] of X1.
 // NBUF chunks of point rows (and of the text) in flight per thread, WGS workgroups per CU (register budget 512 / WGS).
@@ -195,7 +214,7 @@ __global__ __launch_bounds__(256, WGS) void query_kernel(const float* __restrict
                         if constexpr (VOTE) vote_add(scores[row * c + col], hv);
                         else scores[row * c + col] = hv;
                     }
-                    if (v > bestv[r] || (v == bestv[r] && col < besti[r])) { bestv[r] = v; besti[r] = col; }
+                    if (q_better(v, col, bestv[r], besti[r])) { bestv[r] = v; besti[r] = col; }
                 }
             }
         }
@@ -208,13 +227,13 @@ __global__ __launch_bounds__(256, WGS) void query_kernel(const float* __restrict
             for (int m = 1; m < 32; m <<= 1) {
                 const float ov = __shfl_xor(v, m, 64);
                 const int oi = __shfl_xor(i, m, 64);
-                if (ov > v || (ov == v && oi < i)) { v = ov; i = oi; }
+                if (q_better(ov, oi, v, i)) { v = ov; i = oi; }
             }
             if ((lane & 31) == 0) {
                 const int lrow = wave * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                 const float pv = bestv_s[lrow];
                 const int pi = besti_s[lrow];
-                if (v > pv || (v == pv && i < pi)) { bestv_s[lrow] = v; besti_s[lrow] = i; }
+                if (q_better(v, i, pv, pi)) { bestv_s[lrow] = v; besti_s[lrow] = i; }
             }
         }
     }
@@ -321,28 +340,40 @@ __global__ __launch_bounds__(512, 1) void query_wide_kernel(const float* __restr
             // through ds_bpermute: 160 per tile and wave, half the kernel's time.)
             const int col = 32 * wave + (lane & 31);
             _Float16* dst = sc + size_t(i & 1) * QW_TP * LS + col;
+            // NaN (an overflowed feature gives inf - inf): torch.max returns the FIRST NaN of a row, but the bit order below puts a
+            // positive NaN above +inf at its payload's place and a negative one below -inf.  Every NaN therefore becomes the top key
+            // 0x7FFF (its complemented label then picks the lowest NaN column) -- off the per-score path: an fp16 NaN comes from an
+            // fp32 NaN only, eight unordered compares per tile find out whether this wave holds one, and only such a tile (none, on
+            // finite features) runs the epilogue that canonicalises.
+            bool nan_l = false;
 #pragma unroll
-            for (int r = 0; r < 16; ++r) {
-                const int lrow = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                const _Float16 hv = (_Float16)acc[r];
-                if (scores) dst[lrow * LS] = hv;
-                // torch.max compares VALUES: -0.0 == +0.0 (the lower label wins the tie), so -0 is made +0 before the bits are ordered.
-                // NaN: the bit order puts a positive NaN above every number and a negative one below -- torch.max would return the
-                // first NaN; scores here are cosine products of finite features, a NaN score means NaN input rows (documented in
-                // labels of such points are unspecified in both kernels).
-                uint32_t hb = uint32_t(__builtin_bit_cast(uint16_t, hv));
-                hb = hb == 0x8000u ? 0u : hb;
-                const uint32_t ord = (hb & 0x8000u) ? (~hb & 0xFFFFu) : (hb | 0x8000u);
-                uint32_t key = col < c ? ((ord << 16) | (0xFFFFu - uint32_t(col))) : 0u;
+            for (int r = 0; r < 16; r += 2) nan_l |= __builtin_isunordered(acc[r], acc[r + 1]);
+            const bool nan_tile = __builtin_amdgcn_ballot_w64(nan_l) != 0;       // wave-uniform
+            auto epilogue = [&](auto canon_c) {
+                constexpr bool CANON_NAN = decltype(canon_c)::value;
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int lrow = (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+                    const _Float16 hv = (_Float16)acc[r];
+                    if (scores) dst[lrow * LS] = hv;
+                    // torch.max compares VALUES: -0.0 == +0.0 (the lower label wins the tie), so -0 is made +0 before the bits are ordered.
+                    uint32_t hb = uint32_t(__builtin_bit_cast(uint16_t, hv));
+                    hb = hb == 0x8000u ? 0u : hb;
+                    if constexpr (CANON_NAN) hb = (hb & 0x7FFFu) > 0x7C00u ? 0x7FFFu : hb;
+                    const uint32_t ord = (hb & 0x8000u) ? (~hb & 0xFFFFu) : (hb | 0x8000u);
+                    uint32_t key = col < c ? ((ord << 16) | (0xFFFFu - uint32_t(col))) : 0u;
 #define QW_ROR(K_) key = max(key, uint32_t(__builtin_amdgcn_update_dpp(0, int(key), 0x120 + (K_), 0xF, 0xF, false)));
-                QW_ROR(8) QW_ROR(4) QW_ROR(2) QW_ROR(1)
+                    QW_ROR(8) QW_ROR(4) QW_ROR(2) QW_ROR(1)
 #undef QW_ROR
-                // lane 15 of rows 0 / 2 into rows 1 / 3 (row_bcast15, rows 1 and 3 written): lanes 16 .. 31 and 48 .. 63 then hold the
-                // maximum of their 32-lane half
-                const uint32_t up = uint32_t(__builtin_amdgcn_update_dpp(int(key), int(key), 0x142, 0xA, 0xF, false));
-                key = max(key, up);
-                if ((lane & 31) == 31) mkey[i & 1][wave][lrow] = key;
-            }
+                    // lane 15 of rows 0 / 2 into rows 1 / 3 (row_bcast15, rows 1 and 3 written): lanes 16 .. 31 and 48 .. 63 then hold the
+                    // maximum of their 32-lane half
+                    const uint32_t up = uint32_t(__builtin_amdgcn_update_dpp(int(key), int(key), 0x142, 0xA, 0xF, false));
+                    key = max(key, up);
+                    if ((lane & 31) == 31) mkey[i & 1][wave][lrow] = key;
+                }
+            };
+            if (nan_tile) epilogue(std::true_type());
+            else epilogue(std::false_type());
         }
         __syncthreads();                                                 // (the producers' last merge)
     } else {
@@ -518,13 +549,13 @@ __global__ __launch_bounds__(256) void rows_argmax_kernel(const float* __restric
     int bi = 0x7fffffff;
     for (int col = lane; col < c; col += 64) {
         const float v = row[col];
-        if (v > bv || (v == bv && col < bi) || bi == 0x7fffffff) { bv = v; bi = col; }
+        if (q_better(v, col, bv, bi)) { bv = v; bi = col; }
     }
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) {
         const float ov = __shfl_xor(bv, m, 64);
         const int oi = __shfl_xor(bi, m, 64);
-        if (oi != 0x7fffffff && (bi == 0x7fffffff || ov > bv || (ov == bv && oi < bi))) { bv = ov; bi = oi; }
+        if (q_better(ov, oi, bv, bi)) { bv = ov; bi = oi; }     // (a lane without a column holds (-inf, INT_MAX): it never wins)
     }
     if (lane == 0) labels[p] = bi == 0x7fffffff ? 0 : bi;
 }
