@@ -725,6 +725,48 @@ int osn_objects_find(const void* heat_f16, const float* xyz, int64_t n, int q, c
                      int64_t* out_n_objects, int32_t* point_object, const void* ws, size_t ws_bytes, void* records,
                      size_t records_bytes, osn_stream_t stream);
 
+/* ---- regions without a prompt (csrc/regions.hip) ---------------------------------------------------------------- *
+ * README "Applications": "open-vocabulary 3D scene understanding and exploration" -- materials, affordances, room type,
+ * "what is in this room?" -- needs a partition of a scene that exists before anyone has typed a word and serves every
+ * later prompt.  A region is a connected component of the graph over the voxels whose edges are the pairs of neighbouring
+ * voxels (3^3 self-map; 26 or 6 neighbours) with agreeing features: single linkage.  All three calls OR their error bits
+ * into the device word err (int32 [1], zeroed by the caller): 1 = a neighbour row outside [-1, n_voxels), 2 = a point's
+ * voxel row outside [0, n_voxels), 4 = a region entry outside [-1, n_regions).  Such entries are skipped, never
+ * dereferenced.  All three are asynchronous and need no workspace.
+ *
+ * osn_regions_edges (the hot path): vox fp16 [n_voxels, d] (device, 16-byte aligned), d % 8 == 0, 8 <= d <=
+ *   OSN_BANK_POOL_MAX_DIM; nbr int32 [27, n_voxels] (osn_kmap_build_self, ksize 3); connectivity 26 or 6.
+ *   sim float32 [n_off, n_voxels]: n_off = 13 for connectivity 26 -- the offsets below the centre, k = 0 .. 12 -- and 3 for
+ *   connectivity 6 -- k = 4, 10, 12 (-z, -y, -x), in that order.  With u = nbr[k_i, v]:
+ *       sim[i, v] = sum over c of float(vox[v, c]) * float(vox[u, c]),  accumulated in fp32
+ *   No division: the caller supplies unit rows.  An absent neighbour (u < 0) gives -inf; u >= n_voxels gives -inf and ORs
+ *   bit 1; a NaN anywhere in either row gives NaN.  The self-map is its own mirror, so every undirected edge is computed
+ *   once.  A product of two fp16 values is exact in fp32, so only the additions round; their order is fixed (a lane adds
+ *   the products of its 16-byte vectors in element order, the lanes of the wave are added by an xor butterfly): no
+ *   floating-point atomics, two calls give the same bits.  fp16 subnormals enter with their value.
+ *
+ * osn_regions_label: voxels v and u = nbr[k_i, v] are united iff u is a valid row and sim[i, v] >= threshold (a float32
+ *   comparison; threshold finite; NaN and -inf never unite), with the union-find of osn_objects_label: larger root under
+ *   smaller, compare-and-swap, path halving, a flatten launch after the unite launch.  voxel_root int32 [n_voxels]:
+ *   the smallest voxel row of v's component -- a canonical labelling that does not depend on scheduling.  Every voxel
+ *   belongs to exactly one component; a voxel without an accepted edge is its own.
+ *
+ * osn_regions_records: voxel_region int32 [n_voxels] with values in -1 .. n_regions - 1 (-1: in no region); xyz float32
+ *   [n, 3], inverse int32 [n] (point -> voxel row), coords4 int32 [n_voxels, 4] (scene, x, y, z; 16-byte aligned).  Per
+ *   region, with integer atomics only (exact, bitwise repeatable): n_points int64, n_voxels int64, vox_sum int64 [.., 3]
+ *   = the sum over the region's POINTS of their voxel's (x, y, z) (as in osn_objects_find), box_min / box_max float32
+ *   [.., 3] over the points' xyz through order-preserving integer min / max (a region without points: zeros), scene
+ *   int32 = the scene column of the region's smallest voxel row (-1: a region without voxels).  Points whose voxel has
+ *   region -1 are counted nowhere.                                                                                   */
+int osn_regions_edges(const void* vox_f16, int64_t n_voxels, int d, const int32_t* nbr, int connectivity, float* sim,
+                      int32_t* err, osn_stream_t stream);
+int osn_regions_label(const float* sim, const int32_t* nbr, int64_t n_voxels, int connectivity, float threshold,
+                      int32_t* voxel_root, int32_t* err, osn_stream_t stream);
+int osn_regions_records(const int32_t* voxel_region, int64_t n_voxels, int64_t n_regions, const float* xyz,
+                        const int32_t* inverse, int64_t n, const int32_t* coords4, int64_t* n_points,
+                        int64_t* n_voxels_out, int64_t* vox_sum, float* box_min, float* box_max, int32_t* scene,
+                        int32_t* err, osn_stream_t stream);
+
 /* ---- hash voxelisation --------------------------------------------------- *
  * Replaces Voxelizer.voxelize (dataset/voxelizer.py:117-129) +
  * sparse_quantize / fnv_hash_vec (dataset/voxelization_utils.py:9-22,112-132):

@@ -12,6 +12,7 @@ Python surface (mirrors the reference's own, file:line in each module):
     openscene_amd.search           README "Applications": a bank of scenes searched by text or image embedding
     openscene_amd.objects          the same, as objects: connected components of a heat-map, ranked per scene
     openscene_amd.descriptors      and back: scenes, objects and regions of the bank as descriptors (the next query)
+    openscene_amd.regions          scenes cut into regions of agreeing features before any prompt: label, list, query by region
     install_minkowski_alias()      make `import MinkowskiEngine` resolve to openscene_amd.minkowski
 
 There is no CPU fallback: every op raises if libopenscene_amd.so is missing or
@@ -68,6 +69,12 @@ def describe_scenes(bank, normalize=True):
     """One descriptor per scene of a FeatureBank (openscene_amd.descriptors.describe_scenes)."""
     from .descriptors import describe_scenes as f
     return f(bank, normalize=normalize)
+
+
+def segment(bank, grid, similarity=0.9, min_points=1, names=None):
+    """Regions of a grid's scenes by feature similarity of neighbouring voxels, no prompt needed (openscene_amd.regions.segment)."""
+    from .regions import segment as f
+    return f(bank, grid, similarity=similarity, min_points=min_points, names=names)
 
 
 def install_minkowski_alias(force=False, accelerate=True):

@@ -26,6 +26,7 @@
 // Integer atomics only: count, 2^24 fixed-point int64 score sum, (score key, ~point) 64-bit max, order-preserving
 // uint32 min / max of the float box, int64 voxel sums.  Sums of integers and min / max do not depend on order.
 #include "common.h"
+#include "uf.h"              // ld_agent, uf_find, uf_unite, f2o, o2f: shared with regions.hip
 
 namespace osn {
 
@@ -47,17 +48,6 @@ __device__ inline bool obj_hit(uint16_t hb, float th) {
     if ((hb & 0x7C00u) == 0x7C00u) return false;            // NaN, +inf, -inf
     return (float)__builtin_bit_cast(_Float16, hb) >= th;
 }
-// order-preserving uint32 of a float (and back)
-__device__ inline uint32_t f2o(float f) {
-    const uint32_t b = __builtin_bit_cast(uint32_t, f);
-    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-__device__ inline float o2f(uint32_t o) {
-    const uint32_t b = (o & 0x80000000u) ? (o & 0x7FFFFFFFu) : ~o;
-    return __builtin_bit_cast(float, b);
-}
-
-__device__ inline int ld_agent(const int32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 
 // ------------------------------------------------------------------------------------------------------ checks
 __global__ void objects_check_kernel(const int64_t* __restrict__ off, int S, int64_t n, int32_t* __restrict__ err) {
@@ -84,29 +74,6 @@ __global__ __launch_bounds__(OBJ_T) void objects_activate_kernel(const uint16_t*
 }
 
 // ------------------------------------------------------------------------------------------------------ label
-__device__ inline int uf_find(int32_t* L, int x) {
-    int p = ld_agent(L + x);
-    while (p != x) {
-        const int g = ld_agent(L + p);                       // g <= p < x
-        if (g != p) __hip_atomic_store(L + x, g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // path halving: still an ancestor
-        x = p;
-        p = g;
-    }
-    return x;
-}
-
-__device__ inline void uf_unite(int32_t* L, int a, int b) {
-    while (true) {
-        a = uf_find(L, a);
-        b = uf_find(L, b);
-        if (a == b) return;
-        if (a < b) { const int t = a; a = b; b = t; }        // hook the larger root a under the smaller b
-        const int old = atomicCAS(L + a, a, b);
-        if (old == a) return;
-        a = old;                                             // a had been hooked meanwhile: go on from its parent
-    }
-}
-
 // offsets below the centre of the 3^3 map, k = ix + 3 iy + 9 iz; the three faces among them: -z = 4, -y = 10, -x = 12
 __device__ inline int obj_face(int i) { return i == 0 ? 4 : i == 1 ? 10 : 12; }
 

@@ -1666,6 +1666,138 @@ def objects_find(heat, thresholds, xyz, inverse, coords4, nbr, scene_offsets, co
     return out
 
 
+# --------------------------------------------------------------------- regions
+REGIONS_E_NBR, REGIONS_E_INVERSE, REGIONS_E_REGION = 1, 2, 4      # the bits of the regions' err word (csrc/regions.hip)
+
+
+def regions_n_off(connectivity):
+    """Rows of a `sim` array: the offsets below the centre of the 3^3 map (13), or the three faces among them."""
+    if connectivity not in (6, 26):
+        raise ValueError("connectivity must be 6 or 26 (got %r)" % (connectivity,))
+    return 13 if connectivity == 26 else 3
+
+
+def regions_check(err):
+    """Raise if a regions call recorded an entry out of range in `err` (int32 [1]); zeroes the word.  Synchronises."""
+    bits = int(err.item())
+    if bits == 0:
+        return
+    err.zero_()
+    what = [text for bit, text in ((REGIONS_E_NBR, "a neighbour row outside [-1, n_voxels)"),
+                                   (REGIONS_E_INVERSE, "a point's voxel row outside [0, n_voxels)"),
+                                   (REGIONS_E_REGION, "a region entry outside [-1, n_regions)")) if bits & bit]
+    raise _lib.OpenSceneAmdError("regions: %s (err bits %d); such entries were skipped" % ("; ".join(what) or "unknown error", bits))
+
+
+def _regions_err(err, dev):
+    if err is None:
+        return torch.zeros(1, dtype=torch.int32, device=dev), True
+    if not isinstance(err, torch.Tensor) or err.dtype != torch.int32 or err.numel() != 1 or err.device != dev:
+        raise ValueError("err must be an int32 [1] tensor on the inputs' device")
+    return err, False
+
+
+def _regions_nbr(nbr, v, dev):
+    if not isinstance(nbr, torch.Tensor) or nbr.dtype != torch.int32 or tuple(nbr.shape) != (27, v) or nbr.device != dev \
+            or not nbr.is_contiguous():
+        raise ValueError("nbr must be a contiguous int32 [27, %d] table on the rows' device" % v)
+
+
+def regions_edges(vox, nbr, connectivity=26, err=None):
+    """sim float32 [n_off, V]: the fp32 dot product of every voxel row with its neighbours below the centre of the 3^3 map
+    (n_off = 13: k = 0 .. 12; connectivity 6: k = 4, 10, 12), every undirected edge once.  vox fp16 [V, d] unit rows,
+    d % 8 == 0, 8 <= d <= BANK_POOL_MAX_DIM; nbr int32 [27, V] = kmap_build(..., 3, 1, self_map=True).  An absent
+    neighbour gives -inf, a NaN in either row NaN.  Fixed order of additions: bitwise repeatable.  A neighbour row >= V is
+    skipped and recorded in `err` when one is given (regions_check raises), and checked here otherwise."""
+    if not isinstance(vox, torch.Tensor) or vox.dtype != torch.float16:
+        raise TypeError("vox must be a float16 tensor")
+    dev = vox.device
+    lib = _prep(dev)
+    if vox.dim() != 2 or not vox.is_contiguous():
+        raise ValueError("vox must be a contiguous [voxels, dim] matrix")
+    v, d = vox.shape
+    if d < 8 or d % 8:
+        raise ValueError("the feature dim must be a multiple of 8 (got %d)" % d)
+    if d > BANK_POOL_MAX_DIM:
+        raise ValueError("the feature dim must be at most %d (got %d)" % (BANK_POOL_MAX_DIM, d))
+    n_off = regions_n_off(connectivity)
+    _regions_nbr(nbr, v, dev)
+    err, own = _regions_err(err, dev)
+    sim = torch.empty((n_off, v), dtype=torch.float32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_regions_edges(_p(vox), v, d, _p(nbr), int(connectivity), _p(sim), _p(err), _stream(dev)), "osn_regions_edges")
+    if own and v > 0:
+        regions_check(err)
+    return sim
+
+
+def regions_label(sim, nbr, connectivity=26, threshold=0.9, err=None):
+    """voxel_root int32 [V]: the smallest voxel row of every voxel's component in the graph whose edges are the neighbour
+    pairs with sim >= threshold (float32; NaN and -inf never unite).  sim float32 [n_off, V] (regions_edges), nbr its
+    table.  The labelling is canonical: it does not depend on scheduling.  `err` as regions_edges."""
+    if not isinstance(sim, torch.Tensor) or sim.dtype != torch.float32:
+        raise TypeError("sim must be a float32 tensor")
+    dev = sim.device
+    lib = _prep(dev)
+    n_off = regions_n_off(connectivity)
+    if sim.dim() != 2 or sim.shape[0] != n_off or not sim.is_contiguous():
+        raise ValueError("sim must be a contiguous float32 [%d, V] matrix for connectivity %d" % (n_off, connectivity))
+    v = sim.shape[1]
+    _regions_nbr(nbr, v, dev)
+    threshold = float(threshold)
+    if threshold != threshold or threshold in (float("inf"), float("-inf")):
+        raise ValueError("the threshold must be finite (got %r)" % (threshold,))
+    err, own = _regions_err(err, dev)
+    root = torch.empty(v, dtype=torch.int32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_regions_label(_p(sim), _p(nbr), v, int(connectivity), threshold, _p(root), _p(err), _stream(dev)),
+              "osn_regions_label")
+    if own and v > 0:
+        regions_check(err)
+    return root
+
+
+def regions_records(voxel_region, n_regions, xyz, inverse, coords4, err=None):
+    """Exact records of the regions of a labelling.  voxel_region int32 [V] in -1 .. R - 1; xyz float32 [N, 3]; inverse
+    int32 [N] (point -> voxel row); coords4 int32 [V, 4] (scene, x, y, z).
+    -> dict: n_points, n_voxels int64 [R]; vox_sum int64 [R, 3] (over the points, of their voxel's cell); box_min / box_max
+       float32 [R, 3]; scene int32 [R].  Integer atomics only: bitwise repeatable.  Points of voxels with region -1 are
+    counted nowhere.  An entry out of range is skipped and recorded in `err` (as regions_edges)."""
+    if not isinstance(voxel_region, torch.Tensor) or voxel_region.dtype != torch.int32:
+        raise TypeError("voxel_region must be an int32 tensor")
+    dev = voxel_region.device
+    lib = _prep(dev)
+    if voxel_region.dim() != 1 or not voxel_region.is_contiguous():
+        raise ValueError("voxel_region must be a contiguous int32 [V] vector")
+    v = voxel_region.shape[0]
+    r = int(n_regions)
+    if not 0 <= r <= v:
+        raise ValueError("n_regions must lie in 0 .. %d (got %d)" % (v, r))
+    if xyz.dtype != torch.float32 or xyz.dim() != 2 or xyz.shape[1] != 3 or xyz.device != dev or not xyz.is_contiguous():
+        raise ValueError("xyz must be a contiguous float32 [N, 3] matrix on the labelling's device")
+    n = xyz.shape[0]
+    if inverse.dtype != torch.int32 or tuple(inverse.shape) != (n,) or inverse.device != dev or not inverse.is_contiguous():
+        raise ValueError("inverse must be a contiguous int32 [%d] vector on the labelling's device" % n)
+    if coords4.dtype != torch.int32 or tuple(coords4.shape) != (v, 4) or coords4.device != dev or not coords4.is_contiguous():
+        raise ValueError("coords4 must be contiguous int32 [%d, 4] rows on the labelling's device" % v)
+    err, own = _regions_err(err, dev)
+    out = {
+        "n_points": torch.empty(r, dtype=torch.int64, device=dev),
+        "n_voxels": torch.empty(r, dtype=torch.int64, device=dev),
+        "vox_sum": torch.empty((r, 3), dtype=torch.int64, device=dev),
+        "box_min": torch.empty((r, 3), dtype=torch.float32, device=dev),
+        "box_max": torch.empty((r, 3), dtype=torch.float32, device=dev),
+        "scene": torch.empty(r, dtype=torch.int32, device=dev),
+    }
+    with _Dev(dev):
+        check(lib.osn_regions_records(_p(voxel_region), v, r, _p(xyz), _p(inverse), n, _p(coords4), _p(out["n_points"]),
+                                      _p(out["n_voxels"]), _p(out["vox_sum"]), _p(out["box_min"]), _p(out["box_max"]),
+                                      _p(out["scene"]), _p(err), _stream(dev)), "osn_regions_records")
+    if own and (v > 0 or n > 0):
+        regions_check(err)
+    return out
+
+
 # ------------------------------------------------------------------- voxelizer
 def voxelize_fnv(xyz, T):
     """xyz float64 [N,3] (device), T 4x4 float64 (host, numpy or tensor) ->
