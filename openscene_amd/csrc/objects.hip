@@ -21,23 +21,18 @@
 //
 // Reduce.  A workgroup stages 256 heat rows x 32 queries through LDS (the rows are read coalesced along Q), then a lane
 // owns one point and walks the queries, so the 64 lanes of a wave hold 64 CONSECUTIVE points of ONE query -- neighbours in
-// the scan, usually on the same object.  Lanes that target the same record are combined by a butterfly before ONE lane
-// issues the atomics (a floor puts tens of thousands of hits on one record: 13 same-address atomics per hit otherwise).
-// Integer atomics only: count, 2^24 fixed-point int64 score sum, (score key, ~point) 64-bit max, order-preserving
-// uint32 min / max of the float box, int64 voxel sums.  Sums of integers and min / max do not depend on order.
-#include "common.h"
-#include "uf.h"              // ld_agent, uf_find, uf_unite, f2o, o2f: shared with regions.hip
+// the scan, usually on the same object.  Lanes that target the same record are combined before ONE lane issues the atomics
+// (components.h: wave_combine, its all-lanes contract and why the records are the same bits on every call).  Integer atomics
+// only: count, 2^24 fixed-point int64 score sum, (score key, ~point) 64-bit max, and the voxel sums and box of BoxVox.
+#include "components.h"      // the union-find, BoxVox and wave_combine: shared with regions.hip
 
 namespace osn {
 
 constexpr int OBJ_E_INVERSE = 1, OBJ_E_SCENE = 2, OBJ_E_OFFSETS = 4, OBJ_E_NBR = 8;
-constexpr int OBJ_T = 256;          // threads of a workgroup
+constexpr int OBJ_T = COMPONENTS_T;
 constexpr int OBJ_QC = 32;          // queries of a staged tile
 constexpr int OBJ_LD = OBJ_QC + 2;  // halfs per staged row: 17 words, odd -> lanes one row apart hit different banks
-constexpr int OBJ_COMBINE_MIN = 4;  // lanes on one record from which the butterfly beats their own atomics
 constexpr int OBJ_MAX_M = 64;
-
-typedef unsigned long long u64;
 
 // monotone key of a finite fp16 score (-0 -> +0: equal values tie on the point, as search.hip)
 __device__ inline uint32_t obj_key(uint16_t hb) {
@@ -74,9 +69,6 @@ __global__ __launch_bounds__(OBJ_T) void objects_activate_kernel(const uint16_t*
 }
 
 // ------------------------------------------------------------------------------------------------------ label
-// offsets below the centre of the 3^3 map, k = ix + 3 iy + 9 iz; the three faces among them: -z = 4, -y = 10, -x = 12
-__device__ inline int obj_face(int i) { return i == 0 ? 4 : i == 1 ? 10 : 12; }
-
 __global__ __launch_bounds__(OBJ_T) void objects_unite_kernel(int32_t* label, const int32_t* __restrict__ nbr, int64_t V,
                                                               int Q, int conn, int32_t* __restrict__ err) {
     const int64_t total = int64_t(Q) * V;
@@ -87,7 +79,7 @@ __global__ __launch_bounds__(OBJ_T) void objects_unite_kernel(int32_t* label, co
         int32_t* L = label + int64_t(q) * V;
         if (L[v] < 0) continue;                              // (active words stay >= 0 for good: a plain load will do)
         for (int i = 0; i < n_off; ++i) {
-            const int k = conn == 26 ? i : obj_face(i);
+            const int k = conn == 26 ? i : face_offset(i);
             const int u = nbr[int64_t(k) * V + v];
             if (u < 0) continue;
             if (u >= V) { atomicOr(err, OBJ_E_NBR); continue; }
@@ -104,14 +96,7 @@ __global__ __launch_bounds__(OBJ_T) void objects_flatten_kernel(int32_t* label, 
         const int q = int(e / V);
         const int v = int(e - int64_t(q) * V);
         int32_t* L = label + int64_t(q) * V;
-        int x = L[v];
-        if (x < 0) continue;
-        while (true) {                                       // (parents only move towards the root while others flatten)
-            const int p = ld_agent(L + x);
-            if (p == x) break;
-            x = p;
-        }
-        if (x != v) __hip_atomic_store(L + v, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (L[v] >= 0) uf_flatten(L, v);
     }
 }
 
@@ -164,7 +149,7 @@ struct Records {                    // one array per field, C entries each
     u64* score_sum;                 // two's complement int64
     u64* peak;                      // (score key << 32) | ~point
     u64* vox_sum;                   // [3][C]
-    uint32_t* box;                  // [6][C]: min x y z (preset ~0), max x y z (preset 0), order-preserving
+    uint32_t* box;                  // [6][C]: min x y z, max x y z, order-preserving
     int32_t* rank;                  // place among the kept objects of its item, or -1
 };
 constexpr size_t OBJ_REC_BYTES = 4 + 4 + 8 + 8 + 24 + 24 + 4;
@@ -183,12 +168,13 @@ static Records records_at(void* base, int64_t c) {
     r.rank = reinterpret_cast<int32_t*>(p);
     return r;
 }
+__device__ inline BoxArrays box_arrays(const Records& R, int64_t C) { return {R.vox_sum, R.box, R.box + 3 * C, C, 1}; }
 
 __global__ void objects_preset_kernel(Records R, int64_t C) {
     const int64_t c = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (c >= C) return;
     R.n_points[c] = 0; R.n_voxels[c] = 0; R.score_sum[c] = 0; R.peak[c] = 0; R.rank[c] = -1;
-    for (int j = 0; j < 3; ++j) { R.vox_sum[j * C + c] = 0; R.box[j * C + c] = 0xFFFFFFFFu; R.box[(3 + j) * C + c] = 0u; }
+    BoxVox::preset(box_arrays(R, C), c);
 }
 
 // component of the active word (q, v), or -1
@@ -218,10 +204,18 @@ __global__ __launch_bounds__(OBJ_T) void objects_voxels_kernel(const int32_t* __
     }
 }
 
-__device__ inline u64 shfl_xor_u64(u64 v, int m) {
-    const uint32_t lo = __shfl_xor(uint32_t(v), m, 64), hi = __shfl_xor(uint32_t(v >> 32), m, 64);
-    return (u64(hi) << 32) | lo;
-}
+// what a hit adds to its component's record
+struct ObjHit {
+    BoxVox b;
+    u64 sc, pk;                     // 2^24 fixed-point score (sum); (score key << 32) | ~point (max)
+    __device__ static ObjHit identity() { return {BoxVox::identity(), 0, 0}; }
+    __device__ void merge_xor(int mask) {
+        sc += shfl_xor_u64(sc, mask);
+        const u64 o = shfl_xor_u64(pk, mask);
+        pk = o > pk ? o : pk;
+        b.merge_xor(mask);
+    }
+};
 
 // COMBINE = false issues every hit's atomics on its own (tools/micro_objects.py measures the difference)
 template <bool COMBINE>
@@ -231,7 +225,7 @@ __global__ __launch_bounds__(OBJ_T) void objects_reduce_kernel(const uint16_t* _
                                                                const int32_t* __restrict__ label, const int32_t* __restrict__ slot,
                                                                const uint32_t* __restrict__ item_start, int64_t V, int S, int64_t C, Records R) {
     __shared__ uint16_t tile[OBJ_T][OBJ_LD];
-    const int tid = threadIdx.x, lane = tid & 63;
+    const int tid = threadIdx.x;
     const int64_t p0 = int64_t(blockIdx.x) * OBJ_T;
     const int64_t p = p0 + tid;
     const bool live = p < n;
@@ -252,6 +246,13 @@ __global__ __launch_bounds__(OBJ_T) void objects_reduce_kernel(const uint16_t* _
         else pt = uint32_t(p - o);
         bx = f2o(xyz[p * 3 + 0]); by = f2o(xyz[p * 3 + 1]); bz = f2o(xyz[p * 3 + 2]);
     }
+    const BoxArrays A = box_arrays(R, C);
+    const auto commit = [&](int c, const ObjHit& h, int cnt) {
+        atomicAdd(&R.n_points[c], uint32_t(cnt));
+        atomicAdd(&R.score_sum[c], h.sc);
+        atomicMax(&R.peak[c], h.pk);
+        h.b.commit(A, c);
+    };
     for (int q0 = 0; q0 < Q; q0 += OBJ_QC) {
         const int qn = Q - q0 < OBJ_QC ? Q - q0 : OBJ_QC;
         __syncthreads();
@@ -269,73 +270,13 @@ __global__ __launch_bounds__(OBJ_T) void objects_reduce_kernel(const uint16_t* _
                 const int64_t c64 = obj_component(label, slot, coords, item_start, V, Q, S, q, v, &s);
                 if (c64 >= 0 && c64 < C && s == scene_p) comp = int(c64);
             }
-            u64 todo = __ballot(comp >= 0);
-            if (!todo) continue;
-            const u64 sc = u64((long long)((float)__builtin_bit_cast(_Float16, hb) * 16777216.0f));
-            const u64 pk = (u64(obj_key(hb)) << 32) | u64(~pt);
-            if (!COMBINE) {
-                if (comp >= 0) {
-                    atomicAdd(&R.n_points[comp], 1u);
-                    atomicAdd(&R.score_sum[comp], sc);
-                    atomicMax(&R.peak[comp], pk);
-                    atomicAdd(&R.vox_sum[0 * C + comp], u64((long long)vx));
-                    atomicAdd(&R.vox_sum[1 * C + comp], u64((long long)vy));
-                    atomicAdd(&R.vox_sum[2 * C + comp], u64((long long)vz));
-                    atomicMin(&R.box[0 * C + comp], bx); atomicMin(&R.box[1 * C + comp], by); atomicMin(&R.box[2 * C + comp], bz);
-                    atomicMax(&R.box[3 * C + comp], bx); atomicMax(&R.box[4 * C + comp], by); atomicMax(&R.box[5 * C + comp], bz);
-                }
-                continue;
-            }
-            while (todo) {                                   // (wave-uniform: one turn per distinct record among the lanes)
-                const int leader = __ffsll((long long)todo) - 1;
-                const int lc = __shfl(comp, leader, 64);
-                const bool mine = comp == lc;
-                const u64 m = __ballot(mine);
-                todo &= ~m;
-                const int cnt = __popcll(m);
-                if (cnt < OBJ_COMBINE_MIN) {
-                    if (mine) {
-                        atomicAdd(&R.n_points[comp], 1u);
-                        atomicAdd(&R.score_sum[comp], sc);
-                        atomicMax(&R.peak[comp], pk);
-                        atomicAdd(&R.vox_sum[0 * C + comp], u64((long long)vx));
-                        atomicAdd(&R.vox_sum[1 * C + comp], u64((long long)vy));
-                        atomicAdd(&R.vox_sum[2 * C + comp], u64((long long)vz));
-                        atomicMin(&R.box[0 * C + comp], bx); atomicMin(&R.box[1 * C + comp], by); atomicMin(&R.box[2 * C + comp], bz);
-                        atomicMax(&R.box[3 * C + comp], bx); atomicMax(&R.box[4 * C + comp], by); atomicMax(&R.box[5 * C + comp], bz);
-                    }
-                    continue;
-                }
-                // butterfly over the whole wave, the other lanes holding each operation's identity
-                u64 a_sc = mine ? sc : 0, a_pk = mine ? pk : 0;
-                uint32_t lo_x = mine ? bx : 0xFFFFFFFFu, lo_y = mine ? by : 0xFFFFFFFFu, lo_z = mine ? bz : 0xFFFFFFFFu;
-                uint32_t hi_x = mine ? bx : 0u, hi_y = mine ? by : 0u, hi_z = mine ? bz : 0u;
-                int s_vx = mine ? vx : 0, s_vy = mine ? vy : 0, s_vz = mine ? vz : 0;          // 64 x |coordinate| < 2^21
-#pragma unroll
-                for (int mk = 32; mk >= 1; mk >>= 1) {
-                    a_sc += shfl_xor_u64(a_sc, mk);
-                    const u64 o_pk = shfl_xor_u64(a_pk, mk);
-                    a_pk = o_pk > a_pk ? o_pk : a_pk;
-                    s_vx += __shfl_xor(s_vx, mk, 64); s_vy += __shfl_xor(s_vy, mk, 64); s_vz += __shfl_xor(s_vz, mk, 64);
-                    uint32_t t;
-                    t = __shfl_xor(lo_x, mk, 64); lo_x = t < lo_x ? t : lo_x;
-                    t = __shfl_xor(lo_y, mk, 64); lo_y = t < lo_y ? t : lo_y;
-                    t = __shfl_xor(lo_z, mk, 64); lo_z = t < lo_z ? t : lo_z;
-                    t = __shfl_xor(hi_x, mk, 64); hi_x = t > hi_x ? t : hi_x;
-                    t = __shfl_xor(hi_y, mk, 64); hi_y = t > hi_y ? t : hi_y;
-                    t = __shfl_xor(hi_z, mk, 64); hi_z = t > hi_z ? t : hi_z;
-                }
-                if (lane == leader) {
-                    atomicAdd(&R.n_points[lc], uint32_t(cnt));
-                    atomicAdd(&R.score_sum[lc], a_sc);
-                    atomicMax(&R.peak[lc], a_pk);
-                    atomicAdd(&R.vox_sum[0 * C + lc], u64((long long)s_vx));
-                    atomicAdd(&R.vox_sum[1 * C + lc], u64((long long)s_vy));
-                    atomicAdd(&R.vox_sum[2 * C + lc], u64((long long)s_vz));
-                    atomicMin(&R.box[0 * C + lc], lo_x); atomicMin(&R.box[1 * C + lc], lo_y); atomicMin(&R.box[2 * C + lc], lo_z);
-                    atomicMax(&R.box[3 * C + lc], hi_x); atomicMax(&R.box[4 * C + lc], hi_y); atomicMax(&R.box[5 * C + lc], hi_z);
-                }
-            }
+            if (!__ballot(comp >= 0)) continue;              // (wave-uniform; most waves of a sparse heat-map leave here)
+            ObjHit h;
+            h.b = BoxVox::point(vx, vy, vz, bx, by, bz);
+            h.sc = u64((long long)((float)__builtin_bit_cast(_Float16, hb) * 16777216.0f));
+            h.pk = (u64(obj_key(hb)) << 32) | u64(~pt);
+            if (COMBINE) wave_combine<COMBINE_MIN>(comp, h, commit);
+            else if (comp >= 0) commit(comp, h, 1);
         }
     }
 }
@@ -454,11 +395,6 @@ static ObjectsWs objects_ws(int64_t V, int S, int Q) {
     return w;
 }
 
-static unsigned grid_for(int64_t elems) {
-    const int64_t b = cdiv(elems > 0 ? elems : 1, OBJ_T);
-    return unsigned(b < (int64_t(1) << 16) ? b : (int64_t(1) << 16));
-}
-
 }  // namespace osn
 
 using namespace osn;
@@ -507,11 +443,11 @@ extern "C" int osn_objects_label(const void* heat_f16, int64_t n, int q, const f
         hipLaunchKernelGGL(objects_check_kernel, dim3(unsigned(cdiv(n_scenes, 256))), dim3(256), 0, st, scene_offsets, n_scenes, n, err);
     if (n > 0 && words > 0 && n_scenes > 0) {
         const int4* c4 = reinterpret_cast<const int4*>(coords4);
-        hipLaunchKernelGGL(objects_activate_kernel, dim3(grid_for(n * q)), dim3(OBJ_T), 0, st, static_cast<const uint16_t*>(heat_f16), n, q,
+        hipLaunchKernelGGL(objects_activate_kernel, dim3(components_grid(n * q)), dim3(OBJ_T), 0, st, static_cast<const uint16_t*>(heat_f16), n, q,
                            thresholds, inverse, V, label, err);
-        hipLaunchKernelGGL(objects_unite_kernel, dim3(grid_for(words)), dim3(OBJ_T), 0, st, label, nbr, V, q, connectivity, err);
-        hipLaunchKernelGGL(objects_flatten_kernel, dim3(grid_for(words)), dim3(OBJ_T), 0, st, label, V, q);
-        hipLaunchKernelGGL(objects_number_kernel, dim3(grid_for(words)), dim3(OBJ_T), 0, st, label, c4, V, q, n_scenes, item_count, slot, err);
+        hipLaunchKernelGGL(objects_unite_kernel, dim3(components_grid(words)), dim3(OBJ_T), 0, st, label, nbr, V, q, connectivity, err);
+        hipLaunchKernelGGL(objects_flatten_kernel, dim3(components_grid(words)), dim3(OBJ_T), 0, st, label, V, q);
+        hipLaunchKernelGGL(objects_number_kernel, dim3(components_grid(words)), dim3(OBJ_T), 0, st, label, c4, V, q, n_scenes, item_count, slot, err);
     }
     hipLaunchKernelGGL(objects_scan_kernel, dim3(1), dim3(OBJ_T), 0, st, item_count, items, item_start);
     OSN_LAUNCH_CHECK();
@@ -560,7 +496,7 @@ extern "C" int osn_objects_find(const void* heat_f16, const float* xyz, int64_t 
     const int64_t words = int64_t(q) * V;
     if (C > 0) {
         hipLaunchKernelGGL(objects_preset_kernel, dim3(unsigned(cdiv(C, 256))), dim3(256), 0, st, R, C);
-        hipLaunchKernelGGL(objects_voxels_kernel, dim3(grid_for(words)), dim3(OBJ_T), 0, st, label, slot, c4, item_start, V, q, n_scenes, C, R);
+        hipLaunchKernelGGL(objects_voxels_kernel, dim3(components_grid(words)), dim3(OBJ_T), 0, st, label, slot, c4, item_start, V, q, n_scenes, C, R);
         const dim3 grid(unsigned(cdiv(n, OBJ_T)));
         if (combine)
             hipLaunchKernelGGL(objects_reduce_kernel<true>, grid, dim3(OBJ_T), 0, st, heat, xyz, n, q, thresholds, inverse, c4, scene_offsets,
@@ -576,7 +512,7 @@ extern "C" int osn_objects_find(const void* heat_f16, const float* xyz, int64_t 
     hipLaunchKernelGGL(objects_select_kernel, dim3(unsigned(int64_t(n_scenes) * q)), dim3(OBJ_T), 0, st, item_start, R, C, q, heat, scene_offsets,
                        n, uint32_t(min_points), max_objects, O);
     if (point_object && n > 0)
-        hipLaunchKernelGGL(objects_point_ids_kernel, dim3(grid_for(n * q)), dim3(OBJ_T), 0, st, heat, n, q, thresholds, inverse, c4, label, slot,
+        hipLaunchKernelGGL(objects_point_ids_kernel, dim3(components_grid(n * q)), dim3(OBJ_T), 0, st, heat, n, q, thresholds, inverse, c4, label, slot,
                            item_start, V, n_scenes, C, R, point_object);
     OSN_LAUNCH_CHECK();
     return OSN_OK;

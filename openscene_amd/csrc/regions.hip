@@ -4,7 +4,7 @@
 // voxels: two voxels of the 3^3 self-map are joined iff the dot product of their (unit) feature rows reaches a threshold.
 //
 //   osn_regions_edges    sim[i, v] = <vox[v], vox[nbr[k_i, v]]> for the offsets below the centre (every undirected edge once)
-//   osn_regions_label    union-find (uf.h) over the edges with sim >= threshold -> voxel_root[v] = smallest row of v's component
+//   osn_regions_label    union-find (components.h) over the edges with sim >= threshold -> voxel_root[v] = smallest row of v's component
 //   osn_regions_records  per region: points, voxels, voxel sums, float box, scene -- integer atomics only
 //
 // Edges (the hot path).  One wave per voxel.  A row of d fp16 values is d / 8 vectors of 16 bytes; lane l holds vectors
@@ -17,26 +17,20 @@
 //
 // Label.  voxel_root starts as the identity; one thread per voxel unites it with the earlier neighbours whose sim passes
 // (float32 >=: NaN and -inf never pass); a second launch replaces every word by its root.  The root of a tree is its
-// smallest row whatever order the hooks landed in (uf.h), so the labelling is canonical.
+// smallest row whatever order the hooks landed in (components.h), so the labelling is canonical.
 //
-// Records.  A lane owns one point; the lanes of a wave that target one region are combined by a butterfly before one lane
-// issues the atomics (a floor puts thousands of consecutive points on one record).  Sums of integers and min / max do not
-// depend on order: exact and bitwise repeatable.  The box is kept as order-preserving uint32 words in the output arrays
-// and turned into floats by the last launch; the region's scene is read at its smallest voxel row.
+// Records.  A lane owns one point; the lanes of a wave that target one region are combined before one lane issues the
+// atomics (components.h: wave_combine and BoxVox, with the all-lanes contract and why the records are exact and bitwise
+// repeatable).  The box is kept as order-preserving uint32 words in the output arrays and turned into floats by the last
+// launch; the region's scene is read at its smallest voxel row.
 #include "bank.h"            // half8
-#include "uf.h"
+#include "components.h"
 
 namespace osn {
 
 constexpr int REG_E_NBR = 1, REG_E_INVERSE = 2, REG_E_REGION = 4;
-constexpr int REG_T = 256;                  // threads of a workgroup
+constexpr int REG_T = COMPONENTS_T;
 constexpr int REG_WAVES = REG_T / 64;       // voxels of an edge workgroup
-constexpr int REG_COMBINE_MIN = 4;          // lanes on one record from which the butterfly beats their own atomics
-
-typedef unsigned long long u64;
-
-// offsets below the centre of the 3^3 map, k = ix + 3 iy + 9 iz; the three faces among them: -z = 4, -y = 10, -x = 12
-__device__ inline int reg_face(int i) { return i == 0 ? 4 : i == 1 ? 10 : 12; }
 
 // ------------------------------------------------------------------------------------------------------ edges
 // NV: 16-byte vectors of a row per lane (1: d <= 512, 2: d <= 1024); NOFF: 13 (connectivity 26) or 3 (6)
@@ -50,7 +44,7 @@ __global__ __launch_bounds__(REG_T) void regions_edges_kernel(const half8* __res
     int u[NOFF];
 #pragma unroll
     for (int i = 0; i < NOFF; ++i) {
-        const int k = NOFF == 13 ? i : reg_face(i);
+        const int k = NOFF == 13 ? i : face_offset(i);
         int x = __builtin_amdgcn_readfirstlane(nbr[int64_t(k) * V + v]);
         if (x >= V) {                                        // skipped, never dereferenced
             if (lane == 0) atomicOr(err, REG_E_NBR);
@@ -102,7 +96,7 @@ __global__ __launch_bounds__(REG_T) void regions_unite_kernel(int32_t* L, const 
     const int n_off = conn == 26 ? 13 : 3;
     for (int64_t v = int64_t(blockIdx.x) * REG_T + threadIdx.x; v < V; v += int64_t(gridDim.x) * REG_T) {
         for (int i = 0; i < n_off; ++i) {
-            const int k = conn == 26 ? i : reg_face(i);
+            const int k = conn == 26 ? i : face_offset(i);
             const int u = nbr[int64_t(k) * V + v];
             if (u < 0) continue;
             if (u >= V) { atomicOr(err, REG_E_NBR); continue; }
@@ -113,15 +107,7 @@ __global__ __launch_bounds__(REG_T) void regions_unite_kernel(int32_t* L, const 
 }
 
 __global__ __launch_bounds__(REG_T) void regions_flatten_kernel(int32_t* L, int64_t V) {
-    for (int64_t v = int64_t(blockIdx.x) * REG_T + threadIdx.x; v < V; v += int64_t(gridDim.x) * REG_T) {
-        int x = ld_agent(L + v);
-        while (true) {                                       // (parents only move towards the root while others flatten)
-            const int p = ld_agent(L + x);
-            if (p == x) break;
-            x = p;
-        }
-        if (x != int(v)) __hip_atomic_store(L + v, x, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
+    for (int64_t v = int64_t(blockIdx.x) * REG_T + threadIdx.x; v < V; v += int64_t(gridDim.x) * REG_T) uf_flatten(L, int(v));
 }
 
 // ------------------------------------------------------------------------------------------------------ records
@@ -129,13 +115,14 @@ struct RegOut {
     u64* n_points; u64* n_voxels; u64* vox_sum;              // two's complement int64; vox_sum [R][3]
     uint32_t* box_min; uint32_t* box_max;                    // [R][3]: order-preserving words until the finish launch
     int32_t* scene;                                          // the smallest voxel row until the finish launch
+    __device__ BoxArrays box_arrays() const { return {vox_sum, box_min, box_max, 1, 3}; }
 };
 
 __global__ __launch_bounds__(REG_T) void regions_preset_kernel(RegOut O, int64_t R) {
     const int64_t r = int64_t(blockIdx.x) * REG_T + threadIdx.x;
     if (r >= R) return;
     O.n_points[r] = 0; O.n_voxels[r] = 0; O.scene[r] = 0x7FFFFFFF;
-    for (int j = 0; j < 3; ++j) { O.vox_sum[r * 3 + j] = 0; O.box_min[r * 3 + j] = 0xFFFFFFFFu; O.box_max[r * 3 + j] = 0u; }
+    BoxVox::preset(O.box_arrays(), r);
 }
 
 __global__ __launch_bounds__(REG_T) void regions_voxels_kernel(const int32_t* __restrict__ region, int64_t V, int64_t R, RegOut O,
@@ -152,7 +139,6 @@ __global__ __launch_bounds__(REG_T) void regions_voxels_kernel(const int32_t* __
 __global__ __launch_bounds__(REG_T) void regions_points_kernel(const float* __restrict__ xyz, const int32_t* __restrict__ inv, int64_t n,
                                                                const int4* __restrict__ coords, const int32_t* __restrict__ region,
                                                                int64_t V, int64_t R, RegOut O, int32_t* __restrict__ err) {
-    const int lane = threadIdx.x & 63;
     const int64_t p = int64_t(blockIdx.x) * REG_T + threadIdx.x;
     int reg = -1, vx = 0, vy = 0, vz = 0;
     uint32_t bx = 0, by = 0, bz = 0;
@@ -172,53 +158,10 @@ __global__ __launch_bounds__(REG_T) void regions_points_kernel(const float* __re
             }
         }
     }
-    u64 todo = __ballot(reg >= 0);
-    while (todo) {                                           // (wave-uniform: one turn per distinct region among the lanes)
-        const int leader = __ffsll((long long)todo) - 1;
-        const int lr = __shfl(reg, leader, 64);
-        const bool mine = reg == lr;
-        const u64 m = __ballot(mine);
-        todo &= ~m;
-        const int cnt = __popcll(m);
-        if (cnt < REG_COMBINE_MIN) {
-            if (mine) {
-                atomicAdd(&O.n_points[reg], u64(1));
-                atomicAdd(&O.vox_sum[int64_t(reg) * 3 + 0], u64((long long)vx));
-                atomicAdd(&O.vox_sum[int64_t(reg) * 3 + 1], u64((long long)vy));
-                atomicAdd(&O.vox_sum[int64_t(reg) * 3 + 2], u64((long long)vz));
-                atomicMin(&O.box_min[int64_t(reg) * 3 + 0], bx); atomicMin(&O.box_min[int64_t(reg) * 3 + 1], by);
-                atomicMin(&O.box_min[int64_t(reg) * 3 + 2], bz);
-                atomicMax(&O.box_max[int64_t(reg) * 3 + 0], bx); atomicMax(&O.box_max[int64_t(reg) * 3 + 1], by);
-                atomicMax(&O.box_max[int64_t(reg) * 3 + 2], bz);
-            }
-            continue;
-        }
-        // butterfly over the whole wave, the other lanes holding each operation's identity
-        uint32_t lo_x = mine ? bx : 0xFFFFFFFFu, lo_y = mine ? by : 0xFFFFFFFFu, lo_z = mine ? bz : 0xFFFFFFFFu;
-        uint32_t hi_x = mine ? bx : 0u, hi_y = mine ? by : 0u, hi_z = mine ? bz : 0u;
-        int s_vx = mine ? vx : 0, s_vy = mine ? vy : 0, s_vz = mine ? vz : 0;                  // 64 x |coordinate| < 2^21
-#pragma unroll
-        for (int mk = 32; mk >= 1; mk >>= 1) {
-            s_vx += __shfl_xor(s_vx, mk, 64); s_vy += __shfl_xor(s_vy, mk, 64); s_vz += __shfl_xor(s_vz, mk, 64);
-            uint32_t t;
-            t = __shfl_xor(lo_x, mk, 64); lo_x = t < lo_x ? t : lo_x;
-            t = __shfl_xor(lo_y, mk, 64); lo_y = t < lo_y ? t : lo_y;
-            t = __shfl_xor(lo_z, mk, 64); lo_z = t < lo_z ? t : lo_z;
-            t = __shfl_xor(hi_x, mk, 64); hi_x = t > hi_x ? t : hi_x;
-            t = __shfl_xor(hi_y, mk, 64); hi_y = t > hi_y ? t : hi_y;
-            t = __shfl_xor(hi_z, mk, 64); hi_z = t > hi_z ? t : hi_z;
-        }
-        if (lane == leader) {
-            atomicAdd(&O.n_points[lr], u64(cnt));
-            atomicAdd(&O.vox_sum[int64_t(lr) * 3 + 0], u64((long long)s_vx));
-            atomicAdd(&O.vox_sum[int64_t(lr) * 3 + 1], u64((long long)s_vy));
-            atomicAdd(&O.vox_sum[int64_t(lr) * 3 + 2], u64((long long)s_vz));
-            atomicMin(&O.box_min[int64_t(lr) * 3 + 0], lo_x); atomicMin(&O.box_min[int64_t(lr) * 3 + 1], lo_y);
-            atomicMin(&O.box_min[int64_t(lr) * 3 + 2], lo_z);
-            atomicMax(&O.box_max[int64_t(lr) * 3 + 0], hi_x); atomicMax(&O.box_max[int64_t(lr) * 3 + 1], hi_y);
-            atomicMax(&O.box_max[int64_t(lr) * 3 + 2], hi_z);
-        }
-    }
+    wave_combine<COMBINE_MIN>(reg, BoxVox::point(vx, vy, vz, bx, by, bz), [&](int r, const BoxVox& b, int cnt) {
+        atomicAdd(&O.n_points[r], u64(cnt));
+        b.commit(O.box_arrays(), r);
+    });
 }
 
 // words -> floats (a region without points: a zero box); smallest voxel row -> its scene (-1: a region without voxels)
@@ -233,11 +176,6 @@ __global__ __launch_bounds__(REG_T) void regions_finish_kernel(RegOut O, int64_t
     }
     const int first = O.scene[r];
     O.scene[r] = (first >= 0 && first < V) ? coords[first].x : -1;
-}
-
-static unsigned reg_grid(int64_t elems) {
-    const int64_t b = cdiv(elems > 0 ? elems : 1, REG_T);
-    return unsigned(b < (int64_t(1) << 16) ? b : (int64_t(1) << 16));
 }
 
 template <int NV>
@@ -283,9 +221,9 @@ extern "C" int osn_regions_label(const float* sim, const int32_t* nbr, int64_t n
     OSN_REQUIRE(err, OSN_E_ARG, "osn_regions_label: null err");
     if (V == 0) return OSN_OK;
     OSN_REQUIRE(sim && nbr && voxel_root, OSN_E_ARG, "osn_regions_label: null pointer");
-    hipLaunchKernelGGL(regions_init_kernel, dim3(reg_grid(V)), dim3(REG_T), 0, st, voxel_root, V);
-    hipLaunchKernelGGL(regions_unite_kernel, dim3(reg_grid(V)), dim3(REG_T), 0, st, voxel_root, sim, nbr, V, connectivity, threshold, err);
-    hipLaunchKernelGGL(regions_flatten_kernel, dim3(reg_grid(V)), dim3(REG_T), 0, st, voxel_root, V);
+    hipLaunchKernelGGL(regions_init_kernel, dim3(components_grid(V)), dim3(REG_T), 0, st, voxel_root, V);
+    hipLaunchKernelGGL(regions_unite_kernel, dim3(components_grid(V)), dim3(REG_T), 0, st, voxel_root, sim, nbr, V, connectivity, threshold, err);
+    hipLaunchKernelGGL(regions_flatten_kernel, dim3(components_grid(V)), dim3(REG_T), 0, st, voxel_root, V);
     OSN_LAUNCH_CHECK();
     return OSN_OK;
 }
@@ -309,7 +247,7 @@ extern "C" int osn_regions_records(const int32_t* voxel_region, int64_t n_voxels
     O.box_min = reinterpret_cast<uint32_t*>(box_min); O.box_max = reinterpret_cast<uint32_t*>(box_max); O.scene = scene;
     const int4* c4 = reinterpret_cast<const int4*>(coords4);
     if (R > 0) hipLaunchKernelGGL(regions_preset_kernel, dim3(unsigned(cdiv(R, REG_T))), dim3(REG_T), 0, st, O, R);
-    if (V > 0) hipLaunchKernelGGL(regions_voxels_kernel, dim3(reg_grid(V)), dim3(REG_T), 0, st, voxel_region, V, R, O, err);
+    if (V > 0) hipLaunchKernelGGL(regions_voxels_kernel, dim3(components_grid(V)), dim3(REG_T), 0, st, voxel_region, V, R, O, err);
     if (n > 0) hipLaunchKernelGGL(regions_points_kernel, dim3(unsigned(cdiv(n, REG_T))), dim3(REG_T), 0, st, xyz, inverse, n, c4, voxel_region, V, R, O, err);
     if (R > 0) hipLaunchKernelGGL(regions_finish_kernel, dim3(unsigned(cdiv(R, REG_T))), dim3(REG_T), 0, st, O, R, c4, V);
     OSN_LAUNCH_CHECK();

@@ -164,6 +164,17 @@ def assert_same(result, ref, voxel_size, point_ids=True):
         assert result.point_object is not None and torch.equal(result.point_object.cpu(), ref["point_object"]), "point_object"
 
 
+def wave_groups():
+    """Group per point, int64 [197], for the tests of the wave-combined record reduction (csrc/components.h): three full waves
+    of 64 consecutive points and one of 5.  Wave 0: groups 0 .. 4 of 1, 3, 4, 5 and 51 lanes (either side of the threshold of
+    4 lanes from which a group is merged before the atomics), interleaved by a fixed permutation of the 64 places so that no
+    group is a run of neighbours.  Wave 1: 64 lanes on group 5.  Wave 2: groups 6 .. 69, one lane each.  Wave 3: four lanes
+    on group 70 around one lane that is left out (-1)."""
+    wave0 = np.empty(64, dtype=np.int64)
+    wave0[(np.arange(64) * 37 + 11) % 64] = np.repeat(np.arange(5), [1, 3, 4, 5, 51])          # (37 is odd: a permutation)
+    return np.concatenate([wave0, np.full(64, 5), np.arange(6, 70), [70, 70, -1, 70, 70]])
+
+
 # ---- CPU stand-ins for ops.coords_unique / ops.kmap_build / ops.objects_find (host-logic tests only)
 def coords_unique(coords4, stride=1):
     from oracle import coords as oc

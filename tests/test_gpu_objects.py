@@ -213,6 +213,34 @@ def test_fifty_thousand_hits_on_one_record_and_duplicate_points():
         assert sorted(res.n_voxels[0, j, :3].cpu().tolist()) == [1, 1, 25]
 
 
+def test_hand_made_waves_with_and_without_the_wave_combine():
+    """objects_reference.wave_groups as connected components: every group in one or two voxels of its own, three voxels from the
+    next group's, every score over the threshold except on the lane that is left out.  33 queries: a full tile of 32 and a
+    tile of one.  Each wave is a scene of its own kind: 64 objects is the most a (scene, query) returns."""
+    from openscene_amd import ops
+    from openscene_amd.objects import VoxelGrid
+    group = oref.wave_groups()
+    n, q = group.shape[0], 33
+    gen = torch.Generator().manual_seed(37)
+    g = np.where(group >= 0, group, group.max() + 1)                         # the left-out lane: a voxel of its own
+    cell = np.stack([3 * (g % 9) - 12 + np.arange(n) % 2, 3 * (g // 9) - 12, np.full(n, -5)], 1)
+    xyz = (torch.from_numpy(cell).double() + 0.5 + (torch.rand(n, 3, generator=gen, dtype=torch.float64) - 0.5) * 0.6) * VS
+    heat = (0.5 + 0.5 * torch.rand(n, q, generator=gen)).half()
+    heat[group < 0] = 0.25
+    offsets = [0, 128, 192, n]
+    res, _ = run(xyz, offsets, heat, 0.5, max_objects=64)
+    assert res.n_objects.cpu().tolist() == [[6] * q, [64] * q, [1] * q]
+    grid = VoxelGrid(xyz.to(dev()), offsets, voxel_size=VS)
+    thr = torch.full((q,), 0.5, device=dev())
+    both = [ops.objects_find(heat.to(dev()), thr, grid.xyz, grid.inverse, grid.coords, grid.nbr, grid.offsets_tensor(), max_objects=64,
+                             return_point_ids=True, combine=combine) for combine in (True, False)]
+    for f in oref.FIELDS + ("n_objects", "point_object"):
+        a, b = both[0][f], both[1][f]
+        assert a.dtype == b.dtype and a.shape == b.shape, f
+        assert torch.equal(a.contiguous().view(torch.uint8), b.contiguous().view(torch.uint8)), f
+        assert torch.equal(a, getattr(res, f)), f
+
+
 def test_repeatable_bit_for_bit_also_after_unrelated_work():
     from openscene_amd.objects import VoxelGrid, find_objects
     gen = torch.Generator().manual_seed(19)

@@ -168,6 +168,28 @@ def test_records_of_an_arbitrary_labelling_bit_for_bit(n_regions):
     assert all(torch.equal(got[f], again[f]) for f in rr.RECORD_FIELDS)
 
 
+def test_records_of_hand_made_waves_bit_for_bit():
+    """objects_reference.wave_groups as regions: groups under, at and over the merge threshold, interleaved in their wave; a
+    whole wave on one region; 64 regions in one wave; a short last wave with a lane whose voxel has region -1."""
+    from objects_reference import wave_groups
+    from openscene_amd import ops
+    group = torch.from_numpy(wave_groups())
+    n_regions = int(group.max()) + 1
+    gen = torch.Generator().manual_seed(51)
+    # two voxels per region and one voxel of region -1 (the last row), negative cells
+    region = torch.cat([torch.arange(n_regions).repeat_interleave(2), torch.tensor([-1])]).int()
+    v_n = region.shape[0]
+    coords4 = torch.cat([torch.randint(0, 3, (v_n, 1), generator=gen), torch.randint(-300, -1, (v_n, 3), generator=gen)], 1).int()
+    inverse = torch.where(group >= 0, 2 * group + torch.arange(group.shape[0]) % 2, torch.tensor(v_n - 1)).int()
+    xyz = (torch.randn(group.shape[0], 3, generator=gen) * 10).float()
+    xyz[70] = torch.tensor([-0.0, 0.0, -1e-30])                              # in the merged wave: both signs of the box words
+    xyz[130] = torch.tensor([0.0, -0.0, -7.5])                               # on a lane that issues its own atomics
+    assert group.shape[0] == 197 and int((region[inverse.long()] == -1).sum()) == 1
+    got = ops.regions_records(region.to(dev()), n_regions, xyz.to(dev()), inverse.to(dev()), coords4.to(dev()))
+    rr.assert_records(got, rr.records(region.numpy(), n_regions, xyz.numpy(), inverse.numpy(), coords4.numpy()))
+    assert got["n_points"].cpu().tolist() == torch.bincount(group[group >= 0]).tolist()
+
+
 @pytest.mark.parametrize("min_points", [1, 3])
 def test_segment_numbers_filters_and_records_like_the_reference(min_points):
     from openscene_amd.objects import VoxelGrid
