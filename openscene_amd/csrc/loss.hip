@@ -15,6 +15,10 @@ namespace osn {
 
 constexpr float LOSS_EPS = 1e-8f;     // torch.nn.CosineSimilarity's eps: each norm is clamped from below
 
+// max(r, eps) that keeps a NaN norm (fmaxf returns the other operand: a NaN in a row would leave kb finite, and the row's gradient
+// a finite b / (eps nb) beside a NaN loss); the same bits as fmaxf for every other r
+__device__ inline float clamp_norm(float r) { return r <= LOSS_EPS ? LOSS_EPS : r; }
+
 __device__ inline float wave_sum(float v) {
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
@@ -60,7 +64,7 @@ __global__ __launch_bounds__(256) void loss_rows_kernel(const float* __restrict_
         s1 = wave_sum(s1);
         s2 = wave_sum(s2);
         if (lane == 0) {
-            const float na = fmaxf(sqrtf(s1), LOSS_EPS), nb = fmaxf(sqrtf(s2), LOSS_EPS);
+            const float na = clamp_norm(sqrtf(s1)), nb = clamp_norm(sqrtf(s2));
             stats[3 * j + 0] = s0; stats[3 * j + 1] = s1; stats[3 * j + 2] = s2;
             val[j] = 1.f - s0 / (na * nb);
         }
@@ -106,7 +110,7 @@ __global__ __launch_bounds__(256) void loss_grad_kernel(const float* __restrict_
     const float up = gloss ? *gloss : 1.f;
     if (KIND == 0) {
         const float dot = stats[3 * j + 0], a2 = stats[3 * j + 1], b2 = stats[3 * j + 2];
-        const float na = fmaxf(sqrtf(a2), LOSS_EPS), nb = fmaxf(sqrtf(b2), LOSS_EPS);
+        const float na = clamp_norm(sqrtf(a2)), nb = clamp_norm(sqrtf(b2));
         // cos = dot / (na nb) with clamped norms (torch normalises each operand by its clamped norm):
         // d cos / d a = b / (na nb) - dot a / (na^3 nb)   (the clamp is inactive for any row of a trained network)
         const float s = -up / float(n_sel);

@@ -222,15 +222,20 @@ def test_row_sparse_head_with_a_narrow_head(monkeypatch):
             assert torch.equal(res[0][k], res[1][k]), k
 
 
-@pytest.mark.parametrize("kind", ["cosine", "l1"])
-def test_row_sparse_head_gradients_equal_the_dense_path(kind, monkeypatch):
+@pytest.mark.parametrize("kind,unsorted", [("cosine", False), ("l1", False), ("cosine", True), ("l1", True)],
+                         ids=["cosine", "l1", "cosine-unsorted", "l1-unsorted"])
+def test_row_sparse_head_gradients_equal_the_dense_path(kind, unsorted, monkeypatch):
     """Round 4: distill_loss hands the executor the non-zero rows of the output gradient (the loss sees `output[sel]`,
     run/distill.py:322) and the head's weight / input gradients run on those rows only.  Against the dense head backward
     (OSN_ROW_SPARSE_HEAD=0) and against torch's own `out[mask]` + CosineSimilarity / L1Loss chain: the input gradient rows
     are computed by the same kernel row by row (=> everything upstream is BITWISE equal), the head's weight gradient sums
-    the same products without the zero rows (fp32 round-off)."""
+    the same products without the zero rows (fp32 round-off).
+    unsorted: the selection in a random order with the target rows in the same order (the contract is "distinct indices", the
+    loader's mask.nonzero() happens to be sorted): the head pairs rows through the loss's inverse table, not by rank.  On the
+    smaller scene of test_row_hint_is_dropped... (MinkUNet14A, ~6 k points) with the same 512-channel head."""
     from openscene_amd import executor as E, losses
     from openscene_amd.disnet import DisNet
+    from openscene_amd.mink_unet import mink_unet
     from openscene_amd.sparse import SparseTensor
 
     class Cfg:
@@ -238,13 +243,21 @@ def test_row_sparse_head_gradients_equal_the_dense_path(kind, monkeypatch):
         feature_2d_extractor = "lseg"
 
     torch.manual_seed(11)
-    net = DisNet(Cfg()).to(dev()).train()
-    coords = torch.from_numpy(scene_coords(5, 12000, 0.04)).to(dev())
+    if unsorted:
+        net = mink_unet(3, 512, 3, "MinkUNet14A").to(dev()).train()
+        coords = torch.from_numpy(scene_coords(7, 6000, 0.05)).to(dev())
+    else:
+        net = DisNet(Cfg()).to(dev()).train()
+        coords = torch.from_numpy(scene_coords(5, 12000, 0.04)).to(dev())
     n = coords.shape[0]
     feats = torch.rand(n, 3, device=dev())
     g = torch.Generator().manual_seed(2)
     sel = torch.randperm(n, generator=g)[:n // 5].sort()[0].to(dev())
     target = torch.nn.functional.normalize(torch.randn(sel.shape[0], 512, generator=g), dim=1).to(dev())
+    if unsorted:
+        order = torch.randperm(sel.shape[0], generator=g).to(dev())
+        sel, target = sel[order].contiguous(), target[order].contiguous()
+        assert bool((sel[1:] < sel[:-1]).any())
     used = []
     real = E.UNetExecutor._run_backward
     monkeypatch.setattr(E.UNetExecutor, "_run_backward",
@@ -270,7 +283,8 @@ def test_row_sparse_head_gradients_equal_the_dense_path(kind, monkeypatch):
     l_torch, g_torch = step(True, torch_loss=True)
     assert used == [True, True, False]                       # the hint travels with the HIP loss's gradient only
     assert torch.equal(l_sparse, l_dense)
-    head = "net3d.final.kernel"
+    head = "final.kernel" if unsorted else "net3d.final.kernel"
+    assert head in g_dense
     for k in g_dense:
         if k == head:
             assert rel_l2(g_sparse[k], g_dense[k]) <= 2e-6, k
