@@ -824,6 +824,44 @@ int osn_fusion_accumulate(const float* feat2d, int D, int H, int W, const int64_
 int osn_fusion_finish(const float* sum_features, const float* counter, int64_t n, int D, float* feat_bank,
                       osn_stream_t stream);
 
+/* ---- scene views: point-splat rasteriser with an exact z-buffer, and its shading pass (csrc/render.hip) ------------ *
+ * The reference's headline is a picture -- the demo that highlights the regions matching a typed phrase -- and its
+ * run/evaluate.py:343-376 exports coloured point clouds for an outside viewer; scripts/feature_fusion/nuscenes_openseg.py
+ * calls compute_mapping with depth=None, so features bleed through walls.  One z-buffer serves both: pictures of any
+ * per-point result, and a depth image rendered from the cloud itself for osn_fusion_project's occlusion test.
+ *
+ * osn_render_splat: coords3 double [n, 3] (device), n < 2^32 - 1; views20 (HOST) = n_views x (world_to_camera row-major
+ *   4 x 4, then fx fy cx cy); image H x W, H * W < 2^31; radius (metres, finite, >= 0); max_px in 0 .. 16; near finite > 0;
+ *   zbuf uint64 [n_views, H, W] (device).  zbuf is first filled with all ones (background).  Per (view, point):
+ *     the camera-space point p and the rounded centre pixel (ur, vr) with exactly the arithmetic of osn_fusion_project
+ *       (one shared body: csrc/project.h), so the centre is bit for bit the pixel compute_mapping gives;
+ *     skipped unless p2 >= near (NaN fails), float32(p2) is finite, and |ur|, |vr| < 2^30 (NaN fails);
+ *     r = 0 if radius == 0, else min(max_px, max(0, rint((radius * fx) / p2))) -- separate IEEE double multiply and
+ *       divide, the clamp taken before the conversion to int (NaN gives 0);
+ *     key = (uint64(bits of float32(p2), round to nearest) << 32) | point index;
+ *     every pixel (ur + dx, vr + dy) with dx^2 + dy^2 <= r^2 inside the image takes the 64-bit unsigned atomic min of the
+ *       key -- the footprint is clipped, a centre outside the image still draws what lies inside.
+ *   The result is a pure function of the inputs whatever the schedule: the nearest float32 depth wins, equal depths go to
+ *   the lower point index; two calls give the same bits.  One launch per view on `stream`, asynchronous, no workspace.
+ *
+ * osn_render_shade: zbuf [n_pixels] -> point_id int32 (-1 background), depth float32 (0 background: ScanNet's "no depth",
+ *   which the occlusion test |d - p2| <= vis * d rejects), and rgb uint8 [n_pixels, 3] by mode (0: rgb is not written):
+ *     1 colours  rgb = colors[id], colors uint8 [n, 3]
+ *     2 labels   l = values[offset + id * stride] (int32: value_bytes 4, int64: 8); table = palette uint8 [table_rows, 3];
+ *                rgb = table[l], or `other` when l is outside [0, table_rows)
+ *     3 heat     h = values[offset + id * stride] (fp16: value_bytes 2, fp32: 4) -- one column of a [N, Q] heat-map in
+ *                place; finite lo < hi; table = LUT uint8 [256, 3] (table_rows = 256).  NaN gives `other`; h < lo gives
+ *                colors[id] when colors (the base image) is given, else table[0]; otherwise, with correctly rounded fp32
+ *                operations, t = (float(h) - lo) / (hi - lo) and rgb = table[min(255, (int)rint(t * 255))].
+ *   Background pixels get `background` in every mode; other_rgb / background_rgb are r | g << 8 | b << 16.  A point index
+ *   >= n in zbuf is never dereferenced: the pixel gets `other`.  n < 2^31.  Integers and selected inputs only: exact.  */
+int osn_render_splat(const double* coords3, int64_t n, const double* views20, int n_views, int H, int W, double radius,
+                     int max_px, double near, uint64_t* zbuf, osn_stream_t stream);
+int osn_render_shade(const uint64_t* zbuf, int64_t n_pixels, int64_t n, int32_t* point_id, float* depth, uint8_t* rgb,
+                     int mode, const uint8_t* colors, const void* values, int value_bytes, int64_t value_offset,
+                     int64_t value_stride, const uint8_t* table, int table_rows, float lo, float hi, uint32_t other_rgb,
+                     uint32_t background_rgb, osn_stream_t stream);
+
 /* ---- elastic distortion: the pre-voxeliser transform of Point3DLoader (dataset/point_loader.py:156) ---------- *
  * ElasticDistortion.elastic_distortion (dataset/augmentation.py:159-201), bit-identical to numpy / scipy given the
  * same noise draw; the draw (np.random.randn(*noise_dim, 3).astype(float32)) and np.linspace of the axes stay on the host.

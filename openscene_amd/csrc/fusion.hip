@@ -5,18 +5,15 @@
 //   osn_fusion_accumulate   scripts/feature_fusion/scannet_openseg.py:93-106 (per view: counter += 1, sum += feat[:, y, x])
 //   osn_fusion_finish       scripts/feature_fusion/scannet_openseg.py:108-109 (counter == 0 -> 1e-5, sum / counter)
 //
-// Pure streaming / gather work (HBM- and L2-bound), fp64 for the projection exactly as numpy computes it:
-//   p = world_to_camera @ [x y z 1]^T     an FMA chain in dgemm's order (m0*x, then +m1*y, +m2*z, +m3*1 fused)
-//   u = (p0 * fx) / p2 + cx               separate IEEE multiply, divide, add (numpy does not contract)
-//   round half to even (np.round), pixel-boundary test on the rounded value, then
+// Pure streaming / gather work (HBM- and L2-bound), fp64 for the projection exactly as numpy computes it (project.h: the
+// body shared with the splat rasteriser of render.hip), then the pixel-boundary test on the rounded value and
 //   |depth[v, u] - p2| <= vis * depth[v, u]   (or p2 > 0 when there is no depth image).
-#include "common.h"
+#include "project.h"
 
 namespace osn {
 
 struct ProjectArgs {
-    double m[12];          // rows 0..2 of world_to_camera (row-major 3 x 4)
-    double fx, fy, cx, cy;
+    Pinhole cam;
     double vis;
     int H, W, cut;
 };
@@ -26,18 +23,8 @@ __global__ __launch_bounds__(256) void fusion_project_kernel(const double* __res
                                                              int64_t* __restrict__ mapping) {
     const int64_t i = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
     if (i >= n) return;
-    const double x = coords[3 * i + 0], y = coords[3 * i + 1], z = coords[3 * i + 2];
-    double p[3];
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-        double s = __dmul_rn(a.m[4 * r + 0], x);
-        s = fma(a.m[4 * r + 1], y, s);
-        s = fma(a.m[4 * r + 2], z, s);
-        p[r] = fma(a.m[4 * r + 3], 1.0, s);
-    }
-    const double u = __dadd_rn(__ddiv_rn(__dmul_rn(p[0], a.fx), p[2]), a.cx);
-    const double v = __dadd_rn(__ddiv_rn(__dmul_rn(p[1], a.fy), p[2]), a.cy);
-    const double ur = rint(u), vr = rint(v);                // round half to even; NaN / inf fail every comparison below
+    const Projected q = project_point(coords, i, a.cam);
+    const double p2 = q.p2, ur = q.ur, vr = q.vr;           // NaN / inf fail every comparison below
     bool inside = ur >= double(a.cut) && vr >= double(a.cut) && ur < double(a.W - a.cut) && vr < double(a.H - a.cut);
     int64_t pu = 0, pv = 0;
     if (inside) {
@@ -45,9 +32,9 @@ __global__ __launch_bounds__(256) void fusion_project_kernel(const double* __res
         pv = int64_t(vr);
         if (depth) {
             const double d = depth[pv * a.W + pu];
-            inside = fabs(__dsub_rn(d, p[2])) <= __dmul_rn(a.vis, d);
+            inside = fabs(__dsub_rn(d, p2)) <= __dmul_rn(a.vis, d);
         } else {
-            inside = p[2] > 0.0;
+            inside = p2 > 0.0;
         }
     }
     mapping[3 * i + 0] = inside ? pv : 0;
@@ -130,8 +117,7 @@ extern "C" int osn_fusion_project(const double* coords3, int64_t n, const double
     if (n == 0) return OSN_OK;
     OSN_REQUIRE(coords3 && mapping, OSN_E_ARG, "osn_fusion_project: null pointer");
     ProjectArgs a;
-    for (int i = 0; i < 12; ++i) a.m[i] = world_to_camera16[i];
-    a.fx = intrinsic4[0]; a.fy = intrinsic4[1]; a.cx = intrinsic4[2]; a.cy = intrinsic4[3];
+    a.cam = make_pinhole(world_to_camera16, intrinsic4);
     a.vis = vis_thres;
     a.H = H; a.W = W; a.cut = cut_bound;
     hipLaunchKernelGGL(fusion_project_kernel, dim3(unsigned(cdiv(n, 256))), dim3(256), 0, st, coords3, n, a, depth, mapping);

@@ -144,3 +144,28 @@ def scene_to_device(scene_path, feature_path, device):
     feat, mask_full = load_fused_features(feature_path)
     t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
     return FusedScene(t(xyz.astype(np.float64)), t(colors), t(labels), feat.to(device), mask_full.to(device))
+
+
+def save_png(path, rgb):
+    """Write uint8 [H, W, 3] (numpy array or tensor, any device) as an 8-bit RGB PNG: the signature, IHDR, one IDAT of the
+    zlib-compressed scanlines (filter type 0 on every line) and IEND -- standard library only (zlib, struct)."""
+    import struct
+    import zlib
+    if isinstance(rgb, torch.Tensor):
+        rgb = rgb.detach().cpu().numpy()
+    rgb = np.asarray(rgb)
+    if rgb.dtype != np.uint8 or rgb.ndim != 3 or rgb.shape[2] != 3 or rgb.shape[0] < 1 or rgb.shape[1] < 1:
+        raise ValueError("save_png takes a uint8 [H, W, 3] image with H, W >= 1 (got %s %s)" % (rgb.dtype, rgb.shape))
+    h, w = rgb.shape[:2]
+    lines = np.zeros((h, 1 + 3 * w), dtype=np.uint8)            # a filter-type byte (0: none) in front of every scanline
+    lines[:, 1:] = rgb.reshape(h, 3 * w)
+
+    def chunk(kind, data):
+        return struct.pack(">I", len(data)) + kind + data + struct.pack(">I", zlib.crc32(kind + data) & 0xFFFFFFFF)
+
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n")
+        f.write(chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)))       # 8 bits, colour type 2 (RGB)
+        f.write(chunk(b"IDAT", zlib.compress(lines.tobytes(), 6)))
+        f.write(chunk(b"IEND", b""))
+    return path

@@ -1946,6 +1946,132 @@ def fusion_finish(sum_features, counter):
     return bank
 
 
+# ------------------------------------------------------- scene views: splat rasteriser and shading (csrc/render.hip)
+RENDER_MAX_PX = 16                      # the largest footprint radius in pixels (csrc/render.hip)
+RENDER_BACKGROUND = -1                  # a zbuf word nothing was drawn on: all ones
+_SHADE_MODES = {None: 0, "colors": 1, "labels": 2, "heat": 3}
+
+
+def _rgb_word(c, name):
+    c = tuple(int(v) for v in c)
+    if len(c) != 3 or not all(0 <= v <= 255 for v in c):
+        raise ValueError("%s must be three integers in 0 .. 255 (got %r)" % (name, c))
+    return c[0] | c[1] << 8 | c[2] << 16
+
+
+def _rgb_rows(t, rows, name, dev):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8:
+        raise TypeError("%s must be a uint8 tensor" % name)
+    if t.dim() != 2 or t.shape[1] != 3 or (rows is not None and t.shape[0] != rows) or t.device != dev or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous uint8 [%s, 3] matrix on the z-buffer's device" % (name, "rows" if rows is None else rows))
+    return t
+
+
+def render_splat(coords3, world_to_camera, intrinsics, image_hw, radius=0.02, max_px=4, near=0.05):
+    """zbuf int64 [V, H, W]: per pixel the 64-bit unsigned minimum, over the points whose footprint covers it, of
+    (bits of float32(depth) << 32 | point index), held as the int64 of the same bits; -1 (all ones) is background.
+    coords3 float64 [n, 3] on the device (as fusion_project takes them); world_to_camera float64 [V, 4, 4] and intrinsics
+    (fx, fy, cx, cy) [V, 4] numpy arrays on the host.  The centre pixel is bit for bit fusion_project's; the footprint is the
+    disc of min(max_px, rint(radius * fx / depth)) pixels, clipped to the image.  A pure function of the inputs."""
+    import numpy as np
+    if not isinstance(coords3, torch.Tensor) or coords3.dtype != torch.float64:
+        raise TypeError("coords must be a float64 tensor (the projection is fusion_project's)")
+    dev = coords3.device
+    if coords3.dim() != 2 or coords3.shape[1] != 3 or not coords3.is_contiguous():
+        raise ValueError("coords must be a contiguous float64 [n, 3] matrix")
+    n = coords3.shape[0]
+    if n >= 2 ** 32 - 1:
+        raise ValueError("at most 2^32 - 2 points (got %d)" % n)
+    w2c = np.ascontiguousarray(np.asarray(world_to_camera, dtype=np.float64))
+    k4 = np.ascontiguousarray(np.asarray(intrinsics, dtype=np.float64))
+    if w2c.ndim != 3 or w2c.shape[1:] != (4, 4) or k4.shape != (w2c.shape[0], 4):
+        raise ValueError("world_to_camera must be [V, 4, 4] and intrinsics [V, 4] (got %s and %s)" % (w2c.shape, k4.shape))
+    V = w2c.shape[0]
+    H, W = int(image_hw[0]), int(image_hw[1])
+    if H < 1 or W < 1 or H * W >= 2 ** 31:
+        raise ValueError("the image must be at least 1 x 1 and below 2^31 pixels (got %d x %d)" % (H, W))
+    radius, near, max_px = float(radius), float(near), int(max_px)
+    if not 0.0 <= radius < float("inf"):
+        raise ValueError("radius must be finite and >= 0 (got %r)" % (radius,))
+    if not 0 <= max_px <= RENDER_MAX_PX:
+        raise ValueError("max_px must be in 0 .. %d (got %d)" % (RENDER_MAX_PX, max_px))
+    if not 0.0 < near < float("inf"):
+        raise ValueError("near must be finite and > 0 (got %r)" % (near,))
+    lib = _prep(dev)                              # (after the checks: they hold without a device)
+    views = np.concatenate([w2c.reshape(V, 16), k4], axis=1).reshape(-1)
+    v20 = (ctypes.c_double * max(views.size, 1))(*views.tolist())
+    zbuf = torch.empty((V, H, W), dtype=torch.int64, device=dev)
+    with _Dev(dev):
+        check(lib.osn_render_splat(_p(coords3), n, v20, V, H, W, radius, max_px, near, _p(zbuf), _stream(dev)), "osn_render_splat")
+    return zbuf
+
+
+def render_shade(zbuf, n, mode=None, colors=None, values=None, column=0, table=None, lo=0.0, hi=1.0, other=(255, 0, 255),
+                 background=(0, 0, 0)):
+    """(point_id int32, depth float32, rgb uint8 [..., 3] or None), each of zbuf's shape: the winning point of every pixel
+    (-1: background), its float32 depth (0: background), and its colour by `mode`:
+      None      no picture
+      "colors"  colors[id]; colors uint8 [n, 3]
+      "labels"  table[values[id]]; values int32 / int64 [n], table = palette uint8 [C, 3]; a label outside [0, C): `other`
+      "heat"    values fp16 / fp32 [n] or [n, Q] with `column` (read in place through the row stride); table = LUT uint8
+                [256, 3]; NaN: `other`; below lo: colors[id] when colors (a base image, uint8 [n, 3]) is given, else table[0];
+                else table[min(255, rint((h - lo) / (hi - lo) * 255))] in correctly rounded float32.
+    Background pixels get `background`.  n is the number of points the z-buffer was drawn from."""
+    if not isinstance(zbuf, torch.Tensor) or zbuf.dtype != torch.int64:
+        raise TypeError("zbuf must be the int64 tensor render_splat returns")
+    dev = zbuf.device
+    if not zbuf.is_contiguous():
+        raise ValueError("zbuf must be contiguous")
+    n = int(n)
+    if not 0 <= n < 2 ** 31:
+        raise ValueError("n must be in 0 .. 2^31 - 1 (got %d)" % n)
+    if mode not in _SHADE_MODES:
+        raise ValueError('mode must be None, "colors", "labels" or "heat" (got %r)' % (mode,))
+    P = zbuf.numel()
+    vbytes, offset, stride = 0, 0, 1
+    lo, hi = float(lo), float(hi)
+    if mode == "colors" or (mode == "heat" and colors is not None):
+        _rgb_rows(colors, n, "colors", dev)
+    elif colors is not None:
+        raise ValueError("colors is for the modes \"colors\" and \"heat\"")
+    if mode in ("labels", "heat"):
+        kinds = {torch.int32: 4, torch.int64: 8} if mode == "labels" else {torch.float16: 2, torch.float32: 4}
+        if not isinstance(values, torch.Tensor) or values.dtype not in kinds:
+            raise TypeError("%s values must be a tensor of %s" % (mode, " or ".join(str(k) for k in kinds)))
+        if values.device != dev:
+            raise ValueError("values must live on the z-buffer's device")
+        vbytes = kinds[values.dtype]
+        column = int(column)
+        if values.dim() == 1 and column == 0 and values.shape[0] == n:
+            stride = values.stride(0) if n > 1 else 1
+        elif mode == "heat" and values.dim() == 2 and values.shape[0] == n and 0 <= column < values.shape[1]:
+            stride = values.stride(0) if n > 1 else 1
+            if values.stride(1) != 1 and values.shape[1] > 1:
+                raise ValueError("the heat rows must be contiguous")
+            offset = column
+        else:
+            raise ValueError("values must be [%d]%s (got %s, column %d)" % (n, " or [%d, Q] with a column in range" % n if mode == "heat" else "",
+                                                                             tuple(values.shape), column))
+        if stride < 1:
+            raise ValueError("the values' row stride must be positive")
+        _rgb_rows(table, 256 if mode == "heat" else None, "the LUT" if mode == "heat" else "the palette", dev)
+        if mode == "heat" and not (lo < hi and hi - lo < float("inf") and torch.tensor(hi, dtype=torch.float32).item() >
+                                   torch.tensor(lo, dtype=torch.float32).item()):
+            raise ValueError("need finite lo < hi, distinct in float32 (got %r, %r)" % (lo, hi))
+    elif values is not None or table is not None:
+        raise ValueError("values and table are for the modes \"labels\" and \"heat\"")
+    other, background = _rgb_word(other, "other"), _rgb_word(background, "background")
+    lib = _prep(dev)                              # (after the checks: they hold without a device)
+    point_id = torch.empty(zbuf.shape, dtype=torch.int32, device=dev)
+    depth = torch.empty(zbuf.shape, dtype=torch.float32, device=dev)
+    rgb = None if mode is None else torch.empty(tuple(zbuf.shape) + (3,), dtype=torch.uint8, device=dev)
+    with _Dev(dev):
+        check(lib.osn_render_shade(_p(zbuf), P, n, _p(point_id), _p(depth), _p(rgb), _SHADE_MODES[mode], _p(colors), _p(values), vbytes,
+                                   offset, stride, _p(table), 0 if table is None else table.shape[0], lo, hi,
+                                   other, background, _stream(dev)), "osn_render_shade")
+    return point_id, depth, rgb
+
+
 # ------------------------------------------------- supervised segmentation head: cross-entropy, argmax, confusion, votes
 def _seg_index(t, name, n, dev):
     if t.dtype != torch.int64 or t.dim() != 1 or t.device != dev or (n is not None and t.shape[0] != n):

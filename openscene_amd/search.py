@@ -11,7 +11,8 @@ against CLIP text embeddings (``:291``, ``:305,310``) and can save them per scen
                      with negative queries the scores are relevancies against the best negative (same pass)
     heat_map         the one-scene convenience
     SearchResult     .rank_scenes(q, by=...) orders the scenes for a query; .find_objects(grid, thresholds) groups the
-                     heat-map into ranked objects (openscene_amd.objects)
+                     heat-map into ranked objects (openscene_amd.objects); .render(raster, scene, q) draws a heat column
+                     over rendered views of the scene (openscene_amd.render)
 
 Kernels: csrc/search.hip through ops.bank_append / ops.bank_search and their _fp8 twins (osn_bank_search_contrast[_fp8]
 when negatives are given); no CPU path.
@@ -316,6 +317,24 @@ class SearchResult:
         from .objects import find_objects
         kw.setdefault("names", self.names)
         return find_objects(grid, self.heat, thresholds, **kw)
+
+    def render(self, raster, scene, q, lo=None, hi=None, base=None, **kw):
+        """uint8 [V, H, W, 3]: the views of `raster` (openscene_amd.render.rasterize of that scene's points) shaded with
+        column q of the scene's heat-map, read in place through the row stride.  After a search with negatives the
+        defaults are lo = 0.5 ("as likely as the best negative") and hi = 1; plain scores have no natural range: lo and hi
+        are required.  base uint8 [n, 3]: the points below lo keep their own colour and the hits stand out, the demo's
+        look.  Needs a search with return_heat."""
+        heat = self.scene_heat(scene)
+        q = int(q)
+        if not 0 <= q < heat.shape[1]:
+            raise IndexError("query %d of %d" % (q, heat.shape[1]))
+        if heat.shape[0] != raster.n:
+            raise ValueError("the scene has %d points but the raster was drawn from %d" % (heat.shape[0], raster.n))
+        if self.relevancy:
+            lo, hi = (0.5 if lo is None else lo), (1.0 if hi is None else hi)
+        elif lo is None or hi is None:
+            raise ValueError("lo and hi are required for plain scores (only relevancies have the default range 0.5 .. 1)")
+        return raster.heat(heat, lo, hi, base=base, column=q, **kw)
 
 
 def _queries(queries, dim, device, what="queries", letter="Q"):
