@@ -862,6 +862,40 @@ int osn_render_shade(const uint64_t* zbuf, int64_t n_pixels, int64_t n, int32_t*
                      int64_t value_stride, const uint8_t* table, int table_rows, float lo, float hi, uint32_t other_rgb,
                      uint32_t background_rgb, osn_stream_t stream);
 
+/* ---- spatial neighbours on the voxel grid: k-nearest search, blend, vote (csrc/neighbors.hip) -------------------- *
+ * Every application result is a tensor over the bank's own points; these entries move one to other points: into the rows
+ * feature fusion never saw (run/evaluate.py:297-300), onto a foreign point set, or over a point's surroundings.
+ * The err word (device int32, OR-ed into, never cleared here): 1 = an order entry outside [0, m), 2 = a cell column or a
+ * table entry out of range, 4 = a cell's list range or point out of range, 8 = a neighbour index or count out of range.
+ * Such entries are skipped, never dereferenced; the caller reads the word.  All calls are asynchronous on `stream`.
+ *
+ * osn_knn_grid: source xyz float32 [n, 3]; cell_start int32 [n_voxels + 1] and cell_points int32 [n_src]: the CSR of the
+ *   source points per voxel row; nbr int32 [27, n_cells] (-1 absent): the voxel rows around each cell column; per query
+ *   q < m its query_xyz float32 [m, 3], its column q_cell (-1: invalid, no neighbours), its exclude (a point never
+ *   returned; the array may be null) and its place in `order` (null: row order), the sequence the lanes take the queries
+ *   in -- cell order keeps a wave on the same lists; it must be a permutation of 0 .. m - 1 (a query it does not name is
+ *   not written).  1 <= k <= 16; r2 finite >= 0.
+ *   Candidates: the points cell_points[cell_start[v] .. cell_start[v + 1]) of the 27 rows v = nbr[o, q_cell[q]] >= 0,
+ *   without exclude[q].  dx = q.x - p.x (dy, dz alike), d2 = fl(fl(fl(dx dx) + fl(dy dy)) + fl(dz dz)), separately rounded
+ *   float32 operations; kept when d2 <= r2 (NaN fails).  key = bits(d2) << 32 | point index; the k smallest keys ascending
+ *   -> idx int32 [m, k] (-1 past count), dist2 float32 [m, k] (+inf past count), count int32 [m].  A pure function of the
+ *   inputs whatever the schedule; two calls give the same bits.
+ * osn_knn_blend: values fp16 (value_bytes 2) or fp32 (4) [n, n_cols], n_cols >= 1; per query over j < count in ascending
+ *   j: w_j = 1 (inverse == 0) or 1 / (dist2_j + eps); out = (w_0 v_0 + w_1 v_1 + ...) / (w_0 + w_1 + ...), every product,
+ *   sum and the divide one float32 rounding, the result rounded once to the values' type; the sums start at their first
+ *   term, so k = 1 uniform copies the row bit for bit.  count == 0: out = fill, found = 0 (found uint8 [m]).
+ * osn_knn_vote: labels int64 [n]; negative labels are ignored; out int64 [m] = the label most of the count neighbours
+ *   hold, a tie going to the label whose first holder has the smallest j; `fill` without a non-negative label.  Exact. */
+int osn_knn_grid(const float* xyz, int64_t n, const int32_t* cell_start, const int32_t* cell_points, int64_t n_src,
+                 int64_t n_voxels, const int32_t* nbr, int64_t n_cells, const float* query_xyz, const int32_t* q_cell,
+                 const int32_t* exclude, const int32_t* order, int64_t m, int k, float r2, int32_t* idx, float* dist2,
+                 int32_t* count, int32_t* err, osn_stream_t stream);
+int osn_knn_blend(const void* values, int value_bytes, int64_t n, int64_t n_cols, const int32_t* idx, const float* dist2,
+                  const int32_t* count, int64_t m, int k, int inverse, float eps, float fill, void* out, uint8_t* found,
+                  int32_t* err, osn_stream_t stream);
+int osn_knn_vote(const int64_t* labels, int64_t n, const int32_t* idx, const int32_t* count, int64_t m, int k, int64_t fill,
+                 int64_t* out, int32_t* err, osn_stream_t stream);
+
 /* ---- elastic distortion: the pre-voxeliser transform of Point3DLoader (dataset/point_loader.py:156) ---------- *
  * ElasticDistortion.elastic_distortion (dataset/augmentation.py:159-201), bit-identical to numpy / scipy given the
  * same noise draw; the draw (np.random.randn(*noise_dim, 3).astype(float32)) and np.linspace of the axes stay on the host.

@@ -14,6 +14,7 @@ Python surface (mirrors the reference's own, file:line in each module):
     openscene_amd.descriptors      and back: scenes, objects and regions of the bank as descriptors (the next query)
     openscene_amd.regions          scenes cut into regions of agreeing features before any prompt: label, list, query by region
     openscene_amd.render           views of a scene on the GPU: point-splat z-buffer -> heat-map / label / colour pictures, depth for fusion
+    openscene_amd.neighbors        results on other points: k-nearest search on the voxel grid, transfer, fill of unseen rows, smoothing
     install_minkowski_alias()      make `import MinkowskiEngine` resolve to openscene_amd.minkowski
 
 There is no CPU fallback: every op raises if libopenscene_amd.so is missing or

@@ -153,6 +153,9 @@ PROTOTYPES = {
     "osn_render_splat": (_i32, [_vp, _i64, _c.POINTER(_c.c_double), _i32, _i32, _i32, _c.c_double, _i32, _c.c_double, _vp, _vp]),
     "osn_render_shade": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _i32, _vp, _vp, _i32, _i64, _i64, _vp, _i32, _f32, _f32,
                                 _c.c_uint32, _c.c_uint32, _vp]),
+    "osn_knn_grid": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "osn_knn_blend": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
+    "osn_knn_vote": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp]),
     "osn_bbox_ws_bytes": (_sz, [_i64]),
     "osn_bbox": (_i32, [_vp, _i64, _vp, _vp, _sz, _vp]),
     "osn_elastic_blur_ws_bytes": (_sz, [_i32, _i32, _i32]),

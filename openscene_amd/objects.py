@@ -27,6 +27,7 @@ class VoxelGrid:
         xyz       float32 [N, 3] (the boxes are taken over these)
         coords    int32 [V, 4] unique (scene, x, y, z) rows       inverse  int32 [N] point -> voxel row
         nbr       int32 [27, V] neighbour table of the rows over themselves
+        table     the hash table of the rows (ops.HashTable; None for an empty grid): what ops.kmap_build probes for foreign cells
     Points of different scenes never share or neighbour a voxel.  A coordinate outside the packable range raises."""
 
     def __init__(self, xyz, offsets=None, voxel_size=0.05, connectivity=26):
@@ -56,6 +57,7 @@ class VoxelGrid:
             self.coords = torch.empty((0, 4), dtype=torch.int32, device=dev)
             self.inverse = torch.empty(0, dtype=torch.int32, device=dev)
             self.nbr = torch.empty((27, 0), dtype=torch.int32, device=dev)
+            self.table = None
             return
         cell = torch.floor(xyz.detach().double() / voxel_size)
         if not bool(((cell > -COORD_LIMIT) & (cell < COORD_LIMIT)).all()):          # (NaN and inf fail it too)
@@ -64,10 +66,10 @@ class VoxelGrid:
         rows = torch.tensor([b - a for a, b in zip(offsets[:-1], offsets[1:])], dtype=torch.int64).to(dev)
         scene = torch.repeat_interleave(torch.arange(len(offsets) - 1, device=dev), rows, output_size=n)
         coords4 = torch.cat([scene.to(torch.int32)[:, None], cell.to(torch.int32)], 1).contiguous()
-        self.coords, self.inverse, _first, table = ops.coords_unique(coords4)
+        self.coords, self.inverse, _first, self.table = ops.coords_unique(coords4)
         self.coords = self.coords.contiguous()
         self.inverse = self.inverse.contiguous()
-        self.nbr = ops.kmap_build(table, self.coords, 3, 1, self_map=True)
+        self.nbr = ops.kmap_build(self.table, self.coords, 3, 1, self_map=True)
 
     @classmethod
     def from_scenes(cls, scenes, voxel_size=0.05, connectivity=26):

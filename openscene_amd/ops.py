@@ -2072,6 +2072,163 @@ def render_shade(zbuf, n, mode=None, colors=None, values=None, column=0, table=N
     return point_id, depth, rgb
 
 
+# ------------------------------------------------------------------- neighbours
+KNN_MAX_K = 16
+KNN_E_ORDER, KNN_E_CELL, KNN_E_POINT, KNN_E_NEIGHBOR = 1, 2, 4, 8      # the bits of the err word (csrc/neighbors.hip)
+
+
+def knn_check(err):
+    """Raise if a neighbour call recorded an entry out of range in `err` (int32 [1]); zeroes the word.  Synchronises."""
+    bits = int(err.item())
+    if bits == 0:
+        return
+    err.zero_()
+    what = [text for bit, text in ((KNN_E_ORDER, "an order entry outside [0, M)"),
+                                   (KNN_E_CELL, "a cell column or a table entry out of range"),
+                                   (KNN_E_POINT, "a cell's list range or point out of range"),
+                                   (KNN_E_NEIGHBOR, "a neighbour index or count out of range")) if bits & bit]
+    raise _lib.OpenSceneAmdError("neighbours: %s (err bits %d); such entries were skipped" % ("; ".join(what) or "unknown error", bits))
+
+
+def _knn_vec(t, name, dtype, shape, dev, optional=False):
+    if t is None and optional:
+        return
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype:
+        raise TypeError("%s must be a %s tensor" % (name, str(dtype).replace("torch.", "")))
+    if tuple(t.shape) != tuple(shape) or t.device != dev or not t.is_contiguous():
+        raise ValueError("%s must be a contiguous %s %s tensor on the points' device" % (name, str(dtype).replace("torch.", ""), list(shape)))
+
+
+def knn_k(k):
+    k = int(k)
+    if not 1 <= k <= KNN_MAX_K:
+        raise ValueError("k must be in 1 .. %d (got %d)" % (KNN_MAX_K, k))
+    return k
+
+
+def knn_grid(xyz, cell_start, cell_points, nbr, query_xyz, q_cell, k, r2, exclude=None, order=None, err=None):
+    """The k nearest source points of every query inside the 27 cells around it.
+    xyz float32 [N, 3] the grid's points; cell_start int32 [V + 1] / cell_points int32 [n_src]: the CSR of the SOURCE points
+    per voxel row; nbr int32 [27, C] the voxel rows around each cell column (-1 absent); query_xyz float32 [M, 3]; q_cell
+    int32 [M] the column of each query (-1: no neighbours); exclude int32 [M] a point never returned, or None; order int32
+    [M] the sequence the lanes take the queries in (cell order), or None; 1 <= k <= 16; r2 the float32 squared radius.
+    -> (idx int32 [M, k] (-1 past count), dist2 float32 [M, k] (+inf past count), count int32 [M]): ascending (d2, index)
+    over the candidates with d2 <= r2, d2 from separately rounded float32 operations.  Exact and bitwise repeatable.  An
+    entry out of range is skipped and recorded in `err` when one is given (knn_check raises), and checked here otherwise."""
+    if not isinstance(xyz, torch.Tensor) or xyz.dtype != torch.float32:
+        raise TypeError("xyz must be a float32 tensor")
+    dev = xyz.device
+    if xyz.dim() != 2 or xyz.shape[1] != 3 or not xyz.is_contiguous():
+        raise ValueError("xyz must be a contiguous float32 [N, 3] matrix")
+    n = xyz.shape[0]
+    if not isinstance(cell_start, torch.Tensor) or cell_start.dtype != torch.int32:
+        raise TypeError("cell_start must be an int32 tensor")
+    if cell_start.dim() != 1 or cell_start.shape[0] < 1 or cell_start.device != dev or not cell_start.is_contiguous():
+        raise ValueError("cell_start must be a contiguous int32 [V + 1] vector on the points' device")
+    v = cell_start.shape[0] - 1
+    if not isinstance(cell_points, torch.Tensor) or cell_points.dtype != torch.int32:
+        raise TypeError("cell_points must be an int32 tensor")
+    if cell_points.dim() != 1 or cell_points.shape[0] > n or cell_points.device != dev or not cell_points.is_contiguous():
+        raise ValueError("cell_points must be a contiguous int32 vector of at most %d entries on the points' device" % n)
+    if not isinstance(nbr, torch.Tensor) or nbr.dtype != torch.int32:
+        raise TypeError("nbr must be an int32 tensor")
+    if nbr.dim() != 2 or nbr.shape[0] != 27 or nbr.device != dev or not nbr.is_contiguous():
+        raise ValueError("nbr must be a contiguous int32 [27, C] table on the points' device")
+    if not isinstance(query_xyz, torch.Tensor) or query_xyz.dtype != torch.float32:
+        raise TypeError("query_xyz must be a float32 tensor")
+    if query_xyz.dim() != 2 or query_xyz.shape[1] != 3 or query_xyz.device != dev or not query_xyz.is_contiguous():
+        raise ValueError("query_xyz must be a contiguous float32 [M, 3] matrix on the points' device")
+    m = query_xyz.shape[0]
+    if m >= (1 << 31) // KNN_MAX_K:
+        raise ValueError("fewer than 2^27 queries per call (got %d)" % m)
+    _knn_vec(q_cell, "q_cell", torch.int32, (m,), dev)
+    _knn_vec(exclude, "exclude", torch.int32, (m,), dev, optional=True)
+    _knn_vec(order, "order", torch.int32, (m,), dev, optional=True)
+    k = knn_k(k)
+    r2 = float(r2)
+    if not (r2 >= 0.0 and r2 != float("inf")):
+        raise ValueError("r2 must be finite and >= 0 (got %r)" % (r2,))
+    err, own = _regions_err(err, dev)
+    lib = _prep(dev)                              # (after the checks: they hold without a device)
+    idx = torch.empty((m, k), dtype=torch.int32, device=dev)
+    dist2 = torch.empty((m, k), dtype=torch.float32, device=dev)
+    count = torch.empty(m, dtype=torch.int32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_knn_grid(_p(xyz), n, _p(cell_start), _p(cell_points), cell_points.shape[0], v, _p(nbr), nbr.shape[1],
+                               _p(query_xyz), _p(q_cell), _p(exclude), _p(order), m, k, r2, _p(idx), _p(dist2), _p(count), _p(err),
+                               _stream(dev)), "osn_knn_grid")
+    if own and m > 0:
+        knn_check(err)
+    return idx, dist2, count
+
+
+def knn_blend(values, idx, dist2, count, inverse=False, eps=0.0, fill=0.0, err=None):
+    """Blend rows of `values` along neighbour lists: out[m] = sum_j w_j values[idx[m, j]] / sum_j w_j over j < count[m] in
+    ascending j, w_j = 1 or (inverse) 1 / (dist2[m, j] + eps); float32 products, sums and divide, rounded once to the values'
+    type.  values fp16 / fp32 [N, C], C >= 1; idx int32 [M, k], dist2 float32 [M, k], count int32 [M] as knn_grid returns
+    them.  -> (out [M, C] in the values' type, found bool [M]); count == 0 gives `fill` and found False.  k = 1 without
+    inverse copies the row bit for bit.  `err` as knn_grid."""
+    if not isinstance(values, torch.Tensor) or values.dtype not in (torch.float16, torch.float32):
+        raise TypeError("values must be a float16 or float32 tensor (got %s)"
+                        % (values.dtype if isinstance(values, torch.Tensor) else type(values).__name__))
+    dev = values.device
+    if values.dim() != 2 or values.shape[1] < 1 or not values.is_contiguous():
+        raise ValueError("values must be a contiguous [N, C] matrix with C >= 1")
+    n, c = values.shape
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32:
+        raise TypeError("idx must be an int32 tensor")
+    if idx.dim() != 2 or idx.device != dev or not idx.is_contiguous():
+        raise ValueError("idx must be a contiguous int32 [M, k] matrix on the values' device")
+    m, k = idx.shape
+    k = knn_k(k)
+    if m >= (1 << 31) // KNN_MAX_K:
+        raise ValueError("fewer than 2^27 queries per call (got %d)" % m)
+    _knn_vec(dist2, "dist2", torch.float32, (m, k), dev)
+    _knn_vec(count, "count", torch.int32, (m,), dev)
+    eps, fill = float(eps), float(fill)
+    if inverse and not (eps > 0.0 and eps != float("inf")):
+        raise ValueError("inverse weights need a finite eps > 0 (got %r)" % (eps,))
+    err, own = _regions_err(err, dev)
+    lib = _prep(dev)
+    out = torch.empty((m, c), dtype=values.dtype, device=dev)
+    found = torch.empty(m, dtype=torch.bool, device=dev)
+    with _Dev(dev):
+        check(lib.osn_knn_blend(_p(values), values.element_size(), n, c, _p(idx), _p(dist2), _p(count), m, k, int(bool(inverse)), eps,
+                                fill, _p(out), _p(found), _p(err), _stream(dev)), "osn_knn_blend")
+    if own and m > 0:
+        knn_check(err)
+    return out, found
+
+
+def knn_vote(labels, idx, count, fill=-1, err=None):
+    """The label most of a query's neighbours hold.  labels int64 [N] (negative: ignored); idx int32 [M, k], count int32 [M].
+    -> int64 [M]: a tie goes to the label whose first holder is nearest (the smallest j); `fill` without a labelled
+    neighbour.  Exact.  `err` as knn_grid."""
+    if not isinstance(labels, torch.Tensor) or labels.dtype != torch.int64:
+        raise TypeError("labels must be an int64 tensor")
+    dev = labels.device
+    if labels.dim() != 1 or not labels.is_contiguous():
+        raise ValueError("labels must be a contiguous int64 [N] vector")
+    if not isinstance(idx, torch.Tensor) or idx.dtype != torch.int32:
+        raise TypeError("idx must be an int32 tensor")
+    if idx.dim() != 2 or idx.device != dev or not idx.is_contiguous():
+        raise ValueError("idx must be a contiguous int32 [M, k] matrix on the labels' device")
+    m, k = idx.shape
+    k = knn_k(k)
+    if m >= (1 << 31) // KNN_MAX_K:
+        raise ValueError("fewer than 2^27 queries per call (got %d)" % m)
+    _knn_vec(count, "count", torch.int32, (m,), dev)
+    fill = int(fill)
+    err, own = _regions_err(err, dev)
+    lib = _prep(dev)
+    out = torch.empty(m, dtype=torch.int64, device=dev)
+    with _Dev(dev):
+        check(lib.osn_knn_vote(_p(labels), labels.shape[0], _p(idx), _p(count), m, k, fill, _p(out), _p(err), _stream(dev)), "osn_knn_vote")
+    if own and m > 0:
+        knn_check(err)
+    return out
+
+
 # ------------------------------------------------- supervised segmentation head: cross-entropy, argmax, confusion, votes
 def _seg_index(t, name, n, dev):
     if t.dtype != torch.int64 or t.dim() != 1 or t.device != dev or (n is not None and t.shape[0] != n):
