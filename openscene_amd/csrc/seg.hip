@@ -65,6 +65,10 @@ struct SegRow {
             if (k < c && k != bi) s += expf(v[t] - m);
         }
         s1 = group_sum<G>(s);
+        // A maximum that is not finite (+inf; -inf: every logit is -inf; the lone NaN of c = 1) has no softmax: torch's row loss
+        // and every element of the row's gradient are NaN.  Left alone, a +inf row has s1 = 0 (exp(-inf) elsewhere, the argmax
+        // kept out): a finite gradient from an overflowed logit.  Rows with a finite maximum keep their bits.
+        if (!(fabsf(m) < INFINITY)) s1 = __builtin_nanf("");
     }
 
     __device__ inline float at(int y, int g) const {      // x[y] (every lane of the group gets it)
@@ -110,7 +114,7 @@ __global__ __launch_bounds__(SEG_THREADS) void seg_fwd_kernel(const float* __res
         if (g == 0) {
             if (pred) pred[j] = row.bi == 0x7fffffff ? 0 : row.bi;
             if (lab) {
-                acc += double((row.m - xy) + log1pf(row.s1));    // m - x[y] is exact (Sterbenz)
+                acc += double((row.m - xy) + log1pf(row.s1));    // (m - x[y]: exact by Sterbenz while m / 2 <= x[y], else one rounding)
                 ++cnt;
                 if (conf) {
                     const int cell = row.bi * c + int(y);
