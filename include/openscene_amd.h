@@ -406,6 +406,11 @@ int osn_bn_backward_multi(const float* x, const float* y, const float* const* gy
                           int64_t n, int c, void* ws, size_t ws_bytes, osn_stream_t stream);
 /* the same with `beta`: for a batch norm + ReLU WITHOUT a residual, y may be null -- the mask (y > 0) is recomputed from x
  * with the forward pass's own expression, so neither backward pass reads y (models/resnet_base.py:98: bn -> relu)       */
+/* gres (a batch norm with a residual): the column-sum pass stores g = the masked sum of the sources to gres and the apply pass
+ * reads it back instead of forming it a second time from y and the sources.  ALIASING RULE: that data flow is used only when
+ * gres [n, c] overlaps none of x, y, gx and the gradient sources (each source's range is (n - 1) * ld + c floats); a gres that
+ * overlaps any of them (e.g. gres written in place over source 0) takes the earlier flow, in which both passes form g and
+ * the apply pass writes gres element by element.  Every output is bit for bit the same on both flows.                    */
 int osn_bn_backward_multi2(const float* x, const float* y, const float* const* gy_host, const int64_t* gy_ld_host, int n_gy,
                            const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu,
                            int training, float* gx, float* gres, float* ggamma, float* gbeta, int64_t n, int c, void* ws,

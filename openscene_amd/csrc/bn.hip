@@ -56,12 +56,16 @@ static ColReducePlan plan_colreduce(int64_t n, int c) {
 }
 
 // MODE 0: (sum x, sum x^2)        MODE 1: (sum g, sum g*xhat), g = relu ? gy*(y>0) : gy
-template <int MODE>
-__global__ __launch_bounds__(256) void col_reduce_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                         const GySrc gy, const float* __restrict__ mean,
-                                                         const float* __restrict__ var, float eps, int relu, int64_t n,
-                                                         int c, int rows_per_block, double* __restrict__ partial,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta) {
+// STORE_G (MODE 1, a batch norm with a residual): the masked g this pass already holds is stored as gres -- the value the apply
+// pass used to form a second time from y and the sources -- and bn_bwd_apply_gres_kernel reads it back: one read of y and of
+// every source less per residual norm.  Every (row, column) is visited by exactly one thread, so gres is written once.
+template <int MODE, bool STORE_G>
+__device__ __forceinline__ void col_reduce_body(const float* __restrict__ x, const float* __restrict__ y, const GySrc gy,
+                                                const float* __restrict__ mean, const float* __restrict__ var, float eps,
+                                                int relu, int64_t n, int c, int rows_per_block, double* __restrict__ partial,
+                                                const float* __restrict__ gamma, const float* __restrict__ beta,
+                                                float* __restrict__ gres) {
+    static_assert(!STORE_G || MODE == 1, "only the backward sums form g");
     __shared__ double red[2][CR_RL][CR_COLS];
     const int tid = threadIdx.x;
     const int cl = tid & 15, rl = tid >> 4;
@@ -72,7 +76,7 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const float* __restrict
     double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
     float4 mu = make_float4(0, 0, 0, 0), is = make_float4(0, 0, 0, 0);
     float4 ga = make_float4(0, 0, 0, 0), be = make_float4(0, 0, 0, 0);
-    const bool from_x = MODE == 1 && relu && !y;             // the ReLU mask recomputed from x (no residual): y is not read
+    const bool from_x = MODE == 1 && !STORE_G && relu && !y; // the ReLU mask recomputed from x (no residual): y is not read
     if (MODE == 1 && on) {
         mu = *reinterpret_cast<const float4*>(mean + col);
         const float4 v = *reinterpret_cast<const float4*>(var + col);
@@ -101,6 +105,7 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const float* __restrict
                     g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f;
                     g.z = yv.z > 0.f ? g.z : 0.f; g.w = yv.w > 0.f ? g.w : 0.f;
                 }
+                if (STORE_G) *reinterpret_cast<float4*>(gres + r * c + col) = g;
                 s1[0] += g.x; s1[1] += g.y; s1[2] += g.z; s1[3] += g.w;
                 s2[0] += double(g.x) * ((xv.x - mu.x) * is.x); s2[1] += double(g.y) * ((xv.y - mu.y) * is.y);
                 s2[2] += double(g.z) * ((xv.z - mu.z) * is.z); s2[3] += double(g.w) * ((xv.w - mu.w) * is.w);
@@ -121,6 +126,23 @@ __global__ __launch_bounds__(256) void col_reduce_kernel(const float* __restrict
         const int gc = blockIdx.y * CR_COLS + cc;
         if (gc < c) partial[(int64_t(blockIdx.x) * 2 + which) * c + gc] = s;
     }
+}
+
+template <int MODE>
+__global__ __launch_bounds__(256) void col_reduce_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                         const GySrc gy, const float* __restrict__ mean,
+                                                         const float* __restrict__ var, float eps, int relu, int64_t n,
+                                                         int c, int rows_per_block, double* __restrict__ partial,
+                                                         const float* __restrict__ gamma, const float* __restrict__ beta) {
+    col_reduce_body<MODE, false>(x, y, gy, mean, var, eps, relu, n, c, rows_per_block, partial, gamma, beta, nullptr);
+}
+
+__global__ __launch_bounds__(256) void col_reduce_gres_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                              const GySrc gy, const float* __restrict__ mean,
+                                                              const float* __restrict__ var, float eps, int relu, int64_t n,
+                                                              int c, int rows_per_block, double* __restrict__ partial,
+                                                              float* __restrict__ gres) {
+    col_reduce_body<1, true>(x, y, gy, mean, var, eps, relu, n, c, rows_per_block, partial, nullptr, nullptr, gres);
 }
 
 // Final column sums: 64 columns x 16 slices of the partial blocks per workgroup
@@ -238,23 +260,25 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
     }
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                           const GySrc gy, const float* __restrict__ mean,
-                                                           const float* __restrict__ var, const float* __restrict__ gamma,
-                                                           float eps, int relu, int training,
-                                                           const float* __restrict__ sum_g,
-                                                           const float* __restrict__ sum_gx, float inv_n,
-                                                           float* __restrict__ gx, float* __restrict__ gres,
-                                                           int64_t total4, int c4, const float* __restrict__ beta) {
-    const bool from_x = relu && !y;                          // ReLU mask recomputed from x: one tensor less to read
+// LOAD_G: g was stored to gres by col_reduce_gres_kernel; y and the sources are not read and gres is not written.
+template <bool LOAD_G>
+__device__ __forceinline__ void bn_bwd_apply_body(const float* __restrict__ x, const float* __restrict__ y, const GySrc& gy,
+                                                  const float* __restrict__ mean, const float* __restrict__ var,
+                                                  const float* __restrict__ gamma, float eps, int relu, int training,
+                                                  const float* __restrict__ sum_g, const float* __restrict__ sum_gx, float inv_n,
+                                                  float* __restrict__ gx, float* __restrict__ gres, int64_t total4, int c4,
+                                                  const float* __restrict__ beta) {
+    const bool from_x = !LOAD_G && relu && !y;               // ReLU mask recomputed from x: one tensor less to read
     for (int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; e < total4; e += int64_t(gridDim.x) * blockDim.x) {
         const int col = int(e % c4) * 4;
-        float4 g = gy_load(gy, e / c4, col);
+        float4 g = LOAD_G ? ld4(gres + e * 4) : gy_load(gy, e / c4, col);
         const float4 vv = ld4(var + col), ga = ld4(gamma + col);
         const float4 is = make_float4(bn_is(vv.x, eps), bn_is(vv.y, eps), bn_is(vv.z, eps), bn_is(vv.w, eps));
         float4 xv = make_float4(0, 0, 0, 0), mu = make_float4(0, 0, 0, 0);
         if (training || from_x) { xv = ld4(x + e * 4); mu = ld4(mean + col); }
-        if (from_x) {
+        if (LOAD_G) {
+            // (already summed and masked)
+        } else if (from_x) {
             const float4 be = ld4(beta + col);
             g.x = bn_val(xv.x, mu.x, is.x, ga.x, be.x) > 0.f ? g.x : 0.f;
             g.y = bn_val(xv.y, mu.y, is.y, ga.y, be.y) > 0.f ? g.y : 0.f;
@@ -265,7 +289,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
             g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f;
             g.z = yv.z > 0.f ? g.z : 0.f; g.w = yv.w > 0.f ? g.w : 0.f;
         }
-        if (gres) *reinterpret_cast<float4*>(gres + e * 4) = g;
+        if (!LOAD_G && gres) *reinterpret_cast<float4*>(gres + e * 4) = g;
         float4 o;
         if (training) {
             const float4 sg = ld4(sum_g + col), sx = ld4(sum_gx + col);
@@ -278,6 +302,27 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restri
         }
         *reinterpret_cast<float4*>(gx + e * 4) = o;
     }
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                           const GySrc gy, const float* __restrict__ mean,
+                                                           const float* __restrict__ var, const float* __restrict__ gamma,
+                                                           float eps, int relu, int training,
+                                                           const float* __restrict__ sum_g,
+                                                           const float* __restrict__ sum_gx, float inv_n,
+                                                           float* __restrict__ gx, float* __restrict__ gres,
+                                                           int64_t total4, int c4, const float* __restrict__ beta) {
+    bn_bwd_apply_body<false>(x, y, gy, mean, var, gamma, eps, relu, training, sum_g, sum_gx, inv_n, gx, gres, total4, c4, beta);
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_apply_gres_kernel(const float* __restrict__ x, const float* __restrict__ mean,
+                                                                const float* __restrict__ var, const float* __restrict__ gamma,
+                                                                float eps, int training, const float* __restrict__ sum_g,
+                                                                const float* __restrict__ sum_gx, float inv_n,
+                                                                float* __restrict__ gx, const float* __restrict__ gres,
+                                                                int64_t total4, int c4) {
+    bn_bwd_apply_body<true>(x, nullptr, GySrc{}, mean, var, gamma, eps, 0, training, sum_g, sum_gx, inv_n, gx,
+                            const_cast<float*>(gres), total4, c4, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -388,6 +433,12 @@ __global__ __launch_bounds__(SB_THREADS) void bn_small_fwd_kernel(const float* _
         *reinterpret_cast<float4*>(y + int64_t(r) * c + col) = o;
         if (y2) *reinterpret_cast<float4*>(y2 + int64_t(r) * ld2 + col) = o;
     }
+}
+
+// [a, a + na) and [b, b + nb) floats share an address
+static bool ranges_overlap(const float* a, size_t na, const float* b, size_t nb) {
+    const uintptr_t a0 = reinterpret_cast<uintptr_t>(a), b0 = reinterpret_cast<uintptr_t>(b);
+    return a0 < b0 + nb * sizeof(float) && b0 < a0 + na * sizeof(float);
 }
 
 static int ew_grid(int64_t total4) {
@@ -511,13 +562,29 @@ extern "C" int osn_bn_backward_multi2(const float* x, const float* y, const floa
     const size_t need = size_t(p.n_rb) * 2 * size_t(c) * 8;
     OSN_REQUIRE(ws && ws_bytes >= need, OSN_E_WS, "osn_bn_backward: workspace %zu < %zu", ws_bytes, need);
     double* partial = static_cast<double*>(ws);
-    hipLaunchKernelGGL((col_reduce_kernel<1>), dim3(p.n_rb, p.n_cg), dim3(256), 0, st, x, y, src, mean, var, eps, relu, n,
-                       c, p.rows_per_block, partial, gamma, beta);
+    // A residual's gradient is stored by the reduction and read back by the apply pass -- unless gres overlaps x, y, gx or a
+    // source: the reduction would then overwrite rows another workgroup has yet to read, so the apply pass forms g itself as before.
+    const size_t span = size_t(n) * size_t(c);
+    bool via_gres = gres != nullptr && !ranges_overlap(gres, span, x, span) && !(y && ranges_overlap(gres, span, y, span)) &&
+                    !ranges_overlap(gres, span, gx, span);
+    for (int i = 0; via_gres && i < n_gy; ++i)
+        via_gres = !ranges_overlap(gres, span, src.p[i], size_t(n - 1) * size_t(src.ld[i]) + size_t(c));
+    const dim3 rgrid(p.n_rb, p.n_cg);
+    if (via_gres)
+        hipLaunchKernelGGL(col_reduce_gres_kernel, rgrid, dim3(256), 0, st, x, y, src, mean, var, eps, relu, n, c,
+                           p.rows_per_block, partial, gres);
+    else
+        hipLaunchKernelGGL((col_reduce_kernel<1>), rgrid, dim3(256), 0, st, x, y, src, mean, var, eps, relu, n, c,
+                           p.rows_per_block, partial, gamma, beta);
     // ggamma = sum g*xhat, gbeta = sum g  (also the two column sums the apply pass needs)
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(c, FIN_COLS)), dim3(FIN_COLS * FIN_PARTS), 0, st, partial, p.n_rb, c, gbeta, ggamma);
     const int64_t total4 = n * (c / 4);
-    hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, st, x, y, src, mean, var, gamma, eps,
-                       relu, training, gbeta, ggamma, 1.f / float(n), gx, gres, total4, c / 4, beta);
+    if (via_gres)
+        hipLaunchKernelGGL(bn_bwd_apply_gres_kernel, dim3(ew_grid(total4)), dim3(256), 0, st, x, mean, var, gamma, eps, training,
+                           gbeta, ggamma, 1.f / float(n), gx, (const float*)gres, total4, c / 4);
+    else
+        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, st, x, y, src, mean, var, gamma, eps,
+                           relu, training, gbeta, ggamma, 1.f / float(n), gx, gres, total4, c / 4, beta);
     OSN_LAUNCH_CHECK();
     return OSN_OK;
 }

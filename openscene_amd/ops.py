@@ -1058,9 +1058,11 @@ def bn_forward_train2(x, gamma, beta, eps, residual, relu, running_mean, running
     return y, mv[0], mv[1]
 
 
-def bn_backward_multi(x, y, gys, mean, var, gamma, eps, relu, training, want_gres, beta=None):
+def bn_backward_multi(x, y, gys, mean, var, gamma, eps, relu, training, want_gres, beta=None, gres_out=None):
     """bn_backward whose incoming gradient is the SUM of the matrices in `gys` (1 .. 3, each possibly a column window of a
-    wider matrix): the sum is formed while reading.  y None with relu needs beta (mask recomputed from x; no residual)."""
+    wider matrix): the sum is formed while reading.  y None with relu needs beta (mask recomputed from x; no residual).
+    gres_out: a contiguous float32 [n, c] destination for gres (with want_gres) instead of a new tensor; it may be one of the
+    contiguous sources itself (include/openscene_amd.h, osn_bn_backward_multi2: the aliasing rule)."""
     dev = x.device
     lib = _prep(dev)
     n, c = x.shape
@@ -1070,7 +1072,10 @@ def bn_backward_multi(x, y, gys, mean, var, gamma, eps, relu, training, want_gre
     ptrs = (ctypes.c_void_p * len(views))(*[v[0] for v in views])
     lds = (ctypes.c_int64 * len(views))(*[v[1] for v in views])
     gx = torch.empty_like(x)
-    gres = torch.empty_like(x) if want_gres else None
+    if gres_out is not None and (not want_gres or gres_out.dtype != torch.float32 or gres_out.shape != x.shape or
+                                 gres_out.device != dev or not gres_out.is_contiguous()):
+        raise ValueError("gres_out must be a contiguous float32 tensor shaped like x, on its device, and needs want_gres")
+    gres = (gres_out if gres_out is not None else torch.empty_like(x)) if want_gres else None
     ggamma = torch.empty(c, dtype=torch.float32, device=dev)
     gbeta = torch.empty(c, dtype=torch.float32, device=dev)
     ws = _ws(_cached("osn_bn_ws_bytes", n, c), dev)
