@@ -416,6 +416,17 @@ int osn_bn_backward_multi2(const float* x, const float* y, const float* const* g
                            int training, float* gx, float* gres, float* ggamma, float* gbeta, int64_t n, int c, void* ws,
                            size_t ws_bytes, osn_stream_t stream);
 
+/* The launch plan of the apply kernels (osn_bn_apply2, the apply pass of osn_bn_backward_multi2) for total4 = n * c / 4 quads of
+ * c4 = c / 4 column quads: *grid = workgroups of 256 threads.  *flat = 0: grid * 256 is a multiple of c4 -- the smallest such grid
+ * >= min(2048, ceil(total4 / 256)), at most 127 above it -- and every thread keeps its column quad (per-column constants and the
+ * four 1 / sqrt(var + eps) taken once per thread).  *flat = 1: no such grid (wide odd c4); the flat kernels, which take column and
+ * constants again for every quad, run on min(2048, ceil(total4 / 256)) workgroups.  Host only, no device needed.            */
+int osn_bn_apply_plan(int64_t total4, int c4, int* grid, int* flat);
+/* Tests and A/B only, process-wide: on != 0 runs the batch-norm kernels of the earlier rounds -- the flat apply kernels whatever
+ * the plan says, and column sums with one row in flight per thread.  Every result is bit for bit the same either way.
+ * Returns the previous setting.                                                                                              */
+int osn_bn_set_flat_kernels(int on);
+
 /* ---- distillation loss on the supervised rows ------------------------------- *
  * Replaces run/distill.py:322-328 and its autograd chain:
  *     output_3d = output_3d[mask]

@@ -8,6 +8,8 @@
 #include "common.h"
 #include "epilogue.h"
 
+#include <atomic>
+
 namespace osn {
 
 constexpr int CR_COLS = 64;    // columns per block (16 lanes x float4)
@@ -55,17 +57,55 @@ static ColReducePlan plan_colreduce(int64_t n, int c) {
     return p;
 }
 
+__device__ inline float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+
+// Rows a thread of the column sums keeps IN FLIGHT (its rows r, r + 16, ...: all their loads are issued before the first add).
+// With one row per thread a CU holds ~16 KB of loads and the kernel runs at a third of the HBM roof, for as long as the loaded
+// latency -- which the weight-gradient stream beside it raises.  Per instance: a row costs one quad of
+// VGPRs in the statistics pass and 2 - 5 (x, the sources, y) in the backward passes.  1 = the loop of the earlier rounds.
+#ifndef OSN_BN_ROWS_STATS
+#define OSN_BN_ROWS_STATS 4
+#endif
+#ifndef OSN_BN_ROWS_BWD
+#define OSN_BN_ROWS_BWD 2
+#endif
+#ifndef OSN_BN_ROWS_GRES
+#define OSN_BN_ROWS_GRES 2
+#endif
+
+// one row's operands as they arrive (the sources are added afterwards, in gy_load's order)
+struct CrRow {
+    float4 x, y, g[BN_MAX_SRC];
+};
+
+template <int MODE>
+__device__ __forceinline__ void cr_load(CrRow& w, const float* __restrict__ x, const float* __restrict__ y, const GySrc& gy,
+                                        bool need_y, int64_t r, int c, int col) {
+    w.x = ld4(x + r * c + col);
+    if (MODE == 1) {
+        w.g[0] = ld4(gy.p[0] + r * gy.ld[0] + col);
+#pragma unroll
+        for (int i = 1; i < BN_MAX_SRC; ++i)
+            if (i < gy.n) w.g[i] = ld4(gy.p[i] + r * gy.ld[i] + col);
+        if (need_y) w.y = ld4(y + r * c + col);
+    }
+}
+
 // MODE 0: (sum x, sum x^2)        MODE 1: (sum g, sum g*xhat), g = relu ? gy*(y>0) : gy
 // STORE_G (MODE 1, a batch norm with a residual): the masked g this pass already holds is stored as gres -- the value the apply
 // pass used to form a second time from y and the sources -- and bn_bwd_apply_gres_kernel reads it back: one read of y and of
 // every source less per residual norm.  Every (row, column) is visited by exactly one thread, so gres is written once.
-template <int MODE, bool STORE_G>
+// R rows in flight: the loads of rows r, r + 16, ... r + 16 (R - 1) first, then the adds in row order into the same accumulators
+// -- every sum is formed in the order of the one-row loop, bit for bit.  A ragged last round loads its missing rows from row r
+// (an address inside the matrix) and does not add them.
+template <int MODE, bool STORE_G, int R>
 __device__ __forceinline__ void col_reduce_body(const float* __restrict__ x, const float* __restrict__ y, const GySrc gy,
                                                 const float* __restrict__ mean, const float* __restrict__ var, float eps,
                                                 int relu, int64_t n, int c, int rows_per_block, double* __restrict__ partial,
                                                 const float* __restrict__ gamma, const float* __restrict__ beta,
                                                 float* __restrict__ gres) {
     static_assert(!STORE_G || MODE == 1, "only the backward sums form g");
+    static_assert(R >= 1 && R <= 4, "rows in flight");
     __shared__ double red[2][CR_RL][CR_COLS];
     const int tid = threadIdx.x;
     const int cl = tid & 15, rl = tid >> 4;
@@ -77,6 +117,7 @@ __device__ __forceinline__ void col_reduce_body(const float* __restrict__ x, con
     float4 mu = make_float4(0, 0, 0, 0), is = make_float4(0, 0, 0, 0);
     float4 ga = make_float4(0, 0, 0, 0), be = make_float4(0, 0, 0, 0);
     const bool from_x = MODE == 1 && !STORE_G && relu && !y; // the ReLU mask recomputed from x (no residual): y is not read
+    const bool need_y = MODE == 1 && relu && !from_x;
     if (MODE == 1 && on) {
         mu = *reinterpret_cast<const float4*>(mean + col);
         const float4 v = *reinterpret_cast<const float4*>(var + col);
@@ -86,29 +127,53 @@ __device__ __forceinline__ void col_reduce_body(const float* __restrict__ x, con
             be = *reinterpret_cast<const float4*>(beta + col);
         }
     }
+    auto add_row = [&](const CrRow& w, int64_t r) {
+        const float4 xv = w.x;
+        if (MODE == 0) {
+            s1[0] += xv.x; s1[1] += xv.y; s1[2] += xv.z; s1[3] += xv.w;
+            s2[0] += double(xv.x) * xv.x; s2[1] += double(xv.y) * xv.y;
+            s2[2] += double(xv.z) * xv.z; s2[3] += double(xv.w) * xv.w;
+        } else {
+            float4 g = w.g[0];
+#pragma unroll
+            for (int i = 1; i < BN_MAX_SRC; ++i)
+                if (i < gy.n) { g.x += w.g[i].x; g.y += w.g[i].y; g.z += w.g[i].z; g.w += w.g[i].w; }
+            if (from_x) {
+                g.x = bn_val(xv.x, mu.x, is.x, ga.x, be.x) > 0.f ? g.x : 0.f;
+                g.y = bn_val(xv.y, mu.y, is.y, ga.y, be.y) > 0.f ? g.y : 0.f;
+                g.z = bn_val(xv.z, mu.z, is.z, ga.z, be.z) > 0.f ? g.z : 0.f;
+                g.w = bn_val(xv.w, mu.w, is.w, ga.w, be.w) > 0.f ? g.w : 0.f;
+            } else if (relu) {
+                const float4 yv = w.y;
+                g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f;
+                g.z = yv.z > 0.f ? g.z : 0.f; g.w = yv.w > 0.f ? g.w : 0.f;
+            }
+            if (STORE_G) *reinterpret_cast<float4*>(gres + r * c + col) = g;
+            s1[0] += g.x; s1[1] += g.y; s1[2] += g.z; s1[3] += g.w;
+            s2[0] += double(g.x) * ((xv.x - mu.x) * is.x); s2[1] += double(g.y) * ((xv.y - mu.y) * is.y);
+            s2[2] += double(g.z) * ((xv.z - mu.z) * is.z); s2[3] += double(g.w) * ((xv.w - mu.w) * is.w);
+        }
+    };
     if (on) {
-        for (int64_t r = r0 + rl; r < r1; r += CR_RL) {
-            const float4 xv = *reinterpret_cast<const float4*>(x + r * c + col);
-            if (MODE == 0) {
-                s1[0] += xv.x; s1[1] += xv.y; s1[2] += xv.z; s1[3] += xv.w;
-                s2[0] += double(xv.x) * xv.x; s2[1] += double(xv.y) * xv.y;
-                s2[2] += double(xv.z) * xv.z; s2[3] += double(xv.w) * xv.w;
-            } else {
-                float4 g = gy_load(gy, r, col);
-                if (from_x) {
-                    g.x = bn_val(xv.x, mu.x, is.x, ga.x, be.x) > 0.f ? g.x : 0.f;
-                    g.y = bn_val(xv.y, mu.y, is.y, ga.y, be.y) > 0.f ? g.y : 0.f;
-                    g.z = bn_val(xv.z, mu.z, is.z, ga.z, be.z) > 0.f ? g.z : 0.f;
-                    g.w = bn_val(xv.w, mu.w, is.w, ga.w, be.w) > 0.f ? g.w : 0.f;
-                } else if (relu) {
-                    const float4 yv = *reinterpret_cast<const float4*>(y + r * c + col);
-                    g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f;
-                    g.z = yv.z > 0.f ? g.z : 0.f; g.w = yv.w > 0.f ? g.w : 0.f;
+        int64_t r = r0 + rl;
+        for (; r + (R - 1) * CR_RL < r1; r += R * CR_RL) {
+            CrRow w[R];
+#pragma unroll
+            for (int k = 0; k < R; ++k) cr_load<MODE>(w[k], x, y, gy, need_y, r + k * CR_RL, c, col);
+#pragma unroll
+            for (int k = 0; k < R; ++k) add_row(w[k], r + k * CR_RL);
+        }
+        if constexpr (R > 1) {
+            if (r < r1) {                                    // ragged last round: 1 .. R - 1 rows
+                CrRow w[R - 1];
+#pragma unroll
+                for (int k = 0; k < R - 1; ++k) {
+                    const int64_t rk = r + k * CR_RL;
+                    cr_load<MODE>(w[k], x, y, gy, need_y, rk < r1 ? rk : r, c, col);
                 }
-                if (STORE_G) *reinterpret_cast<float4*>(gres + r * c + col) = g;
-                s1[0] += g.x; s1[1] += g.y; s1[2] += g.z; s1[3] += g.w;
-                s2[0] += double(g.x) * ((xv.x - mu.x) * is.x); s2[1] += double(g.y) * ((xv.y - mu.y) * is.y);
-                s2[2] += double(g.z) * ((xv.z - mu.z) * is.z); s2[3] += double(g.w) * ((xv.w - mu.w) * is.w);
+#pragma unroll
+                for (int k = 0; k < R - 1; ++k)
+                    if (r + k * CR_RL < r1) add_row(w[k], r + k * CR_RL);
             }
         }
     }
@@ -128,21 +193,30 @@ __device__ __forceinline__ void col_reduce_body(const float* __restrict__ x, con
     }
 }
 
+#define OSN_CR_PARAMS                                                                                                          \
+    const float *__restrict__ x, const float *__restrict__ y, const GySrc gy, const float *__restrict__ mean,                    \
+        const float *__restrict__ var, float eps, int relu, int64_t n, int c, int rows_per_block, double *__restrict__ partial
+
 template <int MODE>
-__global__ __launch_bounds__(256) void col_reduce_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                         const GySrc gy, const float* __restrict__ mean,
-                                                         const float* __restrict__ var, float eps, int relu, int64_t n,
-                                                         int c, int rows_per_block, double* __restrict__ partial,
-                                                         const float* __restrict__ gamma, const float* __restrict__ beta) {
-    col_reduce_body<MODE, false>(x, y, gy, mean, var, eps, relu, n, c, rows_per_block, partial, gamma, beta, nullptr);
+__global__ __launch_bounds__(256) void col_reduce_kernel(OSN_CR_PARAMS, const float* __restrict__ gamma,
+                                                         const float* __restrict__ beta) {
+    col_reduce_body<MODE, false, MODE == 0 ? OSN_BN_ROWS_STATS : OSN_BN_ROWS_BWD>(x, y, gy, mean, var, eps, relu, n, c, rows_per_block,
+                                                                                  partial, gamma, beta, nullptr);
 }
 
-__global__ __launch_bounds__(256) void col_reduce_gres_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                              const GySrc gy, const float* __restrict__ mean,
-                                                              const float* __restrict__ var, float eps, int relu, int64_t n,
-                                                              int c, int rows_per_block, double* __restrict__ partial,
-                                                              float* __restrict__ gres) {
-    col_reduce_body<1, true>(x, y, gy, mean, var, eps, relu, n, c, rows_per_block, partial, nullptr, nullptr, gres);
+__global__ __launch_bounds__(256) void col_reduce_gres_kernel(OSN_CR_PARAMS, float* __restrict__ gres) {
+    col_reduce_body<1, true, OSN_BN_ROWS_GRES>(x, y, gy, mean, var, eps, relu, n, c, rows_per_block, partial, nullptr, nullptr, gres);
+}
+
+// One row in flight: the loops of the earlier rounds, run by osn_bn_set_flat_kernels(1) (tests, A/B).
+template <int MODE>
+__global__ __launch_bounds__(256) void col_reduce_1row_kernel(OSN_CR_PARAMS, const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta) {
+    col_reduce_body<MODE, false, 1>(x, y, gy, mean, var, eps, relu, n, c, rows_per_block, partial, gamma, beta, nullptr);
+}
+
+__global__ __launch_bounds__(256) void col_reduce_gres_1row_kernel(OSN_CR_PARAMS, float* __restrict__ gres) {
+    col_reduce_body<1, true, 1>(x, y, gy, mean, var, eps, relu, n, c, rows_per_block, partial, nullptr, nullptr, gres);
 }
 
 // Final column sums: 64 columns x 16 slices of the partial blocks per workgroup
@@ -228,11 +302,11 @@ __global__ __launch_bounds__(FIN_COLS * FIN_PARTS) void bn_bwd_finalize_kernel(c
     sum_gx[j] = float(s2);
 }
 
-__device__ inline float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
 // (bn_val / bn_is / bn_relu: epilogue.h -- one definition shared with the convolution kernels' evaluation-mode epilogues)
 
-__global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
+// The FLAT apply kernels (a grid-stride walk over quads; column, constants and the four 1 / sqrt taken again for every quad): run where
+// no grid keeps a thread on its columns (plan_apply: wide odd c4) and by osn_bn_set_flat_kernels(1).
+__global__ __launch_bounds__(256) void bn_apply_flat_kernel(const float* __restrict__ x, const float* __restrict__ mean,
                                                        const float* __restrict__ var, const float* __restrict__ gamma,
                                                        const float* __restrict__ beta, float eps,
                                                        const float* __restrict__ residual, int relu,
@@ -262,7 +336,7 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__
 
 // LOAD_G: g was stored to gres by col_reduce_gres_kernel; y and the sources are not read and gres is not written.
 template <bool LOAD_G>
-__device__ __forceinline__ void bn_bwd_apply_body(const float* __restrict__ x, const float* __restrict__ y, const GySrc& gy,
+__device__ __forceinline__ void bn_bwd_apply_flat_body(const float* __restrict__ x, const float* __restrict__ y, const GySrc& gy,
                                                   const float* __restrict__ mean, const float* __restrict__ var,
                                                   const float* __restrict__ gamma, float eps, int relu, int training,
                                                   const float* __restrict__ sum_g, const float* __restrict__ sum_gx, float inv_n,
@@ -301,6 +375,158 @@ __device__ __forceinline__ void bn_bwd_apply_body(const float* __restrict__ x, c
             o.x = ga.x * is.x * g.x; o.y = ga.y * is.y * g.y; o.z = ga.z * is.z * g.z; o.w = ga.w * is.w * g.w;
         }
         *reinterpret_cast<float4*>(gx + e * 4) = o;
+    }
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_apply_flat_kernel(const float* __restrict__ x, const float* __restrict__ y,
+                                                           const GySrc gy, const float* __restrict__ mean,
+                                                           const float* __restrict__ var, const float* __restrict__ gamma,
+                                                           float eps, int relu, int training,
+                                                           const float* __restrict__ sum_g,
+                                                           const float* __restrict__ sum_gx, float inv_n,
+                                                           float* __restrict__ gx, float* __restrict__ gres,
+                                                           int64_t total4, int c4, const float* __restrict__ beta) {
+    bn_bwd_apply_flat_body<false>(x, y, gy, mean, var, gamma, eps, relu, training, sum_g, sum_gx, inv_n, gx, gres, total4, c4, beta);
+}
+
+__global__ __launch_bounds__(256) void bn_bwd_apply_gres_flat_kernel(const float* __restrict__ x, const float* __restrict__ mean,
+                                                                const float* __restrict__ var, const float* __restrict__ gamma,
+                                                                float eps, int training, const float* __restrict__ sum_g,
+                                                                const float* __restrict__ sum_gx, float inv_n,
+                                                                float* __restrict__ gx, const float* __restrict__ gres,
+                                                                int64_t total4, int c4) {
+    bn_bwd_apply_flat_body<true>(x, nullptr, GySrc{}, mean, var, gamma, eps, 0, training, sum_g, sum_gx, inv_n, gx,
+                            const_cast<float*>(gres), total4, c4, nullptr);
+}
+
+// The apply kernels whose threads KEEP THEIR COLUMNS: the launch plan (plan_apply) makes the grid's stride a multiple of c4, so a
+// thread's quads all lie in one column quad, `stride / c4` rows apart.  Column and first row come from one 32-bit division, mean,
+// bn_is(var), gamma, beta (backward: sum_g, sum_gx) are taken once, and the walk advances pointers.  Per quad that leaves the
+// loads that carry new data and the per-element arithmetic -- the flat kernels spend ~165 VALU instructions (8 transcendental,
+// 16 v_div_*) and 6 loads per quad on a forward pass, these 23 and 2 (profiles/r23_bn_rows_in_flight_resource_usage.txt).
+// Per-element expressions: those of the flat kernels; every element is read and then written by the same thread (in place is fine).
+__global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
+                                                       const float* __restrict__ var, const float* __restrict__ gamma,
+                                                       const float* __restrict__ beta, float eps,
+                                                       const float* __restrict__ residual, int relu,
+                                                       float* __restrict__ y, float* __restrict__ y2, int64_t ld2,
+                                                       int64_t total4, int c4) {
+    const unsigned e0 = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;        // stride % c4 == 0
+    if (e0 >= total4) return;
+    const unsigned row0 = e0 / unsigned(c4);
+    const int col = int(e0 - row0 * unsigned(c4)) * 4;
+    const int64_t rstep = stride / unsigned(c4), step = int64_t(stride) * 4;
+    const float4 mu = ld4(mean + col), vv = ld4(var + col), ga = ld4(gamma + col), be = ld4(beta + col);
+    const float4 is = make_float4(bn_is(vv.x, eps), bn_is(vv.y, eps), bn_is(vv.z, eps), bn_is(vv.w, eps));
+    const float* xp = x + int64_t(e0) * 4;
+    const float* rp = residual ? residual + int64_t(e0) * 4 : nullptr;
+    float* yp = y + int64_t(e0) * 4;
+    float* y2p = y2 ? y2 + int64_t(row0) * ld2 + col : nullptr;
+    for (int64_t e = e0; e < total4; e += stride) {
+        const float4 xv = ld4(xp);
+        float4 rv = make_float4(0, 0, 0, 0);
+        if (residual) {                                      // (issued with x, ahead of the arithmetic: one round trip per quad)
+            rv = ld4(rp);
+            rp += step;
+        }
+        float4 o;
+        o.x = bn_val(xv.x, mu.x, is.x, ga.x, be.x);
+        o.y = bn_val(xv.y, mu.y, is.y, ga.y, be.y);
+        o.z = bn_val(xv.z, mu.z, is.z, ga.z, be.z);
+        o.w = bn_val(xv.w, mu.w, is.w, ga.w, be.w);
+        if (residual) {
+            o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
+        }
+        if (relu) {
+            o.x = bn_relu(o.x); o.y = bn_relu(o.y); o.z = bn_relu(o.z); o.w = bn_relu(o.w);
+        }
+        *reinterpret_cast<float4*>(yp) = o;
+        if (y2) {
+            *reinterpret_cast<float4*>(y2p) = o;
+            y2p += rstep * ld2;
+        }
+        xp += step;
+        yp += step;
+    }
+}
+
+// The flat backward kernels are compiled with floating-point contraction: of  ga * is * (g - sg * inv_n - (x - mu) * is * sx * inv_n)
+// the compiler fuses the two products with inv_n into the subtractions.  Here  ga * is  and  sg * inv_n  no longer sit beside
+// their uses (they do not change along a thread's walk), so the same roundings are WRITTEN: contraction off, the two fused steps
+// as __fmaf_rn.  (The forward expression has nothing to contract: bn_val is an explicit fma.)
+template <bool LOAD_G>
+__device__ __forceinline__ void bn_bwd_apply_body(const float* __restrict__ x, const float* __restrict__ y, const GySrc& gy,
+                                                  const float* __restrict__ mean, const float* __restrict__ var,
+                                                  const float* __restrict__ gamma, float eps, int relu, int training,
+                                                  const float* __restrict__ sum_g, const float* __restrict__ sum_gx, float inv_n,
+                                                  float* __restrict__ gx, float* __restrict__ gres, int64_t total4, int c4,
+                                                  const float* __restrict__ beta) {
+#pragma clang fp contract(off)
+    const bool from_x = !LOAD_G && relu && !y;               // ReLU mask recomputed from x: one tensor less to read
+    const unsigned e0 = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;        // stride % c4 == 0
+    if (e0 >= total4) return;
+    const unsigned row0 = e0 / unsigned(c4);
+    const int col = int(e0 - row0 * unsigned(c4)) * 4;
+    const int64_t rstep = stride / unsigned(c4), step = int64_t(stride) * 4;
+    const float4 z = make_float4(0, 0, 0, 0);
+    const float4 vv = ld4(var + col), ga = ld4(gamma + col);
+    const float4 is = make_float4(bn_is(vv.x, eps), bn_is(vv.y, eps), bn_is(vv.z, eps), bn_is(vv.w, eps));
+    const float4 mu = (training || from_x) ? ld4(mean + col) : z;
+    const float4 be = from_x ? ld4(beta + col) : z;
+    const float4 sg = training ? ld4(sum_g + col) : z, sx = training ? ld4(sum_gx + col) : z;
+    const float4 gi = make_float4(ga.x * is.x, ga.y * is.y, ga.z * is.z, ga.w * is.w);
+    const int64_t off = int64_t(e0) * 4;
+    int64_t so[BN_MAX_SRC], sstep[BN_MAX_SRC];               // the sources' element offsets of this thread's quad, and their steps
+#pragma unroll
+    for (int i = 0; i < BN_MAX_SRC; ++i) {
+        so[i] = LOAD_G ? 0 : int64_t(row0) * gy.ld[i] + col;
+        sstep[i] = LOAD_G ? 0 : rstep * gy.ld[i];
+    }
+    for (int64_t e = e0, o4 = off; e < total4; e += stride, o4 += step) {
+        // every load of the quad first (x, the sources or gres, y), then the arithmetic: one round trip per quad
+        float4 xv = z, yv = z, gs[BN_MAX_SRC];
+        if (training || from_x) xv = ld4(x + o4);
+        if (LOAD_G) {
+            gs[0] = ld4(gres + o4);                          // (already summed and masked)
+        } else {
+            gs[0] = ld4(gy.p[0] + so[0]);
+            so[0] += sstep[0];
+#pragma unroll
+            for (int i = 1; i < BN_MAX_SRC; ++i)
+                if (i < gy.n) {
+                    gs[i] = ld4(gy.p[i] + so[i]);
+                    so[i] += sstep[i];
+                }
+            if (relu && !from_x) yv = ld4(y + o4);
+        }
+        float4 g = gs[0];
+        if (!LOAD_G) {
+#pragma unroll
+            for (int i = 1; i < BN_MAX_SRC; ++i)
+                if (i < gy.n) { g.x += gs[i].x; g.y += gs[i].y; g.z += gs[i].z; g.w += gs[i].w; }
+        }
+        if (LOAD_G) {
+        } else if (from_x) {
+            g.x = bn_val(xv.x, mu.x, is.x, ga.x, be.x) > 0.f ? g.x : 0.f;
+            g.y = bn_val(xv.y, mu.y, is.y, ga.y, be.y) > 0.f ? g.y : 0.f;
+            g.z = bn_val(xv.z, mu.z, is.z, ga.z, be.z) > 0.f ? g.z : 0.f;
+            g.w = bn_val(xv.w, mu.w, is.w, ga.w, be.w) > 0.f ? g.w : 0.f;
+        } else if (relu) {
+            g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f;
+            g.z = yv.z > 0.f ? g.z : 0.f; g.w = yv.w > 0.f ? g.w : 0.f;
+        }
+        if (!LOAD_G && gres) *reinterpret_cast<float4*>(gres + o4) = g;
+        float4 o;
+        if (training) {
+            // ga * is * (g - sg * inv_n - (xv - mu) * is * sx * inv_n), with the flat kernels' two contractions
+            o.x = gi.x * __fmaf_rn(-((xv.x - mu.x) * is.x * sx.x), inv_n, __fmaf_rn(-sg.x, inv_n, g.x));
+            o.y = gi.y * __fmaf_rn(-((xv.y - mu.y) * is.y * sx.y), inv_n, __fmaf_rn(-sg.y, inv_n, g.y));
+            o.z = gi.z * __fmaf_rn(-((xv.z - mu.z) * is.z * sx.z), inv_n, __fmaf_rn(-sg.z, inv_n, g.z));
+            o.w = gi.w * __fmaf_rn(-((xv.w - mu.w) * is.w * sx.w), inv_n, __fmaf_rn(-sg.w, inv_n, g.w));
+        } else {
+            o.x = gi.x * g.x; o.y = gi.y * g.y; o.z = gi.z * g.z; o.w = gi.w * g.w;
+        }
+        *reinterpret_cast<float4*>(gx + o4) = o;
     }
 }
 
@@ -448,9 +674,50 @@ static int ew_grid(int64_t total4) {
     return int(g);
 }
 
+// The apply kernels' launch plan, stated once: the smallest grid >= ew_grid(total4) whose stride (grid x 256 quads) is a multiple of
+// c4 -- a multiple of c4 / gcd(c4, 256) -- at most EW_SLACK workgroups above it (workgroups past the last quad leave at once, but a
+// wide odd c4 would ask for up to c4 - 1 of them).  keep = false: no such grid, the flat kernels run on ew_grid(total4).
+constexpr int EW_SLACK = 127;
+struct ApplyPlan {
+    int grid;
+    bool keep;
+};
+
+static ApplyPlan plan_apply(int64_t total4, int c4) {
+    const int g = ew_grid(total4);
+    int a = c4, b = 256;
+    while (b) { const int t = a % b; a = b; b = t; }
+    const int64_t m = c4 / a;
+    const int64_t up = cdiv(int64_t(g), m) * m;
+    if (up - g <= EW_SLACK) return ApplyPlan{int(up), true};
+    return ApplyPlan{g, false};
+}
+
+// osn_bn_set_flat_kernels: the kernels of the earlier rounds (flat apply walks, one row in flight in the column sums)
+static std::atomic<int> g_flat_kernels{0};
+
+#ifndef OSN_BN_KEEP_COLUMNS
+#define OSN_BN_KEEP_COLUMNS 1                                // 0: an A/B build whose apply passes are always the flat kernels
+#endif
+
+static ApplyPlan launch_plan_apply(int64_t total4, int c4) {
+    if (!OSN_BN_KEEP_COLUMNS || g_flat_kernels.load(std::memory_order_relaxed)) return ApplyPlan{ew_grid(total4), false};
+    return plan_apply(total4, c4);
+}
+
 }  // namespace osn
 
 using namespace osn;
+
+extern "C" int osn_bn_set_flat_kernels(int on) { return g_flat_kernels.exchange(on ? 1 : 0); }
+
+extern "C" int osn_bn_apply_plan(int64_t total4, int c4, int* grid, int* flat) {
+    OSN_REQUIRE(total4 >= 0 && c4 >= 1 && grid && flat, OSN_E_ARG, "osn_bn_apply_plan: need total4 >= 0, c4 >= 1 and two outputs");
+    const ApplyPlan p = plan_apply(total4, c4);
+    *grid = p.grid;
+    *flat = p.keep ? 0 : 1;
+    return OSN_OK;
+}
 
 extern "C" size_t osn_bn_ws_bytes(int64_t n, int c) {
     (void)n;
@@ -466,7 +733,8 @@ extern "C" int osn_bn_stats(const float* x, int64_t n, int c, float* mean, float
     const size_t need = size_t(p.n_rb) * 2 * size_t(c) * 8;
     OSN_REQUIRE(ws && ws_bytes >= need, OSN_E_WS, "osn_bn_stats: workspace %zu < %zu", ws_bytes, need);
     double* partial = static_cast<double*>(ws);
-    hipLaunchKernelGGL((col_reduce_kernel<0>), dim3(p.n_rb, p.n_cg), dim3(256), 0, st, x, (const float*)nullptr,
+    const auto kern = g_flat_kernels.load(std::memory_order_relaxed) ? col_reduce_1row_kernel<0> : col_reduce_kernel<0>;
+    hipLaunchKernelGGL(kern, dim3(p.n_rb, p.n_cg), dim3(256), 0, st, x, (const float*)nullptr,
                        GySrc{}, (const float*)nullptr, (const float*)nullptr, 0.f, 0, n, c,
                        p.rows_per_block, partial, (const float*)nullptr, (const float*)nullptr);
     hipLaunchKernelGGL(bn_stats_finalize_kernel, dim3(cdiv(c, FIN_COLS)), dim3(FIN_COLS * FIN_PARTS), 0, st, partial, p.n_rb, n, c, mean, var,
@@ -488,7 +756,8 @@ extern "C" int osn_bn_apply2(const float* x, const float* mean, const float* var
     OSN_REQUIRE(!y2 || (aligned16(y2) && ld2 >= c && (ld2 & 3) == 0), OSN_E_ARG,
                 "osn_bn_apply2: the second destination needs a 16-byte aligned pointer and a row stride >= c, %% 4 == 0");
     const int64_t total4 = n * (c / 4);
-    hipLaunchKernelGGL(bn_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, st, x, mean, var, gamma, beta, eps,
+    const ApplyPlan ap = launch_plan_apply(total4, c / 4);
+    hipLaunchKernelGGL(ap.keep ? bn_apply_kernel : bn_apply_flat_kernel, dim3(ap.grid), dim3(256), 0, st, x, mean, var, gamma, beta, eps,
                        residual, relu, y, y2, ld2, total4, c / 4);
     OSN_LAUNCH_CHECK();
     return OSN_OK;
@@ -570,21 +839,23 @@ extern "C" int osn_bn_backward_multi2(const float* x, const float* y, const floa
     for (int i = 0; via_gres && i < n_gy; ++i)
         via_gres = !ranges_overlap(gres, span, src.p[i], size_t(n - 1) * size_t(src.ld[i]) + size_t(c));
     const dim3 rgrid(p.n_rb, p.n_cg);
+    const bool one_row = g_flat_kernels.load(std::memory_order_relaxed) != 0;
     if (via_gres)
-        hipLaunchKernelGGL(col_reduce_gres_kernel, rgrid, dim3(256), 0, st, x, y, src, mean, var, eps, relu, n, c,
-                           p.rows_per_block, partial, gres);
+        hipLaunchKernelGGL(one_row ? col_reduce_gres_1row_kernel : col_reduce_gres_kernel, rgrid, dim3(256), 0, st, x, y, src, mean,
+                           var, eps, relu, n, c, p.rows_per_block, partial, gres);
     else
-        hipLaunchKernelGGL((col_reduce_kernel<1>), rgrid, dim3(256), 0, st, x, y, src, mean, var, eps, relu, n, c,
-                           p.rows_per_block, partial, gamma, beta);
+        hipLaunchKernelGGL(one_row ? col_reduce_1row_kernel<1> : col_reduce_kernel<1>, rgrid, dim3(256), 0, st, x, y, src, mean, var,
+                           eps, relu, n, c, p.rows_per_block, partial, gamma, beta);
     // ggamma = sum g*xhat, gbeta = sum g  (also the two column sums the apply pass needs)
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(c, FIN_COLS)), dim3(FIN_COLS * FIN_PARTS), 0, st, partial, p.n_rb, c, gbeta, ggamma);
     const int64_t total4 = n * (c / 4);
+    const ApplyPlan ap = launch_plan_apply(total4, c / 4);
     if (via_gres)
-        hipLaunchKernelGGL(bn_bwd_apply_gres_kernel, dim3(ew_grid(total4)), dim3(256), 0, st, x, mean, var, gamma, eps, training,
-                           gbeta, ggamma, 1.f / float(n), gx, (const float*)gres, total4, c / 4);
+        hipLaunchKernelGGL(ap.keep ? bn_bwd_apply_gres_kernel : bn_bwd_apply_gres_flat_kernel, dim3(ap.grid), dim3(256), 0, st, x, mean,
+                           var, gamma, eps, training, gbeta, ggamma, 1.f / float(n), gx, (const float*)gres, total4, c / 4);
     else
-        hipLaunchKernelGGL(bn_bwd_apply_kernel, dim3(ew_grid(total4)), dim3(256), 0, st, x, y, src, mean, var, gamma, eps,
-                           relu, training, gbeta, ggamma, 1.f / float(n), gx, gres, total4, c / 4, beta);
+        hipLaunchKernelGGL(ap.keep ? bn_bwd_apply_kernel : bn_bwd_apply_flat_kernel, dim3(ap.grid), dim3(256), 0, st, x, y, src, mean, var,
+                           gamma, eps, relu, training, gbeta, ggamma, 1.f / float(n), gx, gres, total4, c / 4, beta);
     OSN_LAUNCH_CHECK();
     return OSN_OK;
 }

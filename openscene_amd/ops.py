@@ -1087,6 +1087,41 @@ def bn_backward_multi(x, y, gys, mean, var, gamma, eps, relu, training, want_gre
     return gx, gres, ggamma, gbeta
 
 
+def bn_apply2(x, mean, var, gamma, beta, eps, residual=None, relu=False, y2=None, out=None):
+    """bn_apply with the second destination `y2` (a [n, c] column window of a wider matrix, or None) and a caller's destination
+    `out` (contiguous float32 shaped like x; x itself normalises in place: every element is read before it is written).  -> y"""
+    dev = x.device
+    lib = _prep(dev)
+    x = _f32c(x, "x")
+    n, c = x.shape
+    if residual is not None:
+        residual = _f32c(residual, "residual")
+        if residual.shape != x.shape:
+            raise ValueError("residual shape %s != %s" % (tuple(residual.shape), tuple(x.shape)))
+    if out is not None and (out.dtype != torch.float32 or out.shape != x.shape or out.device != dev or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous float32 tensor shaped like x, on its device")
+    p2, ld2 = _row_view(y2, c, "y2") if y2 is not None else (None, 0)
+    y = out if out is not None else torch.empty_like(x)
+    with _Dev(dev):
+        check(lib.osn_bn_apply2(_p(x), _p(mean), _p(var), _p(gamma), _p(beta), float(eps), _p(residual), int(bool(relu)),
+                                _p(y), p2, ld2, n, c, _stream(dev)), "osn_bn_apply2")
+    return y
+
+
+def bn_apply_plan(total4, c4):
+    """(grid, flat) of the apply kernels' launch plan for total4 = n * c / 4 quads in c4 = c / 4 column quads (osn_bn_apply_plan:
+    flat = the grid-stride kernels run because no grid near the wanted one keeps a thread on its columns).  Needs no device."""
+    grid, flat = ctypes.c_int32(), ctypes.c_int32()
+    check(_lib.load().osn_bn_apply_plan(int(total4), int(c4), ctypes.byref(grid), ctypes.byref(flat)), "osn_bn_apply_plan")
+    return grid.value, bool(flat.value)
+
+
+def bn_set_flat_kernels(on):
+    """Tests and A/B: run the batch-norm kernels of the earlier rounds (flat apply kernels, one row in flight in the column sums),
+    process-wide; results are bitwise the same.  Returns the previous setting."""
+    return bool(_lib.load().osn_bn_set_flat_kernels(int(bool(on))))
+
+
 # ------------------------------------------------------- elementwise (a11)
 def relu_fwd(x):
     dev = x.device
