@@ -27,17 +27,13 @@ struct GySrc {
     int n;
 };
 
-__device__ inline float4 gy_load(const GySrc& s, int64_t r, int col) {
-    float4 g = *reinterpret_cast<const float4*>(s.p[0] + r * s.ld[0] + col);
+// the source quads of (row r, columns col .. col + 3) as they arrive; bn_masked_grad (epilogue.h) adds them
+__device__ __forceinline__ void gy_load(float4 (&g)[BN_MAX_SRC], const GySrc& s, int64_t r, int col) {
+    g[0] = ld4(s.p[0] + r * s.ld[0] + col);
 #pragma unroll
     for (int i = 1; i < BN_MAX_SRC; ++i)
-        if (i < s.n) {
-            const float4 v = *reinterpret_cast<const float4*>(s.p[i] + r * s.ld[i] + col);
-            g.x += v.x; g.y += v.y; g.z += v.z; g.w += v.w;
-        }
-    return g;
+        if (i < s.n) g[i] = ld4(s.p[i] + r * s.ld[i] + col);
 }
-
 
 struct ColReducePlan {
     int n_rb;            // row blocks
@@ -57,8 +53,6 @@ static ColReducePlan plan_colreduce(int64_t n, int c) {
     return p;
 }
 
-__device__ inline float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
-
 // Rows a thread of the column sums keeps IN FLIGHT (its rows r, r + 16, ...: all their loads are issued before the first add).
 // With one row per thread a CU holds ~16 KB of loads and the kernel runs at a third of the HBM roof, for as long as the loaded
 // latency -- which the weight-gradient stream beside it raises.  Per instance: a row costs one quad of
@@ -73,7 +67,7 @@ __device__ inline float4 ld4(const float* p) { return *reinterpret_cast<const fl
 #define OSN_BN_ROWS_GRES 2
 #endif
 
-// one row's operands as they arrive (the sources are added afterwards, in gy_load's order)
+// one row's operands as they arrive (the sources are added afterwards, source 0 first)
 struct CrRow {
     float4 x, y, g[BN_MAX_SRC];
 };
@@ -83,10 +77,7 @@ __device__ __forceinline__ void cr_load(CrRow& w, const float* __restrict__ x, c
                                         bool need_y, int64_t r, int c, int col) {
     w.x = ld4(x + r * c + col);
     if (MODE == 1) {
-        w.g[0] = ld4(gy.p[0] + r * gy.ld[0] + col);
-#pragma unroll
-        for (int i = 1; i < BN_MAX_SRC; ++i)
-            if (i < gy.n) w.g[i] = ld4(gy.p[i] + r * gy.ld[i] + col);
+        gy_load(w.g, gy, r, col);
         if (need_y) w.y = ld4(y + r * c + col);
     }
 }
@@ -114,17 +105,17 @@ __device__ __forceinline__ void col_reduce_body(const float* __restrict__ x, con
     const int64_t r0 = int64_t(blockIdx.x) * rows_per_block;
     const int64_t r1 = min(n, r0 + rows_per_block);
     double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
-    float4 mu = make_float4(0, 0, 0, 0), is = make_float4(0, 0, 0, 0);
-    float4 ga = make_float4(0, 0, 0, 0), be = make_float4(0, 0, 0, 0);
+    const float4 z = make_float4(0, 0, 0, 0);
+    EpiCols k{z, z, z, z};
     const bool from_x = MODE == 1 && !STORE_G && relu && !y; // the ReLU mask recomputed from x (no residual): y is not read
     const bool need_y = MODE == 1 && relu && !from_x;
     if (MODE == 1 && on) {
-        mu = *reinterpret_cast<const float4*>(mean + col);
-        const float4 v = *reinterpret_cast<const float4*>(var + col);
-        is = make_float4(bn_is(v.x, eps), bn_is(v.y, eps), bn_is(v.z, eps), bn_is(v.w, eps));
+        k.mu = ld4(mean + col);
+        const float4 v = ld4(var + col);
+        k.is = make_float4(bn_is(v.x, eps), bn_is(v.y, eps), bn_is(v.z, eps), bn_is(v.w, eps));
         if (from_x) {
-            ga = *reinterpret_cast<const float4*>(gamma + col);
-            be = *reinterpret_cast<const float4*>(beta + col);
+            k.ga = ld4(gamma + col);
+            k.be = ld4(beta + col);
         }
     }
     auto add_row = [&](const CrRow& w, int64_t r) {
@@ -134,24 +125,11 @@ __device__ __forceinline__ void col_reduce_body(const float* __restrict__ x, con
             s2[0] += double(xv.x) * xv.x; s2[1] += double(xv.y) * xv.y;
             s2[2] += double(xv.z) * xv.z; s2[3] += double(xv.w) * xv.w;
         } else {
-            float4 g = w.g[0];
-#pragma unroll
-            for (int i = 1; i < BN_MAX_SRC; ++i)
-                if (i < gy.n) { g.x += w.g[i].x; g.y += w.g[i].y; g.z += w.g[i].z; g.w += w.g[i].w; }
-            if (from_x) {
-                g.x = bn_val(xv.x, mu.x, is.x, ga.x, be.x) > 0.f ? g.x : 0.f;
-                g.y = bn_val(xv.y, mu.y, is.y, ga.y, be.y) > 0.f ? g.y : 0.f;
-                g.z = bn_val(xv.z, mu.z, is.z, ga.z, be.z) > 0.f ? g.z : 0.f;
-                g.w = bn_val(xv.w, mu.w, is.w, ga.w, be.w) > 0.f ? g.w : 0.f;
-            } else if (relu) {
-                const float4 yv = w.y;
-                g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f;
-                g.z = yv.z > 0.f ? g.z : 0.f; g.w = yv.w > 0.f ? g.w : 0.f;
-            }
+            const float4 g = bn_masked_grad(w.g, gy.n, xv, w.y, k, relu, from_x);
             if (STORE_G) *reinterpret_cast<float4*>(gres + r * c + col) = g;
             s1[0] += g.x; s1[1] += g.y; s1[2] += g.z; s1[3] += g.w;
-            s2[0] += double(g.x) * ((xv.x - mu.x) * is.x); s2[1] += double(g.y) * ((xv.y - mu.y) * is.y);
-            s2[2] += double(g.z) * ((xv.z - mu.z) * is.z); s2[3] += double(g.w) * ((xv.w - mu.w) * is.w);
+            s2[0] += double(g.x) * ((xv.x - k.mu.x) * k.is.x); s2[1] += double(g.y) * ((xv.y - k.mu.y) * k.is.y);
+            s2[2] += double(g.z) * ((xv.z - k.mu.z) * k.is.z); s2[3] += double(g.w) * ((xv.w - k.mu.w) * k.is.w);
         }
     };
     if (on) {
@@ -302,253 +280,127 @@ __global__ __launch_bounds__(FIN_COLS * FIN_PARTS) void bn_bwd_finalize_kernel(c
     sum_gx[j] = float(s2);
 }
 
-// (bn_val / bn_is / bn_relu: epilogue.h -- one definition shared with the convolution kernels' evaluation-mode epilogues)
+// The apply passes (forward, backward, backward reading gres) are each written ONCE, over one of two walks through the quads of an
+// [n, c] matrix, c4 = c / 4 quads a row.  Per-element expressions: epilogue.h.  Every element is read and then written by the same
+// thread (in place is fine).
+//   KEEP   the thread keeps its columns: the launch plan (plan_apply) makes the grid's stride a multiple of c4, so a thread's quads
+//          all lie in one column quad, `stride / c4` rows apart.  Column and first row come from one 32-bit division, the column
+//          constants (four 1 / sqrt among them) are taken once, and the walk advances offsets.  Per quad that leaves the loads that
+//          carry new data and the per-element arithmetic: 35 VALU instructions and 2 loads on a forward pass.
+//   flat   a grid-stride walk; column and constants are taken again for every quad (241 VALU instructions, 9 transcendental, 16 v_div_*,
+//          and 6 loads: profiles/r24_bn_one_definition_resource_usage.txt).  Runs where no grid keeps a thread on its columns
+//          (plan_apply: wide odd c4) and by osn_bn_set_flat_kernels(1).
+template <bool KEEP>
+struct QuadWalk {
+    int64_t e, stride, row_, rstep;                          // quad index and its step; (KEEP) row and its step
+    int col_;
+    __device__ QuadWalk(int c4) {
+        if constexpr (KEEP) {
+            const unsigned e0 = blockIdx.x * 256u + threadIdx.x, s = gridDim.x * 256u;        // s % c4 == 0
+            const unsigned row0 = e0 / unsigned(c4);
+            col_ = int(e0 - row0 * unsigned(c4)) * 4;
+            e = e0; stride = s; row_ = row0; rstep = s / unsigned(c4);
+        } else {
+            e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+            stride = int64_t(gridDim.x) * blockDim.x;
+        }
+    }
+    __device__ int col(int c4) const { return KEEP ? col_ : int(e % c4) * 4; }
+    __device__ int64_t row(int c4) const { return KEEP ? row_ : e / c4; }
+    __device__ int64_t off() const { return e * 4; }         // element offset of the quad in a contiguous [n, c] matrix
+    __device__ void next() {
+        e += stride;
+        if constexpr (KEEP) row_ += rstep;
+    }
+};
 
-// The FLAT apply kernels (a grid-stride walk over quads; column, constants and the four 1 / sqrt taken again for every quad): run where
-// no grid keeps a thread on its columns (plan_apply: wide odd c4) and by osn_bn_set_flat_kernels(1).
-__global__ __launch_bounds__(256) void bn_apply_flat_kernel(const float* __restrict__ x, const float* __restrict__ mean,
-                                                       const float* __restrict__ var, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, float eps,
-                                                       const float* __restrict__ residual, int relu,
-                                                       float* __restrict__ y, float* __restrict__ y2, int64_t ld2,
-                                                       int64_t total4, int c4) {
-    for (int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; e < total4; e += int64_t(gridDim.x) * blockDim.x) {
-        const int col = int(e % c4) * 4;
-        const float4 xv = ld4(x + e * 4), mu = ld4(mean + col), vv = ld4(var + col), ga = ld4(gamma + col),
-                     be = ld4(beta + col);
-        float4 o;
-        o.x = bn_val(xv.x, mu.x, bn_is(vv.x, eps), ga.x, be.x);
-        o.y = bn_val(xv.y, mu.y, bn_is(vv.y, eps), ga.y, be.y);
-        o.z = bn_val(xv.z, mu.z, bn_is(vv.z, eps), ga.z, be.z);
-        o.w = bn_val(xv.w, mu.w, bn_is(vv.w, eps), ga.w, be.w);
-        if (residual) {
-            const float4 rv = ld4(residual + e * 4);
-            o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
-        }
-        if (relu) {
-            o.x = bn_relu(o.x); o.y = bn_relu(o.y); o.z = bn_relu(o.z); o.w = bn_relu(o.w);
-        }
-        *reinterpret_cast<float4*>(y + e * 4) = o;
+template <bool KEEP>
+__device__ __forceinline__ void bn_apply_body(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ var,
+                                              const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
+                                              const float* __restrict__ residual, int relu, float* __restrict__ y,
+                                              float* __restrict__ y2, int64_t ld2, int64_t total4, int c4) {
+    QuadWalk<KEEP> w(c4);
+    if (w.e >= total4) return;
+    EpiCols k;
+    if (KEEP) k = epi_cols(mean, var, gamma, beta, eps, w.col(c4));
+    for (; w.e < total4; w.next()) {
+        const int col = w.col(c4);
+        const int64_t o4 = w.off();
+        if (!KEEP) k = epi_cols(mean, var, gamma, beta, eps, col);
+        // (the residual is issued with x, ahead of the arithmetic: one round trip per quad)
+        const float4 xv = ld4(x + o4), rv = residual ? ld4(residual + o4) : make_float4(0, 0, 0, 0);
+        const float4 o = bn_fwd_quad(xv, k, residual != nullptr, [&] { return rv; }, relu);
+        *reinterpret_cast<float4*>(y + o4) = o;
         // second store: the same rows as a column window of a wider matrix (ME.cat written in place by its producers)
-        if (y2) *reinterpret_cast<float4*>(y2 + (e / c4) * ld2 + col) = o;
+        if (y2) *reinterpret_cast<float4*>(y2 + w.row(c4) * ld2 + col) = o;
     }
 }
 
 // LOAD_G: g was stored to gres by col_reduce_gres_kernel; y and the sources are not read and gres is not written.
-template <bool LOAD_G>
-__device__ __forceinline__ void bn_bwd_apply_flat_body(const float* __restrict__ x, const float* __restrict__ y, const GySrc& gy,
-                                                  const float* __restrict__ mean, const float* __restrict__ var,
-                                                  const float* __restrict__ gamma, float eps, int relu, int training,
-                                                  const float* __restrict__ sum_g, const float* __restrict__ sum_gx, float inv_n,
-                                                  float* __restrict__ gx, float* __restrict__ gres, int64_t total4, int c4,
-                                                  const float* __restrict__ beta) {
-    const bool from_x = !LOAD_G && relu && !y;               // ReLU mask recomputed from x: one tensor less to read
-    for (int64_t e = int64_t(blockIdx.x) * blockDim.x + threadIdx.x; e < total4; e += int64_t(gridDim.x) * blockDim.x) {
-        const int col = int(e % c4) * 4;
-        float4 g = LOAD_G ? ld4(gres + e * 4) : gy_load(gy, e / c4, col);
-        const float4 vv = ld4(var + col), ga = ld4(gamma + col);
-        const float4 is = make_float4(bn_is(vv.x, eps), bn_is(vv.y, eps), bn_is(vv.z, eps), bn_is(vv.w, eps));
-        float4 xv = make_float4(0, 0, 0, 0), mu = make_float4(0, 0, 0, 0);
-        if (training || from_x) { xv = ld4(x + e * 4); mu = ld4(mean + col); }
-        if (LOAD_G) {
-            // (already summed and masked)
-        } else if (from_x) {
-            const float4 be = ld4(beta + col);
-            g.x = bn_val(xv.x, mu.x, is.x, ga.x, be.x) > 0.f ? g.x : 0.f;
-            g.y = bn_val(xv.y, mu.y, is.y, ga.y, be.y) > 0.f ? g.y : 0.f;
-            g.z = bn_val(xv.z, mu.z, is.z, ga.z, be.z) > 0.f ? g.z : 0.f;
-            g.w = bn_val(xv.w, mu.w, is.w, ga.w, be.w) > 0.f ? g.w : 0.f;
-        } else if (relu) {
-            const float4 yv = ld4(y + e * 4);
-            g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f;
-            g.z = yv.z > 0.f ? g.z : 0.f; g.w = yv.w > 0.f ? g.w : 0.f;
-        }
-        if (!LOAD_G && gres) *reinterpret_cast<float4*>(gres + e * 4) = g;
-        float4 o;
-        if (training) {
-            const float4 sg = ld4(sum_g + col), sx = ld4(sum_gx + col);
-            o.x = ga.x * is.x * (g.x - sg.x * inv_n - (xv.x - mu.x) * is.x * sx.x * inv_n);
-            o.y = ga.y * is.y * (g.y - sg.y * inv_n - (xv.y - mu.y) * is.y * sx.y * inv_n);
-            o.z = ga.z * is.z * (g.z - sg.z * inv_n - (xv.z - mu.z) * is.z * sx.z * inv_n);
-            o.w = ga.w * is.w * (g.w - sg.w * inv_n - (xv.w - mu.w) * is.w * sx.w * inv_n);
-        } else {
-            o.x = ga.x * is.x * g.x; o.y = ga.y * is.y * g.y; o.z = ga.z * is.z * g.z; o.w = ga.w * is.w * g.w;
-        }
-        *reinterpret_cast<float4*>(gx + e * 4) = o;
-    }
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_apply_flat_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                           const GySrc gy, const float* __restrict__ mean,
-                                                           const float* __restrict__ var, const float* __restrict__ gamma,
-                                                           float eps, int relu, int training,
-                                                           const float* __restrict__ sum_g,
-                                                           const float* __restrict__ sum_gx, float inv_n,
-                                                           float* __restrict__ gx, float* __restrict__ gres,
-                                                           int64_t total4, int c4, const float* __restrict__ beta) {
-    bn_bwd_apply_flat_body<false>(x, y, gy, mean, var, gamma, eps, relu, training, sum_g, sum_gx, inv_n, gx, gres, total4, c4, beta);
-}
-
-__global__ __launch_bounds__(256) void bn_bwd_apply_gres_flat_kernel(const float* __restrict__ x, const float* __restrict__ mean,
-                                                                const float* __restrict__ var, const float* __restrict__ gamma,
-                                                                float eps, int training, const float* __restrict__ sum_g,
-                                                                const float* __restrict__ sum_gx, float inv_n,
-                                                                float* __restrict__ gx, const float* __restrict__ gres,
-                                                                int64_t total4, int c4) {
-    bn_bwd_apply_flat_body<true>(x, nullptr, GySrc{}, mean, var, gamma, eps, 0, training, sum_g, sum_gx, inv_n, gx,
-                            const_cast<float*>(gres), total4, c4, nullptr);
-}
-
-// The apply kernels whose threads KEEP THEIR COLUMNS: the launch plan (plan_apply) makes the grid's stride a multiple of c4, so a
-// thread's quads all lie in one column quad, `stride / c4` rows apart.  Column and first row come from one 32-bit division, mean,
-// bn_is(var), gamma, beta (backward: sum_g, sum_gx) are taken once, and the walk advances pointers.  Per quad that leaves the
-// loads that carry new data and the per-element arithmetic -- the flat kernels spend ~165 VALU instructions (8 transcendental,
-// 16 v_div_*) and 6 loads per quad on a forward pass, these 23 and 2 (profiles/r23_bn_rows_in_flight_resource_usage.txt).
-// Per-element expressions: those of the flat kernels; every element is read and then written by the same thread (in place is fine).
-__global__ __launch_bounds__(256) void bn_apply_kernel(const float* __restrict__ x, const float* __restrict__ mean,
-                                                       const float* __restrict__ var, const float* __restrict__ gamma,
-                                                       const float* __restrict__ beta, float eps,
-                                                       const float* __restrict__ residual, int relu,
-                                                       float* __restrict__ y, float* __restrict__ y2, int64_t ld2,
-                                                       int64_t total4, int c4) {
-    const unsigned e0 = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;        // stride % c4 == 0
-    if (e0 >= total4) return;
-    const unsigned row0 = e0 / unsigned(c4);
-    const int col = int(e0 - row0 * unsigned(c4)) * 4;
-    const int64_t rstep = stride / unsigned(c4), step = int64_t(stride) * 4;
-    const float4 mu = ld4(mean + col), vv = ld4(var + col), ga = ld4(gamma + col), be = ld4(beta + col);
-    const float4 is = make_float4(bn_is(vv.x, eps), bn_is(vv.y, eps), bn_is(vv.z, eps), bn_is(vv.w, eps));
-    const float* xp = x + int64_t(e0) * 4;
-    const float* rp = residual ? residual + int64_t(e0) * 4 : nullptr;
-    float* yp = y + int64_t(e0) * 4;
-    float* y2p = y2 ? y2 + int64_t(row0) * ld2 + col : nullptr;
-    for (int64_t e = e0; e < total4; e += stride) {
-        const float4 xv = ld4(xp);
-        float4 rv = make_float4(0, 0, 0, 0);
-        if (residual) {                                      // (issued with x, ahead of the arithmetic: one round trip per quad)
-            rv = ld4(rp);
-            rp += step;
-        }
-        float4 o;
-        o.x = bn_val(xv.x, mu.x, is.x, ga.x, be.x);
-        o.y = bn_val(xv.y, mu.y, is.y, ga.y, be.y);
-        o.z = bn_val(xv.z, mu.z, is.z, ga.z, be.z);
-        o.w = bn_val(xv.w, mu.w, is.w, ga.w, be.w);
-        if (residual) {
-            o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
-        }
-        if (relu) {
-            o.x = bn_relu(o.x); o.y = bn_relu(o.y); o.z = bn_relu(o.z); o.w = bn_relu(o.w);
-        }
-        *reinterpret_cast<float4*>(yp) = o;
-        if (y2) {
-            *reinterpret_cast<float4*>(y2p) = o;
-            y2p += rstep * ld2;
-        }
-        xp += step;
-        yp += step;
-    }
-}
-
-// The flat backward kernels are compiled with floating-point contraction: of  ga * is * (g - sg * inv_n - (x - mu) * is * sx * inv_n)
-// the compiler fuses the two products with inv_n into the subtractions.  Here  ga * is  and  sg * inv_n  no longer sit beside
-// their uses (they do not change along a thread's walk), so the same roundings are WRITTEN: contraction off, the two fused steps
-// as __fmaf_rn.  (The forward expression has nothing to contract: bn_val is an explicit fma.)
-template <bool LOAD_G>
+template <bool KEEP, bool LOAD_G>
 __device__ __forceinline__ void bn_bwd_apply_body(const float* __restrict__ x, const float* __restrict__ y, const GySrc& gy,
                                                   const float* __restrict__ mean, const float* __restrict__ var,
                                                   const float* __restrict__ gamma, float eps, int relu, int training,
                                                   const float* __restrict__ sum_g, const float* __restrict__ sum_gx, float inv_n,
                                                   float* __restrict__ gx, float* __restrict__ gres, int64_t total4, int c4,
                                                   const float* __restrict__ beta) {
-#pragma clang fp contract(off)
     const bool from_x = !LOAD_G && relu && !y;               // ReLU mask recomputed from x: one tensor less to read
-    const unsigned e0 = blockIdx.x * 256u + threadIdx.x, stride = gridDim.x * 256u;        // stride % c4 == 0
-    if (e0 >= total4) return;
-    const unsigned row0 = e0 / unsigned(c4);
-    const int col = int(e0 - row0 * unsigned(c4)) * 4;
-    const int64_t rstep = stride / unsigned(c4), step = int64_t(stride) * 4;
-    const float4 z = make_float4(0, 0, 0, 0);
-    const float4 vv = ld4(var + col), ga = ld4(gamma + col);
-    const float4 is = make_float4(bn_is(vv.x, eps), bn_is(vv.y, eps), bn_is(vv.z, eps), bn_is(vv.w, eps));
-    const float4 mu = (training || from_x) ? ld4(mean + col) : z;
-    const float4 be = from_x ? ld4(beta + col) : z;
-    const float4 sg = training ? ld4(sum_g + col) : z, sx = training ? ld4(sum_gx + col) : z;
-    const float4 gi = make_float4(ga.x * is.x, ga.y * is.y, ga.z * is.z, ga.w * is.w);
-    const int64_t off = int64_t(e0) * 4;
-    int64_t so[BN_MAX_SRC], sstep[BN_MAX_SRC];               // the sources' element offsets of this thread's quad, and their steps
-#pragma unroll
-    for (int i = 0; i < BN_MAX_SRC; ++i) {
-        so[i] = LOAD_G ? 0 : int64_t(row0) * gy.ld[i] + col;
-        sstep[i] = LOAD_G ? 0 : rstep * gy.ld[i];
-    }
-    for (int64_t e = e0, o4 = off; e < total4; e += stride, o4 += step) {
+    QuadWalk<KEEP> w(c4);
+    if (w.e >= total4) return;
+    BnBwdCols k;
+    if (KEEP) k = bn_bwd_cols(mean, var, gamma, beta, sum_g, sum_gx, eps, training, from_x, w.col(c4));
+    for (; w.e < total4; w.next()) {
+        const int col = w.col(c4);
+        const int64_t o4 = w.off();
+        if (!KEEP) k = bn_bwd_cols(mean, var, gamma, beta, sum_g, sum_gx, eps, training, from_x, col);
         // every load of the quad first (x, the sources or gres, y), then the arithmetic: one round trip per quad
-        float4 xv = z, yv = z, gs[BN_MAX_SRC];
+        float4 xv = make_float4(0, 0, 0, 0), yv, gs[BN_MAX_SRC];
         if (training || from_x) xv = ld4(x + o4);
         if (LOAD_G) {
             gs[0] = ld4(gres + o4);                          // (already summed and masked)
         } else {
-            gs[0] = ld4(gy.p[0] + so[0]);
-            so[0] += sstep[0];
-#pragma unroll
-            for (int i = 1; i < BN_MAX_SRC; ++i)
-                if (i < gy.n) {
-                    gs[i] = ld4(gy.p[i] + so[i]);
-                    so[i] += sstep[i];
-                }
+            gy_load(gs, gy, w.row(c4), col);
             if (relu && !from_x) yv = ld4(y + o4);
         }
-        float4 g = gs[0];
-        if (!LOAD_G) {
-#pragma unroll
-            for (int i = 1; i < BN_MAX_SRC; ++i)
-                if (i < gy.n) { g.x += gs[i].x; g.y += gs[i].y; g.z += gs[i].z; g.w += gs[i].w; }
-        }
-        if (LOAD_G) {
-        } else if (from_x) {
-            g.x = bn_val(xv.x, mu.x, is.x, ga.x, be.x) > 0.f ? g.x : 0.f;
-            g.y = bn_val(xv.y, mu.y, is.y, ga.y, be.y) > 0.f ? g.y : 0.f;
-            g.z = bn_val(xv.z, mu.z, is.z, ga.z, be.z) > 0.f ? g.z : 0.f;
-            g.w = bn_val(xv.w, mu.w, is.w, ga.w, be.w) > 0.f ? g.w : 0.f;
-        } else if (relu) {
-            g.x = yv.x > 0.f ? g.x : 0.f; g.y = yv.y > 0.f ? g.y : 0.f;
-            g.z = yv.z > 0.f ? g.z : 0.f; g.w = yv.w > 0.f ? g.w : 0.f;
-        }
+        const float4 g = bn_masked_grad(gs, LOAD_G ? 1 : gy.n, xv, yv, k.c, !LOAD_G && relu, from_x);
         if (!LOAD_G && gres) *reinterpret_cast<float4*>(gres + o4) = g;
-        float4 o;
-        if (training) {
-            // ga * is * (g - sg * inv_n - (xv - mu) * is * sx * inv_n), with the flat kernels' two contractions
-            o.x = gi.x * __fmaf_rn(-((xv.x - mu.x) * is.x * sx.x), inv_n, __fmaf_rn(-sg.x, inv_n, g.x));
-            o.y = gi.y * __fmaf_rn(-((xv.y - mu.y) * is.y * sx.y), inv_n, __fmaf_rn(-sg.y, inv_n, g.y));
-            o.z = gi.z * __fmaf_rn(-((xv.z - mu.z) * is.z * sx.z), inv_n, __fmaf_rn(-sg.z, inv_n, g.z));
-            o.w = gi.w * __fmaf_rn(-((xv.w - mu.w) * is.w * sx.w), inv_n, __fmaf_rn(-sg.w, inv_n, g.w));
-        } else {
-            o.x = gi.x * g.x; o.y = gi.y * g.y; o.z = gi.z * g.z; o.w = gi.w * g.w;
-        }
-        *reinterpret_cast<float4*>(gx + o4) = o;
+        *reinterpret_cast<float4*>(gx + o4) = bn_bwd_quad(g, xv, k, inv_n, training);
     }
 }
 
-__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const float* __restrict__ x, const float* __restrict__ y,
-                                                           const GySrc gy, const float* __restrict__ mean,
-                                                           const float* __restrict__ var, const float* __restrict__ gamma,
-                                                           float eps, int relu, int training,
-                                                           const float* __restrict__ sum_g,
-                                                           const float* __restrict__ sum_gx, float inv_n,
-                                                           float* __restrict__ gx, float* __restrict__ gres,
-                                                           int64_t total4, int c4, const float* __restrict__ beta) {
-    bn_bwd_apply_body<false>(x, y, gy, mean, var, gamma, eps, relu, training, sum_g, sum_gx, inv_n, gx, gres, total4, c4, beta);
-}
+#define OSN_BN_APPLY_PARAMS                                                                                                    \
+    const float *__restrict__ x, const float *__restrict__ mean, const float *__restrict__ var, const float *__restrict__ gamma,  \
+        const float *__restrict__ beta, float eps, const float *__restrict__ residual, int relu, float *__restrict__ y,          \
+        float *__restrict__ y2, int64_t ld2, int64_t total4, int c4
+#define OSN_BN_BWD_PARAMS                                                                                                      \
+    const float *__restrict__ x, const float *__restrict__ y, const GySrc gy, const float *__restrict__ mean,                    \
+        const float *__restrict__ var, const float *__restrict__ gamma, float eps, int relu, int training,                       \
+        const float *__restrict__ sum_g, const float *__restrict__ sum_gx, float inv_n, float *__restrict__ gx,                  \
+        float *__restrict__ gres, int64_t total4, int c4, const float *__restrict__ beta
+#define OSN_BN_BWD_GRES_PARAMS                                                                                                 \
+    const float *__restrict__ x, const float *__restrict__ mean, const float *__restrict__ var, const float *__restrict__ gamma,  \
+        float eps, int training, const float *__restrict__ sum_g, const float *__restrict__ sum_gx, float inv_n,                 \
+        float *__restrict__ gx, const float *__restrict__ gres, int64_t total4, int c4
 
-__global__ __launch_bounds__(256) void bn_bwd_apply_gres_kernel(const float* __restrict__ x, const float* __restrict__ mean,
-                                                                const float* __restrict__ var, const float* __restrict__ gamma,
-                                                                float eps, int training, const float* __restrict__ sum_g,
-                                                                const float* __restrict__ sum_gx, float inv_n,
-                                                                float* __restrict__ gx, const float* __restrict__ gres,
-                                                                int64_t total4, int c4) {
-    bn_bwd_apply_body<true>(x, nullptr, GySrc{}, mean, var, gamma, eps, 0, training, sum_g, sum_gx, inv_n, gx,
-                            const_cast<float*>(gres), total4, c4, nullptr);
+__global__ __launch_bounds__(256) void bn_apply_kernel(OSN_BN_APPLY_PARAMS) {
+    bn_apply_body<true>(x, mean, var, gamma, beta, eps, residual, relu, y, y2, ld2, total4, c4);
+}
+__global__ __launch_bounds__(256) void bn_apply_flat_kernel(OSN_BN_APPLY_PARAMS) {
+    bn_apply_body<false>(x, mean, var, gamma, beta, eps, residual, relu, y, y2, ld2, total4, c4);
+}
+__global__ __launch_bounds__(256) void bn_bwd_apply_kernel(OSN_BN_BWD_PARAMS) {
+    bn_bwd_apply_body<true, false>(x, y, gy, mean, var, gamma, eps, relu, training, sum_g, sum_gx, inv_n, gx, gres, total4, c4, beta);
+}
+__global__ __launch_bounds__(256) void bn_bwd_apply_flat_kernel(OSN_BN_BWD_PARAMS) {
+    bn_bwd_apply_body<false, false>(x, y, gy, mean, var, gamma, eps, relu, training, sum_g, sum_gx, inv_n, gx, gres, total4, c4, beta);
+}
+__global__ __launch_bounds__(256) void bn_bwd_apply_gres_kernel(OSN_BN_BWD_GRES_PARAMS) {
+    bn_bwd_apply_body<true, true>(x, nullptr, GySrc{}, mean, var, gamma, eps, 0, training, sum_g, sum_gx, inv_n, gx,
+                                  const_cast<float*>(gres), total4, c4, nullptr);
+}
+__global__ __launch_bounds__(256) void bn_bwd_apply_gres_flat_kernel(OSN_BN_BWD_GRES_PARAMS) {
+    bn_bwd_apply_body<false, true>(x, nullptr, GySrc{}, mean, var, gamma, eps, 0, training, sum_g, sum_gx, inv_n, gx,
+                                   const_cast<float*>(gres), total4, c4, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -638,24 +490,13 @@ __global__ __launch_bounds__(SB_THREADS) void bn_small_fwd_kernel(const float* _
         }
     }
     if (!con) return;
-    const float4 ga = ld4(gamma + col), be = ld4(beta + col);
-    const float is0 = bn_is(vr[0], eps), is1 = bn_is(vr[1], eps), is2 = bn_is(vr[2], eps), is3 = bn_is(vr[3], eps);
+    const EpiCols k{make_float4(mu[0], mu[1], mu[2], mu[3]),
+                    make_float4(bn_is(vr[0], eps), bn_is(vr[1], eps), bn_is(vr[2], eps), bn_is(vr[3], eps)), ld4(gamma + col), ld4(beta + col)};
 #pragma unroll
     for (int j = 0; j < SB_PER; ++j) {
         const int r = rl + SB_RL * j;
         if (r >= n) continue;
-        float4 o;
-        o.x = bn_val(v[j].x, mu[0], is0, ga.x, be.x);
-        o.y = bn_val(v[j].y, mu[1], is1, ga.y, be.y);
-        o.z = bn_val(v[j].z, mu[2], is2, ga.z, be.z);
-        o.w = bn_val(v[j].w, mu[3], is3, ga.w, be.w);
-        if (residual) {
-            const float4 rv = ld4(residual + int64_t(r) * c + col);
-            o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
-        }
-        if (relu) {
-            o.x = bn_relu(o.x); o.y = bn_relu(o.y); o.z = bn_relu(o.z); o.w = bn_relu(o.w);
-        }
+        const float4 o = bn_fwd_quad(v[j], k, residual != nullptr, [&] { return ld4(residual + int64_t(r) * c + col); }, relu);
         *reinterpret_cast<float4*>(y + int64_t(r) * c + col) = o;
         if (y2) *reinterpret_cast<float4*>(y2 + int64_t(r) * ld2 + col) = o;
     }
@@ -705,6 +546,19 @@ static ApplyPlan launch_plan_apply(int64_t total4, int c4) {
     return plan_apply(total4, c4);
 }
 
+// The pointers of a forward pass.  quad_stats: mean and var are read as quads (the apply kernels; the one-launch kernel writes them
+// element by element).
+static int check_fwd_args(const char* who, const float* x, const float* mean, const float* var, bool quad_stats, const float* gamma,
+                          const float* beta, const float* residual, const float* y, const float* y2, int64_t ld2, int c) {
+    OSN_REQUIRE(x && mean && var && gamma && beta && y, OSN_E_ARG, "%s: null pointer", who);
+    OSN_REQUIRE(aligned16(x) && aligned16(y) && (!quad_stats || (aligned16(mean) && aligned16(var))) && aligned16(gamma) &&
+                    aligned16(beta) && (!residual || aligned16(residual)),
+                OSN_E_ARG, "%s: pointers must be 16-byte aligned", who);
+    OSN_REQUIRE(!y2 || (aligned16(y2) && ld2 >= c && (ld2 & 3) == 0), OSN_E_ARG,
+                "%s: the second destination needs a 16-byte aligned pointer and a row stride >= c, %% 4 == 0", who);
+    return OSN_OK;
+}
+
 }  // namespace osn
 
 using namespace osn;
@@ -749,12 +603,7 @@ extern "C" int osn_bn_apply2(const float* x, const float* mean, const float* var
     hipStream_t st = static_cast<hipStream_t>(stream);
     OSN_REQUIRE(n >= 0 && c >= 4 && (c & 3) == 0, OSN_E_ARG, "osn_bn_apply: need c %% 4 == 0 (c=%d)", c);
     if (n == 0) return OSN_OK;
-    OSN_REQUIRE(x && mean && var && gamma && beta && y, OSN_E_ARG, "osn_bn_apply: null pointer");
-    OSN_REQUIRE(aligned16(x) && aligned16(y) && aligned16(mean) && aligned16(var) && aligned16(gamma) && aligned16(beta) &&
-                    (!residual || aligned16(residual)),
-                OSN_E_ARG, "osn_bn_apply: pointers must be 16-byte aligned");
-    OSN_REQUIRE(!y2 || (aligned16(y2) && ld2 >= c && (ld2 & 3) == 0), OSN_E_ARG,
-                "osn_bn_apply2: the second destination needs a 16-byte aligned pointer and a row stride >= c, %% 4 == 0");
+    if (int rc = check_fwd_args("osn_bn_apply2", x, mean, var, true, gamma, beta, residual, y, y2, ld2, c)) return rc;
     const int64_t total4 = n * (c / 4);
     const ApplyPlan ap = launch_plan_apply(total4, c / 4);
     hipLaunchKernelGGL(ap.keep ? bn_apply_kernel : bn_apply_flat_kernel, dim3(ap.grid), dim3(256), 0, st, x, mean, var, gamma, beta, eps,
@@ -778,11 +627,7 @@ extern "C" int osn_bn_forward_train2(const float* x, int64_t n, int c, const flo
                                      size_t ws_bytes, osn_stream_t stream) {
     if (n >= 1 && n <= SB_MAX_ROWS && c >= 4 && (c & 3) == 0) {
         hipStream_t st = static_cast<hipStream_t>(stream);
-        OSN_REQUIRE(x && mean && var && gamma && beta && y, OSN_E_ARG, "osn_bn_forward_train: null pointer");
-        OSN_REQUIRE(aligned16(x) && aligned16(y) && aligned16(gamma) && aligned16(beta) && (!residual || aligned16(residual)),
-                    OSN_E_ARG, "osn_bn_forward_train: pointers must be 16-byte aligned");
-        OSN_REQUIRE(!y2 || (aligned16(y2) && ld2 >= c && (ld2 & 3) == 0), OSN_E_ARG,
-                    "osn_bn_forward_train2: the second destination needs a 16-byte aligned pointer and a row stride >= c, %% 4 == 0");
+        if (int rc = check_fwd_args("osn_bn_forward_train2", x, mean, var, false, gamma, beta, residual, y, y2, ld2, c)) return rc;
         hipLaunchKernelGGL(bn_small_fwd_kernel, dim3(unsigned(cdiv(c, SB_COLS))), dim3(SB_THREADS), 0, st, x, int(n), c, gamma,
                            beta, eps, residual, relu, momentum, mean, var, running_mean, running_var, y, y2, ld2);
         OSN_LAUNCH_CHECK();

@@ -40,17 +40,102 @@ inline Epi epi_none() { return Epi{nullptr, nullptr, nullptr, nullptr, nullptr, 
 struct EpiCols {
     float4 mu, is, ga, be;
 };
-__device__ inline EpiCols epi_cols(const Epi& e, int col) {
+__device__ inline float4 ld4(const float* p) { return *reinterpret_cast<const float4*>(p); }
+__device__ inline EpiCols epi_cols(const float* mean, const float* var, const float* gamma, const float* beta, float eps, int col) {
     EpiCols c;
-    c.mu = *reinterpret_cast<const float4*>(e.mean + col);
-    const float4 vv = *reinterpret_cast<const float4*>(e.var + col);
-    c.is = make_float4(bn_is(vv.x, e.eps), bn_is(vv.y, e.eps), bn_is(vv.z, e.eps), bn_is(vv.w, e.eps));
-    c.ga = *reinterpret_cast<const float4*>(e.gamma + col);
-    c.be = *reinterpret_cast<const float4*>(e.beta + col);
+    c.mu = ld4(mean + col);
+    const float4 vv = ld4(var + col);
+    c.is = make_float4(bn_is(vv.x, eps), bn_is(vv.y, eps), bn_is(vv.z, eps), bn_is(vv.w, eps));
+    c.ga = ld4(gamma + col);
+    c.be = ld4(beta + col);
     return c;
 }
+__device__ inline EpiCols epi_cols(const Epi& e, int col) { return epi_cols(e.mean, e.var, e.gamma, e.beta, e.eps, col); }
 
-// columns col .. col + 3 of output row `row` (row pitch cout for the residual): normalise, add, clamp, second store; returns the quad to store
+// The forward quad, ONE definition for the three forward kernels of bn.hip: normalise, add the residual quad, clamp.  res() gives the
+// residual quad and is called only with has_res: a caller loads it there (behind the branch) or hands over a quad it loaded ahead.
+template <class Res>
+__device__ inline float4 bn_fwd_quad(float4 x, const EpiCols& c, bool has_res, Res res, int relu) {
+    float4 o;
+    o.x = bn_val(x.x, c.mu.x, c.is.x, c.ga.x, c.be.x);
+    o.y = bn_val(x.y, c.mu.y, c.is.y, c.ga.y, c.be.y);
+    o.z = bn_val(x.z, c.mu.z, c.is.z, c.ga.z, c.be.z);
+    o.w = bn_val(x.w, c.mu.w, c.is.w, c.ga.w, c.be.w);
+    if (has_res) {
+        const float4 rv = res();
+        o.x += rv.x; o.y += rv.y; o.z += rv.z; o.w += rv.w;
+    }
+    if (relu) {
+        o.x = bn_relu(o.x); o.y = bn_relu(o.y); o.z = bn_relu(o.z); o.w = bn_relu(o.w);
+    }
+    return o;
+}
+
+// The gradient at a batch norm's pre-activation, ONE definition for the column sums and the backward apply passes: the sum of the
+// n_src loaded source quads, source 0 first, under the ReLU mask -- none (no relu), from y, or (from_x) from x through the forward
+// expression (bn_val with the constants c: bit for bit the y > 0 of a norm without a residual).  x, y and c are read only under their
+// mask: they may be unset.  No contraction pragma here: nothing to contract.
+template <int N>
+__device__ inline float4 bn_masked_grad(const float4 (&gs)[N], int n_src, const float4& x, const float4& y, const EpiCols& c,
+                                        bool relu, bool from_x) {
+    float4 g = gs[0];
+#pragma unroll
+    for (int i = 1; i < N; ++i)
+        if (i < n_src) { g.x += gs[i].x; g.y += gs[i].y; g.z += gs[i].z; g.w += gs[i].w; }
+    if (from_x) {
+        g.x = bn_val(x.x, c.mu.x, c.is.x, c.ga.x, c.be.x) > 0.f ? g.x : 0.f;
+        g.y = bn_val(x.y, c.mu.y, c.is.y, c.ga.y, c.be.y) > 0.f ? g.y : 0.f;
+        g.z = bn_val(x.z, c.mu.z, c.is.z, c.ga.z, c.be.z) > 0.f ? g.z : 0.f;
+        g.w = bn_val(x.w, c.mu.w, c.is.w, c.ga.w, c.be.w) > 0.f ? g.w : 0.f;
+    } else if (relu) {
+        g.x = y.x > 0.f ? g.x : 0.f; g.y = y.y > 0.f ? g.y : 0.f;
+        g.z = y.z > 0.f ? g.z : 0.f; g.w = y.w > 0.f ? g.w : 0.f;
+    }
+    return g;
+}
+
+// The column constants of a backward apply pass, each taken only where it is used: mean with batch statistics or the mask from x,
+// beta with the mask from x, the two column sums with batch statistics.  gi = ga * is: the output's  ga * is * (...)  is
+// (ga * is) * (...), and bn_is is a pure function, so forming gi once per thread or once per quad gives the same bits.
+struct BnBwdCols {
+    EpiCols c;
+    float4 gi, sg, sx;
+};
+__device__ inline BnBwdCols bn_bwd_cols(const float* mean, const float* var, const float* gamma, const float* beta, const float* sum_g,
+                                        const float* sum_gx, float eps, bool training, bool from_x, int col) {
+    const float4 z = make_float4(0, 0, 0, 0), vv = ld4(var + col);
+    BnBwdCols k;
+    k.c.is = make_float4(bn_is(vv.x, eps), bn_is(vv.y, eps), bn_is(vv.z, eps), bn_is(vv.w, eps));
+    k.c.ga = ld4(gamma + col);
+    k.c.mu = (training || from_x) ? ld4(mean + col) : z;
+    k.c.be = from_x ? ld4(beta + col) : z;
+    k.sg = training ? ld4(sum_g + col) : z;
+    k.sx = training ? ld4(sum_gx + col) : z;
+    k.gi = make_float4(k.c.ga.x * k.c.is.x, k.c.ga.y * k.c.is.y, k.c.ga.z * k.c.is.z, k.c.ga.w * k.c.is.w);
+    return k;
+}
+
+// The backward output quad, ONE definition:  ga * is * (g - sg / n - xhat * sx / n)  with batch statistics,  ga * is * g  without.
+// Contraction is off INSIDE this function (a helper keeps the setting of the scope it is written in, wherever it is inlined) and the
+// two fused steps are written, so no batch-norm output depends on what the compiler chooses to contract.
+__device__ inline float4 bn_bwd_quad(float4 g, float4 x, const BnBwdCols& k, float inv_n, int training) {
+#pragma clang fp contract(off)
+    float4 o;
+    if (training) {
+        o.x = k.gi.x * __fmaf_rn(-((x.x - k.c.mu.x) * k.c.is.x * k.sx.x), inv_n, __fmaf_rn(-k.sg.x, inv_n, g.x));
+        o.y = k.gi.y * __fmaf_rn(-((x.y - k.c.mu.y) * k.c.is.y * k.sx.y), inv_n, __fmaf_rn(-k.sg.y, inv_n, g.y));
+        o.z = k.gi.z * __fmaf_rn(-((x.z - k.c.mu.z) * k.c.is.z * k.sx.z), inv_n, __fmaf_rn(-k.sg.z, inv_n, g.z));
+        o.w = k.gi.w * __fmaf_rn(-((x.w - k.c.mu.w) * k.c.is.w * k.sx.w), inv_n, __fmaf_rn(-k.sg.w, inv_n, g.w));
+    } else {
+        o.x = k.gi.x * g.x; o.y = k.gi.y * g.y; o.z = k.gi.z * g.z; o.w = k.gi.w * g.w;
+    }
+    return o;
+}
+
+// columns col .. col + 3 of output row `row` (row pitch cout for the residual): normalise, add, clamp, second store; returns the quad to store.
+// The one remaining SECOND COPY of bn_fwd_quad's text: written through bn_fwd_quad -- the residual loaded ahead, handed over as a
+// pointer, or loaded by a callable inside the helper -- at least one convolution kernel compiles to another instruction order, and
+// their ISA is to stay what it was.  Keep the two in step (tests/test_gpu_unet.py compares the two paths bit for bit).
 __device__ inline float4 epi_apply(const Epi& e, const EpiCols& c, float4 x, int64_t row, int col, int cout) {
     float4 o;
     o.x = bn_val(x.x, c.mu.x, c.is.x, c.ga.x, c.be.x);

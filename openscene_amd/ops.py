@@ -987,15 +987,20 @@ def bn_stats(x, running_mean=None, running_var=None, momentum=0.1):
     return mean, var
 
 
-def bn_apply(x, mean, var, gamma, beta, eps, residual=None, relu=False):
-    dev = x.device
-    lib = _prep(dev)
+def _bn_fwd_args(x, residual):
+    """(x, residual, n, c) of a forward pass: contiguous float32, the residual (or None) shaped like x."""
     x = _f32c(x, "x")
-    n, c = x.shape
     if residual is not None:
         residual = _f32c(residual, "residual")
         if residual.shape != x.shape:
             raise ValueError("residual shape %s != %s" % (tuple(residual.shape), tuple(x.shape)))
+    return x, residual, x.shape[0], x.shape[1]
+
+
+def bn_apply(x, mean, var, gamma, beta, eps, residual=None, relu=False):
+    dev = x.device
+    lib = _prep(dev)
+    x, residual, n, c = _bn_fwd_args(x, residual)
     y = torch.empty_like(x)
     with _Dev(dev):
         check(lib.osn_bn_apply(_p(x), _p(mean), _p(var), _p(gamma), _p(beta), float(eps), _p(residual), int(bool(relu)),
@@ -1007,12 +1012,7 @@ def bn_forward_train(x, gamma, beta, eps, residual, relu, running_mean, running_
     """(y, mean, var): batch statistics (running buffers updated in place) + normalise (+ residual) (+ ReLU), one C call."""
     dev = x.device
     lib = _prep(dev)
-    x = _f32c(x, "x")
-    n, c = x.shape
-    if residual is not None:
-        residual = _f32c(residual, "residual")
-        if residual.shape != x.shape:
-            raise ValueError("residual shape %s != %s" % (tuple(residual.shape), tuple(x.shape)))
+    x, residual, n, c = _bn_fwd_args(x, residual)
     mv = torch.empty((2, c), dtype=torch.float32, device=dev)
     y = torch.empty_like(x)
     ws = _ws(_cached("osn_bn_ws_bytes", n, c), dev)
@@ -1043,10 +1043,7 @@ def bn_forward_train2(x, gamma, beta, eps, residual, relu, running_mean, running
     place by its producer).  -> (y, mean, var)."""
     dev = x.device
     lib = _prep(dev)
-    x = _f32c(x, "x")
-    n, c = x.shape
-    if residual is not None:
-        residual = _f32c(residual, "residual")
+    x, residual, n, c = _bn_fwd_args(x, residual)
     p2, ld2 = _row_view(y2, c, "y2")
     mv = torch.empty((2, c), dtype=torch.float32, device=dev)
     y = torch.empty_like(x)
@@ -1092,12 +1089,7 @@ def bn_apply2(x, mean, var, gamma, beta, eps, residual=None, relu=False, y2=None
     `out` (contiguous float32 shaped like x; x itself normalises in place: every element is read before it is written).  -> y"""
     dev = x.device
     lib = _prep(dev)
-    x = _f32c(x, "x")
-    n, c = x.shape
-    if residual is not None:
-        residual = _f32c(residual, "residual")
-        if residual.shape != x.shape:
-            raise ValueError("residual shape %s != %s" % (tuple(residual.shape), tuple(x.shape)))
+    x, residual, n, c = _bn_fwd_args(x, residual)
     if out is not None and (out.dtype != torch.float32 or out.shape != x.shape or out.device != dev or not out.is_contiguous()):
         raise ValueError("out must be a contiguous float32 tensor shaped like x, on its device")
     p2, ld2 = _row_view(y2, c, "y2") if y2 is not None else (None, 0)

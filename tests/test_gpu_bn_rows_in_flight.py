@@ -18,9 +18,15 @@ backward: gx, gres, ggamma, gbeta).
                      reduction stores it) / gres written in place over a contiguous source 0 (the aliased flow)
 Float64: where the reference of tests/bn_bounds.py (long-double column sums) takes well under a second -- n x c <= 450 000, which holds
 for every width up to 209 rows, for 4097 rows at c <= 100 and for 70001 x 4 -- one configuration of bb.CONFIGS per shape (rotating with
-the shape, as the source count does) is also held to the limits of bn_bounds.limits().  The larger shapes rest on the bitwise equality
-with the earlier kernels, which tests/test_gpu_bn_bounds.py and tests/test_gpu_bn_backward_gres.py hold to the same limits.
+the shape, as the source count does) is also held to the limits of bn_bounds.limits().  Both sets of kernels take their per-element
+expressions from one definition each (csrc/epilogue.h), so at the larger shapes the bitwise comparison covers the walks and the loop
+structure -- rows in flight, ragged rounds, kept columns -- against the earlier ones; the expressions themselves are held by
+tests/test_gpu_bn_bounds.py (the same limits) and tests/test_gpu_bn_backward_gres.py (gres bitwise against torch).
+Every case also prints  BITS <n>x<c> <sha256>  over every tensor it compares, in the order produced (_feed): two builds of the library
+are compared by running this file once with each and comparing the lines.
 """
+import hashlib
+
 import numpy as np
 import pytest
 import torch
@@ -59,7 +65,20 @@ def _same(names, a, b, label):
             assert torch.equal(_bits(u), _bits(v)), "%s: %s differs" % (label, name)
 
 
-def _three_runs(ops, names, fn, label):
+def _feed(digest, *outs):
+    """Every tensor of `outs` into the case's digest: its shape and two 64-bit sums of its 32-bit words, taken on the device (the largest
+    case compares some 60 GB: minutes of hashing on the host).  The sums wrap, under the odd weights 2 i + 1 and 2 i^2 + 1 of word i: a
+    changed word changes both, whatever the change."""
+    for t in outs:
+        if t is None:
+            continue
+        w = _bits(t).reshape(-1).to(torch.int64)
+        i = torch.arange(w.numel(), dtype=torch.int64, device=w.device)
+        sums = torch.stack([(w * (2 * i + 1)).sum(), (w * (2 * i * i + 1)).sum()])
+        digest.update(repr(tuple(t.shape)).encode() + sums.cpu().numpy().tobytes())
+
+
+def _three_runs(ops, names, fn, label, digest):
     """fn() with the new kernels, with the earlier ones, with the new ones again: every output bitwise the same.  -> the first."""
     new = fn()
     assert ops.bn_set_flat_kernels(True) is False
@@ -67,8 +86,10 @@ def _three_runs(ops, names, fn, label):
         old = fn()
     finally:
         assert ops.bn_set_flat_kernels(False) is True
+    again = fn()
+    _feed(digest, *new, *old, *again)
     _same(names, new, old, label + ": new kernels against the earlier ones")
-    _same(names, new, fn(), label + ": second call")
+    _same(names, new, again, label + ": second call")
     return new
 
 
@@ -123,6 +144,7 @@ def _device_inputs(n, c):
 def test_new_kernels_give_the_bits_of_the_earlier_ones(n, c):
     ops = _ops()
     index = SHAPES.index((n, c))
+    digest = hashlib.sha256()
     config, nsrc64 = bb.CONFIGS[index % 4], 1 + index % 3
     host = _numpy_inputs(n, c, config) if n * c <= F64_MAX else None
     T = {k: torch.from_numpy(np.ascontiguousarray(v)).to(dev()) for k, v in host.items()} if host else _device_inputs(n, c)
@@ -164,14 +186,15 @@ def test_new_kernels_give_the_bits_of_the_earlier_ones(n, c):
                     w = second() if two else None
                     y = ops.bn_apply2(x, rm, rv, gamma, beta, bb.EPS, r if r is None else res_eval, relu, y2=w[:, 4:4 + c] if two else None)
                     return y, w
-                _three_runs(ops, FWD_NAMES, train, label + ", training")
-                ev = _three_runs(ops, FWD_NAMES[:2], evaluate, label + ", evaluation")
+                _three_runs(ops, FWD_NAMES, train, label + ", training", digest)
+                ev = _three_runs(ops, FWD_NAMES[:2], evaluate, label + ", evaluation", digest)
                 if two:
                     assert torch.equal(_bits(ev[1][:, 4:4 + c]), _bits(ev[0])) and bool((ev[1][:, :4] == 7.0).all()) and bool((ev[1][:, 4 + c:] == 7.0).all())
                 if not two:                       # y in place on x: the bits of the call with a y of its own
                     xin = x.clone()
                     out = ops.bn_apply2(xin, rm, rv, gamma, beta, bb.EPS, r if r is None else res_eval, relu, out=xin)
                     assert out.data_ptr() == xin.data_ptr()
+                    _feed(digest, out)
                     _same(("y",), (ev[0],), (out,), label + ", evaluation in place on x")
 
     # ---- backward
@@ -187,9 +210,9 @@ def test_new_kernels_give_the_bits_of_the_earlier_ones(n, c):
         for k in (1, 2, 3):
             label = "%dx%d backward, relu %d training %d, %d sources" % (n, c, relu, training, k)
             plain = _three_runs(ops, BWD_NAMES, lambda: ops.bn_backward_multi(x, y, srcs[:k], mean, var, gamma, bb.EPS, relu, training, False),
-                                label + ", no gres")
+                                label + ", no gres", digest)
             own = _three_runs(ops, BWD_NAMES, lambda: ops.bn_backward_multi(x, y, srcs[:k], mean, var, gamma, bb.EPS, relu, training, True),
-                              label + ", gres stored by the reduction")
+                              label + ", gres stored by the reduction", digest)
             _same(("gx", "ggamma", "gbeta"), (plain[0],) + plain[2:], (own[0],) + own[2:], label + ": with gres against without")
             g0 = srcs[0].contiguous()
 
@@ -198,15 +221,19 @@ def test_new_kernels_give_the_bits_of_the_earlier_ones(n, c):
                 out = ops.bn_backward_multi(x, y, [inplace] + srcs[1:k], mean, var, gamma, bb.EPS, relu, training, True, gres_out=inplace)
                 assert out[1].data_ptr() == inplace.data_ptr()
                 return out
-            _same(BWD_NAMES, own, _three_runs(ops, BWD_NAMES, aliased, label + ", gres over source 0"), label + ": aliased against a gres of its own")
+            _same(BWD_NAMES, own, _three_runs(ops, BWD_NAMES, aliased, label + ", gres over source 0", digest),
+                  label + ": aliased against a gres of its own")
             if relu:
                 # the mask recomputed from x (no residual: y = relu(bn(x)) is what the kernels rebuild, bit for bit)
                 yx = ops.bn_forward_train(x, gamma, beta, bb.EPS, None, True, rm.clone(), rv.clone(), bb.MOMENTUM)[0] if training else \
                     ops.bn_apply(x, rm, rv, gamma, beta, bb.EPS, None, True)
                 from_x = _three_runs(ops, BWD_NAMES, lambda: ops.bn_backward_multi(x, None, srcs[:k], mean, var, gamma, bb.EPS, True, training, False,
-                                                                                   beta=beta), label + ", mask from x")
-                _same(BWD_NAMES, from_x, ops.bn_backward_multi(x, yx, srcs[:k], mean, var, gamma, bb.EPS, True, training, False),
-                      label + ": mask from x against mask from y")
+                                                                                   beta=beta), label + ", mask from x", digest)
+                from_y = ops.bn_backward_multi(x, yx, srcs[:k], mean, var, gamma, bb.EPS, True, training, False)
+                _feed(digest, yx, *from_y)
+                _same(BWD_NAMES, from_x, from_y, label + ": mask from x against mask from y")
+
+    print("BITS %dx%d %s" % (n, c, digest.hexdigest()))
 
     # ---- one configuration against float64 (bn_bounds)
     if host is None:

@@ -132,3 +132,16 @@ def test_loader_and_query_wrappers_run(mock_ops):
     out = torch.empty(10, 4, dtype=torch.int32)
     ops.batch_coords(torch.zeros(10, 3, dtype=torch.int32), 1, out)
     assert mock_ops["osn_feature_remap"] == 1 and mock_ops["osn_batch_coords"] == 1
+
+
+def test_bn_forward_train2_rejects_a_residual_of_another_shape(mock_ops):
+    """A short residual must not reach the kernel (it would be read out of range): ValueError before any C call."""
+    from openscene_amd import ops
+    x, w = torch.randn(40, 8), torch.zeros(40, 24)
+    gamma, beta, rm, rv = torch.ones(8), torch.zeros(8), torch.zeros(8), torch.ones(8)
+    mock_ops.clear()
+    with pytest.raises(ValueError):
+        ops.bn_forward_train2(x, gamma, beta, 1e-5, torch.randn(39, 8), True, rm, rv, 0.1, w[:, 4:12])
+    assert not mock_ops, dict(mock_ops)
+    ops.bn_forward_train2(x, gamma, beta, 1e-5, torch.randn(40, 8), True, rm, rv, 0.1, w[:, 4:12])
+    assert mock_ops.get("osn_bn_forward_train2") == 1, dict(mock_ops)      # (a residual of x's shape goes through)
