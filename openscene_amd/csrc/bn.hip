@@ -28,10 +28,11 @@ struct GySrc {
 };
 
 // the source quads of (row r, columns col .. col + 3) as they arrive; bn_masked_grad (epilogue.h) adds them
-__device__ __forceinline__ void gy_load(float4 (&g)[BN_MAX_SRC], const GySrc& s, int64_t r, int col) {
+template <int N>
+__device__ __forceinline__ void gy_load(float4 (&g)[N], const GySrc& s, int64_t r, int col) {
     g[0] = ld4(s.p[0] + r * s.ld[0] + col);
 #pragma unroll
-    for (int i = 1; i < BN_MAX_SRC; ++i)
+    for (int i = 1; i < N; ++i)
         if (i < s.n) g[i] = ld4(s.p[i] + r * s.ld[i] + col);
 }
 
@@ -60,20 +61,44 @@ static ColReducePlan plan_colreduce(int64_t n, int c) {
 #ifndef OSN_BN_ROWS_STATS
 #define OSN_BN_ROWS_STATS 4
 #endif
-#ifndef OSN_BN_ROWS_BWD
-#define OSN_BN_ROWS_BWD 2
-#endif
-#ifndef OSN_BN_ROWS_GRES
-#define OSN_BN_ROWS_GRES 2
-#endif
 
-// one row's operands as they arrive (the sources are added afterwards, source 0 first)
-struct CrRow {
-    float4 x, y, g[BN_MAX_SRC];
+// The backward sums run on the main stream BESIDE the weight gradients of the side stream, whose two waves per SIMD hold 320 - 448
+// of a SIMD's 512 VGPRs for a whole launch: a column sum gets the waves that fit into the rest, so the
+// backward sums without a gres store stay within CR_BWD_VGPRS registers (those with the store: col_reduce_gres_kernel below).
+// What a launch does not use is chosen at compile time -- a register that an `if (i < n)` load MAY fill is allocated for every launch:
+//   MASK  none (no ReLU), from x (ReLU, no residual: gamma and beta are read, y is not), from y -- one kernel each, picked by the
+//         host (osn_bn_backward_multi2); CR_MASK_RT: read from the arguments at run time (the one-row kernels of
+//         osn_bn_set_flat_kernels)
+//   NSRC  1: one gradient source; BN_MAX_SRC: gy.n of them, as before; CR_SRC_BRANCH: both row loops in one kernel, chosen by a
+//         uniform branch on gy.n (a kernel's name and grid then say nothing about how many matrices its gradient arrives in: the
+//         module path adds them beforehand, the executor hands them over, and both launch the same kernels)
+constexpr int CR_BWD_VGPRS = 64;
+constexpr int CR_MASK_NONE = 0, CR_MASK_X = 1, CR_MASK_Y = 2, CR_MASK_RT = 3;
+constexpr int CR_SRC_BRANCH = 0;
+
+// Rows in flight of a backward instance.  Two fit in CR_BWD_VGPRS registers where there is one source (60 - 64, no scratch), and
+// measured beside the weight gradient they lose to one: a level-0 backward takes 66.5 us with two rows against 57.9 us with one
+// beside wgrad_tl_kernel<3,3>, 89 against 78 us beside <4,3> (profiles/r25_backward_light_kernels_gate.txt).  With one row the
+// one-source loops hold at most 56 registers.  OSN_BN_ROWS_BWD (1 or 2, an A/B build): the rows of the one-source loops where two fit.
+#ifndef OSN_BN_ROWS_BWD
+#define OSN_BN_ROWS_BWD 1
+#endif
+constexpr int cr_bwd_rows(int mask) {
+    return mask != CR_MASK_Y ? OSN_BN_ROWS_BWD : 1;          // (mask from y: two rows spill)
+}
+template <int V>
+struct CrInt {
+    static constexpr int value = V;
 };
 
-template <int MODE>
-__device__ __forceinline__ void cr_load(CrRow& w, const float* __restrict__ x, const float* __restrict__ y, const GySrc& gy,
+// one row's operands as they arrive (the sources are added afterwards, source 0 first)
+template <int NSRC>
+struct CrRow {
+    float4 x, y, g[NSRC];
+};
+
+template <int MODE, int NSRC>
+__device__ __forceinline__ void cr_load(CrRow<NSRC>& w, const float* __restrict__ x, const float* __restrict__ y, const GySrc& gy,
                                         bool need_y, int64_t r, int c, int col) {
     w.x = ld4(x + r * c + col);
     if (MODE == 1) {
@@ -88,8 +113,9 @@ __device__ __forceinline__ void cr_load(CrRow& w, const float* __restrict__ x, c
 // every source less per residual norm.  Every (row, column) is visited by exactly one thread, so gres is written once.
 // R rows in flight: the loads of rows r, r + 16, ... r + 16 (R - 1) first, then the adds in row order into the same accumulators
 // -- every sum is formed in the order of the one-row loop, bit for bit.  A ragged last round loads its missing rows from row r
-// (an address inside the matrix) and does not add them.
-template <int MODE, bool STORE_G, int R>
+// (an address inside the matrix) and does not add them.  (R: the rows of the statistics pass, of the one-source loop, and of the
+// run-time loop of the one-row kernels; the loop over gy.n sources of a CR_SRC_BRANCH kernel keeps one.)
+template <int MODE, bool STORE_G, int R, int NSRC = BN_MAX_SRC, int MASK = CR_MASK_RT>
 __device__ __forceinline__ void col_reduce_body(const float* __restrict__ x, const float* __restrict__ y, const GySrc gy,
                                                 const float* __restrict__ mean, const float* __restrict__ var, float eps,
                                                 int relu, int64_t n, int c, int rows_per_block, double* __restrict__ partial,
@@ -97,6 +123,8 @@ __device__ __forceinline__ void col_reduce_body(const float* __restrict__ x, con
                                                 float* __restrict__ gres) {
     static_assert(!STORE_G || MODE == 1, "only the backward sums form g");
     static_assert(R >= 1 && R <= 4, "rows in flight");
+    static_assert(NSRC == 1 || NSRC == BN_MAX_SRC || NSRC == CR_SRC_BRANCH, "one source, gy.n of them, or a branch between the two");
+    static_assert(MASK != CR_MASK_X || !STORE_G, "a residual's mask is y's");
     __shared__ double red[2][CR_RL][CR_COLS];
     const int tid = threadIdx.x;
     const int cl = tid & 15, rl = tid >> 4;
@@ -107,8 +135,10 @@ __device__ __forceinline__ void col_reduce_body(const float* __restrict__ x, con
     double s1[4] = {0, 0, 0, 0}, s2[4] = {0, 0, 0, 0};
     const float4 z = make_float4(0, 0, 0, 0);
     EpiCols k{z, z, z, z};
-    const bool from_x = MODE == 1 && !STORE_G && relu && !y; // the ReLU mask recomputed from x (no residual): y is not read
-    const bool need_y = MODE == 1 && relu && !from_x;
+    constexpr bool RT = MASK == CR_MASK_RT;
+    const bool from_x = RT ? MODE == 1 && !STORE_G && relu && !y : MASK == CR_MASK_X; // the ReLU mask recomputed from x (no residual): y is not read
+    const bool need_y = RT ? MODE == 1 && relu && !from_x : MASK == CR_MASK_Y;
+    const bool masked = RT ? relu != 0 : MASK != CR_MASK_NONE;
     if (MODE == 1 && on) {
         k.mu = ld4(mean + col);
         const float4 v = ld4(var + col);
@@ -118,41 +148,54 @@ __device__ __forceinline__ void col_reduce_body(const float* __restrict__ x, con
             k.be = ld4(beta + col);
         }
     }
-    auto add_row = [&](const CrRow& w, int64_t r) {
+    auto add_row = [&](const auto& w, int n_src, int64_t r) {
         const float4 xv = w.x;
         if (MODE == 0) {
             s1[0] += xv.x; s1[1] += xv.y; s1[2] += xv.z; s1[3] += xv.w;
             s2[0] += double(xv.x) * xv.x; s2[1] += double(xv.y) * xv.y;
             s2[2] += double(xv.z) * xv.z; s2[3] += double(xv.w) * xv.w;
         } else {
-            const float4 g = bn_masked_grad(w.g, gy.n, xv, w.y, k, relu, from_x);
+            const float4 g = bn_masked_grad(w.g, n_src, xv, w.y, k, masked, from_x);
             if (STORE_G) *reinterpret_cast<float4*>(gres + r * c + col) = g;
             s1[0] += g.x; s1[1] += g.y; s1[2] += g.z; s1[3] += g.w;
             s2[0] += double(g.x) * ((xv.x - k.mu.x) * k.is.x); s2[1] += double(g.y) * ((xv.y - k.mu.y) * k.is.y);
             s2[2] += double(g.z) * ((xv.z - k.mu.z) * k.is.z); s2[3] += double(g.w) * ((xv.w - k.mu.w) * k.is.w);
         }
     };
-    if (on) {
-        int64_t r = r0 + rl;
-        for (; r + (R - 1) * CR_RL < r1; r += R * CR_RL) {
-            CrRow w[R];
+    // the row loop over NS sources (1: one; BN_MAX_SRC: gy.n of them), RR rows in flight
+    auto rows = [&](auto ns, auto rr) {
+        constexpr int NS = decltype(ns)::value, RR = decltype(rr)::value;
+        const int n_src = NS == 1 ? 1 : gy.n;
+        // (the row inside the block as a 32-bit count: one register for the loop instead of a 64-bit row and its compare)
+        const int nr = int(r1 - r0);                         // 1 .. rows_per_block
+        int i = rl;
+        for (; i + (RR - 1) * CR_RL < nr; i += RR * CR_RL) {
+            const int64_t r = r0 + i;
+            CrRow<NS> w[RR];
 #pragma unroll
-            for (int k = 0; k < R; ++k) cr_load<MODE>(w[k], x, y, gy, need_y, r + k * CR_RL, c, col);
+            for (int k = 0; k < RR; ++k) cr_load<MODE>(w[k], x, y, gy, need_y, r + k * CR_RL, c, col);
 #pragma unroll
-            for (int k = 0; k < R; ++k) add_row(w[k], r + k * CR_RL);
+            for (int k = 0; k < RR; ++k) add_row(w[k], n_src, r + k * CR_RL);
         }
-        if constexpr (R > 1) {
-            if (r < r1) {                                    // ragged last round: 1 .. R - 1 rows
-                CrRow w[R - 1];
+        if constexpr (RR > 1) {
+            if (i < nr) {                                    // ragged last round: 1 .. RR - 1 rows
+                const int64_t r = r0 + i;
+                CrRow<NS> w[RR - 1];
 #pragma unroll
-                for (int k = 0; k < R - 1; ++k) {
-                    const int64_t rk = r + k * CR_RL;
-                    cr_load<MODE>(w[k], x, y, gy, need_y, rk < r1 ? rk : r, c, col);
-                }
+                for (int k = 0; k < RR - 1; ++k)
+                    cr_load<MODE>(w[k], x, y, gy, need_y, i + k * CR_RL < nr ? r + k * CR_RL : r, c, col);
 #pragma unroll
-                for (int k = 0; k < R - 1; ++k)
-                    if (r + k * CR_RL < r1) add_row(w[k], r + k * CR_RL);
+                for (int k = 0; k < RR - 1; ++k)
+                    if (i + k * CR_RL < nr) add_row(w[k], n_src, r + k * CR_RL);
             }
+        }
+    };
+    if (on) {
+        if constexpr (NSRC == CR_SRC_BRANCH) {
+            if (gy.n == 1) rows(CrInt<1>{}, CrInt<R>{});
+            else rows(CrInt<BN_MAX_SRC>{}, CrInt<1>{});
+        } else {
+            rows(CrInt<NSRC>{}, CrInt<R>{});
         }
     }
 #pragma unroll
@@ -175,13 +218,20 @@ __device__ __forceinline__ void col_reduce_body(const float* __restrict__ x, con
     const float *__restrict__ x, const float *__restrict__ y, const GySrc gy, const float *__restrict__ mean,                    \
         const float *__restrict__ var, float eps, int relu, int64_t n, int c, int rows_per_block, double *__restrict__ partial
 
-template <int MODE>
-__global__ __launch_bounds__(256) void col_reduce_kernel(OSN_CR_PARAMS, const float* __restrict__ gamma,
-                                                         const float* __restrict__ beta) {
-    col_reduce_body<MODE, false, MODE == 0 ? OSN_BN_ROWS_STATS : OSN_BN_ROWS_BWD>(x, y, gy, mean, var, eps, relu, n, c, rows_per_block,
-                                                                                  partial, gamma, beta, nullptr);
+// MODE 0: the statistics pass (MASK unused).  MODE 1: one kernel per mask.
+template <int MODE, int MASK = CR_MASK_NONE>
+__global__ __launch_bounds__(256, 512 / CR_BWD_VGPRS) void col_reduce_kernel(OSN_CR_PARAMS, const float* __restrict__ gamma,
+                                                                             const float* __restrict__ beta) {
+    col_reduce_body<MODE, false, MODE == 0 ? OSN_BN_ROWS_STATS : cr_bwd_rows(MASK), MODE == 0 ? 1 : CR_SRC_BRANCH, MASK>(
+        x, y, gy, mean, var, eps, relu, n, c, rows_per_block, partial, gamma, beta, nullptr);
 }
 
+// The sums that store gres keep the loop of round 23 -- every operand a run-time choice, two rows in flight, 106 registers: held to
+// CR_BWD_VGPRS with one row in flight (60 - 64 registers, a kernel per mask) they were 9 % SLOWER in the step (0.287 -> 0.312 ms over
+// their 16 launches, profiles/r25_backward_light_kernels_ab_steps.txt), where the sums without the store gained 4 %.
+#ifndef OSN_BN_ROWS_GRES
+#define OSN_BN_ROWS_GRES 2
+#endif
 __global__ __launch_bounds__(256) void col_reduce_gres_kernel(OSN_CR_PARAMS, float* __restrict__ gres) {
     col_reduce_body<1, true, OSN_BN_ROWS_GRES>(x, y, gy, mean, var, eps, relu, n, c, rows_per_block, partial, nullptr, nullptr, gres);
 }
@@ -685,12 +735,17 @@ extern "C" int osn_bn_backward_multi2(const float* x, const float* y, const floa
         via_gres = !ranges_overlap(gres, span, src.p[i], size_t(n - 1) * size_t(src.ld[i]) + size_t(c));
     const dim3 rgrid(p.n_rb, p.n_cg);
     const bool one_row = g_flat_kernels.load(std::memory_order_relaxed) != 0;
-    if (via_gres)
-        hipLaunchKernelGGL(one_row ? col_reduce_gres_1row_kernel : col_reduce_gres_kernel, rgrid, dim3(256), 0, st, x, y, src, mean,
-                           var, eps, relu, n, c, p.rows_per_block, partial, gres);
-    else
-        hipLaunchKernelGGL(one_row ? col_reduce_1row_kernel<1> : col_reduce_kernel<1>, rgrid, dim3(256), 0, st, x, y, src, mean, var,
-                           eps, relu, n, c, p.rows_per_block, partial, gamma, beta);
+    // the kernel of the column sums by its ReLU mask: none, from x (no y given) or from y
+    const int mask = !relu ? CR_MASK_NONE : (y ? CR_MASK_Y : CR_MASK_X);
+    if (via_gres) {
+        const auto kern = one_row ? col_reduce_gres_1row_kernel : col_reduce_gres_kernel;
+        hipLaunchKernelGGL(kern, rgrid, dim3(256), 0, st, x, y, src, mean, var, eps, relu, n, c, p.rows_per_block, partial, gres);
+    } else {
+        const auto kern = one_row ? col_reduce_1row_kernel<1>
+                                  : (mask == CR_MASK_X ? col_reduce_kernel<1, CR_MASK_X>
+                                                       : (mask == CR_MASK_Y ? col_reduce_kernel<1, CR_MASK_Y> : col_reduce_kernel<1, CR_MASK_NONE>));
+        hipLaunchKernelGGL(kern, rgrid, dim3(256), 0, st, x, y, src, mean, var, eps, relu, n, c, p.rows_per_block, partial, gamma, beta);
+    }
     // ggamma = sum g*xhat, gbeta = sum g  (also the two column sums the apply pass needs)
     hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(c, FIN_COLS)), dim3(FIN_COLS * FIN_PARTS), 0, st, partial, p.n_rb, c, gbeta, ggamma);
     const int64_t total4 = n * (c / 4);

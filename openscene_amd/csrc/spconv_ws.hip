@@ -198,9 +198,12 @@ __global__ __launch_bounds__(256) void spconv_ws_kernel(const float* __restrict_
 }
 
 // out[r] = sum over k ascending, nbr[k][r] >= 0, of partial[k][r]  (rows without any neighbour: zeros)
-// KT: offsets of the map when it is one of the two sizes the U-Net has (fully unrolled: all loads in flight), else 0.
+// KT: offsets of the map when it is one of the two sizes the U-Net has (loads in flight in groups of WS_RED_GROUP), else 0.
+// At most 64 VGPRs (8 waves per SIMD): the reductions of the backward pass run beside the weight gradients and get the registers
+// those leave.
+constexpr int WS_RED_GROUP = 9;
 template <int KT, bool EPI = false>
-__global__ __launch_bounds__(256) void spconv_ws_reduce_kernel(const float* __restrict__ partial, const int32_t* __restrict__ nbr,
+__global__ __launch_bounds__(256, 8) void spconv_ws_reduce_kernel(const float* __restrict__ partial, const int32_t* __restrict__ nbr,
                                                                const float* __restrict__ zeros, float* __restrict__ out,
                                                                int64_t n_dst, int K, int c4, const Epi epi) {
     const int64_t total = n_dst * c4;
@@ -210,16 +213,26 @@ __global__ __launch_bounds__(256) void spconv_ws_reduce_kernel(const float* __re
     const int c = int(e - r * c4);
     float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
     if (KT > 0) {
-        // unconditional loads (an absent offset reads a line of zeros: x + 0 == x): K independent loads per thread
-        float4 v[KT > 0 ? KT : 1];
+        // unconditional loads (an absent offset reads a line of zeros: x + 0 == x), WS_RED_GROUP independent quads per thread at a
+        // time and the adds in ascending k behind each group: s = ((0 + v0) + v1) + ..., the sum all K quads in flight gave, bit for
+        // bit, with 36 registers of quads instead of 4 K (108 at K = 27: no wave of this kernel fitted beside a weight-gradient
+        // launch).  The K table entries are read first, all at once, into one mask: a group is one round trip.
+        constexpr int G = KT > 0 && KT % WS_RED_GROUP == 0 ? WS_RED_GROUP : (KT > 0 ? KT : 1);
+        static_assert(KT <= 32 && (KT <= 0 || KT % G == 0), "one mask word, whole groups");
+        unsigned present = 0;
 #pragma unroll
-        for (int k = 0; k < KT; ++k) {
-            const bool on = nbr[int64_t(k) * n_dst + r] >= 0;
-            const float* src = on ? partial + ((int64_t(k) * n_dst + r) * c4 + c) * 4 : zeros;
-            v[k] = *reinterpret_cast<const float4*>(src);
+        for (int k = 0; k < KT; ++k) present |= (nbr[int64_t(k) * n_dst + r] >= 0 ? 1u : 0u) << k;
+#pragma unroll 1
+        for (int k0 = 0; k0 < KT; k0 += G) {                 // (a loop, not unrolled: unrolled, all K loads are hoisted to the top again)
+            float4 v[G];
+#pragma unroll
+            for (int j = 0; j < G; ++j) {
+                const float* src = (present >> (k0 + j)) & 1u ? partial + ((int64_t(k0 + j) * n_dst + r) * c4 + c) * 4 : zeros;
+                v[j] = *reinterpret_cast<const float4*>(src);
+            }
+#pragma unroll
+            for (int j = 0; j < G; ++j) { s.x += v[j].x; s.y += v[j].y; s.z += v[j].z; s.w += v[j].w; }
         }
-#pragma unroll
-        for (int k = 0; k < KT; ++k) { s.x += v[k].x; s.y += v[k].y; s.z += v[k].z; s.w += v[k].w; }
     } else {
         for (int k = 0; k < K; ++k) {
             if (nbr[int64_t(k) * n_dst + r] >= 0) {

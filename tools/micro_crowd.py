@@ -2,7 +2,10 @@
 """Round 6: how much does the weight-gradient stream stretch the main stream's kernels, and does that depend on the weight gradient's
 L2 MISS traffic?  A side stream replays the weight-gradient probe (tools/probes/wgrad_w1.hip) back to back -- with the product's pair
 order and items (386 MB of misses per launch) or with Z-ordered pair arrays and XCD-pinned strided items (100 MB) -- while the main
-stream times a level-0 batch-norm backward, a batch-norm forward and the dominant tile-list convolution.   REPS=n"""
+stream times a level-0 batch-norm backward, a batch-norm forward and the dominant tile-list convolution.   REPS=n
+Round 25 (the register budget beside the weight gradient): SIDE_CIN=128 makes the side stream's product kernel the <4,3> instance (96: <3,3>),
+ONLY=name,... and CASES=tag,... restrict the workloads and the cases, ROUNDS=n repeats every measurement (a list per key: the spread),
+OSN_LIB_PATH picks the library under test.  The hardware probe is built only with PROBE=1."""
 import ctypes
 import json
 import os
@@ -24,16 +27,23 @@ def main():
     side_n = int(os.environ.get("SIDE", "120"))
     dev = torch.device("cuda", 0)
     _lib.load()
-    lib = ctypes.CDLL(W.build_probe())
-    vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
-    lib.osn_dbg_wgrad_w1.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp]
+    probe = os.environ.get("PROBE", "0") == "1"
+    side_cin = int(os.environ.get("SIDE_CIN", "96"))
+    rounds = int(os.environ.get("ROUNDS", "1"))
+    only = [t for t in os.environ.get("ONLY", "").split(",") if t]
+    only_cases = [t for t in os.environ.get("CASES", "").split(",") if t]
+    lib = None
+    if probe:
+        lib = ctypes.CDLL(W.build_probe())
+        vp, i32, i64 = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64
+        lib.osn_dbg_wgrad_w1.argtypes = [vp, vp, vp, vp, i64, i64, i32, i32, i32, vp, i32, i32, vp, vp, vp, vp]
     vox = syn.shuffled(syn.grid_voxels(syn.room_points(0), 0.02), 0)
     cm = CoordinateManager(torch.from_numpy(syn.batch_coords([vox])).to(dev))
     K, c = 27, 96
     n = cm.size(1)
     x = torch.randn(n, c, device=dev)
     g = torch.randn(n, c, device=dev)
-    xs, gs = torch.randn(n, c, device=dev), torch.randn(n, c, device=dev)       # the side stream's own operands
+    xs, gs = torch.randn(n, side_cin, device=dev), torch.randn(n, c, device=dev)       # the side stream's own operands
     gamma, beta = torch.rand(c, device=dev) + 0.5, torch.randn(c, device=dev)
     mean, var = x.mean(0), x.var(0, unbiased=False)
     rm, rv = torch.zeros(c, device=dev), torch.ones(c, device=dev)
@@ -42,8 +52,8 @@ def main():
     w = torch.randn(K, c, c, device=dev) * 0.05
     wf, _ = ops.weight_prep_tl(w, want_dgrad=False)
     side = torch.cuda.Stream(device=dev)
-    ws = torch.empty(512 * c * c, dtype=torch.float32, device=dev)
-    gw = torch.zeros(K, c, c, device=dev)
+    ws = torch.empty(512 * side_cin * c, dtype=torch.float32, device=dev)
+    gw = torch.zeros(K, side_cin, c, device=dev)
 
     def side_setup(order, plan):
         if order == "morton":
@@ -91,11 +101,15 @@ def main():
     workloads["bn_small_L3_128"] = lambda: ops.bn_forward_train(x3, g3, b3, 1e-5, None, True, rm3, rv3, 0.1)
     res = {}
     cases = [("alone", None, None), ("beside_PRODUCT_kernel", "tile", -1), ("beside_PRODUCT_kernel_zorder_xcd_strided", "morton", -2)]
-    if os.environ.get("PROBE", "0") == "1":
+    if probe:
         cases += [("beside_probe_product_order", "tile", 0), ("beside_probe_zorder_xcd", "morton", 1)]
+    if only:
+        workloads = {k: v for k, v in workloads.items() if k in only}
+    if only_cases:
+        cases = [t for t in cases if t[0] in only_cases]
     lib2 = _lib.load()
     job = ctypes.create_string_buffer(64)
-    for tag, order, plan in cases:
+    for tag, order, plan in [t for t in cases for _ in range(rounds)]:
         cfg = side_setup(order, plan) if order else None
         for name, fn in workloads.items():
             fn()
@@ -106,7 +120,7 @@ def main():
                 s0.record(side)
                 if isinstance(it_d, str):             # the product kernel alone (no reduction) on the strided region items
                     for _ in range(side_n):
-                        rc = lib2.osn_spconv_wgrad_tl_partial(xs.data_ptr(), gs.data_ptr(), pl.data_ptr(), 0, gw.data_ptr(), n, n, K, c, c,
+                        rc = lib2.osn_spconv_wgrad_tl_partial(xs.data_ptr(), gs.data_ptr(), pl.data_ptr(), 0, gw.data_ptr(), n, n, K, side_cin, c,
                                                               ws.data_ptr(), ws.numel() * 4, ctypes.addressof(job), side.cuda_stream)
                         assert rc == 0
                 elif it_d is None:                    # the product's own kernel (158 VGPRs, 2 workgroups per CU) + its reduction
@@ -125,9 +139,16 @@ def main():
                 fn()
             e1.record()
             torch.cuda.synchronize()
-            res["%s/%s_us" % (name, tag)] = round(e0.elapsed_time(e1) / reps * 1e3, 2)
-            if cfg:
-                res["%s/%s_side_us_per_launch" % (name, tag)] = round(s0.elapsed_time(s1) * 1e3 / side_n, 1)
+            us = round(e0.elapsed_time(e1) / reps * 1e3, 2)
+            side_us = round(s0.elapsed_time(s1) * 1e3 / side_n, 1) if cfg else None
+            if rounds > 1:
+                res.setdefault("%s/%s_us" % (name, tag), []).append(us)
+                if cfg:
+                    res.setdefault("%s/%s_side_us_per_launch" % (name, tag), []).append(side_us)
+            else:
+                res["%s/%s_us" % (name, tag)] = us
+                if cfg:
+                    res["%s/%s_side_us_per_launch" % (name, tag)] = side_us
     print(json.dumps(res, indent=1))
 
 
