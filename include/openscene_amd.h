@@ -696,6 +696,39 @@ int osn_bank_pool_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int d
                       const int64_t* rows, int64_t n_entries, const float* weights, int normalize, float* sum, float* wsum,
                       int64_t* count, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
 
+/* ---- second moments of point sets over the bank (csrc/gram.hip) -------------------------------------------------- *
+ * How the features of a point set are spread: the Gram matrix X^T X of its rows -- covariance, principal directions and
+ * explained variance follow on the host (openscene_amd.pca) -- next to the first moment from the same operands.  bank /
+ * (codes, exps), n, d, the CSR groups (starts, n_groups, rows nullable, n_entries), err and the guards are exactly
+ * osn_bank_pool's; there are no weights.  With v the stored row of an entry (the fp16 values, or float(code) * 2^e,
+ * decoded exactly):
+ *     normalize = 1:  h = fp16_rne(v / (||v|| + 1e-5)), the norm in fp32 over the stored values -- run/evaluate.py:305,310
+ *                     including its .half(); the quotient is formed as v * r with r = fp32(2^e / (||c|| * 2^e + 1e-5)),
+ *                     within an fp32 ulp of it
+ *     normalize = 0:  h = fp16_rne(v): exact for an fp16 bank, and for fp8 rows whose values lie in fp16's range
+ *     gram  float32 [n_groups, d, d]:  gram[g, a, b] = sum over the entries of group g of h_a * h_b
+ *     sum   float32 [n_groups, d]:     sum[g, a]     = sum over the entries of group g of h_a   (the same h)
+ *     count int64   [n_groups]:        the entries of the group that were not skipped
+ * The Gram matrix is taken with fp16 MFMA: a product of two fp16 values is exact in the fp32 accumulator, only the
+ * accumulation rounds.  Only the 128-column tiles on or above the diagonal are computed; the launch that adds the
+ * partials writes an element and its mirror image from the same value: gram[g] is bitwise symmetric.
+ * Determinism: no floating-point atomics.  A group is cut into slices of OSN_BANK_GRAM_SLICE consecutive entries, counted
+ * from the group's own start; a slice x tile pair is one fp32 partial in ws; a second launch adds a group's partials in
+ * ascending slice order.  The result is a function of the input arrays alone -- bitwise repeatable -- and a group's bits
+ * do not depend on its place in the list.
+ * Guards: an entry whose row is outside [0, n) is skipped (its loads are made from a clamped address inside the bank and not
+ * used; it enters neither gram, sum nor count) and ORs 8 into the bank's err word; starts that do not ascend from 0 to n_entries are clamped before use and OR 32;
+ * osn_bank_check turns the bits into OSN_E_ARG.  An empty group gives zeros; a NaN row makes its own group NaN and no other.
+ * ws: osn_bank_gram_ws_bytes(n_groups, n_entries, d) bytes -- 64 KiB per slice and tile pair.  Asynchronous.            */
+#define OSN_BANK_GRAM_SLICE 2048
+size_t osn_bank_gram_ws_bytes(int64_t n_groups, int64_t n_entries, int d);
+int osn_bank_gram(const void* bank_f16, int64_t n, int d, const int64_t* starts, int64_t n_groups, const int64_t* rows,
+                  int64_t n_entries, int normalize, float* gram, float* sum, int64_t* count, int32_t* err, void* ws,
+                  size_t ws_bytes, osn_stream_t stream);
+int osn_bank_gram_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int d, const int64_t* starts, int64_t n_groups,
+                      const int64_t* rows, int64_t n_entries, int normalize, float* gram, float* sum, int64_t* count,
+                      int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
+
 /* ---- objects in heat-maps (csrc/objects.hip) -------------------------------------------------------------------- *
  * What the README "Applications" do with a heat-map -- rare object search in a 3D scene database, image-based 3-D object
  * detection, interactive object search -- needs objects, not points: WHERE the matches are, how many, how large, how

@@ -12,6 +12,7 @@ Python surface (mirrors the reference's own, file:line in each module):
     openscene_amd.search           README "Applications": a bank of scenes searched by text or image embedding
     openscene_amd.objects          the same, as objects: connected components of a heat-map, ranked per scene
     openscene_amd.descriptors      and back: scenes, objects and regions of the bank as descriptors (the next query)
+    openscene_amd.pca              the features themselves: second moments of a bank, principal feature directions, feature colours
     openscene_amd.regions          scenes cut into regions of agreeing features before any prompt: label, list, query by region
     openscene_amd.render           views of a scene on the GPU: point-splat z-buffer -> heat-map / label / colour pictures, depth for fusion
     openscene_amd.neighbors        results on other points: k-nearest search on the voxel grid, transfer, fill of unseen rows, smoothing
@@ -71,6 +72,18 @@ def describe_scenes(bank, normalize=True):
     """One descriptor per scene of a FeatureBank (openscene_amd.descriptors.describe_scenes)."""
     from .descriptors import describe_scenes as f
     return f(bank, normalize=normalize)
+
+
+def moments(bank, groups=None, normalize=True):
+    """Count, sum and Gram matrix of a FeatureBank's rows per point set (openscene_amd.pca.moments)."""
+    from .pca import moments as f
+    return f(bank, groups, normalize=normalize)
+
+
+def feature_colors(bank, per_scene=False):
+    """Every bank row coloured by its first three principal feature directions (openscene_amd.pca.feature_colors)."""
+    from .pca import feature_colors as f
+    return f(bank, per_scene=per_scene)
 
 
 def segment(bank, grid, similarity=0.9, min_points=1, names=None):

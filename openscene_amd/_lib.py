@@ -133,6 +133,9 @@ PROTOTYPES = {
     "osn_bank_pool_ws_bytes": (_sz, [_i64, _i64, _i32]),
     "osn_bank_pool": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "osn_bank_pool_fp8": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "osn_bank_gram_ws_bytes": (_sz, [_i64, _i64, _i32]),
+    "osn_bank_gram": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "osn_bank_gram_fp8": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "osn_objects_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "osn_objects_records_bytes": (_sz, [_i64]),
     "osn_objects_label": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _sz, _c.POINTER(_i64), _vp]),

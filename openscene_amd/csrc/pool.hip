@@ -5,8 +5,8 @@
 //                                        (run/evaluate.py:305, the normalisation the query scores with) or  w_i * v_i,
 //                                        v_i the stored row (fp16, or code * 2^e decoded exactly), everything in fp32
 //
-// A group is cut into chunks of OSN_BANK_POOL_CHUNK consecutive entries; pool_scan_kernel numbers the chunks (one exclusive
-// scan over the groups' chunk counts).  pool_kernel gives a chunk to a workgroup: wave w takes the chunk's entries w, w + 4, ...
+// A group is cut into chunks of OSN_BANK_POOL_CHUNK consecutive entries; bank_chunk_scan_kernel (bank.h) numbers the chunks (one
+// exclusive scan over the groups' chunk counts).  pool_kernel gives a chunk to a workgroup: wave w takes the chunk's entries w, w + 4, ...
 // in order.  A wave owns a whole row: 16 bytes per lane and load group, the row stays in registers while the sum of squares is
 // reduced across the wave (xor butterfly: every lane ends with the same bits), then the row is scaled and added into the lane's
 // fp32 accumulators.  Four rows are in flight per wave.  The four waves add their accumulators through LDS in wave order into
@@ -22,47 +22,7 @@ namespace osn {
 
 constexpr int P_C = OSN_BANK_POOL_CHUNK;
 constexpr int P_U = 4;             // rows a wave has in flight
-constexpr int P_SCAN_T = 1024;     // threads of the one scan workgroup
 static_assert(P_C % 4 == 0, "a chunk is dealt to four waves");
-
-// entries [a, b) of group g, clamped so that nothing is read out of bounds whatever `starts` holds (pool_scan_kernel reports it)
-__device__ inline void pool_range(const int64_t* __restrict__ starts, int64_t g, int64_t L, int64_t& a, int64_t& b) {
-    a = starts[g];
-    b = starts[g + 1];
-    a = a < 0 ? 0 : (a > L ? L : a);
-    b = b < a ? a : (b > L ? L : b);
-}
-
-// chunk_base[g] = the number of chunks of the groups before g; chunk_base[G] = all chunks
-__global__ __launch_bounds__(P_SCAN_T) void pool_scan_kernel(const int64_t* __restrict__ starts, int64_t G, int64_t L,
-                                                             int64_t* __restrict__ chunk_base, int32_t* __restrict__ err) {
-    __shared__ int64_t sh[P_SCAN_T];
-    const int tid = threadIdx.x;
-    int64_t carry = 0;
-    for (int64_t g0 = 0; g0 < G; g0 += P_SCAN_T) {
-        const int64_t g = g0 + tid;
-        int64_t c = 0;
-        if (g < G) {
-            const int64_t sa = starts[g], sb = starts[g + 1];
-            if (sa < 0 || sb < sa || sb > L || (g == 0 && sa != 0) || (g == G - 1 && sb != L)) atomicOr(err, BANK_E_POOL_STARTS);
-            int64_t a, b;
-            pool_range(starts, g, L, a, b);
-            c = (b - a + P_C - 1) / P_C;
-        }
-        sh[tid] = c;
-        __syncthreads();
-        for (int o = 1; o < P_SCAN_T; o <<= 1) {
-            const int64_t v = sh[tid] + (tid >= o ? sh[tid - o] : 0);
-            __syncthreads();
-            sh[tid] = v;
-            __syncthreads();
-        }
-        if (g < G) chunk_base[g] = carry + sh[tid] - c;
-        carry += sh[P_SCAN_T - 1];
-        __syncthreads();
-    }
-    if (tid == 0) chunk_base[G] = carry;
-}
 
 // one workgroup per chunk.  FP8: rows are e4m3fn codes (16 per 16-byte load) with the exponents E, else fp16 (8 per load);
 // NG = the 16-byte load groups a lane holds of a row (d <= 64 * NG * EL)
@@ -88,7 +48,7 @@ __global__ __launch_bounds__(256) void pool_kernel(const void* __restrict__ B, c
         else hi = mid;
     }
     int64_t a, b;
-    pool_range(starts, lo, L, a, b);
+    bank_group_range(starts, lo, L, a, b);
     const int64_t e0 = a + (chunk - chunk_base[lo]) * P_C;
     const int64_t e1 = e0 + P_C < b ? e0 + P_C : b;
     const int ng = d / EL;
@@ -276,7 +236,7 @@ static int bank_pool_impl(const char* who, const void* bank, const int8_t* exps,
     float* psum = reinterpret_cast<float*>(p + w.psum);
     float* pw = reinterpret_cast<float*>(p + w.pw);
     int32_t* pc = reinterpret_cast<int32_t*>(p + w.pc);
-    hipLaunchKernelGGL(pool_scan_kernel, dim3(1), dim3(P_SCAN_T), 0, st, starts, n_groups, n_entries, chunk_base, err);
+    hipLaunchKernelGGL(bank_chunk_scan_kernel<P_C>, dim3(1), dim3(BANK_SCAN_T), 0, st, starts, n_groups, n_entries, chunk_base, err);
     if (w.max_chunks > 0) {
         // an empty bank: every entry is out of range and skipped; the clamped loads still need 16 readable bytes
         const void* B = n > 0 ? bank : static_cast<const void*>(psum);

@@ -1533,9 +1533,9 @@ BANK_POOL_CHUNK = 512            # OSN_BANK_POOL_CHUNK: the entries of a group t
 BANK_POOL_MAX_DIM = 1024         # OSN_BANK_POOL_MAX_DIM: the widest row a wave keeps in registers
 
 
-def _bank_pool(entry, bank_ptrs, n, d, d_multiple, dev, starts, rows, weights, normalize, n_entries, err):
-    """bank_pool and bank_pool_fp8 behind their own checks of the bank: `entry` is the C entry that takes `bank_ptrs`
-    (the fp16 rows, or the codes and the exponents) ahead of the arguments the two share."""
+def _bank_groups(d, d_multiple, dev, starts, rows, n_entries, err):
+    """What the pool and the Gram matrix check alike: the feature dim and the CSR groups over the bank.
+    -> (starts, g, rows, n_entries, err, own_err)"""
     if d < d_multiple or d % d_multiple:
         raise ValueError("the feature dim must be a multiple of %d (got %d)" % (d_multiple, d))
     if d > BANK_POOL_MAX_DIM:
@@ -1560,17 +1560,24 @@ def _bank_pool(entry, bank_ptrs, n, d, d_multiple, dev, starts, rows, weights, n
     n_entries = int(n_entries)
     if n_entries < 0:
         raise ValueError("n_entries must not be negative (got %d)" % n_entries)
+    own_err = err is None
+    if own_err:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif err.dtype != torch.int32 or err.numel() != 1 or err.device != dev:
+        raise ValueError("err must be an int32 [1] tensor on the bank's device")
+    return starts, g, rows, n_entries, err, own_err
+
+
+def _bank_pool(entry, bank_ptrs, n, d, d_multiple, dev, starts, rows, weights, normalize, n_entries, err):
+    """bank_pool and bank_pool_fp8 behind their own checks of the bank: `entry` is the C entry that takes `bank_ptrs`
+    (the fp16 rows, or the codes and the exponents) ahead of the arguments the two share."""
+    starts, g, rows, n_entries, err, own_err = _bank_groups(d, d_multiple, dev, starts, rows, n_entries, err)
     if weights is not None:
         if not isinstance(weights, torch.Tensor) or weights.dtype != torch.float32:
             raise TypeError("weights must be a float32 tensor")
         if tuple(weights.shape) != (n_entries,) or weights.device != dev:
             raise ValueError("weights must be a float32 [%d] vector on the bank's device (got %s)" % (n_entries, tuple(weights.shape)))
         weights = weights.contiguous()
-    own_err = err is None
-    if own_err:
-        err = torch.zeros(1, dtype=torch.int32, device=dev)
-    elif err.dtype != torch.int32 or err.numel() != 1 or err.device != dev:
-        raise ValueError("err must be an int32 [1] tensor on the bank's device")
     out = torch.empty((g, d), dtype=torch.float32, device=dev)
     wsum = torch.empty((g,), dtype=torch.float32, device=dev)
     count = torch.empty((g,), dtype=torch.int64, device=dev)
@@ -1584,6 +1591,28 @@ def _bank_pool(entry, bank_ptrs, n, d, d_multiple, dev, starts, rows, weights, n
     return out, wsum, count
 
 
+def _fp16_bank(bank):
+    """The checks of an fp16 bank's rows.  -> (n, d)"""
+    if bank.dtype != torch.float16:
+        raise TypeError("the bank must be float16 (got %s)" % bank.dtype)
+    if bank.dim() != 2 or not bank.is_contiguous():
+        raise ValueError("the bank must be a contiguous [rows, dim] matrix")
+    return bank.shape
+
+
+def _fp8_bank(codes, exps):
+    """The checks of an fp8 bank's codes and exponents.  -> (n, d)"""
+    if codes.dtype != torch.uint8:
+        raise TypeError("codes must be uint8 (got %s)" % codes.dtype)
+    if exps.dtype != torch.int8:
+        raise TypeError("exponents must be int8 (got %s)" % exps.dtype)
+    if codes.dim() != 2 or not codes.is_contiguous():
+        raise ValueError("codes must be a contiguous [rows, dim] matrix")
+    if exps.dim() != 1 or exps.shape[0] != codes.shape[0] or exps.device != codes.device or not exps.is_contiguous():
+        raise ValueError("exponents must be a contiguous [%d] vector on the codes' device" % codes.shape[0])
+    return codes.shape
+
+
 def bank_pool(bank, starts, rows=None, weights=None, normalize=True, n_entries=None, err=None):
     """Sums of the (normalised, weighted) rows of every group of a CSR list of bank rows: an entry adds
     ``w * hf / (hf.norm() + 1e-5)`` (`run/evaluate.py:305`; normalize) or ``w * hf`` of its stored fp16 row, in fp32.
@@ -1594,11 +1623,7 @@ def bank_pool(bank, starts, rows=None, weights=None, normalize=True, n_entries=N
     and a negative or non-finite weight skip their entry and are recorded in `err` when one is given (bank_check raises),
     and checked here otherwise."""
     lib = _prep(bank.device)
-    if bank.dtype != torch.float16:
-        raise TypeError("the bank must be float16 (got %s)" % bank.dtype)
-    if bank.dim() != 2 or not bank.is_contiguous():
-        raise ValueError("the bank must be a contiguous [rows, dim] matrix")
-    n, d = bank.shape
+    n, d = _fp16_bank(bank)
     return _bank_pool(lib.osn_bank_pool, (_p(bank),), n, d, 8, bank.device, starts, rows, weights, normalize, n_entries, err)
 
 
@@ -1607,16 +1632,49 @@ def bank_pool_fp8(codes, exps, starts, rows=None, weights=None, normalize=True, 
     code * 2^e, decoded exactly.  Everything else is bank_pool's."""
     dev = codes.device
     lib = _prep(dev)
-    if codes.dtype != torch.uint8:
-        raise TypeError("codes must be uint8 (got %s)" % codes.dtype)
-    if exps.dtype != torch.int8:
-        raise TypeError("exponents must be int8 (got %s)" % exps.dtype)
-    if codes.dim() != 2 or not codes.is_contiguous():
-        raise ValueError("codes must be a contiguous [rows, dim] matrix")
-    if exps.dim() != 1 or exps.shape[0] != codes.shape[0] or exps.device != dev or not exps.is_contiguous():
-        raise ValueError("exponents must be a contiguous [%d] vector on the codes' device" % codes.shape[0])
-    n, d = codes.shape
+    n, d = _fp8_bank(codes, exps)
     return _bank_pool(lib.osn_bank_pool_fp8, (_p(codes), _p(exps)), n, d, 16, dev, starts, rows, weights, normalize, n_entries, err)
+
+
+# ------------------------------------------------------------------------ gram
+BANK_GRAM_SLICE = 2048           # OSN_BANK_GRAM_SLICE: the entries of a group that are reduced into one fp32 partial per tile pair
+
+
+def _bank_gram(entry, bank_ptrs, n, d, d_multiple, dev, starts, rows, normalize, n_entries, err):
+    """bank_gram and bank_gram_fp8 behind their own checks of the bank (the pool's checks of the groups)."""
+    starts, g, rows, n_entries, err, own_err = _bank_groups(d, d_multiple, dev, starts, rows, n_entries, err)
+    gram = torch.empty((g, d, d), dtype=torch.float32, device=dev)
+    total = torch.empty((g, d), dtype=torch.float32, device=dev)
+    count = torch.empty((g,), dtype=torch.int64, device=dev)
+    wsb = _cached("osn_bank_gram_ws_bytes", g, n_entries, d)
+    ws = _ws(wsb, dev)
+    with _Dev(dev):
+        check(entry(*bank_ptrs, n, d, _p(starts), g, _p(rows), n_entries, int(bool(normalize)), _p(gram), _p(total), _p(count),
+                    _p(err), _p(ws), ws.numel(), _stream(dev)), entry.__name__)
+    if own_err and g > 0:
+        bank_check(err)
+    return gram, total, count
+
+
+def bank_gram(bank, starts, rows=None, normalize=True, n_entries=None, err=None):
+    """Second and first moments of the rows of every group of a CSR list of bank rows: with
+    ``h = (hf / (hf.norm() + 1e-5)).half()`` (`run/evaluate.py:305,310`; normalize) or ``h = hf`` of an entry's stored row,
+    gram[g] = sum h h^T (fp16 MFMA: exact products, fp32 accumulation), sum[g] = sum h.
+    bank, starts, rows, n_entries and err as bank_pool.
+    -> (gram float32 [G, d, d], bitwise symmetric; sum float32 [G, d]; count int64 [G]).
+    A group is reduced in slices of BANK_GRAM_SLICE entries in a fixed order: bitwise repeatable."""
+    lib = _prep(bank.device)
+    n, d = _fp16_bank(bank)
+    return _bank_gram(lib.osn_bank_gram, (_p(bank),), n, d, 8, bank.device, starts, rows, normalize, n_entries, err)
+
+
+def bank_gram_fp8(codes, exps, starts, rows=None, normalize=True, n_entries=None, err=None):
+    """bank_gram over an fp8 bank: codes uint8 [N, d] (e4m3fn), exps int8 [N], d % 16 == 0; a row's value is
+    code * 2^e, decoded exactly and rounded to fp16 (after the normalisation).  Everything else is bank_gram's."""
+    dev = codes.device
+    lib = _prep(dev)
+    n, d = _fp8_bank(codes, exps)
+    return _bank_gram(lib.osn_bank_gram_fp8, (_p(codes), _p(exps)), n, d, 16, dev, starts, rows, normalize, n_entries, err)
 
 
 # --------------------------------------------------------------------- objects
