@@ -729,6 +729,49 @@ int osn_bank_gram_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int d
                       const int64_t* rows, int64_t n_entries, int normalize, float* gram, float* sum, int64_t* count,
                       int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
 
+/* ---- bank rows matched to exemplars (csrc/match.hip) ------------------------------------------------------------- *
+ * For each of n_rows bank rows the k most similar of n_exemplars exemplar rows -- label by example, correspondences,
+ * novelty -- without an n_rows x n_exemplars array anywhere.  bank / (codes, exps), n, d, err and the row guard are
+ * osn_bank_gram's; `rows` int64 [n_rows] (device) or null: entry i is bank row i.
+ *   operand  u = fp16_rne(v * r) with v the stored row (the fp16 values, or float(code) * 2^e decoded exactly) and r the fp32
+ *            factor 1 / (||v|| + 1e-5) (run/evaluate.py:305,310; fp8: 2^e / (||c|| * 2^e + 1e-5)); normalize = 0: u = fp16_rne(v).
+ *            Bit for bit the operand h of osn_bank_gram.
+ *   score    s(p, e) = the fp32 MFMA accumulation (v_mfma_f32_16x16x32_f16) of the exact fp16 x fp16 products over d in
+ *            ascending steps of 32 from a zero accumulator, zeros past d: a function of the two operand rows and d alone, not
+ *            of n_rows, n_exemplars, the position of either row, k, or how the exemplars are split over workgroups.
+ *   order    one 64-bit key per candidate: the monotone 32-bit image of the score in the high word, 0xFFFFFFFF - position in
+ *            the low word; the largest key is the best.  A NaN ranks below -inf; -0 ranks as, and is returned as, +0; equal
+ *            scores go to the lower exemplar position.
+ *   result   idx int32 [n_rows, k]: positions in the exemplar list, -1 past count; score float32 [n_rows, k], -inf past
+ *            count; count int32 [n_rows] = min(k, n_exemplars); a row's list in descending key order.  No floating-point
+ *            atomics: bitwise repeatable.
+ * osn_bank_unit_rows gathers a row list and writes its operands as the fp16 image [n_rows, d] (16-byte aligned) that
+ * osn_bank_match takes as `exemplars_f16`; the query side is read straight from the bank and its operands are formed in
+ * the kernel.  A row outside [0, n) writes zeros (unit_rows) or is matched as a zero row (match) and ORs 8 into the err
+ * word; osn_bank_check turns the bit into OSN_E_ARG.
+ * Limits: d % 8 == 0 (fp16 bank) or d % 16 == 0 (fp8 bank), d <= OSN_BANK_POOL_MAX_DIM, 1 <= k <= OSN_BANK_MATCH_MAX_K,
+ * 1 <= n_exemplars < 2^31; n_rows = 0 returns at once.  A workgroup owns OSN_BANK_MATCH_TILE_Q query rows and a contiguous
+ * range of tiles of OSN_BANK_MATCH_TILE_E exemplars; the tiles are cut into `splits` ranges (0: chosen here so that the grid
+ * fills the device; at most OSN_BANK_MATCH_MAX_SPLITS) whose k keys per row a second launch merges.  The result does not
+ * depend on `splits`.
+ * ws: osn_bank_match_ws_bytes(n_rows, n_exemplars, d, k, splits) = 8 * n_rows * k * splits bytes (the splits in effect) plus a
+ * constant below 8 KiB: it never grows with n_rows * n_exemplars.  Asynchronous.                                        */
+#define OSN_BANK_MATCH_MAX_K 8
+#define OSN_BANK_MATCH_TILE_Q 64
+#define OSN_BANK_MATCH_TILE_E 256
+#define OSN_BANK_MATCH_MAX_SPLITS 64
+int osn_bank_unit_rows(const void* bank_f16, int64_t n, int d, const int64_t* rows, int64_t n_rows, int normalize,
+                       void* out_f16, int32_t* err, osn_stream_t stream);
+int osn_bank_unit_rows_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int d, const int64_t* rows, int64_t n_rows,
+                           int normalize, void* out_f16, int32_t* err, osn_stream_t stream);
+size_t osn_bank_match_ws_bytes(int64_t n_rows, int64_t n_exemplars, int d, int k, int splits);
+int osn_bank_match(const void* bank_f16, int64_t n, int d, const int64_t* rows, int64_t n_rows, int normalize,
+                   const void* exemplars_f16, int64_t n_exemplars, int k, int splits, int32_t* idx, float* score,
+                   int32_t* count, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
+int osn_bank_match_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int d, const int64_t* rows, int64_t n_rows,
+                       int normalize, const void* exemplars_f16, int64_t n_exemplars, int k, int splits, int32_t* idx,
+                       float* score, int32_t* count, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
+
 /* ---- objects in heat-maps (csrc/objects.hip) -------------------------------------------------------------------- *
  * What the README "Applications" do with a heat-map -- rare object search in a 3D scene database, image-based 3-D object
  * detection, interactive object search -- needs objects, not points: WHERE the matches are, how many, how large, how

@@ -13,6 +13,7 @@ Python surface (mirrors the reference's own, file:line in each module):
     openscene_amd.objects          the same, as objects: connected components of a heat-map, ranked per scene
     openscene_amd.descriptors      and back: scenes, objects and regions of the bank as descriptors (the next query)
     openscene_amd.pca              the features themselves: second moments of a bank, principal feature directions, feature colours
+    openscene_amd.match            bank rows matched to exemplar rows: label by example, correspondences, novelty
     openscene_amd.regions          scenes cut into regions of agreeing features before any prompt: label, list, query by region
     openscene_amd.render           views of a scene on the GPU: point-splat z-buffer -> heat-map / label / colour pictures, depth for fusion
     openscene_amd.neighbors        results on other points: k-nearest search on the voxel grid, transfer, fill of unseen rows, smoothing
@@ -84,6 +85,18 @@ def feature_colors(bank, per_scene=False):
     """Every bank row coloured by its first three principal feature directions (openscene_amd.pca.feature_colors)."""
     from .pca import feature_colors as f
     return f(bank, per_scene=per_scene)
+
+
+def match_exemplars(bank, exemplars, k=1, rows=None):
+    """For each bank row the k most similar exemplar rows (openscene_amd.match.match; the submodule keeps the short name)."""
+    from .match import match as f
+    return f(bank, exemplars, k=k, rows=rows)
+
+
+def transfer_labels(bank, exemplars, k=1, rows=None, min_score=None, fill=-1):
+    """Labels of the most similar exemplars for every bank row (openscene_amd.match.transfer_labels)."""
+    from .match import transfer_labels as f
+    return f(bank, exemplars, k=k, rows=rows, min_score=min_score, fill=fill)
 
 
 def segment(bank, grid, similarity=0.9, min_points=1, names=None):

@@ -136,6 +136,11 @@ PROTOTYPES = {
     "osn_bank_gram_ws_bytes": (_sz, [_i64, _i64, _i32]),
     "osn_bank_gram": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "osn_bank_gram_fp8": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "osn_bank_unit_rows": (_i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "osn_bank_unit_rows_fp8": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _vp, _vp]),
+    "osn_bank_match_ws_bytes": (_sz, [_i64, _i64, _i32, _i32, _i32]),
+    "osn_bank_match": (_i32, [_vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
+    "osn_bank_match_fp8": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _i32, _vp, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "osn_objects_ws_bytes": (_sz, [_i64, _i32, _i32]),
     "osn_objects_records_bytes": (_sz, [_i64]),
     "osn_objects_label": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _i64, _vp, _i32, _vp, _i32, _vp, _vp, _sz, _c.POINTER(_i64), _vp]),

@@ -7,7 +7,7 @@
 //                                        gram[g] = sum h h^T, sum[g] = sum h over the entries of group g, fp32
 //
 // A group is cut into slices of OSN_BANK_GRAM_SLICE consecutive entries (bank_chunk_scan_kernel numbers them).
-// gram_scale_kernel writes one fp32 factor per entry (with normalize: one wave per row, the pool's reduction).  gram_kernel gives
+// bank_scale_kernel (bank.h) writes one fp32 factor per entry (with normalize: one wave per row, the pool's reduction).  gram_kernel gives
 // a workgroup one slice and one pair of 128-column tiles (ti <= tj): per step of 32 entries it loads the two column strips
 // (16 / 8 bytes per lane and entry), multiplies by the entry's factor, rounds to fp16 and stages the strips ROW-MAJOR
 // [entry][column] in LDS (two buffers, one barrier per step; the loads of four steps are in flight in a register ring).  The
@@ -43,48 +43,6 @@ __device__ inline void gram_pair(int p, int nt, int& ti, int& tj) {
     ti = 0;
     while (p >= nt - ti) { p -= nt - ti; ++ti; }
     tj = ti + p;
-}
-
-// scale[i] = the factor of entry i's row: 2^e / (||c|| 2^e + 1e-5) (fp16 rows: 2^e = 1), or 2^e alone when the rows are taken as
-// they are stored; one wave per entry, the pool's reduction
-template <bool FP8>
-__global__ __launch_bounds__(256) void gram_scale_kernel(const void* __restrict__ B, const int8_t* __restrict__ E, int64_t n, int d,
-                                                         const int64_t* __restrict__ rows, int64_t L, int normalize,
-                                                         float* __restrict__ scale) {
-    constexpr int EL = FP8 ? 16 : 8;
-    constexpr int RB = FP8 ? 1 : 2;
-    const int lane = threadIdx.x & 63;
-    const int64_t i = int64_t(blockIdx.x) * 4 + (threadIdx.x >> 6);
-    if (i >= L) return;
-    const int64_t r = rows ? rows[i] : i;
-    if (r < 0 || r >= n) {                                  // skipped by gram_kernel, which reports it
-        if (lane == 0) scale[i] = 0.f;
-        return;
-    }
-    const float sc = FP8 ? __uint_as_float(uint32_t(127 + int(E[r])) << 23) : 1.f;      // 2^e
-    if (!normalize) {
-        if (lane == 0) scale[i] = sc;
-        return;
-    }
-    const char* row = static_cast<const char*>(B) + r * int64_t(d) * RB;
-    const int ng = d / EL;
-    float ss = 0.f;
-    for (int grp = lane; grp < ng; grp += 64) {
-        const uint4 raw = *reinterpret_cast<const uint4*>(row + int64_t(grp) * 16);
-        if (FP8) {
-            half2 h[8];
-            q8_widen(raw, h);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) { ss = fmaf((float)h[k][0], (float)h[k][0], ss); ss = fmaf((float)h[k][1], (float)h[k][1], ss); }
-        } else {
-            const half8 h = __builtin_bit_cast(half8, raw);
-#pragma unroll
-            for (int k = 0; k < 8; ++k) ss = fmaf((float)h[k], (float)h[k], ss);
-        }
-    }
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) ss += __shfl_xor(ss, m, 64);
-    if (lane == 0) scale[i] = sc / (sqrtf(ss) * sc + 1e-5f);
 }
 
 // one workgroup per (slice, tile pair); the grid is dealt so that the pairs of a slice run on one XCD (one L2)
@@ -164,10 +122,7 @@ __global__ __launch_bounds__(256) void gram_kernel(const void* __restrict__ B, i
         } else {
             v = __builtin_bit_cast(half8, raw);
         }
-        half8 o;
-#pragma unroll
-        for (int k = 0; k < 8; ++k) o[k] = (_Float16)((float)v[k] * s);
-        return o;
+        return bank_round8(v, s);
     };
     auto stage = [&](int buf, int slot) {
 #pragma unroll
@@ -372,7 +327,7 @@ static int bank_gram_impl(const char* who, const void* bank, const int8_t* exps,
     if (w.max_slices > 0) {
         // an empty bank: every entry is out of range and skipped; the clamped loads still need readable bytes
         const void* B = n > 0 ? bank : static_cast<const void*>(pgram);
-        hipLaunchKernelGGL((gram_scale_kernel<FP8>), dim3(unsigned(cdiv(n_entries, 4))), dim3(256), 0, st, B, exps, n, d, rows,
+        hipLaunchKernelGGL((bank_scale_kernel<FP8>), dim3(unsigned(cdiv(n_entries, 4))), dim3(256), 0, st, B, exps, n, d, rows,
                            n_entries, normalize, scale);
         const dim3 grid(unsigned((n_blocks + 7) / 8 * 8)), block(256);
 #define OSN_GRAM_LAUNCH(ROWS)                                                                                                  \

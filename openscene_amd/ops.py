@@ -1677,6 +1677,123 @@ def bank_gram_fp8(codes, exps, starts, rows=None, normalize=True, n_entries=None
     return _bank_gram(lib.osn_bank_gram_fp8, (_p(codes), _p(exps)), n, d, 16, dev, starts, rows, normalize, n_entries, err)
 
 
+# ----------------------------------------------------------------------- match
+BANK_MATCH_MAX_K = 8             # OSN_BANK_MATCH_MAX_K
+BANK_MATCH_TILE_Q = 64           # OSN_BANK_MATCH_TILE_Q: the query rows of a workgroup
+BANK_MATCH_TILE_E = 256          # OSN_BANK_MATCH_TILE_E: the exemplars of a tile
+BANK_MATCH_MAX_SPLITS = 64       # OSN_BANK_MATCH_MAX_SPLITS: the most ranges the exemplar tiles are cut into
+
+
+def _bank_rows(d, d_multiple, dev, rows, n, err):
+    """What unit_rows and match check alike (the pool's wording): the feature dim, the row list, the err word.
+    -> (rows, n_rows, err, own_err)"""
+    if d < d_multiple or d % d_multiple:
+        raise ValueError("the feature dim must be a multiple of %d (got %d)" % (d_multiple, d))
+    if d > BANK_POOL_MAX_DIM:
+        raise ValueError("the feature dim must be at most %d (got %d)" % (BANK_POOL_MAX_DIM, d))
+    if rows is not None:
+        if not isinstance(rows, torch.Tensor) or rows.dtype != torch.int64:
+            raise TypeError("rows must be an int64 tensor (or None: entry i is bank row i)")
+        if rows.dim() != 1 or rows.device != dev:
+            raise ValueError("rows must be an int64 [L] vector on the bank's device")
+        rows = rows.contiguous()
+    n_rows = rows.shape[0] if rows is not None else n
+    own_err = err is None
+    if own_err:
+        err = torch.zeros(1, dtype=torch.int32, device=dev)
+    elif err.dtype != torch.int32 or err.numel() != 1 or err.device != dev:
+        raise ValueError("err must be an int32 [1] tensor on the bank's device")
+    return rows, n_rows, err, own_err
+
+
+def _bank_unit_rows(entry, bank_ptrs, n, d, d_multiple, dev, rows, normalize, err):
+    rows, m, err, own_err = _bank_rows(d, d_multiple, dev, rows, n, err)
+    out = torch.empty((m, d), dtype=torch.float16, device=dev)
+    with _Dev(dev):
+        check(entry(*bank_ptrs, n, d, _p(rows), m, int(bool(normalize)), _p(out), _p(err), _stream(dev)), entry.__name__)
+    if own_err and m > 0:
+        bank_check(err)
+    return out
+
+
+def bank_unit_rows(bank, rows=None, normalize=True, err=None):
+    """The operands of a list of bank rows as an fp16 image [M, d]: ``(hf / (hf.norm() + 1e-5)).half()``
+    (`run/evaluate.py:305,310`; normalize) or the stored row, bit for bit what bank_gram multiplies.  bank fp16 [N, d],
+    d <= BANK_POOL_MAX_DIM; rows int64 [M] on the device or None (every row).  A row outside the bank writes zeros and is
+    recorded in `err` when one is given (bank_check raises), and checked here otherwise."""
+    lib = _prep(bank.device)
+    n, d = _fp16_bank(bank)
+    return _bank_unit_rows(lib.osn_bank_unit_rows, (_p(bank),), n, d, 8, bank.device, rows, normalize, err)
+
+
+def bank_unit_rows_fp8(codes, exps, rows=None, normalize=True, err=None):
+    """bank_unit_rows over an fp8 bank: codes uint8 [N, d] (e4m3fn), exps int8 [N], d % 16 == 0; a row's value is
+    code * 2^e, decoded exactly and rounded to fp16 (after the normalisation)."""
+    dev = codes.device
+    lib = _prep(dev)
+    n, d = _fp8_bank(codes, exps)
+    return _bank_unit_rows(lib.osn_bank_unit_rows_fp8, (_p(codes), _p(exps)), n, d, 16, dev, rows, normalize, err)
+
+
+def bank_match_ws_bytes(n_rows, n_exemplars, d, k, splits=None):
+    """The bytes of workspace a bank_match call takes: 8 * n_rows * k * splits plus a constant, never n_rows * n_exemplars."""
+    return _cached("osn_bank_match_ws_bytes", int(n_rows), int(n_exemplars), int(d), int(k), 0 if splits is None else int(splits))
+
+
+def _bank_match(entry, bank_ptrs, n, d, d_multiple, dev, exemplars, k, rows, normalize, splits, err):
+    if not isinstance(exemplars, torch.Tensor) or exemplars.dtype != torch.float16:
+        raise TypeError("exemplars must be a float16 tensor (bank_unit_rows makes them)")
+    if exemplars.dim() != 2 or exemplars.shape[1] != d:
+        raise ValueError("exemplars must be [M, %d] (got %s)" % (d, tuple(exemplars.shape)))
+    if exemplars.device != dev:
+        raise ValueError("exemplars must be on the bank's device")
+    m = exemplars.shape[0]
+    if not 1 <= m < (1 << 31):
+        raise ValueError("1 .. 2^31 - 1 exemplars per call (got %d)" % m)
+    exemplars = exemplars.contiguous()
+    k = int(k)
+    if not 1 <= k <= BANK_MATCH_MAX_K:
+        raise ValueError("k must be in 1 .. %d (got %d)" % (BANK_MATCH_MAX_K, k))
+    splits = 0 if splits is None else int(splits)
+    if splits != 0 and not 1 <= splits <= BANK_MATCH_MAX_SPLITS:
+        raise ValueError("splits must be in 1 .. %d or None (got %d)" % (BANK_MATCH_MAX_SPLITS, splits))
+    rows, l, err, own_err = _bank_rows(d, d_multiple, dev, rows, n, err)
+    idx = torch.empty((l, k), dtype=torch.int32, device=dev)
+    score = torch.empty((l, k), dtype=torch.float32, device=dev)
+    count = torch.empty((l,), dtype=torch.int32, device=dev)
+    wsb = _cached("osn_bank_match_ws_bytes", l, m, d, k, splits)
+    ws = _ws(wsb, dev)
+    with _Dev(dev):
+        check(entry(*bank_ptrs, n, d, _p(rows), l, int(bool(normalize)), _p(exemplars), m, k, splits, _p(idx), _p(score), _p(count),
+                    _p(err), _p(ws), ws.numel(), _stream(dev)), entry.__name__)
+    if own_err and l > 0:
+        bank_check(err)
+    return idx, score, count
+
+
+def bank_match(bank, exemplars, k=1, rows=None, normalize=True, splits=None, err=None):
+    """For each of the bank rows `rows` (int64 [L] on the device; None: every row) the k most similar of the exemplars.
+    bank fp16 [N, d]; exemplars fp16 [M, d]: an image from bank_unit_rows; 1 <= k <= BANK_MATCH_MAX_K.  The query row's
+    operand is bank_unit_rows' (normalize as there), the score the fp32 MFMA accumulation of the fp16 products over d in a
+    fixed order, equal scores go to the lower exemplar position, a NaN ranks below -inf.
+    -> (idx int32 [L, k], -1 past count; score float32 [L, k], -inf past count; count int32 [L] = min(k, M)).
+    A workgroup takes BANK_MATCH_TILE_Q rows and tiles of BANK_MATCH_TILE_E exemplars; the tiles are cut into `splits`
+    ranges (None: chosen so that the grid fills the device) -- the result does not depend on it.  Bitwise repeatable.  err
+    as bank_unit_rows (a row outside the bank is matched as a zero row)."""
+    lib = _prep(bank.device)
+    n, d = _fp16_bank(bank)
+    return _bank_match(lib.osn_bank_match, (_p(bank),), n, d, 8, bank.device, exemplars, k, rows, normalize, splits, err)
+
+
+def bank_match_fp8(codes, exps, exemplars, k=1, rows=None, normalize=True, splits=None, err=None):
+    """bank_match with the query rows of an fp8 bank: codes uint8 [N, d] (e4m3fn), exps int8 [N], d % 16 == 0.  The
+    exemplars are an fp16 image all the same (bank_unit_rows_fp8 widens fp8 rows once)."""
+    dev = codes.device
+    lib = _prep(dev)
+    n, d = _fp8_bank(codes, exps)
+    return _bank_match(lib.osn_bank_match_fp8, (_p(codes), _p(exps)), n, d, 16, dev, exemplars, k, rows, normalize, splits, err)
+
+
 # --------------------------------------------------------------------- objects
 OBJECTS_MAX_M = 64
 OBJECTS_MAX_POINTS = 1 << 22          # keeps score_sum inside int64 for raw scores at the fp16 maximum
