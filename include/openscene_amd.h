@@ -426,6 +426,12 @@ int osn_bn_apply_plan(int64_t total4, int c4, int* grid, int* flat);
  * the plan says, and column sums with one row in flight per thread.  Every result is bit for bit the same either way.
  * Returns the previous setting.                                                                                              */
 int osn_bn_set_flat_kernels(int on);
+/* With batch statistics, the backward pass of a map of at most 64 row blocks of column sums (n <= 4096 rows), of any width,
+ * runs in TWO launches: the apply pass works in groups of 32 columns, every workgroup adds the row blocks' partial sums of its
+ * columns itself, in the order of the finalize kernel, and the workgroups of the first 32 rows write ggamma and gbeta.  Tests
+ * and A/B only, process-wide: on != 0 keeps the finalize kernel a launch of its own on every map (as evaluation mode and
+ * osn_bn_set_flat_kernels(1) do).  Every result is bit for bit the same either way.  Returns the previous setting.          */
+int osn_bn_set_separate_finalize(int on);
 
 /* ---- distillation loss on the supervised rows ------------------------------- *
  * Replaces run/distill.py:322-328 and its autograd chain:

@@ -98,6 +98,7 @@ PROTOTYPES = {
                                      _vp, _sz, _vp]),
     "osn_bn_apply_plan": (_i32, [_i64, _i32, _c.POINTER(_i32), _c.POINTER(_i32)]),
     "osn_bn_set_flat_kernels": (_i32, [_i32]),
+    "osn_bn_set_separate_finalize": (_i32, [_i32]),
     "osn_net_plan_query": (_i32, [_vp, _vp, _i32, _vp]),
     "osn_net_forward": (_i32, [_vp, _vp, _vp]),
     "osn_net_backward": (_i32, [_vp, _vp, _vp]),

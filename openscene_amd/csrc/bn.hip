@@ -247,9 +247,14 @@ __global__ __launch_bounds__(256) void col_reduce_gres_1row_kernel(OSN_CR_PARAMS
     col_reduce_body<1, true, 1>(x, y, gy, mean, var, eps, relu, n, c, rows_per_block, partial, nullptr, nullptr, gres);
 }
 
-// Final column sums: 64 columns x 16 slices of the partial blocks per workgroup
+// Final column sums: FIN_COLS columns x FIN_PARTS slices of the partial blocks per workgroup
 // (the partial blocks are summed in a fixed order => deterministic).
-constexpr int FIN_COLS = 16, FIN_PARTS = 64;      // 64 slices: 8 dependent partial reads per thread at 512 row blocks (16 slices: 32 reads, 7.5 us per launch)
+// FIN_COLS: columns per finalize workgroup (a power of two; x FIN_PARTS slices = its threads).  4: a workgroup of 256 threads, one wave of 48
+// registers per SIMD.  With 16 (1024 threads: four waves, 192 registers per SIMD, all placed at once) a backward finalize launch found
+// no CU to start on while wgrad_tl_kernel<4,4> held 448 of a SIMD's 512 registers on the side stream, and waited for one of its
+// workgroups to end: the chain column sums -> finalize -> apply of a 3.3 k-row map took 44 us beside it against 20.5 us with 4
+// (17.5 -> 15.8 beside <3,3>, 9.9 -> 9.0 alone; profiles/r28_bn_finalize_in_apply_gate.txt).  The tree of the sums does not depend on it.
+constexpr int FIN_COLS = 4, FIN_PARTS = 64;      // 64 slices: 8 dependent partial reads per thread at 512 row blocks (16 slices: 32 reads, 7.5 us per launch)
 
 constexpr int FIN_ITERS = CR_MAX_BLOCKS / FIN_PARTS;     // partial blocks per thread (8)
 
@@ -330,6 +335,66 @@ __global__ __launch_bounds__(FIN_COLS * FIN_PARTS) void bn_bwd_finalize_kernel(c
     sum_gx[j] = float(s2);
 }
 
+// The finalize step INSIDE a backward apply pass (small maps).  Up to FOLD_MAX_RB row blocks of column sums every apply workgroup
+// forms the column totals it needs from the partials itself, instead of waiting for a launch of bn_bwd_finalize_kernel that moves a
+// few kilobytes (48 launches a step).  What a workgroup reads is n_rb x 16 bytes per column it covers, so these
+// launches walk the matrix in COLUMN GROUPS (GroupWalk below: a workgroup owns FOLD_COLS = 32 columns -- one 128-byte line per row --
+// and 32 row lanes): at most 64 x 32 x 16 bytes = 32 KB out of L2, in ONE round trip -- thread (group g, column j) issues the 16 loads
+// of its eight row blocks before the first add.  A workgroup that covered all c columns (the walks of the larger maps) read 106 KB on
+// the 3.3 k-row x 128 level in 3.5 dependent rounds and lost 1 us against the separate launch, 13 us at 4096 x 256
+// (profiles/r28_bn_finalize_in_apply_gate.txt).
+// The price is read amplification, and it is why FOLD_MAX_RB stays where the plan of the column sums puts a 4096-row map: a workgroup
+// moves a 32 x 32 tile (4 KB each of x, g, gx) and reads up to 32 KB of partials for it -- at 4096 x 256, 1024 workgroups x 32 KB =
+// 32 MB out of L2 for a 4 MB matrix.  It measured 2.3 us faster there than the finalize launch; the ratio grows with n_rb.
+// EXACTLY finalize_sums' tree, so every bit stays: slice `part` there holds block `part` (n_rb <= 64: one block per slice, 0 + v),
+// eight slices are added in order from 0, then the eight group sums in order from 0.  What is left out are adds of +0.0 to a sum that
+// started at +0.0 and so is never -0.0: identities.  The two totals of a column are left as floats in LDS, where the apply walk takes
+// them as it took them from global memory; the workgroups of the first row chunk also write gbeta and ggamma, as
+// bn_bwd_finalize_kernel does.
+constexpr int FOLD_MAX_RB = 64, FOLD_COLS = 32, FOLD_ROWS = 256 / (FOLD_COLS / 4);
+static_assert(FOLD_MAX_RB <= FIN_PARTS && FOLD_MAX_RB == 8 * (256 / FOLD_COLS), "one partial block per slice of finalize_sums, one (group, column) per thread");
+
+// -> the totals in LDS: [2][FOLD_COLS], (sum g, sum g * xhat) of columns blockIdx.y * FOLD_COLS + j
+__device__ __forceinline__ const float* fold_sums(const double* __restrict__ partial, int n_rb, int c, float* __restrict__ sum_g,
+                                                  float* __restrict__ sum_gx) {
+    __shared__ double grp[2][FOLD_MAX_RB / 8][FOLD_COLS];
+    __shared__ __attribute__((aligned(16))) float tot[2][FOLD_COLS];
+    const int ng = (n_rb + 7) >> 3;
+    {
+        const int g = threadIdx.x / FOLD_COLS, j = threadIdx.x % FOLD_COLS, col = blockIdx.y * FOLD_COLS + j;
+        if (g < ng && col < c) {
+            double va[8], vb[8];
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const int blk = g * 8 + q, bc = blk < n_rb ? blk : 0;
+                va[q] = partial[(int64_t(bc) * 2 + 0) * c + col];
+                vb[q] = partial[(int64_t(bc) * 2 + 1) * c + col];
+            }
+            double a = 0, b = 0;
+#pragma unroll
+            for (int q = 0; q < 8; ++q) {
+                const bool on = g * 8 + q < n_rb;
+                a += on ? va[q] : 0.0;
+                b += on ? vb[q] : 0.0;
+            }
+            grp[0][g][j] = a;
+            grp[1][g][j] = b;
+        }
+    }
+    __syncthreads();
+    if (threadIdx.x < 2 * FOLD_COLS) {
+        const int which = threadIdx.x / FOLD_COLS, j = threadIdx.x % FOLD_COLS, col = blockIdx.y * FOLD_COLS + j;
+        if (col < c) {
+            double t = 0;
+            for (int g = 0; g < ng; ++g) t += grp[which][g][j];
+            tot[which][j] = float(t);
+            if (blockIdx.x == 0) (which ? sum_gx : sum_g)[col] = float(t);
+        }
+    }
+    __syncthreads();
+    return &tot[0][0];
+}
+
 // The apply passes (forward, backward, backward reading gres) are each written ONCE, over one of two walks through the quads of an
 // [n, c] matrix, c4 = c / 4 quads a row.  Per-element expressions: epilogue.h.  Every element is read and then written by the same
 // thread (in place is fine).
@@ -364,6 +429,23 @@ struct QuadWalk {
     }
 };
 
+// The walk of the launches that finalize for themselves: workgroup (chunk of FOLD_ROWS rows, column group of FOLD_COLS), thread (row,
+// column quad) -- ONE quad per thread (the grid covers every row: these maps have at most 4096), so the column constants are taken
+// once, as in QuadWalk<true>.  A thread past the last row or the last column has nothing to walk.
+struct GroupWalk {
+    int64_t e, row_;
+    int col_;
+    __device__ GroupWalk(int c4) {
+        col_ = blockIdx.y * FOLD_COLS + int(threadIdx.x % (FOLD_COLS / 4)) * 4;
+        row_ = int64_t(blockIdx.x) * FOLD_ROWS + threadIdx.x / (FOLD_COLS / 4);
+        e = col_ < c4 * 4 ? row_ * c4 + (col_ >> 2) : INT64_MAX;
+    }
+    __device__ int col(int) const { return col_; }
+    __device__ int64_t row(int) const { return row_; }
+    __device__ int64_t off() const { return e * 4; }
+    __device__ void next() { e = INT64_MAX; }
+};
+
 template <bool KEEP>
 __device__ __forceinline__ void bn_apply_body(const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ var,
                                               const float* __restrict__ gamma, const float* __restrict__ beta, float eps,
@@ -387,22 +469,33 @@ __device__ __forceinline__ void bn_apply_body(const float* __restrict__ x, const
 }
 
 // LOAD_G: g was stored to gres by col_reduce_gres_kernel; y and the sources are not read and gres is not written.
-template <bool KEEP, bool LOAD_G>
+// FOLD: the column totals come from fold_sums (above), not from a finalize launch: sum_g / sum_gx are then this launch's OUTPUTS
+// (gbeta / ggamma) and `partial` holds the n_rb row blocks of the column sums; the walk is GroupWalk.  Batch statistics only.
+template <bool KEEP, bool LOAD_G, bool FOLD = false>
 __device__ __forceinline__ void bn_bwd_apply_body(const float* __restrict__ x, const float* __restrict__ y, const GySrc& gy,
                                                   const float* __restrict__ mean, const float* __restrict__ var,
                                                   const float* __restrict__ gamma, float eps, int relu, int training,
                                                   const float* __restrict__ sum_g, const float* __restrict__ sum_gx, float inv_n,
                                                   float* __restrict__ gx, float* __restrict__ gres, int64_t total4, int c4,
-                                                  const float* __restrict__ beta) {
+                                                  const float* __restrict__ beta, const double* __restrict__ partial = nullptr,
+                                                  int n_rb = 0) {
+    static_assert(!FOLD || KEEP, "a launch that finalizes for itself keeps its columns");
     const bool from_x = !LOAD_G && relu && !y;               // ReLU mask recomputed from x: one tensor less to read
-    QuadWalk<KEEP> w(c4);
+    const float *sg = sum_g, *sx = sum_gx;                   // the two column totals as the walk reads them, and the index of column 0 in them
+    int sum_col0 = 0;
+    if constexpr (FOLD) {
+        sg = fold_sums(partial, n_rb, c4 * 4, const_cast<float*>(sum_g), const_cast<float*>(sum_gx));
+        sx = sg + FOLD_COLS;
+        sum_col0 = blockIdx.y * FOLD_COLS;
+    }
+    std::conditional_t<FOLD, GroupWalk, QuadWalk<KEEP>> w(c4);
     if (w.e >= total4) return;
     BnBwdCols k;
-    if (KEEP) k = bn_bwd_cols(mean, var, gamma, beta, sum_g, sum_gx, eps, training, from_x, w.col(c4));
+    if (KEEP) k = bn_bwd_cols(mean, var, gamma, beta, sg, sx, eps, training, from_x, w.col(c4), w.col(c4) - sum_col0);
     for (; w.e < total4; w.next()) {
         const int col = w.col(c4);
         const int64_t o4 = w.off();
-        if (!KEEP) k = bn_bwd_cols(mean, var, gamma, beta, sum_g, sum_gx, eps, training, from_x, col);
+        if (!KEEP) k = bn_bwd_cols(mean, var, gamma, beta, sg, sx, eps, training, from_x, col, col);
         // every load of the quad first (x, the sources or gres, y), then the arithmetic: one round trip per quad
         float4 xv = make_float4(0, 0, 0, 0), yv, gs[BN_MAX_SRC];
         if (training || from_x) xv = ld4(x + o4);
@@ -451,6 +544,23 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_gres_kernel(OSN_BN_BWD_GRES_
 __global__ __launch_bounds__(256) void bn_bwd_apply_gres_flat_kernel(OSN_BN_BWD_GRES_PARAMS) {
     bn_bwd_apply_body<false, true>(x, nullptr, GySrc{}, mean, var, gamma, eps, 0, training, sum_g, sum_gx, inv_n, gx,
                                    const_cast<float*>(gres), total4, c4, nullptr);
+}
+
+// The two kernels that keep their columns, with the finalize step inside (bn_bwd_apply_body<.., FOLD>): `fin` = the workgroup finalizes
+// for itself.  Grid (row chunks, column groups of FOLD_COLS).
+__global__ __launch_bounds__(256) void bn_bwd_apply_fin_kernel(
+    const float* __restrict__ x, const float* __restrict__ y, const GySrc gy, const float* __restrict__ mean, const float* __restrict__ var,
+    const float* __restrict__ gamma, float eps, int relu, float* __restrict__ gbeta, float* __restrict__ ggamma, float inv_n,
+    float* __restrict__ gx, float* __restrict__ gres, int64_t total4, int c4, const float* __restrict__ beta,
+    const double* __restrict__ partial, int n_rb) {
+    bn_bwd_apply_body<true, false, true>(x, y, gy, mean, var, gamma, eps, relu, 1, gbeta, ggamma, inv_n, gx, gres, total4, c4, beta, partial, n_rb);
+}
+__global__ __launch_bounds__(256) void bn_bwd_apply_gres_fin_kernel(
+    const float* __restrict__ x, const float* __restrict__ mean, const float* __restrict__ var, const float* __restrict__ gamma, float eps,
+    float* __restrict__ gbeta, float* __restrict__ ggamma, float inv_n, float* __restrict__ gx, const float* __restrict__ gres,
+    int64_t total4, int c4, const double* __restrict__ partial, int n_rb) {
+    bn_bwd_apply_body<true, true, true>(x, nullptr, GySrc{}, mean, var, gamma, eps, 0, 1, gbeta, ggamma, inv_n, gx, const_cast<float*>(gres),
+                                        total4, c4, nullptr, partial, n_rb);
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -587,6 +697,9 @@ static ApplyPlan plan_apply(int64_t total4, int c4) {
 // osn_bn_set_flat_kernels: the kernels of the earlier rounds (flat apply walks, one row in flight in the column sums)
 static std::atomic<int> g_flat_kernels{0};
 
+// osn_bn_set_separate_finalize: bn_bwd_finalize_kernel as a launch of its own on every map (tests, A/B)
+static std::atomic<int> g_separate_finalize{0};
+
 #ifndef OSN_BN_KEEP_COLUMNS
 #define OSN_BN_KEEP_COLUMNS 1                                // 0: an A/B build whose apply passes are always the flat kernels
 #endif
@@ -614,6 +727,8 @@ static int check_fwd_args(const char* who, const float* x, const float* mean, co
 using namespace osn;
 
 extern "C" int osn_bn_set_flat_kernels(int on) { return g_flat_kernels.exchange(on ? 1 : 0); }
+
+extern "C" int osn_bn_set_separate_finalize(int on) { return g_separate_finalize.exchange(on ? 1 : 0); }
 
 extern "C" int osn_bn_apply_plan(int64_t total4, int c4, int* grid, int* flat) {
     OSN_REQUIRE(total4 >= 0 && c4 >= 1 && grid && flat, OSN_E_ARG, "osn_bn_apply_plan: need total4 >= 0, c4 >= 1 and two outputs");
@@ -746,9 +861,22 @@ extern "C" int osn_bn_backward_multi2(const float* x, const float* y, const floa
                                                        : (mask == CR_MASK_Y ? col_reduce_kernel<1, CR_MASK_Y> : col_reduce_kernel<1, CR_MASK_NONE>));
         hipLaunchKernelGGL(kern, rgrid, dim3(256), 0, st, x, y, src, mean, var, eps, relu, n, c, p.rows_per_block, partial, gamma, beta);
     }
-    // ggamma = sum g*xhat, gbeta = sum g  (also the two column sums the apply pass needs)
-    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(c, FIN_COLS)), dim3(FIN_COLS * FIN_PARTS), 0, st, partial, p.n_rb, c, gbeta, ggamma);
     const int64_t total4 = n * (c / 4);
+    // ggamma = sum g*xhat, gbeta = sum g  (also the two column sums the apply pass needs): a launch of its own, or -- small maps, batch
+    // statistics -- formed by every apply workgroup for its columns and written by those of the first row chunk (fold_sums)
+    const bool fold = training && p.n_rb <= FOLD_MAX_RB && !one_row && !g_separate_finalize.load(std::memory_order_relaxed);
+    if (fold) {
+        const dim3 fgrid(unsigned(cdiv(n, FOLD_ROWS)), unsigned(cdiv(c, FOLD_COLS)));
+        if (via_gres)
+            hipLaunchKernelGGL(bn_bwd_apply_gres_fin_kernel, fgrid, dim3(256), 0, st, x, mean, var, gamma, eps, gbeta, ggamma, 1.f / float(n), gx,
+                               (const float*)gres, total4, c / 4, (const double*)partial, p.n_rb);
+        else
+            hipLaunchKernelGGL(bn_bwd_apply_fin_kernel, fgrid, dim3(256), 0, st, x, y, src, mean, var, gamma, eps, relu, gbeta, ggamma,
+                               1.f / float(n), gx, gres, total4, c / 4, beta, (const double*)partial, p.n_rb);
+        OSN_LAUNCH_CHECK();
+        return OSN_OK;
+    }
+    hipLaunchKernelGGL(bn_bwd_finalize_kernel, dim3(cdiv(c, FIN_COLS)), dim3(FIN_COLS * FIN_PARTS), 0, st, partial, p.n_rb, c, gbeta, ggamma);
     const ApplyPlan ap = launch_plan_apply(total4, c / 4);
     if (via_gres)
         hipLaunchKernelGGL(ap.keep ? bn_bwd_apply_gres_kernel : bn_bwd_apply_gres_flat_kernel, dim3(ap.grid), dim3(256), 0, st, x, mean,

@@ -101,16 +101,17 @@ struct BnBwdCols {
     EpiCols c;
     float4 gi, sg, sx;
 };
+// (sum_col: where column `col` stands in sum_g / sum_gx -- `col` itself, or its place in a workgroup's own totals)
 __device__ inline BnBwdCols bn_bwd_cols(const float* mean, const float* var, const float* gamma, const float* beta, const float* sum_g,
-                                        const float* sum_gx, float eps, bool training, bool from_x, int col) {
+                                        const float* sum_gx, float eps, bool training, bool from_x, int col, int sum_col) {
     const float4 z = make_float4(0, 0, 0, 0), vv = ld4(var + col);
     BnBwdCols k;
     k.c.is = make_float4(bn_is(vv.x, eps), bn_is(vv.y, eps), bn_is(vv.z, eps), bn_is(vv.w, eps));
     k.c.ga = ld4(gamma + col);
     k.c.mu = (training || from_x) ? ld4(mean + col) : z;
     k.c.be = from_x ? ld4(beta + col) : z;
-    k.sg = training ? ld4(sum_g + col) : z;
-    k.sx = training ? ld4(sum_gx + col) : z;
+    k.sg = training ? ld4(sum_g + sum_col) : z;
+    k.sx = training ? ld4(sum_gx + sum_col) : z;
     k.gi = make_float4(k.c.ga.x * k.c.is.x, k.c.ga.y * k.c.is.y, k.c.ga.z * k.c.is.z, k.c.ga.w * k.c.is.w);
     return k;
 }

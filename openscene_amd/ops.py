@@ -1114,6 +1114,13 @@ def bn_set_flat_kernels(on):
     return bool(_lib.load().osn_bn_set_flat_kernels(int(bool(on))))
 
 
+def bn_set_separate_finalize(on):
+    """Tests and A/B: keep the backward pass's finalize kernel a launch of its own on the small maps too (by default the apply pass
+    of a map of at most 4096 rows, with batch statistics, adds the partial sums itself), process-wide; results are bitwise the same.
+    Returns the previous setting."""
+    return bool(_lib.load().osn_bn_set_separate_finalize(int(bool(on))))
+
+
 # ------------------------------------------------------- elementwise (a11)
 def relu_fwd(x):
     dev = x.device

@@ -1,5 +1,5 @@
 """Stand-alone cost of the batch-norm calls on the step's shapes.  HIP events over back-to-back calls.
-usage: python tools/micro_bn.py [iters] [eager|graph]
+usage: python tools/micro_bn.py [iters] [eager|graph|fold]
 eager: the calls as Python issues them -- on the small maps this measures the HOST (three ctypes calls + torch.empty per call:
 ~20 us whatever the size); graph: the same calls replayed from a HIP graph -- the device's own pace (kernel time + dependent-launch
 boundaries): 8.5 - 15 us on the <= 13 k-row maps (profiles/r04_s13_bn_one_launch_exchange_rejected.txt)."""
@@ -45,9 +45,42 @@ def timed_graph(f):
 
 
 MODE = sys.argv[2] if len(sys.argv) > 2 else "eager"
-if MODE == "graph":
+if MODE in ("graph", "fold"):
     timed = timed_graph
 print("# timing mode: %s" % MODE)
+
+
+def fold_gate():
+    import os
+    import statistics
+    rounds = int(os.environ.get("ROUNDS", "6"))
+    print("# us per backward call, median (max - min) of %d rounds: two launches | three launches" % rounds)
+    for n, c in ((730, 256), (3326, 128), (4096, 256), (4096, 64), (209, 256)):
+        x, gy, res = (torch.randn(n, c, device=dev) for _ in range(3))
+        gamma, beta = torch.rand(c, device=dev) + 0.5, torch.randn(c, device=dev) * 0.1
+        rm, rv = torch.zeros(c, device=dev), torch.ones(c, device=dev)
+        _, mean, var = ops.bn_forward_train(x, gamma, beta, 1e-5, None, True, rm, rv, 0.1)
+        yr, _, _ = ops.bn_forward_train(x, gamma, beta, 1e-5, res, True, rm, rv, 0.1)
+        chains = (("mask from x", lambda: ops.bn_backward(x, None, gy, mean, var, gamma, 1e-5, True, True, False, beta=beta)),
+                  ("no mask", lambda: ops.bn_backward(x, None, gy, mean, var, gamma, 1e-5, False, True, False)),
+                  ("residual tail", lambda: ops.bn_backward(x, yr, gy, mean, var, gamma, 1e-5, True, True, True)))
+        for name, f in chains:
+            t = {False: [], True: []}
+            for _ in range(rounds):
+                for sep in (False, True):
+                    ops.bn_set_separate_finalize(sep)
+                    try:
+                        t[sep].append(timed_graph(f))        # (the switch is read when the launches are captured)
+                    finally:
+                        ops.bn_set_separate_finalize(False)
+            print("n %5d c %3d %-13s  %5.2f (%.2f) | %5.2f (%.2f)" % (
+                n, c, name, statistics.median(t[False]), max(t[False]) - min(t[False]), statistics.median(t[True]),
+                max(t[True]) - min(t[True])), flush=True)
+
+
+if MODE == "fold":
+    fold_gate()
+    sys.exit(0)
 print("# us per call (fwd = statistics + apply; bwd-x = ReLU mask from x; bwd-res = residual block tail)")
 for n, c in ((730, 256), (730, 512), (3326, 128), (3326, 384), (13393, 64), (13393, 128), (13393, 192), (52125, 32), (52125, 96),
              (52125, 128), (100999, 32), (100999, 96)):

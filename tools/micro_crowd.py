@@ -5,7 +5,11 @@ order and items (386 MB of misses per launch) or with Z-ordered pair arrays and 
 stream times a level-0 batch-norm backward, a batch-norm forward and the dominant tile-list convolution.   REPS=n
 Round 25 (the register budget beside the weight gradient): SIDE_CIN=128 makes the side stream's product kernel the <4,3> instance (96: <3,3>),
 ONLY=name,... and CASES=tag,... restrict the workloads and the cases, ROUNDS=n repeats every measurement (a list per key: the spread),
-OSN_LIB_PATH picks the library under test.  The hardware probe is built only with PROBE=1."""
+OSN_LIB_PATH picks the library under test.  The hardware probe is built only with PROBE=1.
+Round 28 (the finalize step inside the backward apply pass of the small maps): SIDE_COUT=128 with SIDE_CIN=128 makes the side kernel the
+<4,4> instance; the workloads bn_bwd_L3_128 / bn_bwd_res_L3_128 / bn_bwd_L4_256 (3.3 k rows x 128, mask from x and residual tail; the
+730-row level x 256) run as two launches, their *_sep twins as three (osn_bn_set_separate_finalize); GRAPH=1 replays every workload's
+REPS calls from one HIP graph (the device's own pace: eager calls on these maps measure the host)."""
 import ctypes
 import json
 import os
@@ -29,6 +33,8 @@ def main():
     _lib.load()
     probe = os.environ.get("PROBE", "0") == "1"
     side_cin = int(os.environ.get("SIDE_CIN", "96"))
+    side_cout = int(os.environ.get("SIDE_COUT", "96"))               # (96 = c below: the width of the earlier rounds' side kernel)
+    use_graph = os.environ.get("GRAPH", "0") == "1"
     rounds = int(os.environ.get("ROUNDS", "1"))
     only = [t for t in os.environ.get("ONLY", "").split(",") if t]
     only_cases = [t for t in os.environ.get("CASES", "").split(",") if t]
@@ -43,7 +49,7 @@ def main():
     n = cm.size(1)
     x = torch.randn(n, c, device=dev)
     g = torch.randn(n, c, device=dev)
-    xs, gs = torch.randn(n, side_cin, device=dev), torch.randn(n, c, device=dev)       # the side stream's own operands
+    xs, gs = torch.randn(n, side_cin, device=dev), torch.randn(n, side_cout, device=dev)       # the side stream's own operands
     gamma, beta = torch.rand(c, device=dev) + 0.5, torch.randn(c, device=dev)
     mean, var = x.mean(0), x.var(0, unbiased=False)
     rm, rv = torch.zeros(c, device=dev), torch.ones(c, device=dev)
@@ -52,8 +58,8 @@ def main():
     w = torch.randn(K, c, c, device=dev) * 0.05
     wf, _ = ops.weight_prep_tl(w, want_dgrad=False)
     side = torch.cuda.Stream(device=dev)
-    ws = torch.empty(512 * side_cin * c, dtype=torch.float32, device=dev)
-    gw = torch.zeros(K, side_cin, c, device=dev)
+    ws = torch.empty(512 * side_cin * side_cout, dtype=torch.float32, device=dev)
+    gw = torch.zeros(K, side_cin, side_cout, device=dev)
 
     def side_setup(order, plan):
         if order == "morton":
@@ -99,6 +105,26 @@ def main():
     rm3, rv3 = torch.zeros(128, device=dev), torch.ones(128, device=dev)
     workloads["ws_conv_L3_128"] = lambda: ops.spconv_fwd_ws(x3, wf3, tl3, nbr3, n3, K, 128)
     workloads["bn_small_L3_128"] = lambda: ops.bn_forward_train(x3, g3, b3, 1e-5, None, True, rm3, rv3, 0.1)
+    # the backward chain of a batch norm on the small maps: column sums -> apply, and (_sep) column sums -> finalize -> apply
+    n4 = cm.size(16)
+    for tag, rows, ch in (("L3_128", n3, 128), ("L4_256", n4, 256)):
+        xb, gb, rb = (torch.randn(rows, ch, device=dev) for _ in range(3))
+        ga, be = torch.rand(ch, device=dev) + 0.5, torch.randn(ch, device=dev) * 0.1
+        _, mu, va = ops.bn_forward_train(xb, ga, be, 1e-5, None, True, torch.zeros(ch, device=dev), torch.ones(ch, device=dev), 0.1)
+        yb = ops.bn_forward_train(xb, ga, be, 1e-5, rb, True, torch.zeros(ch, device=dev), torch.ones(ch, device=dev), 0.1)[0]
+        chains = {"bn_bwd_" + tag: (lambda xb=xb, gb=gb, mu=mu, va=va, ga=ga, be=be: ops.bn_backward(xb, None, gb, mu, va, ga, 1e-5, True, True, False, beta=be))}
+        if tag == "L3_128":
+            chains["bn_bwd_res_" + tag] = lambda xb=xb, yb=yb, gb=gb, mu=mu, va=va, ga=ga: ops.bn_backward(xb, yb, gb, mu, va, ga, 1e-5, True, True, True)
+        for name, f in chains.items():
+            workloads[name] = f
+
+            def separate(f=f):
+                ops.bn_set_separate_finalize(True)
+                try:
+                    return f()
+                finally:
+                    ops.bn_set_separate_finalize(False)
+            workloads[name + "_sep"] = separate
     res = {}
     cases = [("alone", None, None), ("beside_PRODUCT_kernel", "tile", -1), ("beside_PRODUCT_kernel_zorder_xcd_strided", "morton", -2)]
     if probe:
@@ -114,13 +140,20 @@ def main():
         for name, fn in workloads.items():
             fn()
             torch.cuda.synchronize()
+            if use_graph:
+                graph = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(graph):
+                    for _ in range(reps):
+                        fn()
+                graph.replay()
+                torch.cuda.synchronize()
             s0, s1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             if cfg:
                 tl, pl, it_d, first_d, ids_d = cfg
                 s0.record(side)
                 if isinstance(it_d, str):             # the product kernel alone (no reduction) on the strided region items
                     for _ in range(side_n):
-                        rc = lib2.osn_spconv_wgrad_tl_partial(xs.data_ptr(), gs.data_ptr(), pl.data_ptr(), 0, gw.data_ptr(), n, n, K, side_cin, c,
+                        rc = lib2.osn_spconv_wgrad_tl_partial(xs.data_ptr(), gs.data_ptr(), pl.data_ptr(), 0, gw.data_ptr(), n, n, K, side_cin, side_cout,
                                                               ws.data_ptr(), ws.numel() * 4, ctypes.addressof(job), side.cuda_stream)
                         assert rc == 0
                 elif it_d is None:                    # the product's own kernel (158 VGPRs, 2 workgroups per CU) + its reduction
@@ -135,8 +168,11 @@ def main():
             if cfg:
                 s1.record(side)
             e0.record()
-            for _ in range(reps):
-                fn()
+            if use_graph:
+                graph.replay()
+            else:
+                for _ in range(reps):
+                    fn()
             e1.record()
             torch.cuda.synchronize()
             us = round(e0.elapsed_time(e1) / reps * 1e3, 2)
