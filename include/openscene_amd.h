@@ -994,6 +994,52 @@ int osn_knn_blend(const void* values, int value_bytes, int64_t n, int64_t n_cols
 int osn_knn_vote(const int64_t* labels, int64_t n, const int32_t* idx, const int32_t* count, int64_t m, int k, int64_t fill,
                  int64_t* out, int32_t* err, osn_stream_t stream);
 
+/* ---- two scans in one frame: rigid RANSAC over correspondences, moments for Kabsch / ICP (csrc/align.hip) --------- *
+ * Pairs are src, dst float32 [n_pairs, 3] on the device: pair p says "point src[p] of one scan is point dst[p] of the
+ * other" (openscene_amd.match.mutual gives the rows).  A transform is 12 float32: R row-major, then t; it takes src onto
+ * dst.  THE RESIDUAL of a pair under a transform is, in float32, every operation rounded on its own (no FMA):
+ *     x_i = ((R_i0 s_0) + (R_i1 s_1)) + (R_i2 s_2)     e_i = (x_i + t_i) - d_i     r2 = ((e_0 e_0) + (e_1 e_1)) + (e_2 e_2)
+ * and the pair is an INLIER iff r2 <= tau2 (a NaN never is); tau2 = float32(threshold) * float32(threshold), rounded once
+ * by the caller.  numpy float32 gives the same bits, so counts and masks are exact.  All calls are asynchronous on
+ * `stream`, allocate nothing and use no floating-point atomics; n_pairs < 2^31, n_hyp <= OSN_RIGID_MAX_HYPOTHESES.
+ *
+ * osn_rigid_from_triplets: triplets int32 [n_hyp, 3] (device) name three pairs each; xf float32 [n_hyp, 12] and valid
+ *   uint8 [n_hyp] receive the motion that takes the src triangle onto the dst triangle.  With p0, p1, p2 widened to
+ *   float64 and every float64 operation rounded on its own, in this order:
+ *     a = p1 - p0, b = p2 - p0, c = p2 - p1;  |v|^2 = ((v0 v0) + (v1 v1)) + (v2 v2), |v| = sqrt(|v|^2);
+ *     u x v = (u1 v2 - u2 v1, u2 v0 - u0 v2, u0 v1 - u1 v0);  e1 = a / |a|, n = a x b, e3 = n / |n|, e2 = e3 x e1;
+ *     R_ij = ((e1d_i e1s_j) + (e2d_i e2s_j)) + (e3d_i e3s_j)               (F_dst F_src^T, F = [e1 e2 e3] as columns)
+ *     t_i = d0_i - (((R_i0 s0_0) + (R_i1 s0_1)) + (R_i2 s0_2))             (with the float64 R)
+ *   R and t are rounded to float32 once, at the end.  A hypothesis is INVALID -- valid = 0, R = identity, t = 0 -- when
+ *   an index lies outside [0, n_pairs) or two are equal (such rows are never dereferenced); when not |n|^2 > area2_min
+ *   for either triangle (NaN fails); or when not | |v|_src - |v|_dst | <= 2 * threshold for any of the sides a, b, c (the
+ *   congruence pre-test: a triplet that holds an outlier rarely passes it).  threshold, area2_min finite and >= 0.
+ * osn_rigid_score: counts int32 [n_hyp] = the number of inliers of every hypothesis of xf float32 [n_hyp, 12] (16-byte
+ *   aligned); -1 where valid (uint8 [n_hyp]; null: all valid) is 0.  n_hyp * n_pairs residuals, no temporary: the grid is
+ *   (tiles of 1024 pairs) x (tiles of 64 hypotheses), the counts are integer atomics (exact, order-free) on a `counts`
+ *   this call initialises.  The contract forbids FMA: 21 VALU operations per residual where a fused form takes 15.
+ * osn_rigid_best: best int32 [2] (device) = (the largest count, the lowest hypothesis that has it), the maximum of one
+ *   64-bit key (count with its sign bit flipped) << 32 | ~h.  n_hyp >= 1.
+ * osn_rigid_moments: under ONE transform xf12 (12 floats in HOST memory, read during the call): pair i is (src[i],
+ *   dst[i]) or, with dst_idx int32 [n_pairs] (the ICP form: a neighbour list, no gathered copy of dst), (src[i],
+ *   dst[dst_idx[i]]); dst float32 [n_dst, 3]; an index < 0 or >= n_dst means no partner and is never dereferenced
+ *   (without dst_idx n_dst >= n_pairs).  Writes inlier uint8 [n_pairs] and r2 float32 [n_pairs] as defined above (no
+ *   partner: 0 and +inf) and moments double [16] (device) over the inliers: n, sum s (3), sum d (3), sum s d^T (9,
+ *   row-major s_i d_j).  float64; a product of two float32 is exact, the additions run in a fixed order -- chunks of
+ *   OSN_RIGID_MOMENTS_CHUNK pairs, each reduced in a fixed tree, the chunk partials added in ascending chunk order -- so
+ *   two calls give the same bits.  ws: osn_rigid_moments_ws_bytes(n_pairs) bytes, 16-byte aligned.                      */
+#define OSN_RIGID_MAX_HYPOTHESES (1 << 20)
+#define OSN_RIGID_MOMENTS_CHUNK 1024
+int osn_rigid_from_triplets(const float* src, const float* dst, int64_t n_pairs, const int32_t* triplets, int n_hyp,
+                            float threshold, double area2_min, float* xf, uint8_t* valid, osn_stream_t stream);
+int osn_rigid_score(const float* src, const float* dst, int64_t n_pairs, const float* xf, const uint8_t* valid, int n_hyp,
+                    float tau2, int32_t* counts, osn_stream_t stream);
+int osn_rigid_best(const int32_t* counts, int n_hyp, int32_t* best, osn_stream_t stream);
+size_t osn_rigid_moments_ws_bytes(int64_t n_pairs);
+int osn_rigid_moments(const float* src, const float* dst, const int32_t* dst_idx, int64_t n_pairs, int64_t n_dst,
+                      const float* xf12_host, float tau2, uint8_t* inlier, float* r2, double* moments, void* ws,
+                      size_t ws_bytes, osn_stream_t stream);
+
 /* ---- elastic distortion: the pre-voxeliser transform of Point3DLoader (dataset/point_loader.py:156) ---------- *
  * ElasticDistortion.elastic_distortion (dataset/augmentation.py:159-201), bit-identical to numpy / scipy given the
  * same noise draw; the draw (np.random.randn(*noise_dim, 3).astype(float32)) and np.linspace of the axes stay on the host.

@@ -17,6 +17,7 @@ Python surface (mirrors the reference's own, file:line in each module):
     openscene_amd.regions          scenes cut into regions of agreeing features before any prompt: label, list, query by region
     openscene_amd.render           views of a scene on the GPU: point-splat z-buffer -> heat-map / label / colour pictures, depth for fusion
     openscene_amd.neighbors        results on other points: k-nearest search on the voxel grid, transfer, fill of unseen rows, smoothing
+    openscene_amd.align            two scans in one frame: rigid RANSAC over feature matches, ICP on the voxel index, overlap
     install_minkowski_alias()      make `import MinkowskiEngine` resolve to openscene_amd.minkowski
 
 There is no CPU fallback: every op raises if libopenscene_amd.so is missing or

@@ -2443,6 +2443,136 @@ def knn_vote(labels, idx, count, fill=-1, err=None):
     return out
 
 
+# ------------------------------------------------------- two scans in one frame: rigid RANSAC, moments (csrc/align.hip)
+RIGID_MAX_HYPOTHESES = 1 << 20       # OSN_RIGID_MAX_HYPOTHESES
+RIGID_MOMENTS_CHUNK = 1024           # OSN_RIGID_MOMENTS_CHUNK: the pairs that are reduced into one float64 partial
+
+
+def _rigid_pairs(src, dst):
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.float32:
+        raise TypeError("src must be a float32 tensor")
+    if src.dim() != 2 or src.shape[1] != 3 or not src.is_contiguous():
+        raise ValueError("src must be a contiguous float32 [P, 3] matrix (got %s)" % (tuple(src.shape),))
+    if not isinstance(dst, torch.Tensor) or dst.dtype != torch.float32:
+        raise TypeError("dst must be a float32 tensor")
+    if dst.dim() != 2 or dst.shape[1] != 3 or not dst.is_contiguous() or dst.device != src.device:
+        raise ValueError("dst must be a contiguous float32 [N, 3] matrix on src's device (got %s)" % (tuple(dst.shape),))
+    if src.shape[0] >= 1 << 31 or dst.shape[0] >= 1 << 31:
+        raise ValueError("fewer than 2^31 pairs per call")
+    return src.device, src.shape[0]
+
+
+def _rigid_xf(xf, dev):
+    if not isinstance(xf, torch.Tensor) or xf.dtype != torch.float32:
+        raise TypeError("xf must be a float32 tensor")
+    if xf.dim() != 2 or xf.shape[1] != 12 or xf.device != dev or not xf.is_contiguous():
+        raise ValueError("xf must be a contiguous float32 [H, 12] matrix on the pairs' device (got %s)" % (tuple(xf.shape),))
+    if xf.shape[0] > RIGID_MAX_HYPOTHESES:
+        raise ValueError("at most %d hypotheses per call (got %d)" % (RIGID_MAX_HYPOTHESES, xf.shape[0]))
+    return xf.shape[0]
+
+
+def _rigid_level(v, name):
+    v = float(v)
+    if not (v >= 0.0 and v != float("inf")):
+        raise ValueError("%s must be finite and >= 0 (got %r)" % (name, v))
+    return v
+
+
+def rigid_from_triplets(src, dst, triplets, threshold, area2_min=0.0):
+    """The rigid motion of every triplet of pairs.  src, dst float32 [P, 3]; triplets int32 [H, 3] on their device: three
+    pair numbers each.  -> (xf float32 [H, 12]: R row-major then t, the motion that takes the src triangle onto the dst
+    triangle, in separately rounded float64 operations rounded once to float32; valid bool [H]).  Invalid -- identity, valid
+    False -- when a number lies outside [0, P) or two are equal, when a triangle's |a x b|^2 is not > area2_min, or when a side
+    differs between the triangles by more than 2 * threshold (include/openscene_amd.h states the order of operations)."""
+    dev, p = _rigid_pairs(src, dst)
+    if dst.shape[0] != p:
+        raise ValueError("src and dst must hold a row per pair (got %d and %d)" % (p, dst.shape[0]))
+    if not isinstance(triplets, torch.Tensor) or triplets.dtype != torch.int32:
+        raise TypeError("triplets must be an int32 tensor")
+    if triplets.dim() != 2 or triplets.shape[1] != 3 or triplets.device != dev or not triplets.is_contiguous():
+        raise ValueError("triplets must be a contiguous int32 [H, 3] matrix on the pairs' device (got %s)" % (tuple(triplets.shape),))
+    h = triplets.shape[0]
+    if h > RIGID_MAX_HYPOTHESES:
+        raise ValueError("at most %d hypotheses per call (got %d)" % (RIGID_MAX_HYPOTHESES, h))
+    threshold, area2_min = _rigid_level(threshold, "threshold"), _rigid_level(area2_min, "area2_min")
+    lib = _prep(dev)
+    xf = torch.empty((h, 12), dtype=torch.float32, device=dev)
+    valid = torch.empty(h, dtype=torch.bool, device=dev)
+    with _Dev(dev):
+        check(lib.osn_rigid_from_triplets(_p(src), _p(dst), p, _p(triplets), h, threshold, area2_min, _p(xf), _p(valid), _stream(dev)),
+              "osn_rigid_from_triplets")
+    return xf, valid
+
+
+def rigid_score(src, dst, xf, tau2, valid=None):
+    """int32 [H]: how many of the P pairs every transform of xf (float32 [H, 12]) moves to within tau2 -- r2 <= tau2 with r2
+    the separately rounded float32 residual of include/openscene_amd.h, exact; -1 where valid (bool [H] or None) is False.
+    H x P residuals and no temporary."""
+    dev, p = _rigid_pairs(src, dst)
+    if dst.shape[0] != p:
+        raise ValueError("src and dst must hold a row per pair (got %d and %d)" % (p, dst.shape[0]))
+    h = _rigid_xf(xf, dev)
+    if valid is not None:
+        if not isinstance(valid, torch.Tensor) or valid.dtype != torch.bool:
+            raise TypeError("valid must be a bool tensor")
+        if tuple(valid.shape) != (h,) or valid.device != dev or not valid.is_contiguous():
+            raise ValueError("valid must be a contiguous bool [%d] vector on the pairs' device" % h)
+    tau2 = _rigid_level(tau2, "tau2")
+    lib = _prep(dev)
+    counts = torch.empty(h, dtype=torch.int32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_rigid_score(_p(src), _p(dst), p, _p(xf), _p(valid), h, tau2, _p(counts), _stream(dev)), "osn_rigid_score")
+    return counts
+
+
+def rigid_best(counts):
+    """int32 [2] on the device: (the largest of counts int32 [H], H >= 1; the lowest hypothesis that has it)."""
+    if not isinstance(counts, torch.Tensor) or counts.dtype != torch.int32:
+        raise TypeError("counts must be an int32 tensor")
+    if counts.dim() != 1 or not 1 <= counts.shape[0] <= RIGID_MAX_HYPOTHESES or not counts.is_contiguous():
+        raise ValueError("counts must be a contiguous int32 [H] vector, 1 <= H <= %d (got %s)" % (RIGID_MAX_HYPOTHESES, tuple(counts.shape)))
+    dev = counts.device
+    lib = _prep(dev)
+    best = torch.empty(2, dtype=torch.int32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_rigid_best(_p(counts), counts.shape[0], _p(best), _stream(dev)), "osn_rigid_best")
+    return best
+
+
+def rigid_moments(src, dst, xf12, tau2, dst_idx=None):
+    """What one transform does to the pairs.  xf12: 12 floats on the host (R row-major, t), taken as float32.  Pair i is
+    (src[i], dst[i]) or, with dst_idx int32 [P], (src[i], dst[dst_idx[i]]) -- an index < 0 or >= len(dst) means no partner.
+    -> (inlier bool [P], r2 float32 [P] (+inf without a partner), moments float64 [16] on the device: over the inliers n,
+    sum s (3), sum d (3), sum s d^T (9, row-major)).  The mask and r2 are the score's, bit for bit; the sums run in a fixed
+    order (chunks of RIGID_MOMENTS_CHUNK pairs): two calls give the same bits."""
+    dev, p = _rigid_pairs(src, dst)
+    n_dst = dst.shape[0]
+    if dst_idx is None:
+        if n_dst != p:
+            raise ValueError("src and dst must hold a row per pair (got %d and %d): pass dst_idx" % (p, n_dst))
+    else:
+        if not isinstance(dst_idx, torch.Tensor) or dst_idx.dtype != torch.int32:
+            raise TypeError("dst_idx must be an int32 tensor")
+        if tuple(dst_idx.shape) != (p,) or dst_idx.device != dev or not dst_idx.is_contiguous():
+            raise ValueError("dst_idx must be a contiguous int32 [%d] vector on the pairs' device" % p)
+    x = [float(v) for v in xf12]
+    if len(x) != 12:
+        raise ValueError("xf12 holds 12 values: R row-major, then t (got %d)" % len(x))
+    x = (ctypes.c_float * 12)(*x)
+    tau2 = _rigid_level(tau2, "tau2")
+    lib = _prep(dev)
+    inlier = torch.empty(p, dtype=torch.bool, device=dev)
+    r2 = torch.empty(p, dtype=torch.float32, device=dev)
+    moments = torch.empty(16, dtype=torch.float64, device=dev)
+    nbytes = _cached("osn_rigid_moments_ws_bytes", p)
+    ws = _ws(nbytes, dev)
+    with _Dev(dev):
+        check(lib.osn_rigid_moments(_p(src), _p(dst), _p(dst_idx), p, n_dst, x, tau2, _p(inlier), _p(r2), _p(moments), _p(ws), ws.numel(),
+                                    _stream(dev)), "osn_rigid_moments")
+    return inlier, r2, moments
+
+
 # ------------------------------------------------- supervised segmentation head: cross-entropy, argmax, confusion, votes
 def _seg_index(t, name, n, dev):
     if t.dtype != torch.int64 or t.dim() != 1 or t.device != dev or (n is not None and t.shape[0] != n):
