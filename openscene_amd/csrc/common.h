@@ -31,6 +31,10 @@ void set_error(const char* fmt, ...);
 
 #define OSN_LAUNCH_CHECK() OSN_HIP(hipGetLastError())
 
+// MFMA accumulator blocks (16x16 and 32x32 results per lane)
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+typedef float f32x16 __attribute__((ext_vector_type(16)));
+
 static inline int64_t cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

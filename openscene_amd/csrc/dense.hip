@@ -11,18 +11,13 @@
 // wave multiplies them with the fragments of its 32 output columns held in registers -- 4 row blocks x 2 column blocks
 // x 6 products per k-step between two barriers -- and stores its accumulators straight to the output rows.  When the
 // whole contraction fits one chunk (Cin <= 128: the head, most shortcuts) the staged rows serve ALL column groups of the
-// workgroup, so the input is read and split once.  Same arithmetic as spconv_tl.hip ("bf16x6": three bf16 pieces per
-// operand, a3b1 + a2b2 + a1b3 + a2b1 + a1b2 + a1b1 in fp32, smallest terms first) and the same weight image
-// (osn_weight_prep_tl with K = 1).
+// workgroup, so the input is read and split once.  Same arithmetic as spconv_tl.hip ("bf16x6", split.h) and the
+// same weight image (osn_weight_prep_tl with K = 1).
 #include "common.h"
 #include "split.h"
 #include "epilogue.h"
 
 namespace osn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int DN_BM = 64;           // rows per workgroup
 
@@ -114,11 +109,11 @@ __global__ __launch_bounds__(256, 2) void dense_kernel(const float* __restrict__
 #pragma unroll
                         for (int pl = 0; pl < 3; ++pl)
                             af[pl] = *reinterpret_cast<const bf16x8*>(&stage[pl][16 * rb + (lane & 15)][ks * 32 + akq]);
-#define DN_MFMA(AP, BP)                                                                                         \
-    _Pragma("unroll") for (int nb = 0; nb < 2; ++nb)                                                            \
-        acc[rb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B[ks][nb][BP], af[AP], acc[rb][nb], 0, 0, 0);
-                        DN_MFMA(2, 0) DN_MFMA(1, 1) DN_MFMA(0, 2) DN_MFMA(1, 0) DN_MFMA(0, 1) DN_MFMA(0, 0)
-#undef DN_MFMA
+                        split_products([&](auto ap, auto bp) {
+#pragma unroll
+                            for (int nb = 0; nb < 2; ++nb)
+                                acc[rb][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B[ks][nb][bp], af[ap], acc[rb][nb], 0, 0, 0);
+                        });
                     }
                 }
             }

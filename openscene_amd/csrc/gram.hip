@@ -27,7 +27,6 @@
 
 namespace osn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int G_S = OSN_BANK_GRAM_SLICE;

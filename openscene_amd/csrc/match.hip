@@ -45,7 +45,6 @@
 
 namespace osn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned long long u64;
 
 constexpr int M_TQ = OSN_BANK_MATCH_TILE_Q;    // query rows of a workgroup

@@ -32,7 +32,6 @@
 
 namespace osn {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 half4 __attribute__((ext_vector_type(4)));
 
 constexpr int S_BM = 128;          // bank rows per workgroup (4 waves x 32)

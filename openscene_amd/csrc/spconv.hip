@@ -33,11 +33,10 @@
 // plan's (cfg, tn) into compile-time tile parameters, table_tail runs the fix-up / reduce.
 #include "common.h"
 #include "weight_prep.h"
+#include "split.h"
 #include <stdlib.h>
 
 namespace osn {
-
-typedef float f32x16 __attribute__((ext_vector_type(16)));
 
 // C layout of the 32x32 MFMA: col = lane&31, row = (reg&3) + 8*(reg>>2) + 4*(lane>>5).
 // `out_rows` (nullable) maps tile rows to tensor rows.
@@ -459,8 +458,6 @@ __global__ __launch_bounds__(256, 2) void spconv_fwd_pipe_kernel(const float* __
 // accumulated in fp32 ("bf16x6"): fp32-level accuracy at 2.7x the fp32 MFMA throughput.  The
 // weights arrive pre-split and k-contiguous (osn_weight_prep_x6); the gathered rows stay fp32 in
 // LDS and are split in registers right before the MFMAs (VALU work that overlaps the matrix pipe).
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-
 template <int WM, int WN, int TN>
 __global__ __launch_bounds__(256, 3) void spconv_fwd_x6_kernel(const float* __restrict__ in, const __bf16* __restrict__ Wp,
                                                               const int32_t* __restrict__ nbr,
@@ -569,8 +566,7 @@ __global__ __launch_bounds__(256, 3) void spconv_fwd_x6_kernel(const float* __re
     };
 
     auto mfma = [&]() {
-        // fp32-equivalent product from six bf16 MFMAs: x = x1 + x2 + x3 (8 mantissa bits each),
-        // a*b ~= a1b1 + a1b2 + a2b1 + a1b3 + a2b2 + a3b1  (dropped terms <= 2^-24 relative).
+        // fp32-equivalent product from six bf16 MFMAs (split.h: the pieces, the products kept and their order).
         // The A rows of BOTH 16-deep k-steps are read up front (the two LDS round trips overlap) and the
         // VALU split of step 1 is scheduled BETWEEN the MFMAs of step 0 (sched_group_barrier), so the
         // matrix pipe is fed while the VALU converts instead of idling for ~40 VALU per k-step.
@@ -586,29 +582,24 @@ __global__ __launch_bounds__(256, 3) void spconv_fwd_x6_kernel(const float* __re
             fv[ks][0] = f0.x; fv[ks][1] = f0.y; fv[ks][2] = f0.z; fv[ks][3] = f0.w;
             fv[ks][4] = f1.x; fv[ks][5] = f1.y; fv[ks][6] = f1.z; fv[ks][7] = f1.w;
         }
-        bf16x8 a1[2], a2[2], a3[2];
+        bf16x8 a[3][2];                              // [piece][k-step]
         auto split = [&](int ks) {
 #pragma unroll
             for (int e = 0; e < 8; ++e) {
-                const __bf16 h1 = (__bf16)fv[ks][e];
-                const float r1 = fv[ks][e] - (float)h1;
-                const __bf16 h2 = (__bf16)r1;
-                const float r2 = r1 - (float)h2;
-                a1[ks][e] = h1; a2[ks][e] = h2; a3[ks][e] = (__bf16)r2;
+                __bf16 h1, h2, h3;
+                split1(fv[ks][e], h1, h2, h3);
+                a[0][ks][e] = h1; a[1][ks][e] = h2; a[2][ks][e] = h3;
             }
         };
         auto mfmas = [&](int ks) {
 #pragma unroll
             for (int t = 0; t < TN; ++t) {
-                const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(&Bp[0][bcol + t * 32][ks * 16 + kq]);
-                const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(&Bp[1][bcol + t * 32][ks * 16 + kq]);
-                const bf16x8 b3 = *reinterpret_cast<const bf16x8*>(&Bp[2][bcol + t * 32][ks * 16 + kq]);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3[ks], b1, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[ks], b2, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[ks], b3, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[ks], b1, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[ks], b2, acc[t], 0, 0, 0);
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[ks], b1, acc[t], 0, 0, 0);
+                bf16x8 b[3];
+#pragma unroll
+                for (int pl = 0; pl < 3; ++pl) b[pl] = *reinterpret_cast<const bf16x8*>(&Bp[pl][bcol + t * 32][ks * 16 + kq]);
+                split_products([&](auto ap, auto bp) {
+                    acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[ap][ks], b[bp], acc[t], 0, 0, 0);
+                });
             }
         };
         split(0);
@@ -617,31 +608,30 @@ __global__ __launch_bounds__(256, 3) void spconv_fwd_x6_kernel(const float* __re
         auto split_pair = [&](int pr) {
 #pragma unroll
             for (int e = 2 * pr; e < 2 * pr + 2; ++e) {
-                const __bf16 h1 = (__bf16)fv[1][e];
-                const float r1 = fv[1][e] - (float)h1;
-                const __bf16 h2 = (__bf16)r1;
-                const float r2 = r1 - (float)h2;
-                a1[1][e] = h1; a2[1][e] = h2; a3[1][e] = (__bf16)r2;
+                __bf16 h1, h2, h3;
+                split1(fv[1][e], h1, h2, h3);
+                a[0][1][e] = h1; a[1][1][e] = h2; a[2][1][e] = h3;
             }
         };
         int pr = 0;
+        // (the six products of split_products (split.h), in its order, written out by hand for the barriers between them)
 #pragma unroll
         for (int t = 0; t < TN; ++t) {
             const bf16x8 b1 = *reinterpret_cast<const bf16x8*>(&Bp[0][bcol + t * 32][kq]);
             const bf16x8 b2 = *reinterpret_cast<const bf16x8*>(&Bp[1][bcol + t * 32][kq]);
             const bf16x8 b3 = *reinterpret_cast<const bf16x8*>(&Bp[2][bcol + t * 32][kq]);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a3[0], b1, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[0], b2, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[2][0], b1, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b2, acc[t], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (pr < 4) split_pair(pr++);
             __builtin_amdgcn_sched_barrier(0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b3, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a2[0], b1, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b3, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[1][0], b1, acc[t], 0, 0, 0);
             __builtin_amdgcn_sched_barrier(0);
             if (TN < 4 && t < 4 - TN && pr < 4) split_pair(pr++);      // TN < 4: a second pair in the first blocks
             __builtin_amdgcn_sched_barrier(0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b2, acc[t], 0, 0, 0);
-            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a1[0], b1, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b2, acc[t], 0, 0, 0);
+            acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(a[0][0], b1, acc[t], 0, 0, 0);
         }
 #pragma unroll
         for (; pr < 4; ++pr) split_pair(pr);                         // TN = 1 / 2: the rest, not hidden

@@ -16,16 +16,12 @@
 //   * a workgroup = 64 (x HALVES) table rows; its four waves take the offsets k = w, w + 4, ... (a quarter of the chain each) and
 //     their partial tiles are summed through LDS in wave order at the end => fixed summation order, bitwise reproducible;
 //   * (block, offset) groups without a single pair skip their MFMAs (wave-uniform); on a tile-ordered table (osn_kmap_sort) most are.
-// Arithmetic: "bf16x6" as everywhere (three bf16 pieces per operand, six MFMAs per product block, fp32 accumulate, smallest terms first).
+// Arithmetic: "bf16x6" as everywhere (split.h: three bf16 pieces per operand, six MFMAs per product block, fp32 accumulate).
 #include "common.h"
 #include "split.h"
 #include "epilogue.h"
 
 namespace osn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int RG_RB = 4;                 // 16-row blocks per wave and half: 64 rows
 
@@ -135,18 +131,14 @@ __global__ __launch_bounds__(256, OCC) void spconv_rg_kernel(const float* __rest
                 if (any[h][rb]) {
 #pragma unroll
                     for (int ks = 0; ks < KS; ++ks) {
-                        bf16x4 a1, a2, a3, b1, b2, b3;
-                        tl_split4(P_cur[h][rb][ks][0], a1, a2, a3);
-                        tl_split4(P_cur[h][rb][ks][1], b1, b2, b3);
-                        const bf16x8 A1 = __builtin_shufflevector(a1, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-                        const bf16x8 A2 = __builtin_shufflevector(a2, b2, 0, 1, 2, 3, 4, 5, 6, 7);
-                        const bf16x8 A3 = __builtin_shufflevector(a3, b3, 0, 1, 2, 3, 4, 5, 6, 7);
-                        // smallest terms first per accumulator; consecutive MFMAs on different accumulators
-#define RG_MFMA(AP, BP)                                                                                            \
-    _Pragma("unroll") for (int cb = 0; cb < NCB; ++cb)                                                             \
-        acc[h][rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B[ks][cb][BP], AP, acc[h][rb][cb], 0, 0, 0);
-                        RG_MFMA(A3, 0) RG_MFMA(A2, 1) RG_MFMA(A1, 2) RG_MFMA(A2, 0) RG_MFMA(A1, 1) RG_MFMA(A1, 0)
-#undef RG_MFMA
+                        bf16x8 A[3];
+                        split8(P_cur[h][rb][ks][0], P_cur[h][rb][ks][1], A);
+                        // split_products' order per accumulator (split.h); consecutive MFMAs on different accumulators
+                        split_products([&](auto ap, auto bp) {
+#pragma unroll
+                            for (int cb = 0; cb < NCB; ++cb)
+                                acc[h][rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B[ks][cb][bp], A[ap], acc[h][rb][cb], 0, 0, 0);
+                        });
                     }
                 }
             }

@@ -27,8 +27,8 @@
 //     summation order: bitwise reproducible whichever workgroup draws which tile;
 //   * the epilogue streams the tile to HBM through the `out_rows` permutation (features stay in the caller's
 //     row order) and can emit the per-tile column sums / sums of squares the following batch norm needs.
-// Arithmetic: "bf16x6" -- x = x1 + x2 + x3 (bf16 pieces), a*b ~= a3b1 + a2b2 + a1b3 + a2b1 + a1b2 + a1b1
-// accumulated in fp32 on v_mfma_f32_16x16x32_bf16 (dropped terms <= 2^-24 relative): fp32-class accuracy.
+// Arithmetic: "bf16x6" (split.h) -- three bf16 pieces per operand, six of the nine products accumulated in fp32 on
+// v_mfma_f32_16x16x32_bf16: fp32-class accuracy.
 #include "common.h"
 #include <atomic>
 #include <type_traits>
@@ -37,10 +37,6 @@
 #include "epilogue.h"
 
 namespace osn {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TL_BMAX = 88;       // rows per tile at most (LDS budget of the 128-column instance, 2 workgroups / CU)
 constexpr int TL_LIST_BMAX = 128; // rows per tile the LISTS can describe (a local row is 8 bits of a packed entry; spconv_pl.hip takes 128)
@@ -450,26 +446,14 @@ __global__ __launch_bounds__(256, OCC) void spconv_tl_kernel(const float* __rest
                                 af[h][pl] = *reinterpret_cast<const bf16x8*>(&stage[pl][(half1 ? h : 0) * 16 + (lane & 15)][ks * 32 + akq]);
                         // product-major order: consecutive MFMAs go to DIFFERENT accumulators (a dependent chain per
                         // accumulator would stall the in-order issue on every MFMA's result); per accumulator the
-                        // order is still smallest terms first: a3b1, a2b2, a1b3, a2b1, a1b2, a1b1
-#define TL_MFMA(H0, H1, AP, BP)                                                                             \
-    _Pragma("unroll") for (int h = H0; h < H1; ++h) _Pragma("unroll") for (int nb = 0; nb < 2; ++nb)          \
-        acc[h][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B[ks][nb][BP], af[h][AP], acc[h][nb], 0, 0, 0);
-                        if (half1) {
-                            TL_MFMA(0, 2, 2, 0)
-                            TL_MFMA(0, 2, 1, 1)
-                            TL_MFMA(0, 2, 0, 2)
-                            TL_MFMA(0, 2, 1, 0)
-                            TL_MFMA(0, 2, 0, 1)
-                            TL_MFMA(0, 2, 0, 0)
-                        } else {
-                            TL_MFMA(0, 1, 2, 0)
-                            TL_MFMA(0, 1, 1, 1)
-                            TL_MFMA(0, 1, 0, 2)
-                            TL_MFMA(0, 1, 1, 0)
-                            TL_MFMA(0, 1, 0, 1)
-                            TL_MFMA(0, 1, 0, 0)
-                        }
-#undef TL_MFMA
+                        // order is that of split_products (split.h)
+                        auto mfma_half = [&](int h, auto ap, auto bp) {
+#pragma unroll
+                            for (int nb = 0; nb < 2; ++nb)
+                                acc[h][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B[ks][nb][bp], af[h][ap], acc[h][nb], 0, 0, 0);
+                        };
+                        if (half1) split_products([&](auto ap, auto bp) { mfma_half(0, ap, bp); mfma_half(1, ap, bp); });
+                        else split_products([&](auto ap, auto bp) { mfma_half(0, ap, bp); });
                     }
                     if (ahead) load_b(ks, n1s);
                 }

@@ -27,10 +27,6 @@
 
 namespace osn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-
 constexpr int WS_NG = 4;            // 32-pair steps per workgroup at most
 constexpr int WS_CH = 32 * WS_NG;   // pairs per workgroup at most
 
@@ -145,16 +141,14 @@ __global__ __launch_bounds__(256) void spconv_ws_kernel(const float* __restrict_
                                 for (int pl = 0; pl < 3; ++pl)
                                     af[h][pl] = *reinterpret_cast<const bf16x8*>(
                                         &stage[buf][pl][(half1 ? h : 0) * 16 + (lane & 15)][ks * 32 + akq]);
-                            // smallest terms first per accumulator, consecutive MFMAs on different accumulators
-#define WS_MFMA(H1, AP, BP)                                                                                   \
-    _Pragma("unroll") for (int h = 0; h < H1; ++h) _Pragma("unroll") for (int nb = 0; nb < 2; ++nb)           \
-        acc[g][h][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B[ks][nb][BP], af[h][AP], acc[g][h][nb], 0, 0, 0);
-                            if (half1) {
-                                WS_MFMA(2, 2, 0) WS_MFMA(2, 1, 1) WS_MFMA(2, 0, 2) WS_MFMA(2, 1, 0) WS_MFMA(2, 0, 1) WS_MFMA(2, 0, 0)
-                            } else {
-                                WS_MFMA(1, 2, 0) WS_MFMA(1, 1, 1) WS_MFMA(1, 0, 2) WS_MFMA(1, 1, 0) WS_MFMA(1, 0, 1) WS_MFMA(1, 0, 0)
-                            }
-#undef WS_MFMA
+                            // split_products' order per accumulator (split.h), consecutive MFMAs on different accumulators
+                            auto mfma_half = [&](int h, auto ap, auto bp) {
+#pragma unroll
+                                for (int nb = 0; nb < 2; ++nb)
+                                    acc[g][h][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B[ks][nb][bp], af[h][ap], acc[g][h][nb], 0, 0, 0);
+                            };
+                            if (half1) split_products([&](auto ap, auto bp) { mfma_half(0, ap, bp); mfma_half(1, ap, bp); });
+                            else split_products([&](auto ap, auto bp) { mfma_half(0, ap, bp); });
                         }
                     }
                 }

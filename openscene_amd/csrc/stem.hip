@@ -147,10 +147,6 @@ __global__ __launch_bounds__(256) void stem_fwd4_kernel(const float* __restrict_
 // step and is 48 KB), partial tiles are summed in wave order through LDS.  Arithmetic: "bf16x6" like every other convolution here
 // (three bf16 pieces per operand, six MFMAs per block, fp32 accumulate: fp32-class, not the exact fmaf chain of the kernels above --
 // the small maps keep those).
-typedef float stem_f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 stem_bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 stem_bf16x4 __attribute__((ext_vector_type(4)));
-
 template <bool EPI>
 __global__ __launch_bounds__(256, 2) void stem_mfma_fwd_kernel(const float* __restrict__ in, const float* __restrict__ W,
                                                                const int32_t* __restrict__ nbr, float* __restrict__ out,
@@ -162,11 +158,11 @@ __global__ __launch_bounds__(256, 2) void stem_mfma_fwd_kernel(const float* __re
     const int l15 = lane & 15, lg = lane >> 4;
     const int64_t row0 = int64_t(blockIdx.x) * 64;
     const int n_steps = ((K + 1) / 2 + 3) / 4;                        // 32-deep k-steps (four offset pairs each)
-    stem_f32x4 acc[4][2];
+    f32x4 acc[4][2];
 #pragma unroll
     for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
-        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = stem_f32x4{0.f, 0.f, 0.f, 0.f};
+        for (int cb = 0; cb < 2; ++cb) acc[rb][cb] = f32x4{0.f, 0.f, 0.f, 0.f};
 
     for (int s = wave; s < n_steps; s += 4) {
         const int k0 = 2 * (4 * s + lg), k1 = k0 + 1;               // this lane's two offsets
@@ -180,7 +176,7 @@ __global__ __launch_bounds__(256, 2) void stem_mfma_fwd_kernel(const float* __re
             i1[rb] = (on && k1 < K) ? nbr[int64_t(k1) * n_out + r] : -1;
         }
         // ---- B fragments of this k-step from the fp32 weight: element e of the lane = W[k0 + (e >> 2)][e & 3][16 cb + l15]
-        stem_bf16x8 B[2][3];
+        bf16x8 B[2][3];
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb) {
             float4 w0 = make_float4(0.f, 0.f, 0.f, 0.f), w1 = make_float4(0.f, 0.f, 0.f, 0.f);
@@ -199,12 +195,7 @@ __global__ __launch_bounds__(256, 2) void stem_mfma_fwd_kernel(const float* __re
                 if (cin > 2) w1.z = p[2 * STEM_COUT];
                 if (cin > 3) w1.w = p[3 * STEM_COUT];
             }
-            stem_bf16x4 a1, a2, a3, b1, b2, b3;
-            tl_split4(w0, a1, a2, a3);
-            tl_split4(w1, b1, b2, b3);
-            B[cb][0] = __builtin_shufflevector(a1, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-            B[cb][1] = __builtin_shufflevector(a2, b2, 0, 1, 2, 3, 4, 5, 6, 7);
-            B[cb][2] = __builtin_shufflevector(a3, b3, 0, 1, 2, 3, 4, 5, 6, 7);
+            split8(w0, w1, B[cb]);
         }
         float4 x0[4], x1[4];
 #pragma unroll
@@ -230,18 +221,14 @@ __global__ __launch_bounds__(256, 2) void stem_mfma_fwd_kernel(const float* __re
         for (int rb = 0; rb < 4; ++rb) {
             // (a row block none of whose 16 rows x 8 offsets has a neighbour: nothing to add -- wave-uniform)
             if (__ballot(i0[rb] >= 0 || i1[rb] >= 0) == 0ull) continue;
-            stem_bf16x4 a1, a2, a3, b1, b2, b3;
-            tl_split4(x0[rb], a1, a2, a3);
-            tl_split4(x1[rb], b1, b2, b3);
-            const stem_bf16x8 A1 = __builtin_shufflevector(a1, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-            const stem_bf16x8 A2 = __builtin_shufflevector(a2, b2, 0, 1, 2, 3, 4, 5, 6, 7);
-            const stem_bf16x8 A3 = __builtin_shufflevector(a3, b3, 0, 1, 2, 3, 4, 5, 6, 7);
-            // smallest terms first per accumulator; consecutive MFMAs on different accumulators
-#define STEM_MFMA(AP, BP)                                                                                      \
-    _Pragma("unroll") for (int cb = 0; cb < 2; ++cb)                                                           \
-        acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B[cb][BP], AP, acc[rb][cb], 0, 0, 0);
-            STEM_MFMA(A3, 0) STEM_MFMA(A2, 1) STEM_MFMA(A1, 2) STEM_MFMA(A2, 0) STEM_MFMA(A1, 1) STEM_MFMA(A1, 0)
-#undef STEM_MFMA
+            bf16x8 A[3];
+            split8(x0[rb], x1[rb], A);
+            // split_products' order per accumulator (split.h); consecutive MFMAs on different accumulators
+            split_products([&](auto ap, auto bp) {
+#pragma unroll
+                for (int cb = 0; cb < 2; ++cb)
+                    acc[rb][cb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B[cb][bp], A[ap], acc[rb][cb], 0, 0, 0);
+            });
         }
     }
     // ---- the four waves' partial tiles -> out, summed in wave order (64 rows x 32 columns through LDS)
@@ -249,7 +236,7 @@ __global__ __launch_bounds__(256, 2) void stem_mfma_fwd_kernel(const float* __re
     for (int rb = 0; rb < 4; ++rb)
 #pragma unroll
         for (int cb = 0; cb < 2; ++cb)
-            *reinterpret_cast<stem_f32x4*>(&red[wave][16 * rb + l15][16 * cb + 4 * lg]) = acc[rb][cb];
+            *reinterpret_cast<f32x4*>(&red[wave][16 * rb + l15][16 * cb + 4 * lg]) = acc[rb][cb];
     __syncthreads();
     EpiCols ec;
     if constexpr (EPI) ec = epi_cols(epi, 4 * (tid & 7));
@@ -371,13 +358,13 @@ __global__ __launch_bounds__(256, 2) void stem_mfma_wgrad_kernel(const float* __
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int l15 = lane & 15, lg = lane >> 4;
-    stem_f32x4 acc[2][STEM_CMAX][2];
+    f32x4 acc[2][STEM_CMAX][2];
 #pragma unroll
     for (int ob = 0; ob < 2; ++ob)
 #pragma unroll
         for (int c = 0; c < STEM_CMAX; ++c)
 #pragma unroll
-            for (int nb = 0; nb < 2; ++nb) acc[ob][c][nb] = stem_f32x4{0.f, 0.f, 0.f, 0.f};
+            for (int nb = 0; nb < 2; ++nb) acc[ob][c][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
     const int64_t n_steps = (n_out + 31) / 32;
     const int kk[2] = {32 * wave + l15, 32 * wave + 16 + l15};               // this lane's offset in either block
     for (int64_t rs = blockIdx.x; rs < n_steps; rs += gridDim.x) {            // ascending rows: fixed summation order
@@ -412,15 +399,10 @@ __global__ __launch_bounds__(256, 2) void stem_mfma_wgrad_kernel(const float* __
                 for (int c = 0; c < STEM_CMAX; ++c) x[ob][c][e] = (idx[ob][e] >= 0 && c < cin) ? p[c] : 0.f;
             }
         // ---- G fragments: element e of the lane = gout[o0 + e][16 nb + l15]
-        stem_bf16x8 G[2][3];
+        bf16x8 G[2][3];
 #pragma unroll
         for (int nb = 0; nb < 2; ++nb) {
-            stem_bf16x4 a1, a2, a3, b1, b2, b3;
-            tl_split4(make_float4(g[nb][0], g[nb][1], g[nb][2], g[nb][3]), a1, a2, a3);
-            tl_split4(make_float4(g[nb][4], g[nb][5], g[nb][6], g[nb][7]), b1, b2, b3);
-            G[nb][0] = __builtin_shufflevector(a1, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-            G[nb][1] = __builtin_shufflevector(a2, b2, 0, 1, 2, 3, 4, 5, 6, 7);
-            G[nb][2] = __builtin_shufflevector(a3, b3, 0, 1, 2, 3, 4, 5, 6, 7);
+            split8(make_float4(g[nb][0], g[nb][1], g[nb][2], g[nb][3]), make_float4(g[nb][4], g[nb][5], g[nb][6], g[nb][7]), G[nb]);
         }
 #pragma unroll
         for (int ob = 0; ob < 2; ++ob) {
@@ -431,17 +413,14 @@ __global__ __launch_bounds__(256, 2) void stem_mfma_wgrad_kernel(const float* __
 #pragma unroll
             for (int c = 0; c < STEM_CMAX; ++c) {
                 if (c < cin) {
-                    stem_bf16x4 a1, a2, a3, b1, b2, b3;
-                    tl_split4(make_float4(x[ob][c][0], x[ob][c][1], x[ob][c][2], x[ob][c][3]), a1, a2, a3);
-                    tl_split4(make_float4(x[ob][c][4], x[ob][c][5], x[ob][c][6], x[ob][c][7]), b1, b2, b3);
-                    const stem_bf16x8 A1 = __builtin_shufflevector(a1, b1, 0, 1, 2, 3, 4, 5, 6, 7);
-                    const stem_bf16x8 A2 = __builtin_shufflevector(a2, b2, 0, 1, 2, 3, 4, 5, 6, 7);
-                    const stem_bf16x8 A3 = __builtin_shufflevector(a3, b3, 0, 1, 2, 3, 4, 5, 6, 7);
-#define STEM_WMFMA(AP, GP)                                                                                     \
-    _Pragma("unroll") for (int nb = 0; nb < 2; ++nb)                                                           \
-        acc[ob][c][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(AP, G[nb][GP], acc[ob][c][nb], 0, 0, 0);
-                    STEM_WMFMA(A3, 0) STEM_WMFMA(A2, 1) STEM_WMFMA(A1, 2) STEM_WMFMA(A2, 0) STEM_WMFMA(A1, 1) STEM_WMFMA(A1, 0)
-#undef STEM_WMFMA
+                    bf16x8 A[3];
+                    split8(make_float4(x[ob][c][0], x[ob][c][1], x[ob][c][2], x[ob][c][3]),
+                           make_float4(x[ob][c][4], x[ob][c][5], x[ob][c][6], x[ob][c][7]), A);
+                    split_products([&](auto ap, auto gp) {
+#pragma unroll
+                        for (int nb = 0; nb < 2; ++nb)
+                            acc[ob][c][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(A[ap], G[nb][gp], acc[ob][c][nb], 0, 0, 0);
+                    });
                 }
             }
         }

@@ -17,7 +17,7 @@
 //     ds_read_b64_tr_b16 (lane i of a 16-lane group receives channel i of four consecutive pairs; semantics
 //     measured in round 1, tools/probes/probe_gfx950.hip), 2 reads per 16 x 32 operand fragment;
 //   * 4 waves as 2 x 2 over the (input channel, output channel) block, MB x NB accumulator blocks of 16 x 16
-//     per wave, six MFMAs per block and step (a3g1 + a2g2 + a1g3 + a2g1 + a1g2 + a1g1, fp32 accumulate).
+//     per wave, six MFMAs per block and step (split_products in split.h, fp32 accumulate).
 #include "common.h"
 #include "split.h"
 #include <cstdlib>
@@ -25,9 +25,6 @@
 
 namespace osn {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 
 __device__ inline int wave_incl_scan_i32(int v, int lane) {
@@ -316,12 +313,9 @@ __global__ __launch_bounds__(256, 2) void wgrad_tl_kernel(const float* __restric
 #pragma unroll
             for (int j = 0; j < NB; ++j) {
                 f32x4 t = acc[i][j];
-                t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][2], fg[j][0], t, 0, 0, 0);
-                t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][1], fg[j][1], t, 0, 0, 0);
-                t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fg[j][2], t, 0, 0, 0);
-                t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][1], fg[j][0], t, 0, 0, 0);
-                t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fg[j][1], t, 0, 0, 0);
-                t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][0], fg[j][0], t, 0, 0, 0);
+                split_products([&](auto ap, auto gp) {
+                    t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][ap], fg[j][gp], t, 0, 0, 0);
+                });
                 acc[i][j] = t;
             }
     }

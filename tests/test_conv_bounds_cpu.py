@@ -109,3 +109,17 @@ def test_piece_aligned_pieces_are_what_the_name_says():
     w = cb.adversarial_weight("piece_aligned", 3, 8, 4, g, 1.0)
     p1, p2, p3 = cb.split3(w)
     assert torch.equal(p2, p1 * 2.0 ** -8) and torch.equal(p3, -p1 * 2.0 ** -17)
+
+
+def test_the_split_and_the_six_products_are_stated_once():
+    """csrc/split.h owns the arithmetic the bounds above describe: every split-bf16 convolution file takes its six products from
+    split_products, nothing but split.h restates the scalar three-way split, and no per-site MFMA macro is left."""
+    import os
+    import re
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "openscene_amd", "csrc")
+    texts = {f: open(os.path.join(csrc, f)).read() for f in sorted(os.listdir(csrc)) if f.endswith((".hip", ".h"))}
+    for f in ("spconv.hip", "spconv_tl.hip", "spconv_ws.hip", "spconv_rg.hip", "dense.hip", "wgrad_tl.hip", "stem.hip"):
+        assert '#include "split.h"' in texts[f] and "split_products(" in texts[f], f
+    assert [f for f, t in texts.items() if "- (float)h1" in t] == ["split.h"]
+    for f, t in texts.items():
+        assert not re.search(r"^\s*#\s*define\s+\w*MFMA\b", t, flags=re.M), f

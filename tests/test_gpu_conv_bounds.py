@@ -22,6 +22,8 @@ Worst err / lim per family and kind, measured on an MI355X (the assertion messag
     wgrad1 wgrad    0.03           0.03           0.01           0.05           0.07           0.64           
     dense fwd       0.12           0.02           0.09           0.30           0.93           -              
 """
+import hashlib
+
 import numpy as np
 import pytest
 import torch
@@ -113,6 +115,11 @@ def padded(x, d):
     return big[:x.shape[0]]
 
 
+def _sha(t):
+    """sha256 of a tensor's bytes: the BITS lines are what two builds of the library are compared by."""
+    return hashlib.sha256(t.detach().contiguous().cpu().numpy().tobytes()).hexdigest()
+
+
 @pytest.mark.parametrize("case", cb.CASES, ids=cb.CASE_IDS)
 def test_per_element_abs_sum_bound(case):
     case, nbr, run = launch_of(case)
@@ -126,6 +133,7 @@ def test_per_element_abs_sum_bound(case):
             gd = padded(gout, d)
             got = run.wgrad(fd, gd)
             assert got.shape == ref.gw.shape
+            print("BITS %s %s %s" % (case.id, kind, _sha(got)))
             ratio, n_bad = cb.worst_ratio(got, ref.gw, ref.b_gw, cb.WGRAD_C)
             print("RATIO %s %s %s %.3f" % (case.family, case.id, kind, ratio))
             if kind == "piece_aligned":
@@ -141,6 +149,7 @@ def test_per_element_abs_sum_bound(case):
             part = torch.zeros(run.tl.n_tiles, 2, case.cout, dtype=torch.float64, device=d)
         got = run.fwd(fd, wd, bn_partial=part) if part is not None else run.fwd(fd, wd)
         assert got.shape == ref.out.shape
+        print("BITS %s %s %s" % (case.id, kind, _sha(got)))
         print("RATIO %s %s %s %.3f" % (case.family, case.id, kind, cb.worst_ratio(got, ref.out, ref.b_out, cb.FWD_C)[0]))
         cb.within(got, ref.out, ref.b_out, cb.FWD_C, label + " forward")
         assert torch.equal(got, run.fwd(fd, wd)), label + ": not bitwise reproducible"

@@ -2,6 +2,8 @@
 oracle.  Tolerance (stated): fp32 products / fp32 accumulation against float64 ->
 max |delta| <= 3e-5 * max |reference| per tensor (observed ~1e-6); kernel maps come
 from the oracle so that a conv failure cannot hide behind a map failure."""
+import hashlib
+
 import numpy as np
 import pytest
 import torch
@@ -322,6 +324,8 @@ def test_table_kernels_in_every_launch_mode_and_tile(mode, n_out, cin, cout, ker
         runs.append(("fp32", lambda: ops.spconv_fwd(fd, wd, **args)))
     for name, run in runs:
         out = run()
+        if name == "split-bf16":                # what two builds of the library are compared by
+            print("BITS %s-%d-%d-%d %s" % (mode, n_out, cin, cout, hashlib.sha256(out.cpu().numpy().tobytes()).hexdigest()))
         close(out, ref, "%s kernel, %s mode" % (name, mode))
         assert torch.equal(out, run()), "%s kernel, %s mode: not bitwise reproducible" % (name, mode)
 
@@ -510,6 +514,7 @@ def test_weight_prep_x6_is_an_exact_three_way_split():
     w = torch.randn(27, 40, 24, generator=g).to(d)
     for flip, dgrad in ((False, False), (True, True), (False, True)):
         wp = ops.weight_prep_x6(w, flip=flip, for_dgrad=dgrad).float()
+        print("BITS weight_prep_x6-flip%d-dgrad%d %s" % (flip, dgrad, hashlib.sha256(wp.cpu().numpy().tobytes()).hexdigest()))
         assert wp.shape == (3, 27, 40 if dgrad else 24, 32 if dgrad else 64)
         rec = wp.sum(0)
         ref = torch.flip(w, dims=[0]) if flip else w
