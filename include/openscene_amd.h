@@ -608,6 +608,15 @@ int osn_eval_check(const int32_t* err, osn_stream_t stream);
  *   fp16 MFMA, fp32 accumulate, one rounding to fp16; with normalize the fp32 accumulator is divided by (norm + 1e-5),
  *   the norm taken from the same chunks that feed the MFMA (the bank is read once) -- within 2^-11 of rounding the
  *   normalised vector first, for unit-norm queries.
+ *   The arithmetic contract (tests/search_bounds.py, held on the device by tests/test_gpu_search_bounds.py): with v the
+ *   stored row, S = sum v_k t_k, A = sum |v_k| |t_k|, N = sqrt(sum v_k^2) in float64, c = 2e-6 (the bound of every fp32-
+ *   accumulating MFMA contraction here) and DELTA = 1.4e-5 (four times the measured error of fp32 sqrtf(sum v^2) + 1e-5f),
+ *     normalize = 0   fp16_rne(S - c A) <= score <= fp16_rne(S + c A)
+ *     normalize = 1   fp16_rne(L) <= score <= fp16_rne(U), L and U the least and the largest of
+ *                     (S -+ c A) / ((N + 1e-5) (1 -+ DELTA)) over the four sign choices
+ *   each end rounded from float64 in one step (a raw score beyond the fp16 range is +-inf).  fp16 subnormals of rows and
+ *   queries count in full.  A row of zeros (of either sign) scores +0.0 bit for bit; a row that holds a NaN scores NaN for
+ *   every query; a row that holds an inf scores NaN for every query with normalize = 1 and S itself with normalize = 0.
  *   heat (nullable) fp16 [n, q]; topk_scores fp16 [n_scenes, q, k]; topk_points int64 [n_scenes, q, k] = the row inside
  *   its scene, ordered by higher score, then lower row; NaN orders below every number (and is stored as NaN in heat);
  *   a scene with fewer than k points pads with (-inf, -1).  counts (nullable, needs thresholds) int64 [n_scenes, q] =
@@ -634,9 +643,13 @@ int osn_bank_search(const void* bank_f16, int64_t n, int d, const int64_t* scene
  * osn_bank_search_fp8: osn_bank_search over (codes, exps) -- the remaining arguments, the workspace
  *   (osn_bank_search_ws_bytes), selection, padding, counts, NaN order and repeatability are osn_bank_search's.  With c the
  *   row of code values, t an fp16 query and acc = sum c_i t_i (fp16 MFMA, exact widening of the codes, fp32 accumulate):
- *     normalize = 1   run/evaluate.py:305,310  acc * 2^e / (sqrt(sum c_i^2) * 2^e + 1e-5), rounded to fp16 once
+ *     normalize = 1   run/evaluate.py:305,310  acc / (sqrt(sum c_i^2) + 1e-5 / 2^e), rounded to fp16 once
  *     normalize = 0   run/evaluate.py:291      acc * 2^e, rounded to fp16 once
- *   A zero row scores exactly 0, a NaN row NaN for every query.                                                      */
+ *   The first is acc * 2^e / (sqrt(sum c_i^2) * 2^e + 1e-5) with 2^e divided out (1e-5 / 2^e is exact in fp32): the same
+ *   bits wherever that form stays inside fp32, and a cosine in [-1, 1] at every exponent up to e = 120, where the scaled
+ *   norm passes 2^128 (from e = 115 on at d = 768) and the scaled form gave 0 or NaN for a finite row.
+ *   A zero row scores exactly +0.0, a NaN row (a row that held a NaN or an inf) NaN for every query.  The contract of
+ *   osn_bank_search holds with v_i = code_i * 2^e: same c, same DELTA, every exponent byte.                          */
 int osn_bank_append_fp8(const void* X, int x_is_f16, int64_t n_rows, const int64_t* gather, int64_t n, int d,
                         uint8_t* codes, int8_t* exps, int64_t row0, int32_t* err, osn_stream_t stream);
 int osn_bank_search_fp8(const uint8_t* codes, const int8_t* exps, int64_t n, int d, const int64_t* scene_offsets,

@@ -11,6 +11,14 @@
 // and rounded to fp16 once.  The scores leave through an LDS tile twice: row-major into the caller's `heat` (optional)
 // and column-major into the workspace (`heatT` [Q][ldT]): a (scene, query) pair is then one contiguous fp16 array.
 //
+// What a score is held to (tests/search_bounds.py; on the device tests/test_gpu_search_bounds.py).  v = the stored row (fp16, or
+// code * 2^e), S = sum v_k t_k, A = sum |v_k| |t_k|, N = sqrt(sum v_k^2) in float64; c = 2e-6, this project's bound for an
+// fp32-accumulating MFMA contraction; DELTA = 1.4e-5, four times the measured error of fp32 sqrtf(sum v^2) + 1e-5f:
+//   raw          fp16_rne(S - c A) <= score <= fp16_rne(S + c A)
+//   normalize    fp16_rne(L) <= score <= fp16_rne(U): L, U = min, max of (S -+ c A) / ((N + 1e-5) (1 -+ DELTA)) over the signs
+// ends rounded from float64 once.  A zero row scores +0.0 bit for bit; a NaN in a row makes every score of it NaN; an inf
+// makes them NaN too (normalize, and any fp8 row: its codes are all NaN) or S itself (raw, fp16 rows).  fp16 subnormals count.
+//
 // Pass 2 selects on heatT with integer arithmetic only.  The fp16 score becomes a monotone 16-bit key (NaN -> 0, below
 // -inf; -0 -> +0).  A two-round 8-bit radix select over per-(scene, query) 256-bin histograms (LDS per workgroup, integer
 // atomics into the global one) finds the k-th key K exactly.  Everything above K is selected; of the points equal to K the
@@ -21,9 +29,10 @@
 // The fp8 bank (osn_bank_append_fp8 / osn_bank_search_fp8) stores a row as d OCP e4m3fn codes and one exponent byte e:
 // value = code * 2^e, e the smallest integer >= -120 with max|x| * 2^-e <= 448.  The append is one wave per row (the
 // row stays in registers between the max and the conversion); the heat pass streams 16 codes per 16-byte load, widens
-// them to fp16 (exact) on the way into LDS (heat_fp8_kernel); 2^e enters where the scores leave.  The two heat kernels call
-// one set of __device__ templates for the query staging, the MFMA loop, the row norms and the score output; each has its own
-// row fetch, stash and stage loop.  Pass 2 and the entries' argument checks are shared too.
+// them to fp16 (exact) on the way into LDS (heat_fp8_kernel); 2^e enters where the scores leave: raw scores are acc * 2^e,
+// normalised ones acc / (||c|| + 1e-5 / 2^e), which never forms a number of the row's own size (e goes up to 120).  The two
+// heat kernels call one set of __device__ templates for the query staging, the MFMA loop, the row norms and the score
+// output; each has its own row fetch, stash and stage loop.  Pass 2 and the entries' argument checks are shared too.
 //
 // Negative queries (osn_bank_search_contrast / _fp8): the heat kernels' CONTRAST instances walk the negatives' column groups
 // first -- same loop, each score rounded to fp16, only the row's maximum kept (rneg, LDS) -- and then write, for the queries,
@@ -125,10 +134,13 @@ __device__ __forceinline__ void mfma_chunk(f32x16 (&acc)[CT], const _Float16 (*X
     __builtin_amdgcn_sched_barrier(0);
 }
 
-// rden[row] = ||row|| [* rscale[row]] + 1e-5 (run/evaluate.py:305) from the partial sums of squares of the LANES lanes that
-// share a row (lane tid % LANES of row ps * (256 / LANES) + tid / LANES)
+// rden[row] = ||row|| + 1e-5 [/ rscale[row]] (run/evaluate.py:305) from the partial sums of squares of the LANES lanes that
+// share a row (lane tid % LANES of row ps * (256 / LANES) + tid / LANES).  SCALED (code rows, value = code * 2^e): the
+// denominator ||c|| 2^e + 1e-5 with 2^e divided out, so that nothing of the size of the row's values is ever formed in fp32:
+// ||c|| 2^e passes 2^128 from e = 115 on at d = 768.  1e-5 / 2^e is exact (a subnormal from e = 110 on, next to ||c|| >= 224).
+// rscale[row] becomes 1 on the way: the normalised scores leave as acc * 1 / rden through the very code the raw ones take
 template <int LANES, bool SCALED>
-__device__ __forceinline__ void row_norms(float* rden, const float (&ss)[S_BM * LANES / 256], const float* rscale, int tid) {
+__device__ __forceinline__ void row_norms(float* rden, const float (&ss)[S_BM * LANES / 256], float* rscale, int tid) {
     constexpr int SWEEP = 256 / LANES;
 #pragma unroll
     for (int ps = 0; ps < S_BM / SWEEP; ++ps) {
@@ -136,14 +148,21 @@ __device__ __forceinline__ void row_norms(float* rden, const float (&ss)[S_BM * 
 #pragma unroll
         for (int m = 1; m < LANES; m <<= 1) s += __shfl_xor(s, m, 64);
         const int row = ps * SWEEP + tid / LANES;
-        if (tid % LANES == 0) rden[row] = SCALED ? sqrtf(s) * rscale[row] + 1e-5f : sqrtf(s) + 1e-5f;
+        if (tid % LANES == 0) {
+            if constexpr (SCALED) {
+                rden[row] = sqrtf(s) + 1e-5f / rscale[row];
+                rscale[row] = 1.f;
+            } else {
+                rden[row] = sqrtf(s) + 1e-5f;
+            }
+        }
     }
     __syncthreads();
 }
 
-// the scores of one column group leave: accumulator [* rscale, exact: a power of two], divided by rden in fp32, rounded to
-// fp16 once into the LDS tile Sc[column][row] (CT * 32 <= 128 rows of the row tile); from there column-major into heatT and,
-// where the caller wants it, row-major into heat.
+// the scores of one column group leave: accumulator [* rscale, exact: 2^e for raw scores, 1 for normalised ones (row_norms)],
+// divided by rden in fp32, rounded to fp16 once into the LDS tile Sc[column][row] (CT * 32 <= 128 rows of the row tile); from
+// there column-major into heatT and, where the caller wants it, row-major into heat.
 // CONTRAST (osn_bank_search_contrast): a group of negatives (`neg`, q = their number) is stored nowhere -- the largest fp16
 // score of a row, NaN if one of them is, is kept in rneg[row]; a group of queries writes, in place of the fp16 score s,
 // fp16(1 / (1 + expf(-(s - rneg[row]) / temperature))), the relevancy against the best negative.
@@ -496,7 +515,7 @@ __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __res
             if (d0 + 2 * S_DK < d) stash(pxa, d0 + 2 * S_DK);
             __syncthreads();
         }
-        if (sumsq) row_norms<8, true>(rden, ss, rscale, tid);       // ||c|| * 2^e + 1e-5
+        if (sumsq) row_norms<8, true>(rden, ss, rscale, tid);       // ||c|| + 1e-5 / 2^e
         scores_out<CT, true, CONTRAST>(acc, Xs, rden, rscale, rneg, neg, temperature, heat, heatT, ldT, row0, n, qg, cg0,
                                        normalize, tid);
     }

@@ -4,7 +4,9 @@ Quantiser: codes and exponents bit for bit against the torch restatement of the 
 torch's own CPU float8_e4m3fn cast).
 Heat-map: against the float64 evaluation of the score formulas on the stored values v = code * 2^e, abs <= 2e-3 -- the
 bound of tests/test_gpu_search.py; its derivation carries over because e4m3 -> fp16 is exact, so the MFMA
-sees the very values the formula is evaluated on, and 2^e is a power of two.
+sees the very values the formula is evaluated on, and 2^e is a power of two.  That 2e-3 is the distance to the REFERENCE's
+expression, which rounds the normalised vector to fp16 first, on unit_rows whose exponents are nearly all equal; the kernel's own
+arithmetic -- every exponent byte, a different one in the neighbouring row -- is held in tests/test_gpu_search_bounds.py.
 Distance to the source rows (normalize = 0): |v_i - x_i| <= 2^-4 |x_i| for a normal code (half a unit of a 3-bit
 mantissa), <= 2^-10 * 2^e for a subnormal one (half the code spacing 2^-9); Cauchy-Schwarz over the row gives
 |score(v) - score(x)| <= 2^-4 |x| |t| + 2^-10 2^e sqrt(d) |t|, plus the 2e-3 above.

@@ -8,7 +8,9 @@ driven through both kernels at the chunk and tile edges the other search tests l
     q   1 and 32 (the one-tile instance and its full tile), 33 (two tiles, one column in the second), 65 (two column groups)
 
 Oracle and bound: the float64 formulas of tests/search_reference.py and tests/search_fp8_reference.py on the stored rows, abs <=
-2e-3 as in test_gpu_search.py / test_gpu_search_fp8.py (derived there for any d; a smaller d only has less rounding).  The
+2e-3 as in test_gpu_search.py / test_gpu_search_fp8.py (derived there for any d; a smaller d only has less rounding).  That 2e-3
+is the distance to the REFERENCE's expression, which rounds the normalised vector to fp16 first; this file is about the edges
+of chunks and tiles.  The kernel's own arithmetic is held in tests/test_gpu_search_bounds.py, per element.  The
 selection is checked against the kernel's own heat-map, so pass 2 is seen reading what the shared store wrote."""
 import pytest
 import torch
