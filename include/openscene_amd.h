@@ -175,9 +175,14 @@ int osn_spconv_fwd_x6(const float* in, const void* Wp, const int32_t* nbr, const
  *                                   row j; tl = null <=> K == 1 identity map.  bn_partial (nullable):
  *                                   double [n_tiles][2][cout] per-tile column sums / sums of squares of
  *                                   `out` (the following batch norm's statistics without a pass over out).
- *                                   ws: osn_spconv_fwd_tl_ws_bytes(..) bytes: tile counters (512 bytes, zeroed by the call) and, on
+ *                                   ws: osn_spconv_fwd_tl_ws_bytes(..) bytes: a 512-byte head and, on
  *                                   small tables, the partial tiles of a launch that splits each tile's offsets over
  *                                   several workgroups (summed in a fixed order; bn_partial must be null there).
+ *                                   counters (nullable): caller-owned PERSISTENT tile counters (128 int32 in device
+ *                                   memory, zero before the first call, one buffer per stream): the kernel's last
+ *                                   workgroup puts them back to zero, so the call needs no memset launch.  A launch
+ *                                   that fails leaves them undefined (zero them again).  counters null: the tile
+ *                                   counters are the head of ws, zeroed by the call.
  *                                   Needs cin % 4 == 0, cout % 4 == 0 and n_in <= 2^24 (OSN_E_RANGE otherwise).  */
 int osn_tile_rows(int64_t n_out);
 size_t osn_tile_lists_bytes(int64_t n_out, int K, int bm);
@@ -186,15 +191,9 @@ size_t osn_weight_prep_tl_bytes(int K, int cin, int cout, int for_dgrad);
 int osn_weight_prep_tl(const float* W, int K, int cin, int cout, int flip, void* Wp_fwd, void* Wp_dgrad,
                        osn_stream_t stream);
 size_t osn_spconv_fwd_tl_ws_bytes(int64_t n_out, int K, int cout, int bm);
-/* osn_spconv_fwd_tl_pc: the same call with caller-owned PERSISTENT tile counters (128 int32 in device memory, zero before
- * the first call, one buffer per stream): the kernel's last workgroup puts them back to zero, so the call needs no memset
- * launch.  A launch that fails leaves them undefined (zero them again).                                                  */
 int osn_spconv_fwd_tl(const float* in, int64_t n_in, const void* Wp, const void* tl, const int32_t* out_rows,
                       float* out, double* bn_partial, int64_t n_out, int K, int cin, int cout, int bm,
-                      void* ws, size_t ws_bytes, osn_stream_t stream);
-int osn_spconv_fwd_tl_pc(const float* in, int64_t n_in, const void* Wp, const void* tl, const int32_t* out_rows,
-                         float* out, double* bn_partial, int64_t n_out, int K, int cin, int cout, int bm,
-                         void* ws, size_t ws_bytes, int32_t* counters, osn_stream_t stream);
+                      void* ws, size_t ws_bytes, int32_t* counters, osn_stream_t stream);
 
 /* ---- every weight image of a model in one launch ----------------------------------------------- *
  * [ME] keeps one `kernel` parameter per MinkowskiConvolution / MinkowskiConvolutionTranspose
@@ -364,59 +363,43 @@ size_t osn_bn_ws_bytes(int64_t n, int c);
 int osn_bn_stats(const float* x, int64_t n, int c, float* mean, float* var,
                  float* running_mean, float* running_var, float momentum,
                  void* ws, size_t ws_bytes, osn_stream_t stream);
-/* y = act( (x - mean) * rsqrt(var + eps) * gamma + beta  [+ residual] ),  act = ReLU if relu */
+/* y = act( (x - mean) * rsqrt(var + eps) * gamma + beta  [+ residual] ),  act = ReLU if relu.
+ * y2 (nullable; ld2 is then not read) is a SECOND destination: the same rows also stored as a column window of a wider
+ * matrix (y2 = first element of the window, ld2 = that matrix's row stride in floats, >= c and % 4 == 0) -- ME.cat
+ * (models/mink_unet.py:147,155,163,171) written in place by the producers of its two halves.                        */
 int osn_bn_apply(const float* x, const float* mean, const float* var, const float* gamma,
                  const float* beta, float eps, const float* residual, int relu, float* y,
-                 int64_t n, int c, osn_stream_t stream);
+                 float* y2, int64_t ld2, int64_t n, int c, osn_stream_t stream);
 /* osn_bn_stats + osn_bn_apply in one call (training-mode forward of MinkowskiBatchNorm [+ residual] [+ MinkowskiReLU],
- * models/mink_unet.py:116-174; mean / var are outputs kept for the backward).                                      */
+ * models/mink_unet.py:116-174; mean / var are outputs kept for the backward; y2 / ld2 as in osn_bn_apply).  Maps of at
+ * most 4096 rows (the deep U-Net levels) run as ONE launch (statistics and apply from registers).                    */
 int osn_bn_forward_train(const float* x, int64_t n, int c, const float* gamma, const float* beta, float eps,
                          const float* residual, int relu, float momentum, float* mean, float* var,
-                         float* running_mean, float* running_var, float* y, void* ws, size_t ws_bytes,
-                         osn_stream_t stream);
+                         float* running_mean, float* running_var, float* y, float* y2, int64_t ld2,
+                         void* ws, size_t ws_bytes, osn_stream_t stream);
 /* Backward of osn_bn_apply.  g = relu ? gy * (y > 0) : gy.
  * training != 0 (batch statistics were used):
  *   gx = gamma * invstd * (g - mean_rows(g) - xhat * mean_rows(g * xhat))
  * training == 0 (running statistics): gx = gamma * invstd * g.
- * ggamma = sum_rows(g * xhat), gbeta = sum_rows(g); gres (nullable) = g.          */
-int osn_bn_backward(const float* x, const float* y, const float* gy, const float* mean,
-                    const float* var, const float* gamma, float eps, int relu, int training,
-                    float* gx, float* gres, float* ggamma, float* gbeta,
-                    int64_t n, int c, void* ws, size_t ws_bytes, osn_stream_t stream);
-
-/* osn_bn_apply with a SECOND destination: the same rows also stored as a column window of a wider matrix
- * (y2 = first element of the window, ld2 = that matrix's row stride in floats) -- ME.cat (models/mink_unet.py:147,155,
- * 163,171) written in place by the producers of its two halves.  y2 null = osn_bn_apply.                           */
-int osn_bn_apply2(const float* x, const float* mean, const float* var, const float* gamma,
-                  const float* beta, float eps, const float* residual, int relu, float* y,
-                  float* y2, int64_t ld2, int64_t n, int c, osn_stream_t stream);
-/* osn_bn_forward_train with the second destination of osn_bn_apply2.  Maps of at most 4096 rows (the deep U-Net levels)
- * run as ONE launch (statistics and apply from registers); osn_bn_forward_train does the same.                         */
-int osn_bn_forward_train2(const float* x, int64_t n, int c, const float* gamma, const float* beta, float eps,
-                          const float* residual, int relu, float momentum, float* mean, float* var,
-                          float* running_mean, float* running_var, float* y, float* y2, int64_t ld2,
-                          void* ws, size_t ws_bytes, osn_stream_t stream);
-/* osn_bn_backward whose incoming gradient is the SUM of n_gy (1..3) row-aligned matrices, each with its own row
- * stride (HOST arrays of device pointers / strides in floats): a block input feeds conv1 and the residual, an encoder
+ * ggamma = sum_rows(g * xhat), gbeta = sum_rows(g); gres (nullable) = g.
+ * gy, the incoming gradient, is the SUM of n_gy (1..3) row-aligned matrices, each with its own row stride (HOST arrays
+ * of device pointers / strides in floats, >= c and % 4 == 0): a block input feeds conv1 and the residual, an encoder
  * output feeds the next stride-2 convolution and -- through ME.cat -- two convolutions of the decoder
- * (models/mink_unet.py:116-174); the sum autograd would form with separate add kernels is formed while reading.   */
-int osn_bn_backward_multi(const float* x, const float* y, const float* const* gy_host, const int64_t* gy_ld_host,
-                          int n_gy, const float* mean, const float* var, const float* gamma, float eps, int relu,
-                          int training, float* gx, float* gres, float* ggamma, float* gbeta,
-                          int64_t n, int c, void* ws, size_t ws_bytes, osn_stream_t stream);
-/* the same with `beta`: for a batch norm + ReLU WITHOUT a residual, y may be null -- the mask (y > 0) is recomputed from x
- * with the forward pass's own expression, so neither backward pass reads y (models/resnet_base.py:98: bn -> relu)       */
-/* gres (a batch norm with a residual): the column-sum pass stores g = the masked sum of the sources to gres and the apply pass
+ * (models/mink_unet.py:116-174); the sum autograd would form with separate add kernels is formed while reading.
+ * beta (nullable): for a batch norm + ReLU WITHOUT a residual, y may be null when beta is given -- the mask (y > 0) is
+ * recomputed from x with the forward pass's own expression, so neither backward pass reads y (models/resnet_base.py:98:
+ * bn -> relu).  relu with neither y nor beta, or a null y together with gres, is OSN_E_ARG.
+ * gres (a batch norm with a residual): the column-sum pass stores g = the masked sum of the sources to gres and the apply pass
  * reads it back instead of forming it a second time from y and the sources.  ALIASING RULE: that data flow is used only when
  * gres [n, c] overlaps none of x, y, gx and the gradient sources (each source's range is (n - 1) * ld + c floats); a gres that
  * overlaps any of them (e.g. gres written in place over source 0) takes the earlier flow, in which both passes form g and
  * the apply pass writes gres element by element.  Every output is bit for bit the same on both flows.                    */
-int osn_bn_backward_multi2(const float* x, const float* y, const float* const* gy_host, const int64_t* gy_ld_host, int n_gy,
-                           const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu,
-                           int training, float* gx, float* gres, float* ggamma, float* gbeta, int64_t n, int c, void* ws,
-                           size_t ws_bytes, osn_stream_t stream);
+int osn_bn_backward(const float* x, const float* y, const float* const* gy_host, const int64_t* gy_ld_host, int n_gy,
+                    const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu,
+                    int training, float* gx, float* gres, float* ggamma, float* gbeta, int64_t n, int c, void* ws,
+                    size_t ws_bytes, osn_stream_t stream);
 
-/* The launch plan of the apply kernels (osn_bn_apply2, the apply pass of osn_bn_backward_multi2) for total4 = n * c / 4 quads of
+/* The launch plan of the apply kernels (osn_bn_apply, the apply pass of osn_bn_backward) for total4 = n * c / 4 quads of
  * c4 = c / 4 column quads: *grid = workgroups of 256 threads.  *flat = 0: grid * 256 is a multiple of c4 -- the smallest such grid
  * >= min(2048, ceil(total4 / 256)), at most 127 above it -- and every thread keeps its column quad (per-column constants and the
  * four 1 / sqrt(var + eps) taken once per thread).  *flat = 1: no such grid (wide odd c4); the flat kernels, which take column and
@@ -451,12 +434,10 @@ int osn_bn_set_separate_finalize(int on);
 size_t osn_distill_loss_state_bytes(int64_t n, int64_t n_sel);
 int osn_distill_loss_fwd(const float* out, const int64_t* sel, const float* target, int64_t n, int64_t n_sel, int d, int kind,
                          float* loss, void* state, size_t state_bytes, osn_stream_t stream);
-int osn_distill_loss_bwd(const float* out, const float* target, const float* gloss, int64_t n, int64_t n_sel, int d, int kind,
-                         float* gout, const void* state, size_t state_bytes, osn_stream_t stream);
-/* the same pass; additionally grows[j, :] = gout[sel[j], :] (nullable): the non-zero rows of the gradient once more, compacted,
+/* grows (nullable): additionally grows[j, :] = gout[sel[j], :], the non-zero rows of the gradient once more, compacted,
  * for osn_net_run.goutput_rows (the first n int32 of `state` are osn_net_run.grows_pos)                                  */
-int osn_distill_loss_bwd_rows(const float* out, const float* target, const float* gloss, int64_t n, int64_t n_sel, int d, int kind,
-                              float* gout, float* grows, const void* state, size_t state_bytes, osn_stream_t stream);
+int osn_distill_loss_bwd(const float* out, const float* target, const float* gloss, int64_t n, int64_t n_sel, int d, int kind,
+                         float* gout, float* grows, const void* state, size_t state_bytes, osn_stream_t stream);
 int osn_distill_loss_check(const void* state, int64_t n, int64_t n_sel, osn_stream_t stream);
 
 /* ---- optimizer step over one flat buffer ------------------------------------------------------------ *
@@ -1153,7 +1134,7 @@ typedef struct osn_events osn_events_t;       /* pool of HIP events for the fork
 #define OSN_NET_RUN_NO_JOIN 1
 /* osn_net_forward, evaluation mode: by default a stage's batch norm (+ residual) (+ ReLU) (+ cat store) is applied in the EPILOGUE of
  * the kernel that finishes the stage's convolution (csrc/epilogue.h: same expression, bitwise the separate launch); this flag keeps
- * the separate osn_bn_apply2 launch (A/B, tests).                                                                         */
+ * the separate osn_bn_apply launch (A/B, tests).                                                                          */
 #define OSN_NET_RUN_NO_BN_EPILOGUE 2
 typedef struct osn_net_run {
     const int64_t* level_rows;   /* [n_levels] rows of every pyramid level                                        */
@@ -1167,7 +1148,7 @@ typedef struct osn_net_run {
     void* fwd_arena; uint64_t fwd_arena_bytes;
     void* bwd_arena; uint64_t bwd_arena_bytes;
     void* ws; uint64_t ws_bytes;
-    int32_t* tl_counters;        /* 128 persistent tile counters of this stream (osn_spconv_fwd_tl_pc)            */
+    int32_t* tl_counters;        /* 128 persistent tile counters of this stream (osn_spconv_fwd_tl counters)      */
     int32_t training;            /* batch statistics + running update (1) or running statistics (0)               */
     int32_t first_op, end_op;    /* ops [first_op, end_op) are executed                                           */
     int32_t flags;               /* OSN_NET_RUN_*                                                                 */

@@ -48,8 +48,7 @@ PROTOTYPES = {
     "osn_weight_prep_job_blocks": (_i64, [_i32, _i32, _i32, _i32, _i32]),
     "osn_weight_prep_batch": (_i32, [_vp, _i32, _i64, _vp]),
     "osn_spconv_fwd_tl_ws_bytes": (_sz, [_i64, _i32, _i32, _i32]),
-    "osn_spconv_fwd_tl": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _sz, _vp]),
-    "osn_spconv_fwd_tl_pc": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
+    "osn_spconv_fwd_tl": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
     "osn_weight_transpose": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp]),
     "osn_spconv_wgrad_ws_bytes": (_sz, [_i64, _i32, _i32, _i32]),
     "osn_spconv_wgrad_items_bytes": (_sz, [_i64, _i32, _i32, _i32]),
@@ -61,8 +60,7 @@ PROTOTYPES = {
     "osn_spconv_wgrad_tl": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _sz, _vp]),
     "osn_distill_loss_state_bytes": (_sz, [_i64, _i64]),
     "osn_distill_loss_fwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
-    "osn_distill_loss_bwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _sz, _vp]),
-    "osn_distill_loss_bwd_rows": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "osn_distill_loss_bwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _sz, _vp]),
     "osn_rows_gather": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "osn_rows_scatter_zero": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp]),
     "osn_distill_loss_check": (_i32, [_vp, _i64, _i64, _vp]),
@@ -84,18 +82,12 @@ PROTOTYPES = {
     "osn_stem_conv_fwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "osn_bn_ws_bytes": (_sz, [_i64, _i32]),
     "osn_bn_stats": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _sz, _vp]),
-    "osn_bn_apply": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _i64, _i32, _vp]),
-    "osn_bn_forward_train": (_i32, [_vp, _i64, _i32, _vp, _vp, _f32, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
-    "osn_bn_backward": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32,
-                               _vp, _sz, _vp]),
-    "osn_bn_apply2": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _vp]),
+    "osn_bn_apply": (_i32, [_vp, _vp, _vp, _vp, _vp, _f32, _vp, _i32, _vp, _vp, _i64, _i64, _i32, _vp]),
     "osn_spconv_fwd_rg_ok": (_i32, [_i64, _i32, _i32, _i32]),
     "osn_spconv_fwd_rg": (_i32, [_vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
-    "osn_bn_forward_train2": (_i32, [_vp, _i64, _i32, _vp, _vp, _f32, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
-    "osn_bn_backward_multi": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32,
-                                     _vp, _sz, _vp]),
-    "osn_bn_backward_multi2": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32,
-                                     _vp, _sz, _vp]),
+    "osn_bn_forward_train": (_i32, [_vp, _i64, _i32, _vp, _vp, _f32, _vp, _i32, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _sz, _vp]),
+    "osn_bn_backward": (_i32, [_vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _i64, _i32,
+                               _vp, _sz, _vp]),
     "osn_bn_apply_plan": (_i32, [_i64, _i32, _c.POINTER(_i32), _c.POINTER(_i32)]),
     "osn_bn_set_flat_kernels": (_i32, [_i32]),
     "osn_bn_set_separate_finalize": (_i32, [_i32]),

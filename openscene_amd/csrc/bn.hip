@@ -67,7 +67,7 @@ static ColReducePlan plan_colreduce(int64_t n, int c) {
 // backward sums without a gres store stay within CR_BWD_VGPRS registers (those with the store: col_reduce_gres_kernel below).
 // What a launch does not use is chosen at compile time -- a register that an `if (i < n)` load MAY fill is allocated for every launch:
 //   MASK  none (no ReLU), from x (ReLU, no residual: gamma and beta are read, y is not), from y -- one kernel each, picked by the
-//         host (osn_bn_backward_multi2); CR_MASK_RT: read from the arguments at run time (the one-row kernels of
+//         host (osn_bn_backward); CR_MASK_RT: read from the arguments at run time (the one-row kernels of
 //         osn_bn_set_flat_kernels)
 //   NSRC  1: one gradient source; BN_MAX_SRC: gy.n of them, as before; CR_SRC_BRANCH: both row loops in one kernel, chosen by a
 //         uniform branch on gy.n (a kernel's name and grid then say nothing about how many matrices its gradient arrives in: the
@@ -762,13 +762,13 @@ extern "C" int osn_bn_stats(const float* x, int64_t n, int c, float* mean, float
     return OSN_OK;
 }
 
-extern "C" int osn_bn_apply2(const float* x, const float* mean, const float* var, const float* gamma, const float* beta,
-                             float eps, const float* residual, int relu, float* y, float* y2, int64_t ld2, int64_t n, int c,
-                             osn_stream_t stream) {
+extern "C" int osn_bn_apply(const float* x, const float* mean, const float* var, const float* gamma, const float* beta,
+                            float eps, const float* residual, int relu, float* y, float* y2, int64_t ld2, int64_t n, int c,
+                            osn_stream_t stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     OSN_REQUIRE(n >= 0 && c >= 4 && (c & 3) == 0, OSN_E_ARG, "osn_bn_apply: need c %% 4 == 0 (c=%d)", c);
     if (n == 0) return OSN_OK;
-    if (int rc = check_fwd_args("osn_bn_apply2", x, mean, var, true, gamma, beta, residual, y, y2, ld2, c)) return rc;
+    if (int rc = check_fwd_args("osn_bn_apply", x, mean, var, true, gamma, beta, residual, y, y2, ld2, c)) return rc;
     const int64_t total4 = n * (c / 4);
     const ApplyPlan ap = launch_plan_apply(total4, c / 4);
     hipLaunchKernelGGL(ap.keep ? bn_apply_kernel : bn_apply_flat_kernel, dim3(ap.grid), dim3(256), 0, st, x, mean, var, gamma, beta, eps,
@@ -777,22 +777,16 @@ extern "C" int osn_bn_apply2(const float* x, const float* mean, const float* var
     return OSN_OK;
 }
 
-extern "C" int osn_bn_apply(const float* x, const float* mean, const float* var, const float* gamma, const float* beta,
-                            float eps, const float* residual, int relu, float* y, int64_t n, int c,
-                            osn_stream_t stream) {
-    return osn_bn_apply2(x, mean, var, gamma, beta, eps, residual, relu, y, nullptr, 0, n, c, stream);
-}
-
 // Training-mode forward in ONE call: statistics (+ running buffers) and the fused normalise (+ residual) (+ ReLU) pass
-// (+ the second destination of osn_bn_apply2).  Up to SB_MAX_ROWS rows: ONE launch (bn_small_fwd_kernel); above: the
-// kernels of osn_bn_stats + osn_bn_apply2.
-extern "C" int osn_bn_forward_train2(const float* x, int64_t n, int c, const float* gamma, const float* beta, float eps,
-                                     const float* residual, int relu, float momentum, float* mean, float* var,
-                                     float* running_mean, float* running_var, float* y, float* y2, int64_t ld2, void* ws,
-                                     size_t ws_bytes, osn_stream_t stream) {
+// (+ the second destination of osn_bn_apply).  Up to SB_MAX_ROWS rows: ONE launch (bn_small_fwd_kernel); above: the
+// kernels of osn_bn_stats + osn_bn_apply.
+extern "C" int osn_bn_forward_train(const float* x, int64_t n, int c, const float* gamma, const float* beta, float eps,
+                                    const float* residual, int relu, float momentum, float* mean, float* var,
+                                    float* running_mean, float* running_var, float* y, float* y2, int64_t ld2, void* ws,
+                                    size_t ws_bytes, osn_stream_t stream) {
     if (n >= 1 && n <= SB_MAX_ROWS && c >= 4 && (c & 3) == 0) {
         hipStream_t st = static_cast<hipStream_t>(stream);
-        if (int rc = check_fwd_args("osn_bn_forward_train2", x, mean, var, false, gamma, beta, residual, y, y2, ld2, c)) return rc;
+        if (int rc = check_fwd_args("osn_bn_forward_train", x, mean, var, false, gamma, beta, residual, y, y2, ld2, c)) return rc;
         hipLaunchKernelGGL(bn_small_fwd_kernel, dim3(unsigned(cdiv(c, SB_COLS))), dim3(SB_THREADS), 0, st, x, int(n), c, gamma,
                            beta, eps, residual, relu, momentum, mean, var, running_mean, running_var, y, y2, ld2);
         OSN_LAUNCH_CHECK();
@@ -800,21 +794,13 @@ extern "C" int osn_bn_forward_train2(const float* x, int64_t n, int c, const flo
     }
     int rc = osn_bn_stats(x, n, c, mean, var, running_mean, running_var, momentum, ws, ws_bytes, stream);
     if (rc) return rc;
-    return osn_bn_apply2(x, mean, var, gamma, beta, eps, residual, relu, y, y2, ld2, n, c, stream);
+    return osn_bn_apply(x, mean, var, gamma, beta, eps, residual, relu, y, y2, ld2, n, c, stream);
 }
 
-extern "C" int osn_bn_forward_train(const float* x, int64_t n, int c, const float* gamma, const float* beta, float eps,
-                                    const float* residual, int relu, float momentum, float* mean, float* var,
-                                    float* running_mean, float* running_var, float* y, void* ws, size_t ws_bytes,
-                                    osn_stream_t stream) {
-    return osn_bn_forward_train2(x, n, c, gamma, beta, eps, residual, relu, momentum, mean, var, running_mean, running_var, y,
-                                 nullptr, 0, ws, ws_bytes, stream);
-}
-
-extern "C" int osn_bn_backward_multi2(const float* x, const float* y, const float* const* gy, const int64_t* gy_ld, int n_gy,
-                                      const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu,
-                                     int training, float* gx, float* gres, float* ggamma, float* gbeta, int64_t n, int c,
-                                     void* ws, size_t ws_bytes, osn_stream_t stream) {
+extern "C" int osn_bn_backward(const float* x, const float* y, const float* const* gy, const int64_t* gy_ld, int n_gy,
+                               const float* mean, const float* var, const float* gamma, const float* beta, float eps, int relu,
+                               int training, float* gx, float* gres, float* ggamma, float* gbeta, int64_t n, int c,
+                               void* ws, size_t ws_bytes, osn_stream_t stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     OSN_REQUIRE(n >= 1 && c >= 4 && (c & 3) == 0, OSN_E_ARG, "osn_bn_backward: need n >= 1 and c %% 4 == 0");
     OSN_REQUIRE(gy && gy_ld && n_gy >= 1 && n_gy <= BN_MAX_SRC, OSN_E_ARG,
@@ -822,7 +808,7 @@ extern "C" int osn_bn_backward_multi2(const float* x, const float* y, const floa
     // y == null with relu: the mask is recomputed from x (the forward expression, bit for bit) -- needs beta, and a batch
     // norm WITHOUT a residual (with one, y = relu(bn(x) + residual) cannot be rebuilt from x alone)
     OSN_REQUIRE(x && mean && var && gamma && gx && ggamma && gbeta && (!relu || y || beta), OSN_E_ARG,
-                "osn_bn_backward: null pointer");
+                "osn_bn_backward: null pointer (relu needs y, or beta to recompute the mask from x)");
     OSN_REQUIRE(!(relu && !y) || !gres, OSN_E_ARG, "osn_bn_backward: the ReLU mask can be recomputed from x only without a residual");
     OSN_REQUIRE(!beta || aligned16(beta), OSN_E_ARG, "osn_bn_backward: beta must be 16-byte aligned");
     OSN_REQUIRE(aligned16(x) && aligned16(gx) && aligned16(mean) && aligned16(var) && aligned16(gamma) &&
@@ -886,22 +872,4 @@ extern "C" int osn_bn_backward_multi2(const float* x, const float* y, const floa
                            gamma, eps, relu, training, gbeta, ggamma, 1.f / float(n), gx, gres, total4, c / 4, beta);
     OSN_LAUNCH_CHECK();
     return OSN_OK;
-}
-
-extern "C" int osn_bn_backward_multi(const float* x, const float* y, const float* const* gy, const int64_t* gy_ld, int n_gy,
-                                     const float* mean, const float* var, const float* gamma, float eps, int relu,
-                                     int training, float* gx, float* gres, float* ggamma, float* gbeta, int64_t n, int c,
-                                     void* ws, size_t ws_bytes, osn_stream_t stream) {
-    OSN_REQUIRE(!relu || y, OSN_E_ARG, "osn_bn_backward_multi: relu needs y (or osn_bn_backward_multi2 with beta)");
-    return osn_bn_backward_multi2(x, y, gy, gy_ld, n_gy, mean, var, gamma, nullptr, eps, relu, training, gx, gres, ggamma, gbeta, n, c,
-                                  ws, ws_bytes, stream);
-}
-
-extern "C" int osn_bn_backward(const float* x, const float* y, const float* gy, const float* mean, const float* var,
-                               const float* gamma, float eps, int relu, int training, float* gx, float* gres,
-                               float* ggamma, float* gbeta, int64_t n, int c, void* ws, size_t ws_bytes,
-                               osn_stream_t stream) {
-    const int64_t ld = c;
-    return osn_bn_backward_multi(x, y, &gy, &ld, 1, mean, var, gamma, eps, relu, training, gx, gres, ggamma, gbeta, n, c, ws,
-                                 ws_bytes, stream);
 }

@@ -188,9 +188,9 @@ extern "C" int osn_distill_loss_fwd(const float* out, const int64_t* sel, const 
     return OSN_OK;
 }
 
-extern "C" int osn_distill_loss_bwd_rows(const float* out, const float* target, const float* gloss, int64_t n, int64_t n_sel, int d,
-                                         int kind, float* gout, float* grows, const void* state, size_t state_bytes,
-                                         osn_stream_t stream) {
+extern "C" int osn_distill_loss_bwd(const float* out, const float* target, const float* gloss, int64_t n, int64_t n_sel, int d,
+                                    int kind, float* gout, float* grows, const void* state, size_t state_bytes,
+                                    osn_stream_t stream) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     OSN_REQUIRE(n >= 1 && n_sel >= 1 && n_sel <= n && d >= 4 && (d & 3) == 0 && (kind == 0 || kind == 1), OSN_E_ARG,
                 "osn_distill_loss_bwd: n=%lld n_sel=%lld d=%d kind=%d", (long long)n, (long long)n_sel, d, kind);
@@ -204,11 +204,6 @@ extern "C" int osn_distill_loss_bwd_rows(const float* out, const float* target, 
     else hipLaunchKernelGGL(loss_grad_kernel<1>, grid, dim3(256), 0, st, out, target, s.pos, s.stats, gloss, n, n_sel, d, gout, grows);
     OSN_LAUNCH_CHECK();
     return OSN_OK;
-}
-
-extern "C" int osn_distill_loss_bwd(const float* out, const float* target, const float* gloss, int64_t n, int64_t n_sel, int d,
-                                    int kind, float* gout, const void* state, size_t state_bytes, osn_stream_t stream) {
-    return osn_distill_loss_bwd_rows(out, target, gloss, n, n_sel, d, kind, gout, nullptr, state, state_bytes, stream);
 }
 
 // 0 = fine; bit 0: an index outside [0, n); bit 1: a row selected twice  (blocks until the forward pass has run)

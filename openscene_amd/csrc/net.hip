@@ -4,8 +4,8 @@
 // side compiles the module tree once into a linear program of stages (include/openscene_amd.h: osn_net_op) and this
 // file plays it -- per stage the same kernel choice the per-module path makes (stem / tile-list / split-bf16
 // output-stationary kernel; pair-array or table weight gradient), training-mode statistics kept for the backward
-// pass, gradient sums formed inside the batch-norm backward (osn_bn_backward_multi), ME.cat written in place by its
-// two producers (osn_bn_apply2).  Host-only code: no kernels here, only calls into the library's own entry points,
+// pass, gradient sums formed inside the batch-norm backward (osn_bn_backward), ME.cat written in place by its
+// two producers (osn_bn_apply).  Host-only code: no kernels here, only calls into the library's own entry points,
 // so results are those of the per-module path (same kernels, same order; only the gradient SUMS are associated
 // differently: (a + b) inside the consumer instead of a separate add).
 #include "common.h"
@@ -401,7 +401,7 @@ extern "C" int osn_net_forward(const osn_net_desc* net, const osn_net_run* run, 
             v = view_of(run->maps[o.map], o.transposed != 0);
         }
         // Inference: the stage's batch norm (+ residual) (+ ReLU) (+ cat store) in the epilogue of the convolution's last kernel
-        // (epilogue.h: bitwise the separate launch): the convolution writes y, the x buffer and the osn_bn_apply2 launch are skipped
+        // (epilogue.h: bitwise the separate launch): the convolution writes y, the x buffer and the osn_bn_apply launch are skipped
         Epi epi = epi_none();
         if (!run->training && o.bn >= 0 && !(run->flags & OSN_NET_RUN_NO_BN_EPILOGUE) && epi_fusable(L.fwd_k[i])) {
             const osn_net_bn& bn = run->bns[o.bn];
@@ -456,11 +456,11 @@ extern "C" int osn_net_forward(const osn_net_desc* net, const osn_net_run* run, 
         }
         if (run->training) {
             float* mv = reinterpret_cast<float*>(A + L.stat_off[i]);
-            rc = osn_bn_forward_train2(x, n_out, o.cout, bn.gamma, bn.beta, bn.eps, res, o.relu, bn.momentum, mv, mv + o.cout,
-                                       bn.running_mean, bn.running_var, y, y2, ld2, r->ws, size_t(r->ws_bytes), sstream);
+            rc = osn_bn_forward_train(x, n_out, o.cout, bn.gamma, bn.beta, bn.eps, res, o.relu, bn.momentum, mv, mv + o.cout,
+                                      bn.running_mean, bn.running_var, y, y2, ld2, r->ws, size_t(r->ws_bytes), sstream);
         } else {
             OSN_REQUIRE(bn.running_mean && bn.running_var, OSN_E_ARG, "osn_net_forward: op %d: evaluation-mode batch norm without running statistics", i);
-            rc = osn_bn_apply2(x, bn.running_mean, bn.running_var, bn.gamma, bn.beta, bn.eps, res, o.relu, y, y2, ld2, n_out, o.cout, sstream);
+            rc = osn_bn_apply(x, bn.running_mean, bn.running_var, bn.gamma, bn.beta, bn.eps, res, o.relu, y, y2, ld2, n_out, o.cout, sstream);
         }
         if (rc) return rc;
         if (on_side) {
@@ -545,9 +545,9 @@ extern "C" int osn_net_backward(const osn_net_desc* net, const osn_net_run* run,
             OSN_REQUIRE(bn.ggamma && bn.gbeta, OSN_E_ARG, "osn_net_backward: op %d: null batch-norm gradient pointers", i);
             // bn -> relu without a residual: the mask is recomputed from x, y is not read (one tensor less per backward kernel)
             const bool from_x = o.relu && o.res < 0 && bn.beta;
-            rc = osn_bn_backward_multi2(x, from_x ? nullptr : y, gsrc, gld, ng, mean, var, bn.gamma, from_x ? bn.beta : nullptr, bn.eps,
-                                        o.relu, run->training, gxw, gres, bn.ggamma, bn.gbeta, n_out, o.cout, r->ws, size_t(r->ws_bytes),
-                                        sstream);
+            rc = osn_bn_backward(x, from_x ? nullptr : y, gsrc, gld, ng, mean, var, bn.gamma, from_x ? bn.beta : nullptr, bn.eps,
+                                 o.relu, run->training, gxw, gres, bn.ggamma, bn.gbeta, n_out, o.cout, r->ws, size_t(r->ws_bytes),
+                                 sstream);
             if (rc) return rc;
             gx = gxw;
         } else {

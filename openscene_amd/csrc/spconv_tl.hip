@@ -823,15 +823,7 @@ int osn::spconv_fwd_tl_epi(const float* in, int64_t n_in, const void* Wp, const 
 
 extern "C" int osn_spconv_fwd_tl(const float* in, int64_t n_in, const void* Wp, const void* tl, const int32_t* out_rows,
                                  float* out, double* bn_partial, int64_t n_out, int K, int cin, int cout, int bm, void* ws,
-                                 size_t ws_bytes, osn_stream_t stream) {
-    return spconv_fwd_tl_impl(in, n_in, Wp, tl, out_rows, out, bn_partial, n_out, K, cin, cout, bm, ws, ws_bytes, nullptr, nullptr,
-                              stream);
-}
-
-extern "C" int osn_spconv_fwd_tl_pc(const float* in, int64_t n_in, const void* Wp, const void* tl, const int32_t* out_rows,
-                                    float* out, double* bn_partial, int64_t n_out, int K, int cin, int cout, int bm, void* ws,
-                                    size_t ws_bytes, int32_t* counters, osn_stream_t stream) {
-    OSN_REQUIRE(counters, OSN_E_ARG, "osn_spconv_fwd_tl_pc: null counters (128 int32, zero before the first call)");
+                                 size_t ws_bytes, int32_t* counters, osn_stream_t stream) {
     return spconv_fwd_tl_impl(in, n_in, Wp, tl, out_rows, out, bn_partial, n_out, K, cin, cout, bm, ws, ws_bytes, counters, nullptr,
                               stream);
 }

@@ -59,9 +59,9 @@ class _DistillLoss(Function):
         # does not catch, the losing copy's row would be uninitialised memory multiplied into the head's gradients)
         grows = torch.zeros((n_sel, d), dtype=torch.float32, device=dev) if ROWS_HINT and n_sel < n else None
         with ops._Dev(dev):
-            check(lib.osn_distill_loss_bwd_rows(ops._p(out), ops._p(target), ops._p(gloss), n, n_sel, d, kind, ops._p(gout),
-                                                ops._p(grows), ops._p(state), state.numel(), ops._stream(dev)),
-                  "osn_distill_loss_bwd_rows")
+            check(lib.osn_distill_loss_bwd(ops._p(out), ops._p(target), ops._p(gloss), n, n_sel, d, kind, ops._p(gout),
+                                           ops._p(grows), ops._p(state), state.numel(), ops._stream(dev)),
+                  "osn_distill_loss_bwd")
         if grows is not None:
             gout._osn_rows = {"ptr": gout.data_ptr(), "shape": tuple(gout.shape), "idx": ctx.sel, "rows": grows,
                               "pos_ptr": state.data_ptr(), "state": state, "version": gout._version}

@@ -114,14 +114,7 @@ _ws_pool = {}
 
 
 def _ws(nbytes, dev):
-    nbytes = max(int(nbytes), 16)
-    i = _idx(dev)
-    key = (i, _stream(dev))
-    buf = _ws_pool.get(key)
-    if buf is None or buf.numel() < nbytes:
-        buf = torch.empty(int(nbytes * 1.25) + 4096, dtype=torch.uint8, device=dev)
-        _ws_pool[key] = buf
-    return buf
+    return ws_on(nbytes, dev, _stream(dev))
 
 
 def ws_on(nbytes, dev, raw_stream):
@@ -681,17 +674,13 @@ def spconv_fwd_tl(feats, wp, tl, n_out, K, cout, bn_partial=None):
     out = torch.empty((n_out, cout), dtype=torch.float32, device=dev)
     ws = _ws(_cached("osn_spconv_fwd_tl_ws_bytes", n_out, K if tl is not None else 1, cout, bm), dev)
     tok = _prof_start("spconv_fwd_tl", dev, n_in=feats.shape[0], n_out=n_out, K=K, cin=cin, cout=cout)
-    st = _stream(dev)
-    ck = (_idx(dev), st)
-    counters = _tl_counters.get(ck)
-    if counters is None:                # 128 tile counters per (device, stream), zero once: the kernel leaves them zero
-        counters = _tl_counters[ck] = torch.zeros(128, dtype=torch.int32, device=dev)
+    counters = tl_counters(dev)
     with _Dev(dev):
         try:
-            check(lib.osn_spconv_fwd_tl_pc(_p(feats), feats.shape[0], _p(wp), _p(buf), _p(rows), _p(out), _p(bn_partial), n_out,
-                                           K, cin, cout, bm, _p(ws), ws.numel(), _p(counters), st), "osn_spconv_fwd_tl_pc")
+            check(lib.osn_spconv_fwd_tl(_p(feats), feats.shape[0], _p(wp), _p(buf), _p(rows), _p(out), _p(bn_partial), n_out,
+                                        K, cin, cout, bm, _p(ws), ws.numel(), _p(counters), _stream(dev)), "osn_spconv_fwd_tl")
         except Exception:
-            _tl_counters.pop(ck, None)      # a failed launch leaves the counters undefined: start from a fresh zero buffer
+            _tl_counters.pop((_idx(dev), _stream(dev)), None)   # a failed launch leaves the counters undefined: start from a fresh zero buffer
             raise
     if tok is not None:
         _profiler.stop(tok)
@@ -997,30 +986,44 @@ def _bn_fwd_args(x, residual):
     return x, residual, x.shape[0], x.shape[1]
 
 
-def bn_apply(x, mean, var, gamma, beta, eps, residual=None, relu=False):
+def bn_apply(x, mean, var, gamma, beta, eps, residual=None, relu=False, y2=None, out=None):
+    """y2: a second destination (a [n, c] column window of a wider matrix: ME.cat written in place by its producer), or None.
+    out: a caller's destination (contiguous float32 shaped like x; x itself normalises in place: every element is read before it
+    is written), or None for a new tensor.  -> y"""
     dev = x.device
     lib = _prep(dev)
     x, residual, n, c = _bn_fwd_args(x, residual)
-    y = torch.empty_like(x)
+    if out is not None and (out.dtype != torch.float32 or out.shape != x.shape or out.device != dev or not out.is_contiguous()):
+        raise ValueError("out must be a contiguous float32 tensor shaped like x, on its device")
+    p2, ld2 = _row_view(y2, c, "y2") if y2 is not None else (None, 0)
+    y = out if out is not None else torch.empty_like(x)
     with _Dev(dev):
         check(lib.osn_bn_apply(_p(x), _p(mean), _p(var), _p(gamma), _p(beta), float(eps), _p(residual), int(bool(relu)),
-                               _p(y), n, c, _stream(dev)), "osn_bn_apply")
+                               _p(y), p2, ld2, n, c, _stream(dev)), "osn_bn_apply")
     return y
 
 
-def bn_forward_train(x, gamma, beta, eps, residual, relu, running_mean, running_var, momentum):
-    """(y, mean, var): batch statistics (running buffers updated in place) + normalise (+ residual) (+ ReLU), one C call."""
+def bn_forward_train(x, gamma, beta, eps, residual, relu, running_mean, running_var, momentum, y2=None):
+    """(y, mean, var): batch statistics (running buffers updated in place) + normalise (+ residual) (+ ReLU), one C call.
+    y2: a second destination as in bn_apply, or None."""
     dev = x.device
     lib = _prep(dev)
     x, residual, n, c = _bn_fwd_args(x, residual)
+    p2, ld2 = _row_view(y2, c, "y2") if y2 is not None else (None, 0)
     mv = torch.empty((2, c), dtype=torch.float32, device=dev)
     y = torch.empty_like(x)
     ws = _ws(_cached("osn_bn_ws_bytes", n, c), dev)
     with _Dev(dev):
         check(lib.osn_bn_forward_train(_p(x), n, c, _p(gamma), _p(beta), float(eps), _p(residual), int(bool(relu)),
-                                       float(momentum), _p(mv[0]), _p(mv[1]), _p(running_mean), _p(running_var), _p(y),
+                                       float(momentum), _p(mv[0]), _p(mv[1]), _p(running_mean), _p(running_var), _p(y), p2, ld2,
                                        _p(ws), ws.numel(), _stream(dev)), "osn_bn_forward_train")
     return y, mv[0], mv[1]
+
+
+# The names these two had while y2 / out were separate wrappers (the C entries behind them are gone): same functions, same
+# argument order, so that code written against them keeps running.  New code uses the plain names.
+bn_apply2 = bn_apply
+bn_forward_train2 = bn_forward_train
 
 
 def bn_backward(x, y, gy, mean, var, gamma, eps, relu, training, want_gres, beta=None):
@@ -1038,28 +1041,11 @@ def _row_view(t, c, name):
     return t.data_ptr(), ld
 
 
-def bn_forward_train2(x, gamma, beta, eps, residual, relu, running_mean, running_var, momentum, y2):
-    """bn_forward_train that ALSO stores the result into `y2`, a [n, c] column window of a wider matrix (ME.cat written in
-    place by its producer).  -> (y, mean, var)."""
-    dev = x.device
-    lib = _prep(dev)
-    x, residual, n, c = _bn_fwd_args(x, residual)
-    p2, ld2 = _row_view(y2, c, "y2")
-    mv = torch.empty((2, c), dtype=torch.float32, device=dev)
-    y = torch.empty_like(x)
-    ws = _ws(_cached("osn_bn_ws_bytes", n, c), dev)
-    with _Dev(dev):
-        check(lib.osn_bn_forward_train2(_p(x), n, c, _p(gamma), _p(beta), float(eps), _p(residual), int(bool(relu)),
-                                        float(momentum), _p(mv[0]), _p(mv[1]), _p(running_mean), _p(running_var), _p(y), p2, ld2,
-                                        _p(ws), ws.numel(), _stream(dev)), "osn_bn_forward_train2")
-    return y, mv[0], mv[1]
-
-
 def bn_backward_multi(x, y, gys, mean, var, gamma, eps, relu, training, want_gres, beta=None, gres_out=None):
     """bn_backward whose incoming gradient is the SUM of the matrices in `gys` (1 .. 3, each possibly a column window of a
     wider matrix): the sum is formed while reading.  y None with relu needs beta (mask recomputed from x; no residual).
     gres_out: a contiguous float32 [n, c] destination for gres (with want_gres) instead of a new tensor; it may be one of the
-    contiguous sources itself (include/openscene_amd.h, osn_bn_backward_multi2: the aliasing rule)."""
+    contiguous sources itself (include/openscene_amd.h, osn_bn_backward: the aliasing rule)."""
     dev = x.device
     lib = _prep(dev)
     n, c = x.shape
@@ -1077,27 +1063,11 @@ def bn_backward_multi(x, y, gys, mean, var, gamma, eps, relu, training, want_gre
     gbeta = torch.empty(c, dtype=torch.float32, device=dev)
     ws = _ws(_cached("osn_bn_ws_bytes", n, c), dev)
     with _Dev(dev):
-        check(lib.osn_bn_backward_multi2(_p(x), _p(y), ptrs, lds, len(views), _p(mean), _p(var), _p(gamma),
-                                         _p(beta) if (relu and y is None) else None, float(eps),
-                                         int(bool(relu)), int(bool(training)), _p(gx), _p(gres), _p(ggamma), _p(gbeta), n, c,
-                                         _p(ws), ws.numel(), _stream(dev)), "osn_bn_backward_multi2")
+        check(lib.osn_bn_backward(_p(x), _p(y), ptrs, lds, len(views), _p(mean), _p(var), _p(gamma),
+                                  _p(beta) if (relu and y is None) else None, float(eps),
+                                  int(bool(relu)), int(bool(training)), _p(gx), _p(gres), _p(ggamma), _p(gbeta), n, c,
+                                  _p(ws), ws.numel(), _stream(dev)), "osn_bn_backward")
     return gx, gres, ggamma, gbeta
-
-
-def bn_apply2(x, mean, var, gamma, beta, eps, residual=None, relu=False, y2=None, out=None):
-    """bn_apply with the second destination `y2` (a [n, c] column window of a wider matrix, or None) and a caller's destination
-    `out` (contiguous float32 shaped like x; x itself normalises in place: every element is read before it is written).  -> y"""
-    dev = x.device
-    lib = _prep(dev)
-    x, residual, n, c = _bn_fwd_args(x, residual)
-    if out is not None and (out.dtype != torch.float32 or out.shape != x.shape or out.device != dev or not out.is_contiguous()):
-        raise ValueError("out must be a contiguous float32 tensor shaped like x, on its device")
-    p2, ld2 = _row_view(y2, c, "y2") if y2 is not None else (None, 0)
-    y = out if out is not None else torch.empty_like(x)
-    with _Dev(dev):
-        check(lib.osn_bn_apply2(_p(x), _p(mean), _p(var), _p(gamma), _p(beta), float(eps), _p(residual), int(bool(relu)),
-                                _p(y), p2, ld2, n, c, _stream(dev)), "osn_bn_apply2")
-    return y
 
 
 def bn_apply_plan(total4, c4):

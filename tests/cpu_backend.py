@@ -345,16 +345,24 @@ def bn_stats(x, running_mean=None, running_var=None, momentum=0.1):
     return mean, var
 
 
-def bn_forward_train(x, gamma, beta, eps, residual, relu, running_mean, running_var, momentum):
+def bn_forward_train(x, gamma, beta, eps, residual, relu, running_mean, running_var, momentum, y2=None):
     mean, var = bn_stats(x, running_mean, running_var, momentum)
-    return bn_apply(x, mean, var, gamma, beta, eps, residual, relu), mean, var
+    return bn_apply(x, mean, var, gamma, beta, eps, residual, relu, y2=y2), mean, var
 
 
-def bn_apply(x, mean, var, gamma, beta, eps, residual=None, relu=False):
+def bn_apply(x, mean, var, gamma, beta, eps, residual=None, relu=False, y2=None, out=None):
+    """y2: a second destination (a column window of a wider matrix); out: the caller's own destination (may be x itself)."""
     y = (x - mean) * torch.rsqrt(var + eps) * gamma + beta
     if residual is not None:
         y = y + residual
-    return F.relu(y) if relu else y
+    if relu:
+        y = F.relu(y)
+    with torch.no_grad():
+        if y2 is not None:
+            y2.copy_(y)
+        if out is not None:
+            y = out.copy_(y)
+    return y
 
 
 def bn_backward(x, y, gy, mean, var, gamma, eps, relu, training, want_gres, beta=None):

@@ -62,7 +62,7 @@ class OnDevice:
         x = self.x if x is None else x
         rm, rv = self.rm.clone(), self.rv.clone()
         a = (x, self.gamma, self.beta, bb.EPS, self.residual(config), config != "plain", rm, rv, bb.MOMENTUM)
-        y, mean, var = ops.bn_forward_train(*a) if window is None else ops.bn_forward_train2(*a, window)
+        y, mean, var = ops.bn_forward_train(*a, y2=window)
         return dict(y=y, mean=mean, var=var, rm=rm, rv=rv)
 
 

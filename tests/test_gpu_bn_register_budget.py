@@ -3,7 +3,7 @@ each with a row loop for one gradient source and one for up to three; the sums t
 weight-stationary reduction that keeps nine of its K quads in flight (csrc/spconv_ws.hip) -- the kernels sized to the registers the
 weight gradients leave on a SIMD.
 
-Batch norm: osn_bn_backward_multi2 against the same call under osn_bn_set_flat_kernels(1) (the one-row loop of the earlier rounds, every
+Batch norm: osn_bn_backward against the same call under osn_bn_set_flat_kernels(1) (the one-row loop of the earlier rounds, every
 operand a run-time choice), bit for bit in gx, gres, ggamma and gbeta.
   rows     1, 15, 16, 17, 31, 32, 33, 209: fewer rows than the 16 row lanes, 16 R and 16 R + 1 for R = 1 and 2 rows in flight (the
            sums without a gres store keep one, those with it two), one below 32, and 209 = several rounds and a ragged one

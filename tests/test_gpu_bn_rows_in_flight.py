@@ -176,7 +176,7 @@ def test_new_kernels_give_the_bits_of_the_earlier_ones(n, c):
                     a, b = rm.clone(), rv.clone()
                     if two:
                         w = second()
-                        y, mean, var = ops.bn_forward_train2(x, gamma, beta, bb.EPS, r, relu, a, b, bb.MOMENTUM, w[:, 4:4 + c])
+                        y, mean, var = ops.bn_forward_train(x, gamma, beta, bb.EPS, r, relu, a, b, bb.MOMENTUM, y2=w[:, 4:4 + c])
                         assert torch.equal(_bits(w[:, 4:4 + c]), _bits(y)), label + ": the second store is not y"
                         return y, w, mean, var, a, b
                     y, mean, var = ops.bn_forward_train(x, gamma, beta, bb.EPS, r, relu, a, b, bb.MOMENTUM)
@@ -184,7 +184,7 @@ def test_new_kernels_give_the_bits_of_the_earlier_ones(n, c):
 
                 def evaluate():
                     w = second() if two else None
-                    y = ops.bn_apply2(x, rm, rv, gamma, beta, bb.EPS, r if r is None else res_eval, relu, y2=w[:, 4:4 + c] if two else None)
+                    y = ops.bn_apply(x, rm, rv, gamma, beta, bb.EPS, r if r is None else res_eval, relu, y2=w[:, 4:4 + c] if two else None)
                     return y, w
                 _three_runs(ops, FWD_NAMES, train, label + ", training", digest)
                 ev = _three_runs(ops, FWD_NAMES[:2], evaluate, label + ", evaluation", digest)
@@ -192,7 +192,7 @@ def test_new_kernels_give_the_bits_of_the_earlier_ones(n, c):
                     assert torch.equal(_bits(ev[1][:, 4:4 + c]), _bits(ev[0])) and bool((ev[1][:, :4] == 7.0).all()) and bool((ev[1][:, 4 + c:] == 7.0).all())
                 if not two:                       # y in place on x: the bits of the call with a y of its own
                     xin = x.clone()
-                    out = ops.bn_apply2(xin, rm, rv, gamma, beta, bb.EPS, r if r is None else res_eval, relu, out=xin)
+                    out = ops.bn_apply(xin, rm, rv, gamma, beta, bb.EPS, r if r is None else res_eval, relu, out=xin)
                     assert out.data_ptr() == xin.data_ptr()
                     _feed(digest, out)
                     _same(("y",), (ev[0],), (out,), label + ", evaluation in place on x")

@@ -26,8 +26,8 @@ def rel(got, ref):
 # ------------------------------------------------------------------ the executor's batch-norm entry points
 @pytest.mark.parametrize("n,c,nsrc", [(700, 256, 3), (3052, 128, 2), (4096, 32, 1), (4097, 32, 3), (47618, 96, 3), (20000, 64, 2)])
 def test_batchnorm_summed_gradient_sources_and_second_destination(n, c, nsrc):
-    """osn_bn_forward_train2 (the result also lands in a column window of a wider matrix: ME.cat in place) and
-    osn_bn_backward_multi (incoming gradient = sum of up to three matrices, column windows included), on both sides of
+    """osn_bn_forward_train with y2 (the result also lands in a column window of a wider matrix: ME.cat in place) and
+    osn_bn_backward (incoming gradient = sum of up to three matrices, column windows included), on both sides of
     the 4096-row switch between the single-launch and the three-launch kernels, vs float64 torch."""
     from openscene_amd import ops
     g = torch.Generator().manual_seed(n + c + nsrc)
@@ -46,7 +46,7 @@ def test_batchnorm_summed_gradient_sources_and_second_destination(n, c, nsrc):
     y_ref.backward(sum(t.double() for t in srcs))
     rm = torch.zeros(c, device=d); rv = torch.ones(c, device=d)
     cat = torch.full((n, c + 40), -7.0, device=d)
-    y, mean, var = ops.bn_forward_train2(x.to(d), gamma.to(d), beta.to(d), 1e-5, res.to(d), True, rm, rv, 0.1, cat[:, 16:16 + c])
+    y, mean, var = ops.bn_forward_train(x.to(d), gamma.to(d), beta.to(d), 1e-5, res.to(d), True, rm, rv, 0.1, y2=cat[:, 16:16 + c])
     assert rel(y, y_ref) < 2e-5
     assert torch.equal(cat[:, 16:16 + c], y) and bool((cat[:, :16] == -7).all()) and bool((cat[:, 16 + c:] == -7).all())
     assert rel(rm, bn.running_mean) < 1e-5 and rel(rv, bn.running_var) < 1e-5

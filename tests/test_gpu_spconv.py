@@ -563,7 +563,7 @@ def test_weight_image_cache_batches_and_follows_the_parameter_version():
 
 
 def test_tile_list_conv_leaves_its_persistent_counters_zero():
-    """osn_spconv_fwd_tl_pc: caller-owned tile counters, zero before the first call and put back to zero by the last
+    """osn_spconv_fwd_tl with counters: caller-owned tile counters, zero before the first call and put back to zero by the last
     workgroup of every launch (no memset per call): many launches of different shapes in a row stay correct and
     bitwise repeatable, and the counters read zero afterwards."""
     from openscene_amd import ops
@@ -587,3 +587,45 @@ def test_tile_list_conv_leaves_its_persistent_counters_zero():
                 assert torch.equal(out, outs[[(32, 32), (96, 128), (64, 20)].index((cin, cout))])
     torch.cuda.synchronize()
     assert ops._tl_counters and all(int(c.abs().sum()) == 0 for c in ops._tl_counters.values())
+
+
+def _first_table(lib, cout, header_only):
+    """The smallest table (rows) of a 27-offset conv whose workspace is the 512-byte header alone / holds partial tiles."""
+    for n in range(1, 1 << 16):
+        if (lib.osn_spconv_fwd_tl_ws_bytes(n, 27, cout, lib.osn_tile_rows(n)) == 512) == header_only:
+            return n
+    raise AssertionError("no such table below 65536 rows")
+
+
+# 32 -> 32, and 32 -> 256: tl_waves(256) = 4 waves of 32 columns per workgroup, so two column groups (two tile counters)
+@pytest.mark.parametrize("cout", [32, 256])
+def test_tile_list_conv_without_persistent_counters(cout):
+    """osn_spconv_fwd_tl with counters == NULL (the half of the entry the wrappers never take): the tile counters are the head of
+    the workspace and the call zeroes them itself.  On the smallest table that runs as a split launch (partial tiles in the
+    workspace), on the smallest that runs whole (the 512-byte head alone) and on the table one row below that one (split, many
+    tiles), two calls in a row on the SAME workspace -- poisoned before the first, left dirty by it before the second -- each give
+    bit for bit what ops.spconv_fwd_tl gives with its persistent counters.  A missing zeroing of the head, or a second call that
+    reads stale counters, shows here."""
+    from openscene_amd import _lib, ops
+    lib = _lib.load()
+    full = torch.from_numpy(cloud("big").kmap(1, 1, 3)).to(dev())
+    K, n_in, cin = full.shape[0], full.shape[1], 32
+    assert K == 27
+    x = torch.randn(n_in, cin, generator=torch.Generator().manual_seed(5)).to(dev())
+    w = (torch.randn(K, cin, cout, generator=torch.Generator().manual_seed(cout)) * 0.1).to(dev())
+    wf, _ = ops.weight_prep_tl(w, want_dgrad=False)
+    first_whole = _first_table(lib, cout, True)
+    # (one row below the first table that runs whole: still split, now with hundreds of tiles)
+    for n_out, header_only in ((_first_table(lib, cout, False), False), (first_whole - 1, False), (first_whole, True)):
+        assert n_out <= n_in
+        tl = ops.tile_lists(full[:, :n_out].contiguous())          # the first n_out rows of a real table: every entry < n_in
+        need = lib.osn_spconv_fwd_tl_ws_bytes(n_out, K, cout, tl.bm)
+        assert (need == 512) == header_only
+        ref = ops.spconv_fwd_tl(x, wf, tl, n_out, K, cout)
+        ws = torch.full((need,), 0xFF, dtype=torch.uint8, device=dev())
+        for call in range(2):
+            out = torch.full((n_out, cout), float("nan"), device=dev())
+            with ops._Dev(dev()):
+                _lib.check(lib.osn_spconv_fwd_tl(ops._p(x), n_in, ops._p(wf), ops._p(tl.buf), None, ops._p(out), None, n_out, K, cin, cout,
+                                                 tl.bm, ops._p(ws), need, None, ops._stream(dev())), "osn_spconv_fwd_tl")
+            assert torch.equal(out.view(torch.int32), ref.view(torch.int32)), (cout, n_out, "call %d" % call)

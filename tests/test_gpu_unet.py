@@ -406,7 +406,7 @@ def test_inference_bn_epilogue_is_bitwise_the_separate_launches(arch, n_pts, vox
     """Round 6: in an inference pass every stage's evaluation-mode batch norm (+ residual, ReLU, cat store) runs in the epilogue of the
     kernel that finishes the stage's convolution (csrc/epilogue.h) -- tile-list (single and split launches), weight-stationary (reduce and
     direct), register-gather, 1x1 and stem kernels.  Same expression, same order: outputs and feature taps bitwise equal to the pass with
-    the separate osn_bn_apply2 launches (OSN_NET_RUN_NO_BN_EPILOGUE), which test_executor_equals_the_module_path ties to the module path."""
+    the separate osn_bn_apply launches (OSN_NET_RUN_NO_BN_EPILOGUE), which test_executor_equals_the_module_path ties to the module path."""
     from openscene_amd import executor
     from openscene_amd.mink_unet import mink_unet
     from openscene_amd.sparse import SparseTensor

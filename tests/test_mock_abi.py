@@ -91,11 +91,11 @@ def test_training_step_runs_through_the_real_wrappers(mock_ops):
     assert (n_conv, n_bn) == (49, 48)                 # MinkUNet18A (a9 / a10)
     # one forward launch per conv, one input gradient each except the stem (its input needs none), one weight
     # gradient each; three BN calls per BatchNorm; at most one weight-prep launch per conv
-    n_fwd = c.get("osn_spconv_fwd", 0) + c.get("osn_spconv_fwd_x6", 0) + c.get("osn_spconv_fwd_tl", 0) + c.get("osn_spconv_fwd_tl_pc", 0) + c.get("osn_stem_conv_fwd", 0) + c.get("osn_spconv_fwd_ws", 0) + c.get("osn_dense_fwd", 0)
+    n_fwd = c.get("osn_spconv_fwd", 0) + c.get("osn_spconv_fwd_x6", 0) + c.get("osn_spconv_fwd_tl", 0) + c.get("osn_stem_conv_fwd", 0) + c.get("osn_spconv_fwd_ws", 0) + c.get("osn_dense_fwd", 0)
     assert n_fwd == 2 * n_conv - 1, c
     assert c.get("osn_spconv_wgrad", 0) + c.get("osn_spconv_wgrad_tl", 0) + c.get("osn_stem_conv_wgrad", 0) == n_conv, c
     assert c.get("osn_pair_lists_build", 0) <= 10, c            # pair arrays: once per map, not per conv
-    assert c["osn_bn_forward_train"] == n_bn and c["osn_bn_backward_multi2"] == n_bn, c  # one C call per BN and direction
+    assert c["osn_bn_forward_train"] == n_bn and c["osn_bn_backward"] == n_bn, c  # one C call per BN and direction
     # weight images of parameters: served from the per-device cache, refreshed by ONE batched launch per optimizer step
     # (this is the second step: every image exists, every parameter version has changed once)
     assert c.get("osn_weight_prep_x6_pair", 0) + c.get("osn_weight_prep_x6", 0) + c.get("osn_weight_prep_tl", 0) == 0, c
@@ -134,14 +134,15 @@ def test_loader_and_query_wrappers_run(mock_ops):
     assert mock_ops["osn_feature_remap"] == 1 and mock_ops["osn_batch_coords"] == 1
 
 
-def test_bn_forward_train2_rejects_a_residual_of_another_shape(mock_ops):
+def test_bn_forward_train_rejects_a_residual_of_another_shape(mock_ops):
     """A short residual must not reach the kernel (it would be read out of range): ValueError before any C call."""
     from openscene_amd import ops
     x, w = torch.randn(40, 8), torch.zeros(40, 24)
     gamma, beta, rm, rv = torch.ones(8), torch.zeros(8), torch.zeros(8), torch.ones(8)
     mock_ops.clear()
     with pytest.raises(ValueError):
-        ops.bn_forward_train2(x, gamma, beta, 1e-5, torch.randn(39, 8), True, rm, rv, 0.1, w[:, 4:12])
+        ops.bn_forward_train(x, gamma, beta, 1e-5, torch.randn(39, 8), True, rm, rv, 0.1, y2=w[:, 4:12])
     assert not mock_ops, dict(mock_ops)
-    ops.bn_forward_train2(x, gamma, beta, 1e-5, torch.randn(40, 8), True, rm, rv, 0.1, w[:, 4:12])
-    assert mock_ops.get("osn_bn_forward_train2") == 1, dict(mock_ops)      # (a residual of x's shape goes through)
+    ops.bn_forward_train(x, gamma, beta, 1e-5, torch.randn(40, 8), True, rm, rv, 0.1, y2=w[:, 4:12])
+    assert mock_ops.get("osn_bn_forward_train") == 1, dict(mock_ops)       # (a residual of x's shape goes through)
+    assert ops.bn_forward_train2 is ops.bn_forward_train and ops.bn_apply2 is ops.bn_apply      # the earlier names: the same functions

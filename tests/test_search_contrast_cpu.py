@@ -138,4 +138,4 @@ def test_contrast_entries_argument_errors(fp8):
         assert name in _lib.last_error()
     rc = call(ws_bytes=need - 1)
     assert rc not in (0, -1) and "workspace" in _lib.last_error()
-    assert h.osn_version() == 2
+    assert h.osn_version() == 3

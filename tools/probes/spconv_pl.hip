@@ -345,7 +345,7 @@ extern "C" int osn_dbg_split_planes(const float* in, int64_t n, int c, void* pla
     return OSN_OK;
 }
 
-// The tile-list convolution on pre-split planes.  Same tile lists, weight image, counters and output as osn_spconv_fwd_tl_pc; cin must be
+// The tile-list convolution on pre-split planes.  Same tile lists, weight image, counters and output as osn_spconv_fwd_tl; cin must be
 // a multiple of 32 with a k-step count the chunking divides (every MinkUNet width), cout a multiple of 32 up to 128 per column group.
 extern "C" int osn_dbg_spconv_fwd_pl(const void* planes, int64_t n_in, const void* Wp, const void* tl, const int32_t* out_rows, float* out,
                                  double* bn_partial, int64_t n_out, int K, int cin, int cout, int bm, int32_t* counters, int occ,

@@ -368,7 +368,7 @@ __global__ __launch_bounds__(64 * (NW + NP)) __attribute__((amdgpu_waves_per_eu(
 
 using namespace osn;
 
-// Same tile lists, weight image, counters and output as osn_spconv_fwd_tl_pc (full channel chunks, feature matrix below 2 GB, no
+// Same tile lists, weight image, counters and output as osn_spconv_fwd_tl (full channel chunks, feature matrix below 2 GB, no
 // offset split).  variant: ring slots R (2 / 3) | gather depth GD (1 / 2) << 4.
 extern "C" int osn_dbg_spconv_fwd_tr(const float* in, int64_t n_in, const void* Wp, const void* tl, const int32_t* out_rows, float* out,
                                      int64_t n_out, int K, int cin, int cout, int bm, int32_t* counters, int variant, int wgs_per_cu,
