@@ -859,6 +859,62 @@ int osn_regions_records(const int32_t* voxel_region, int64_t n_voxels, int64_t n
                         int64_t* n_voxels_out, int64_t* vox_sum, float* box_min, float* box_max, int32_t* scene,
                         int32_t* err, osn_stream_t stream);
 
+/* ---- merge regions by mean feature: region adjacency and star contraction (csrc/merge.hip) ----------------------- *
+ * Single linkage joins the two ends of a chain of pairwise similar voxels however different they are.  The second stage
+ * over-segments with a strict threshold and then merges ADJACENT regions whose mean features agree; the mean of a grown
+ * region does not drift along a chain.  The loop is openscene_amd/merge.py; these are the kernels of one round.  All
+ * calls OR their error bits into the regions err word (above: 1, 2, 4) and add 8 = a pair end outside [0, n_regions).
+ * Bad entries are skipped, never dereferenced.  All are asynchronous; only osn_merge_round needs a workspace.
+ *
+ * Contacts.  voxel_region int32 [n_voxels] with values in -1 .. n_regions - 1, nbr int32 [27, n_voxels].  A contact is a
+ *   voxel pair (v, u = nbr[k_i, v]) over the offsets below the centre (13, or the 3 faces k = 4, 10, 12 for connectivity
+ *   6, as in osn_regions_edges) with u a valid row and both regions >= 0 and different.  Voxels of region -1 touch
+ *   nothing; scenes never touch, because the table holds no such neighbours.  The adjacency list is the sorted distinct
+ *   pairs (lo < hi) with their contact counts.
+ * osn_merge_contacts: key int64 [n_off, n_voxels] = lo << 32 | hi of the contact of (i, v), or -1 where there is none.
+ *   u >= n_voxels ORs bit 1, a region entry outside [-1, n_regions) bit 4; both give -1.  Compaction, sorting and
+ *   counting the distinct keys are the caller's (torch.unique).
+ *
+ * Region rows.  S float32 [R, d] starts as the pool kernel's sums of the regions (osn_bank_pool*, either bank kind); the
+ *   unit rows of a round are X = where(n > 0, S / n, 0) rounded to fp16, n = ||S|| per row, formed by the caller.
+ * osn_rows_pair_dot (the hot path): rows fp16 [n_rows, d] (16-byte aligned), d % 8 == 0, 8 <= d <= OSN_BANK_POOL_MAX_DIM;
+ *   lo, hi int32 [n_pairs]; n_pairs < 2^32 - 1.
+ *       sim[e] = sum over c of float(rows[lo[e], c]) * float(rows[hi[e], c]),  accumulated in fp32
+ *   with the lane layout and the order of additions of osn_regions_edges (one shared body, csrc/rowdot.h: a lane adds the
+ *   products of its 16-byte vectors in element order, then an xor butterfly over the lanes): for the same two rows the
+ *   two entries give the same bits, whichever is lo.  An end outside [0, n_rows) gives -inf and ORs bit 8; a NaN in
+ *   either row gives NaN.  A wave takes a fixed run of consecutive pairs, so a row with thousands of partners costs no
+ *   more per pair than any other.  No LDS, no floating-point atomics: two calls give the same bits.
+ *
+ * A round.  The caller lists the pairs with contacts >= min_contact in ascending (lo, hi) order; e is the index.  An
+ *   edge is eligible iff sim[e] >= threshold (a float32 comparison; threshold finite; NaN and -inf never pass); a pair
+ *   with lo == hi is ignored.  Its key is (order-preserving uint32 of sim[e]) << 32 | (0xFFFFFFFF - e), the same from
+ *   both ends: greater similarity wins, then the lower edge index; -0 orders below +0.  best[a] is the greatest key
+ *   among a's eligible edges (a 64-bit integer atomic maximum: independent of scheduling).  An edge is mutual when both
+ *   ends name it as their best.  Region a with best edge (a, b) is united with b iff that edge is mutual or b's best
+ *   edge is mutual -- a mutual pair plus the regions that point at it, a star.  The globally greatest eligible key is
+ *   always mutual, so a round with an eligible edge merges something.
+ * osn_merge_round: lo, hi int32 [n_pairs], sim float32 [n_pairs], n_pairs < 2^32 - 1, n_regions < 2^31 (both checked
+ *   on the host); ws: osn_merge_ws_bytes(n_regions) bytes, 8-byte aligned (one 64-bit word per region).  parent int32
+ *   [n_regions]: every region's smallest group member, flattened (the union-find of osn_regions_label).  Numbering
+ *   the groups in ascending order of parent keeps the canonical numbering, ascending smallest voxel row.  Four
+ *   launches: preset, best, unite, flatten.  An end out of range ORs bit 8 and the pair is skipped.
+ *
+ * osn_rows_fold: src float32 [n_src, d] (16-byte aligned, d as above); starts int64 [n_groups + 1] ascending from 0 to
+ *   n_members; members int32 [n_members] rows of src.  dst[g] float32 [n_groups, d] = the rows members[starts[g] :
+ *   starts[g + 1]] added to +0 one after the other in list order, in float32 (an empty group: zeros).  No atomics: the
+ *   bits are a function of the inputs.  A member outside [0, n_src) or a bad starts entry ORs bit 4 and is skipped
+ *   (clamped).                                                                                                        */
+int osn_merge_contacts(const int32_t* voxel_region, const int32_t* nbr, int64_t n_voxels, int connectivity,
+                       int64_t n_regions, int64_t* key, int32_t* err, osn_stream_t stream);
+int osn_rows_pair_dot(const void* rows_f16, int64_t n_rows, int d, const int32_t* lo, const int32_t* hi,
+                      int64_t n_pairs, float* sim, int32_t* err, osn_stream_t stream);
+size_t osn_merge_ws_bytes(int64_t n_regions);
+int osn_merge_round(const int32_t* lo, const int32_t* hi, const float* sim, int64_t n_pairs, int64_t n_regions,
+                    float threshold, int32_t* parent, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream);
+int osn_rows_fold(const float* src, int64_t n_src, int d, const int64_t* starts, const int32_t* members,
+                  int64_t n_members, int64_t n_groups, float* dst, int32_t* err, osn_stream_t stream);
+
 /* ---- hash voxelisation --------------------------------------------------- *
  * Replaces Voxelizer.voxelize (dataset/voxelizer.py:117-129) +
  * sparse_quantize / fnv_hash_vec (dataset/voxelization_utils.py:9-22,112-132):

@@ -15,6 +15,7 @@ Python surface (mirrors the reference's own, file:line in each module):
     openscene_amd.pca              the features themselves: second moments of a bank, principal feature directions, feature colours
     openscene_amd.match            bank rows matched to exemplar rows: label by example, correspondences, novelty
     openscene_amd.regions          scenes cut into regions of agreeing features before any prompt: label, list, query by region
+    openscene_amd.merge            ... and merged again by mean feature: region adjacency, star contraction of adjacent regions
     openscene_amd.render           views of a scene on the GPU: point-splat z-buffer -> heat-map / label / colour pictures, depth for fusion
     openscene_amd.neighbors        results on other points: k-nearest search on the voxel grid, transfer, fill of unseen rows, smoothing
     openscene_amd.align            two scans in one frame: rigid RANSAC over feature matches, ICP on the voxel index, overlap
@@ -104,6 +105,12 @@ def segment(bank, grid, similarity=0.9, min_points=1, names=None):
     """Regions of a grid's scenes by feature similarity of neighbouring voxels, no prompt needed (openscene_amd.regions.segment)."""
     from .regions import segment as f
     return f(bank, grid, similarity=similarity, min_points=min_points, names=names)
+
+
+def merge_regions(bank, grid, regions, similarity=0.8, min_contact=1, max_rounds=64):
+    """Adjacent regions of a RegionResult merged while their mean features agree (openscene_amd.merge.merge_regions)."""
+    from .merge import merge_regions as f
+    return f(bank, grid, regions, similarity=similarity, min_contact=min_contact, max_rounds=max_rounds)
 
 
 def install_minkowski_alias(force=False, accelerate=True):

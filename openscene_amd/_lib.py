@@ -142,6 +142,11 @@ PROTOTYPES = {
     "osn_regions_edges": (_i32, [_vp, _i64, _i32, _vp, _i32, _vp, _vp, _vp]),
     "osn_regions_label": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
     "osn_regions_records": (_i32, [_vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "osn_merge_contacts": (_i32, [_vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp]),
+    "osn_rows_pair_dot": (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _vp]),
+    "osn_merge_ws_bytes": (_sz, [_i64]),
+    "osn_merge_round": (_i32, [_vp, _vp, _vp, _i64, _i64, _f32, _vp, _vp, _vp, _sz, _vp]),
+    "osn_rows_fold": (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _i64, _vp, _vp, _vp]),
     "osn_voxelize_ws_bytes": (_sz, [_i64]),
     "osn_voxelize_fnv": (_i32, [_vp, _i64, _c.POINTER(_c.c_double), _vp, _vp, _vp, _c.POINTER(_i64), _vp, _sz, _vp]),
     "osn_fnv_hash": (_i32, [_vp, _i64, _i32, _vp, _vp]),

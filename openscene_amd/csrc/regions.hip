@@ -13,7 +13,8 @@
 // fetches in flight per lane.  A product of two fp16 values is exact in fp32 (22 significant bits, exponent >= -48), so
 // fmaf(a, b, acc) rounds once, at the addition: a lane adds its 8 (16) products in element order, the lanes are added by
 // an xor butterfly (32, 16, .. 1): a fixed tree, the same bits on every call.  No LDS, no floating-point atomics.
-// The packed fp16 dot instruction is not used: its treatment of fp16 subnormals is not the widening's.
+// The packed fp16 dot instruction is not used: its treatment of fp16 subnormals is not the widening's.  The loads and the
+// dot are the body of rowdot.h, which merge.hip runs over an arbitrary pair list.
 //
 // Label.  voxel_root starts as the identity; one thread per voxel unites it with the earlier neighbours whose sim passes
 // (float32 >=: NaN and -inf never pass); a second launch replaces every word by its root.  The root of a tree is its
@@ -23,8 +24,8 @@
 // atomics (components.h: wave_combine and BoxVox, with the all-lanes contract and why the records are exact and bitwise
 // repeatable).  The box is kept as order-preserving uint32 words in the output arrays and turned into floats by the last
 // launch; the region's scene is read at its smallest voxel row.
-#include "bank.h"            // half8
 #include "components.h"
+#include "rowdot.h"          // half8, row_load, row_dot
 
 namespace osn {
 
@@ -52,34 +53,14 @@ __global__ __launch_bounds__(REG_T) void regions_edges_kernel(const half8* __res
         }
         u[i] = x;
     }
-    half8 zero;
-#pragma unroll
-    for (int c = 0; c < 8; ++c) zero[c] = (_Float16)0.0f;
     half8 own[NV], nb[NOFF][NV];
+    row_load<NV>(own, vox, int(v), nvec, lane);
 #pragma unroll
-    for (int j = 0; j < NV; ++j) {
-        const int vec = j * 64 + lane;
-        own[j] = vec < nvec ? vox[v * nvec + vec] : zero;
-    }
-#pragma unroll
-    for (int i = 0; i < NOFF; ++i) {
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-            const int vec = j * 64 + lane;
-            nb[i][j] = (u[i] >= 0 && vec < nvec) ? vox[int64_t(u[i]) * nvec + vec] : zero;
-        }
-    }
+    for (int i = 0; i < NOFF; ++i) row_load<NV>(nb[i], vox, u[i], nvec, lane);
     float out = 0.f;
 #pragma unroll
     for (int i = 0; i < NOFF; ++i) {
-        float acc = 0.f;
-#pragma unroll
-        for (int j = 0; j < NV; ++j) {
-#pragma unroll
-            for (int c = 0; c < 8; ++c) acc = fmaf(float(own[j][c]), float(nb[i][j][c]), acc);
-        }
-#pragma unroll
-        for (int mk = 32; mk >= 1; mk >>= 1) acc += __shfl_xor(acc, mk, 64);
+        float acc = row_dot<NV>(own, nb[i]);                 // (rowdot.h: the body osn_rows_pair_dot shares)
         if (u[i] < 0) acc = -__builtin_inff();
         if (lane == i) out = acc;
     }

@@ -1852,6 +1852,8 @@ def objects_find(heat, thresholds, xyz, inverse, coords4, nbr, scene_offsets, co
 
 # --------------------------------------------------------------------- regions
 REGIONS_E_NBR, REGIONS_E_INVERSE, REGIONS_E_REGION = 1, 2, 4      # the bits of the regions' err word (csrc/regions.hip)
+REGIONS_E_PAIR = 8                                                # ... and the one csrc/merge.hip adds
+MERGE_RUN = 8                    # MERGE_RUN of csrc/merge.hip: the consecutive pairs a wave of rows_pair_dot takes
 
 
 def regions_n_off(connectivity):
@@ -1869,7 +1871,8 @@ def regions_check(err):
     err.zero_()
     what = [text for bit, text in ((REGIONS_E_NBR, "a neighbour row outside [-1, n_voxels)"),
                                    (REGIONS_E_INVERSE, "a point's voxel row outside [0, n_voxels)"),
-                                   (REGIONS_E_REGION, "a region entry outside [-1, n_regions)")) if bits & bit]
+                                   (REGIONS_E_REGION, "a region entry outside [-1, n_regions)"),
+                                   (REGIONS_E_PAIR, "a pair end outside [0, n_regions)")) if bits & bit]
     raise _lib.OpenSceneAmdError("regions: %s (err bits %d); such entries were skipped" % ("; ".join(what) or "unknown error", bits))
 
 
@@ -1980,6 +1983,134 @@ def regions_records(voxel_region, n_regions, xyz, inverse, coords4, err=None):
     if own and (v > 0 or n > 0):
         regions_check(err)
     return out
+
+
+# ----------------------------------------------------------------------- merge
+def regions_contacts(voxel_region, nbr, connectivity, n_regions, err=None):
+    """key int64 [n_off, V]: ``lo << 32 | hi`` of the regions of voxel v and its neighbour nbr[k_i, v] below the centre
+    (n_off and k_i as regions_edges) where both are >= 0 and differ, else -1.  voxel_region int32 [V] in -1 .. R - 1.
+    The distinct non-negative keys, sorted, are the region adjacency list; their multiplicities the contact counts
+    (merge.region_adjacency).  Entries out of range are skipped and recorded in `err` (as regions_edges)."""
+    if not isinstance(voxel_region, torch.Tensor) or voxel_region.dtype != torch.int32:
+        raise TypeError("voxel_region must be an int32 tensor")
+    dev = voxel_region.device
+    lib = _prep(dev)
+    if voxel_region.dim() != 1 or not voxel_region.is_contiguous():
+        raise ValueError("voxel_region must be a contiguous int32 [V] vector")
+    v = voxel_region.shape[0]
+    n_off = regions_n_off(connectivity)
+    _regions_nbr(nbr, v, dev)
+    r = int(n_regions)
+    if not 0 <= r <= v:
+        raise ValueError("n_regions must lie in 0 .. %d (got %d)" % (v, r))
+    err, own = _regions_err(err, dev)
+    key = torch.empty((n_off, v), dtype=torch.int64, device=dev)
+    with _Dev(dev):
+        check(lib.osn_merge_contacts(_p(voxel_region), _p(nbr), v, int(connectivity), r, _p(key), _p(err), _stream(dev)),
+              "osn_merge_contacts")
+    if own and v > 0:
+        regions_check(err)
+    return key
+
+
+def _merge_pairs(lo, hi, dev):
+    for name, t in (("lo", lo), ("hi", hi)):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError("%s must be an int32 tensor" % name)
+    if lo.dim() != 1 or lo.shape != hi.shape or lo.device != dev or hi.device != dev or not lo.is_contiguous() or not hi.is_contiguous():
+        raise ValueError("lo and hi must be contiguous int32 [E] vectors of one length on the rows' device")
+    e = lo.shape[0]
+    if e >= 2 ** 32 - 1:
+        raise ValueError("at most 2^32 - 2 pairs (got %d)" % e)
+    return e
+
+
+def rows_pair_dot(rows, lo, hi, err=None):
+    """sim float32 [E]: the fp32 dot product of rows[lo[e]] and rows[hi[e]].  rows fp16 [R, d], d % 8 == 0, 8 <= d <=
+    BANK_POOL_MAX_DIM; lo, hi int32 [E].  The arithmetic is that of regions_edges -- the same bits for the same two rows --
+    and the order of additions is fixed: bitwise repeatable.  An end outside [0, R) gives -inf and is recorded in `err`
+    when one is given (regions_check raises), and checked here otherwise."""
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.float16:
+        raise TypeError("rows must be a float16 tensor")
+    dev = rows.device
+    lib = _prep(dev)
+    if rows.dim() != 2 or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous [rows, dim] matrix")
+    r, d = rows.shape
+    if d < 8 or d % 8:
+        raise ValueError("the feature dim must be a multiple of 8 (got %d)" % d)
+    if d > BANK_POOL_MAX_DIM:
+        raise ValueError("the feature dim must be at most %d (got %d)" % (BANK_POOL_MAX_DIM, d))
+    e = _merge_pairs(lo, hi, dev)
+    err, own = _regions_err(err, dev)
+    sim = torch.empty(e, dtype=torch.float32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_rows_pair_dot(_p(rows), r, d, _p(lo), _p(hi), e, _p(sim), _p(err), _stream(dev)), "osn_rows_pair_dot")
+    if own and e > 0:
+        regions_check(err)
+    return sim
+
+
+def regions_merge_round(lo, hi, sim, n_regions, threshold, err=None):
+    """parent int32 [R]: the smallest member of every region's group after one round of star contraction over the pairs
+    (lo[e], hi[e]) with sim[e] >= threshold (float32; NaN and -inf never pass): a region joins its best neighbour --
+    greatest sim, then lowest e -- iff they name each other or the neighbour's own best pair is mutual.  Integer atomics and
+    the union-find of regions_label: independent of scheduling.  `err` as rows_pair_dot."""
+    if not isinstance(sim, torch.Tensor) or sim.dtype != torch.float32:
+        raise TypeError("sim must be a float32 tensor")
+    dev = sim.device
+    lib = _prep(dev)
+    e = _merge_pairs(lo, hi, dev)
+    if tuple(sim.shape) != (e,) or not sim.is_contiguous():
+        raise ValueError("sim must be a contiguous float32 [%d] vector, one per pair" % e)
+    r = int(n_regions)
+    if not 0 <= r < 2 ** 31:
+        raise ValueError("n_regions must lie in 0 .. 2^31 - 1 (got %d)" % r)
+    threshold = float(threshold)
+    if threshold != threshold or threshold in (float("inf"), float("-inf")):
+        raise ValueError("the threshold must be finite (got %r)" % (threshold,))
+    err, own = _regions_err(err, dev)
+    parent = torch.empty(r, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(lib.osn_merge_ws_bytes(r)) // 8, 1), dtype=torch.int64, device=dev)
+    with _Dev(dev):
+        check(lib.osn_merge_round(_p(lo), _p(hi), _p(sim), e, r, threshold, _p(parent), _p(err), _p(ws), ws.numel() * 8,
+                                  _stream(dev)), "osn_merge_round")
+    if own and e > 0 and r > 0:
+        regions_check(err)
+    return parent
+
+
+def rows_fold(src, starts, members, err=None):
+    """dst float32 [G, d]: row g is the rows ``src[members[starts[g]:starts[g + 1]]]`` added to +0 one after the other, in list
+    order, in float32 -- no atomics, the bits are a function of the inputs; an empty group gives zeros.  src float32 [R, d],
+    d % 8 == 0, 8 <= d <= BANK_POOL_MAX_DIM; starts int64 [G + 1] on the device, ascending from 0 to L; members int32 [L].
+    A member outside [0, R) or a bad starts entry is skipped and recorded in `err` (as rows_pair_dot)."""
+    if not isinstance(src, torch.Tensor) or src.dtype != torch.float32:
+        raise TypeError("src must be a float32 tensor")
+    dev = src.device
+    lib = _prep(dev)
+    if src.dim() != 2 or not src.is_contiguous():
+        raise ValueError("src must be a contiguous [rows, dim] matrix")
+    r, d = src.shape
+    if d < 8 or d % 8:
+        raise ValueError("the feature dim must be a multiple of 8 (got %d)" % d)
+    if d > BANK_POOL_MAX_DIM:
+        raise ValueError("the feature dim must be at most %d (got %d)" % (BANK_POOL_MAX_DIM, d))
+    if not isinstance(starts, torch.Tensor) or starts.dtype != torch.int64 or starts.dim() != 1 or starts.shape[0] < 1 \
+            or starts.device != dev or not starts.is_contiguous():
+        raise ValueError("starts must be a contiguous int64 [G + 1] vector on the rows' device")
+    if not isinstance(members, torch.Tensor) or members.dtype != torch.int32 or members.dim() != 1 or members.device != dev \
+            or not members.is_contiguous():
+        raise ValueError("members must be a contiguous int32 [L] vector on the rows' device")
+    g = starts.shape[0] - 1
+    err, own = _regions_err(err, dev)
+    dst = torch.empty((g, d), dtype=torch.float32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_rows_fold(_p(src), r, d, _p(starts), _p(members), members.shape[0], g, _p(dst), _p(err), _stream(dev)),
+              "osn_rows_fold")
+    if own and g > 0:
+        regions_check(err)
+    return dst
 
 
 # ------------------------------------------------------------------- voxelizer

@@ -12,7 +12,8 @@ threshold; here the grouping rule needs no heat-map: two neighbouring voxels bel
                       .label(bank, text_features) (label every region with a vocabulary), .point_labels(classes)
 
 A region is a connected component of SINGLE LINKAGE over neighbouring voxels (26 or 6 neighbours, the grid's): a chain of
-pairwise similar voxels joins its two ends however different they are.  What is exact: the partition is the connected
+pairwise similar voxels joins its two ends however different they are (`openscene_amd.merge` is the second stage for
+that: cut strictly here, then merge adjacent regions by their mean features).  What is exact: the partition is the connected
 components of the graph of edges whose float32 similarity is >= the threshold -- a property of the similarities, not of
 scheduling --, the numbering is canonical (regions in ascending order of their smallest voxel row), and every record
 field is an integer, a selected input value, or derived on the host from exact integers.  The similarities themselves
