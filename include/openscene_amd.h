@@ -195,6 +195,35 @@ int osn_spconv_fwd_tl(const float* in, int64_t n_in, const void* Wp, const void*
                       float* out, double* bn_partial, int64_t n_out, int K, int cin, int cout, int bm,
                       void* ws, size_t ws_bytes, int32_t* counters, osn_stream_t stream);
 
+/* ---- reduced-precision inference: the `_pieces` siblings of the four split-bf16 forward entries ---------------------- *
+ * (function parity with the inference call sites of the reference, which round the network's output to fp16 at once:
+ * run/evaluate.py:290-292; the convolutions are those of models/mink_unet.py:47-113 and models/resnet_base.py:38-60, 101-107,
+ * as cited at each base entry.)  Each sibling takes the arguments of its base entry plus a trailing `int pieces`:
+ *     pieces   name     operand pieces   products h_i(a) h_j(b) kept, in accumulation order (smallest first)
+ *       3      bf16x6   h1 h2 h3         31 22 13 21 12 11      -- bit for bit the base entry, which calls the same code with 3
+ *       2      bf16x3   h1 h2            21 12 11
+ *       1      bf16x1   h1               11                     -- one round-to-nearest bf16 per operand
+ * i.e. "ij" is kept iff i + j <= pieces + 1.  fp32 accumulation, fixed summation order, bitwise repeatable, in every mode.
+ * A reduced launch reads planes 0 .. pieces - 1 of the SAME weight image (osn_weight_prep_tl): no other layout, nothing to prepare.
+ * Error against the exact value, per output element and in units of sum_k |a_k||b_k| (on top of the half ulp of the result):
+ * 2e-6 (pieces 3), 2^-15 + 2e-6 (pieces 2), 2^-7 + 2e-6 (pieces 1); against the float64 sum of the kept products of the exact
+ * pieces 2e-6 in every mode (tests/conv_pieces.py).  pieces outside {1, 2, 3}: OSN_E_ARG before anything else is looked at.
+ * Forward inference only: weight gradients, the stem (osn_stem_conv_fwd) and the first-generation kernels have no reduced mode; an
+ * input gradient may be computed through a sibling (it is the same launch on the other weight image) but the library never does.
+ * Every shape of a base entry has reduced instances, except: osn_spconv_fwd_tl_pieces on a feature matrix of 2 GB or more (or of
+ * exactly 2^24 rows) whose input channels fill whole chunks (cin % 32 == 0 and cin / 32 <= 4 or divisible by 4 or 3) runs the
+ * six-product kernel for every `pieces` -- more exact than asked, never an error.                                          */
+int osn_spconv_fwd_tl_pieces(const float* in, int64_t n_in, const void* Wp, const void* tl, const int32_t* out_rows,
+                             float* out, double* bn_partial, int64_t n_out, int K, int cin, int cout, int bm,
+                             void* ws, size_t ws_bytes, int32_t* counters, osn_stream_t stream, int pieces);
+int osn_dense_fwd_pieces(const float* in, const void* Wp, float* out, int64_t n, int cin, int cout, osn_stream_t stream,
+                         int pieces);
+int osn_spconv_fwd_rg_pieces(const float* in, int64_t n_in, const void* Wp, const int32_t* nbr, const int32_t* out_rows,
+                             float* out, int64_t n_out, int K, int cin, int cout, osn_stream_t stream, int pieces);
+int osn_spconv_fwd_ws_pieces(const float* in, int64_t n_in, const void* Wp, const void* pl, int64_t pl_rows, int swap,
+                             int direct, const int32_t* nbr_dst, float* out, int64_t n_dst, int K, int cin, int cout,
+                             void* ws, size_t ws_bytes, osn_stream_t stream, int pieces);
+
 /* ---- every weight image of a model in one launch ----------------------------------------------- *
  * [ME] keeps one `kernel` parameter per MinkowskiConvolution / MinkowskiConvolutionTranspose
  * (models/mink_unet.py:47-113, models/resnet_base.py:38-60); an optimizer step changes all of them at once.
@@ -1192,6 +1221,12 @@ typedef struct osn_events osn_events_t;       /* pool of HIP events for the fork
  * the kernel that finishes the stage's convolution (csrc/epilogue.h: same expression, bitwise the separate launch); this flag keeps
  * the separate osn_bn_apply launch (A/B, tests).                                                                          */
 #define OSN_NET_RUN_NO_BN_EPILOGUE 2
+/* osn_net_forward, evaluation mode only: the reduced-precision modes of the `_pieces` entries above for EVERY convolution launch of
+ * the tile-list, register-gather, weight-stationary and 1x1 families (epilogue instances included); the stem and the first-generation
+ * kernel stay exact.  Both bits, either bit with run.training != 0, and either bit in osn_net_backward: OSN_E_ARG before the first
+ * launch.  osn_net_plan_query does not know the mode: arenas and workspaces are those of the exact pass.                       */
+#define OSN_NET_RUN_PIECES_2 4
+#define OSN_NET_RUN_PIECES_1 8
 typedef struct osn_net_run {
     const int64_t* level_rows;   /* [n_levels] rows of every pyramid level                                        */
     const osn_net_map* maps;

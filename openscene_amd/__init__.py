@@ -20,6 +20,8 @@ Python surface (mirrors the reference's own, file:line in each module):
     openscene_amd.neighbors        results on other points: k-nearest search on the voxel grid, transfer, fill of unseen rows, smoothing
     openscene_amd.align            two scans in one frame: rigid RANSAC over feature matches, ICP on the voxel index, overlap
     install_minkowski_alias()      make `import MinkowskiEngine` resolve to openscene_amd.minkowski
+    conv_precision(name)           context: the convolutions of inference passes in "bf16x6" (default), "bf16x3" or "bf16x1"
+                                   (openscene_amd.precision; set_conv_precision for the process, OSN_INFER_PRECISION at start)
 
 There is no CPU fallback: every op raises if libopenscene_amd.so is missing or
 the tensors are not on a gfx950 device.
@@ -27,6 +29,8 @@ the tensors are not on a gfx950 device.
 import os
 import sys
 import types
+
+from .precision import conv_precision, get_conv_precision, set_conv_precision  # noqa: F401  (inference arithmetic: bf16x6 / x3 / x1)
 
 __version__ = "0.1.0"
 

@@ -157,15 +157,18 @@ __device__ inline float4 epi_quad(const Epi& e, float4 x, int64_t row, int col, 
     return epi_apply(e, epi_cols(e, col), x, row, col, cout);
 }
 
-// ---- the library's convolution launches with an epilogue (net.hip); the extern "C" entry points pass epi_none()
+// ---- the library's convolution launches with an epilogue (net.hip); the extern "C" entry points pass epi_none().
+// pieces (split.h): 3 = the six-product arithmetic, 2 / 1 = the reduced inference modes of the four split-bf16 forward families
 int spconv_fwd_tl_epi(const float* in, int64_t n_in, const void* Wp, const void* tl, const int32_t* out_rows, float* out, int64_t n_out,
-                      int K, int cin, int cout, int bm, void* ws, size_t ws_bytes, int32_t* counters, const Epi& epi, osn_stream_t stream);
+                      int K, int cin, int cout, int bm, void* ws, size_t ws_bytes, int32_t* counters, const Epi& epi, osn_stream_t stream,
+                      int pieces = 3);
 int spconv_fwd_ws_epi(const float* in, int64_t n_in, const void* Wp, const void* pl, int64_t pl_rows, int swap, int direct,
                       const int32_t* nbr_dst, float* out, int64_t n_dst, int K, int cin, int cout, void* ws, size_t ws_bytes, const Epi& epi,
-                      osn_stream_t stream);
+                      osn_stream_t stream, int pieces = 3);
 int spconv_fwd_rg_epi(const float* in, int64_t n_in, const void* Wp, const int32_t* nbr, const int32_t* out_rows, float* out,
-                      int64_t n_out, int K, int cin, int cout, const Epi& epi, osn_stream_t stream);
-int dense_fwd_epi(const float* in, const void* Wp, float* out, int64_t n, int cin, int cout, const Epi& epi, osn_stream_t stream);
+                      int64_t n_out, int K, int cin, int cout, const Epi& epi, osn_stream_t stream, int pieces = 3);
+int dense_fwd_epi(const float* in, const void* Wp, float* out, int64_t n, int cin, int cout, const Epi& epi, osn_stream_t stream,
+                  int pieces = 3);
 int stem_conv_fwd_epi(const float* in, const float* W, const int32_t* nbr, float* out, int64_t n_out, int K, int cin, int cout,
                       const Epi& epi, osn_stream_t stream);
 

@@ -280,27 +280,27 @@ static int run_conv(int kernel, const float* in, int64_t n_in, float* out, int64
                     const float* W, const void* img_x6, const void* img_tl, const int32_t* nbr, const int32_t* t_rows,
                     const int32_t* t_tbl, const uint32_t* t_g, const void* tl, const int32_t* tl_rows, int tl_bm,
                     const void* pl, int64_t pl_rows, int pl_swap, const osn_net_run* run, osn_stream_t stream, int op,
-                    const Epi& epi = epi_none()) {
+                    const Epi& epi = epi_none(), int pieces = 3) {
     OSN_REQUIRE(!epi.mean || epi_fusable(kernel), OSN_E_ARG, "osn_net: op %d: kernel %d takes no epilogue", op, kernel);
     switch (kernel) {
         case OSN_NET_K_DENSE:
             OSN_REQUIRE(img_tl && K == 1 && n_in == n_out, OSN_E_ARG, "osn_net: op %d: the 1x1 kernel needs the fragment-order weight image", op);
-            return dense_fwd_epi(in, img_tl, out, n_out, cin, cout, epi, stream);
+            return dense_fwd_epi(in, img_tl, out, n_out, cin, cout, epi, stream, pieces);
         case OSN_NET_K_WS:
         case OSN_NET_K_WS_DIRECT:
             OSN_REQUIRE(pl && img_tl && nbr, OSN_E_ARG, "osn_net: op %d: pair arrays / tile-list weight image / destination table missing", op);
             return spconv_fwd_ws_epi(in, n_in, img_tl, pl, pl_rows, pl_swap, kernel == OSN_NET_K_WS_DIRECT ? 1 : 0, nbr, out, n_out, K,
-                                     cin, cout, run->ws, size_t(run->ws_bytes), epi, stream);
+                                     cin, cout, run->ws, size_t(run->ws_bytes), epi, stream, pieces);
         case OSN_NET_K_RG:
             OSN_REQUIRE(img_tl && nbr, OSN_E_ARG, "osn_net: op %d: the register-gather kernel needs the tile-list weight image and the table", op);
-            return spconv_fwd_rg_epi(in, n_in, img_tl, t_tbl ? t_tbl : nbr, t_tbl ? t_rows : nullptr, out, n_out, K, cin, cout, epi, stream);
+            return spconv_fwd_rg_epi(in, n_in, img_tl, t_tbl ? t_tbl : nbr, t_tbl ? t_rows : nullptr, out, n_out, K, cin, cout, epi, stream, pieces);
         case OSN_NET_K_STEM:
             OSN_REQUIRE(nbr && W, OSN_E_ARG, "osn_net: op %d: the stem kernel needs the plain table and the fp32 weight", op);
             return stem_conv_fwd_epi(in, W, nbr, out, n_out, K, cin, cout, epi, stream);
         case OSN_NET_K_TL:
             OSN_REQUIRE(tl && img_tl && run->tl_counters, OSN_E_ARG, "osn_net: op %d: tile lists / tile-list weight image / counters missing", op);
             return spconv_fwd_tl_epi(in, n_in, img_tl, tl, tl_rows, out, n_out, K, cin, cout, tl_bm, run->ws, size_t(run->ws_bytes),
-                                     run->tl_counters, epi, stream);
+                                     run->tl_counters, epi, stream, pieces);
         case OSN_NET_K_X6: {
             OSN_REQUIRE(img_x6 && (K == 1 || nbr), OSN_E_ARG, "osn_net: op %d: split-bf16 weight image / table missing", op);
             const int32_t* tbl = K == 1 ? nullptr : (t_tbl ? t_tbl : nbr);
@@ -312,6 +312,14 @@ static int run_conv(int kernel, const float* in, int64_t n_in, float* out, int64
             OSN_REQUIRE(false, OSN_E_ARG, "osn_net: op %d has no kernel", op);
     }
     return OSN_OK;
+}
+
+// the piece count the flags of an evaluation-mode forward pass select (split.h); 0: a combination that is an error
+static int run_pieces(const osn_net_run* run, bool backward) {
+    const int bits = run->flags & (OSN_NET_RUN_PIECES_2 | OSN_NET_RUN_PIECES_1);
+    if (!bits) return 3;
+    if (backward || run->training || bits == (OSN_NET_RUN_PIECES_2 | OSN_NET_RUN_PIECES_1)) return 0;
+    return bits == OSN_NET_RUN_PIECES_2 ? 2 : 1;
 }
 
 static int check_run(const osn_net_desc* net, const osn_net_run* run, const Layout& L, bool backward) {
@@ -355,6 +363,9 @@ extern "C" int osn_net_plan_query(const osn_net_desc* net, const int64_t* level_
 
 extern "C" int osn_net_forward(const osn_net_desc* net, const osn_net_run* run, osn_stream_t stream) {
     OSN_REQUIRE(net && run, OSN_E_ARG, "osn_net_forward: null argument");
+    const int pieces = run_pieces(run, false);
+    OSN_REQUIRE(pieces, OSN_E_ARG, "osn_net_forward: flags %d: OSN_NET_RUN_PIECES_2 and OSN_NET_RUN_PIECES_1 exclude each other and "
+                "need run.training == 0 (reduced precision is for inference)", run->flags);
     Layout L;
     int rc = make_layout(net, run->level_rows, run->training, L);
     if (rc) return rc;
@@ -427,7 +438,7 @@ extern "C" int osn_net_forward(const osn_net_desc* net, const osn_net_run* run, 
             // pair arrays: those of the map's own (strided / self) direction; a transposed conv walks them the other way
             rc = run_conv(L.fwd_k[i], in, n_in, x, n_out, o.K, o.cin, o.cout, w.W, w.x6_fwd, w.tl_fwd, v.nbr_f, v.tf_rows, v.tf_tbl,
                           v.tf_g, v.tl_f, v.tl_f_rows, v.tl_f_bm, o.map >= 0 ? run->maps[o.map].pl_fwd : nullptr,
-                          o.transposed ? n_in : n_out, o.transposed ? 1 : 0, r, sstream, i, epi);
+                          o.transposed ? n_in : n_out, o.transposed ? 1 : 0, r, sstream, i, epi, pieces);
         }
         if (rc) return rc;
         if (o.bn < 0) continue;
@@ -475,6 +486,7 @@ extern "C" int osn_net_forward(const osn_net_desc* net, const osn_net_run* run, 
 
 extern "C" int osn_net_backward(const osn_net_desc* net, const osn_net_run* run, osn_stream_t stream) {
     OSN_REQUIRE(net && run, OSN_E_ARG, "osn_net_backward: null argument");
+    OSN_REQUIRE(run_pieces(run, true), OSN_E_ARG, "osn_net_backward: flags %d: a backward pass has no reduced-precision mode", run->flags);
     Layout L;
     int rc = make_layout(net, run->level_rows, 1, L);
     if (rc) return rc;

@@ -33,163 +33,24 @@ constexpr int WS_CH = 32 * WS_NG;   // pairs per workgroup at most
 // 4 waves; wave w < NW owns output columns [32 w, 32 w + 32) of the workgroup's column group (waves >= NW only gather
 // and stage); KS k-steps of 32 input channels per chunk (B fragments of a chunk: KS x 2 column blocks x 3 planes).
 // EPI (inference, direct launches): the stage's evaluation-mode batch norm in the epilogue (epilogue.h)
-template <int NW, int KS, bool EPI = false>
-__global__ __launch_bounds__(256) void spconv_ws_kernel(const float* __restrict__ in, const bf16x8* __restrict__ Wp,
-                                                        const int32_t* __restrict__ gsrc, const int32_t* __restrict__ gdst,
-                                                        const int32_t* __restrict__ poff, float* __restrict__ partial,
-                                                        float* __restrict__ zeros, int n_dst, int K, int cin, int cout, int ns, int ncb, int chunk,
-                                                        int direct, const Epi epi) {
-    constexpr int NT = 256;
-    constexpr int CK = 32 * KS;               // input channels per chunk
-    constexpr int LDA = CK + 8;               // bf16 row stride of a staged plane (16-byte aligned rows)
-    constexpr int QPR = CK / 4;               // 4-channel quads per staged row
-    constexpr int NQ = (32 * QPR + NT - 1) / NT;
-    __shared__ __attribute__((aligned(16))) __bf16 stage[2][3][32][LDA];
-    __shared__ int sidx[WS_CH], didx[WS_CH];
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int k = blockIdx.y;
-    // the line of zeros the reduction reads for the offsets a row does not have
-    if (blockIdx.x == 0 && blockIdx.y == 0 && blockIdx.z == 0 && tid < 64) zeros[tid] = 0.f;
-    const int pk0 = poff[k], pk1 = poff[k + 1];
-    const int p0 = pk0 + blockIdx.x * chunk;
-    if (p0 >= pk1) return;                                             // this offset has fewer chunks
-    const int np = min(chunk, pk1 - p0);
-    const int nsteps = (np + 31) >> 5;
-    const int col0 = blockIdx.z * (32 * NW);
-    const int cb0 = blockIdx.z * (2 * NW) + 2 * wave;                  // this wave's first 16-column block
-
-    for (int e = tid; e < WS_CH; e += NT) {
-        sidx[e] = e < np ? gsrc[p0 + e] : 0;                           // padded pair: input row 0 (valid address)
-        didx[e] = e < np ? gdst[p0 + e] : -1;
-    }
-    int q_row[NQ], q_col[NQ];
-#pragma unroll
-    for (int j = 0; j < NQ; ++j) {
-        const int idx = tid + NT * j;
-        q_row[j] = (idx / QPR) & 31;
-        q_col[j] = (idx % QPR) * 4;
-    }
-    __syncthreads();
-
-    f32x4 acc[WS_NG][2][2];
-#pragma unroll
-    for (int g = 0; g < WS_NG; ++g)
-#pragma unroll
-        for (int h = 0; h < 2; ++h)
-#pragma unroll
-            for (int nb = 0; nb < 2; ++nb) acc[g][h][nb] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    float4 P[NQ];
-    auto fetch = [&](int g, int s0) {
-#pragma unroll
-        for (int j = 0; j < NQ; ++j) {
-            const unsigned row = unsigned(sidx[32 * g + q_row[j]]);
-            const int ch = 32 * s0 + q_col[j];
-            const unsigned cu = ch < cin ? unsigned(ch) : 0u;
-            P[j] = *reinterpret_cast<const float4*>(in + (uint64_t(row) * unsigned(cin) + cu));
-        }
-    };
-    int buf = 0;
-    for (int s0 = 0; s0 < ns; s0 += KS) {
-        // ---- the chunk's weight fragments: one coalesced 1 KB load each, consumed after the first barrier
-        bf16x8 B[KS][2][3];
-        if (wave < NW) {
-#pragma unroll
-            for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                for (int nb = 0; nb < 2; ++nb) {
-                    const bool on = s0 + ks < ns && cb0 + nb < ncb;
-                    const unsigned sb = on ? unsigned(s0 + ks) : 0u, cb = on ? unsigned(cb0 + nb) : 0u;
-#pragma unroll
-                    for (int pl = 0; pl < 3; ++pl) {
-                        const unsigned blk = (unsigned(pl * K + k) * unsigned(ns) + sb) * unsigned(ncb) + cb;
-                        B[ks][nb][pl] = (Wp + (size_t(blk) << 6))[lane];
-                    }
-                }
-        }
-        fetch(0, s0);
-#pragma unroll
-        for (int g = 0; g < WS_NG; ++g) {
-            if (g < nsteps) {
-                // ---- split the fetched quads into three bf16 pieces, stage them
-#pragma unroll
-                for (int j = 0; j < NQ; ++j) {
-                    const bool ok = 32 * s0 + q_col[j] < cin;
-                    bf16x4 p1, p2, p3;
-                    tl_split4(ok ? P[j] : make_float4(0.f, 0.f, 0.f, 0.f), p1, p2, p3);      // split.h: two elements per conversion
-                    if (NT * NQ == 32 * QPR || tid + NT * j < 32 * QPR) {
-                        *reinterpret_cast<bf16x4*>(&stage[buf][0][q_row[j]][q_col[j]]) = p1;
-                        *reinterpret_cast<bf16x4*>(&stage[buf][1][q_row[j]][q_col[j]]) = p2;
-                        *reinterpret_cast<bf16x4*>(&stage[buf][2][q_row[j]][q_col[j]]) = p3;
-                    }
-                }
-                if (g + 1 < nsteps) fetch(g + 1, s0);      // the next step's rows: in flight during the MFMAs below
-                // one barrier per step: the other stage buffer was last read in the step before this barrier's
-                __syncthreads();
-                if (wave < NW) {
-                    const bool half1 = np - 32 * g > 16;               // the second 16-pair half holds real pairs
-                    const int akq = 8 * (lane >> 4);
-#pragma unroll
-                    for (int ks = 0; ks < KS; ++ks) {
-                        if (s0 + ks < ns) {
-                            bf16x8 af[2][3];
-#pragma unroll
-                            for (int h = 0; h < 2; ++h)
-#pragma unroll
-                                for (int pl = 0; pl < 3; ++pl)
-                                    af[h][pl] = *reinterpret_cast<const bf16x8*>(
-                                        &stage[buf][pl][(half1 ? h : 0) * 16 + (lane & 15)][ks * 32 + akq]);
-                            // split_products' order per accumulator (split.h), consecutive MFMAs on different accumulators
-                            auto mfma_half = [&](int h, auto ap, auto bp) {
-#pragma unroll
-                                for (int nb = 0; nb < 2; ++nb)
-                                    acc[g][h][nb] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(B[ks][nb][bp], af[h][ap], acc[g][h][nb], 0, 0, 0);
-                            };
-                            if (half1) split_products([&](auto ap, auto bp) { mfma_half(0, ap, bp); mfma_half(1, ap, bp); });
-                            else split_products([&](auto ap, auto bp) { mfma_half(0, ap, bp); });
-                        }
-                    }
-                }
-                buf ^= 1;
-            }
-        }
-    }
-    if (wave >= NW) return;
-    EpiCols ec[2];
-    if constexpr (EPI) {                         // (direct launches: the lane's two column quads, constants once)
-#pragma unroll
-        for (int nb = 0; nb < 2; ++nb) {
-            const int col = col0 + 32 * wave + 16 * nb + 4 * (lane >> 4);
-            ec[nb] = epi_cols(epi, col < cout ? col : 0);
-        }
-    }
-    // ---- result rows -> partial[k][dst].  The weight fragment is the MFMA's FIRST operand (the staged rows the second), so a
-    // block comes out transposed: lane l holds columns 4 (l >> 4) .. + 3 of pair l & 15 -- one 16-byte store per block
-#pragma unroll
-    for (int g = 0; g < WS_NG; ++g) {
-        if (g < nsteps) {
-#pragma unroll
-            for (int h = 0; h < 2; ++h) {
-                const int d = didx[32 * g + 16 * h + (lane & 15)];
-                if (d >= 0) {
-                    // direct: every destination row has exactly one pair in the whole map -- `partial` IS the output
-                    float* row = partial + ((direct ? int64_t(0) : int64_t(k) * n_dst) + d) * cout;
-#pragma unroll
-                    for (int nb = 0; nb < 2; ++nb) {
-                        const int col = col0 + 32 * wave + 16 * nb + 4 * (lane >> 4);
-                        if (col < cout) {
-                            float4 v = make_float4(acc[g][h][nb][0], acc[g][h][nb][1], acc[g][h][nb][2], acc[g][h][nb][3]);
-                            if constexpr (EPI) v = epi_apply(epi, ec[nb], v, d, col, cout);
-                            *reinterpret_cast<float4*>(row + col) = v;
-                        }
-                    }
-                }
-            }
-        }
-    }
-}
+// The kernel's text is spconv_ws_kernel.h, included once per kernel template; per accumulator its products and their order are those of
+// split_products() in split.h, for the template's piece count.
+// the three-piece kernel, under the name and template parameters it always had ...
+#define OSN_WS_TEMPLATE template <int NW, int KS, bool EPI = false>
+#define OSN_WS_NAME spconv_ws_kernel
+#define OSN_WS_NP 3
+#include "spconv_ws_kernel.h"
+#undef OSN_WS_TEMPLATE
+#undef OSN_WS_NAME
+#undef OSN_WS_NP
+// ... and the reduced inference modes: the same text with NP_ = 2 or 1 pieces
+#define OSN_WS_TEMPLATE template <int NP_, int NW, int KS, bool EPI = false>
+#define OSN_WS_NAME spconv_ws_pieces_kernel
+#define OSN_WS_NP NP_
+#include "spconv_ws_kernel.h"
+#undef OSN_WS_TEMPLATE
+#undef OSN_WS_NAME
+#undef OSN_WS_NP
 
 // out[r] = sum over k ascending, nbr[k][r] >= 0, of partial[k][r]  (rows without any neighbour: zeros)
 // KT: offsets of the map when it is one of the two sizes the U-Net has (loads in flight in groups of WS_RED_GROUP), else 0.
@@ -261,8 +122,9 @@ extern "C" size_t osn_spconv_fwd_ws_ws_bytes(int64_t n_dst, int K, int cout, int
 
 int osn::spconv_fwd_ws_epi(const float* in, int64_t n_in, const void* Wp, const void* pl, int64_t pl_rows, int swap, int direct,
                            const int32_t* nbr_dst, float* out, int64_t n_dst, int K, int cin, int cout, void* ws, size_t ws_bytes,
-                           const Epi& epi, osn_stream_t stream) {
+                           const Epi& epi, osn_stream_t stream, int pieces) {
     hipStream_t st = static_cast<hipStream_t>(stream);
+    OSN_REQUIRE(pieces >= 1 && pieces <= 3, OSN_E_ARG, "osn_spconv_fwd_ws: pieces=%d (1, 2 or 3)", pieces);
     OSN_REQUIRE(n_dst >= 0 && n_dst < (int64_t(1) << 31) && n_in >= 0 && n_in < (int64_t(1) << 31), OSN_E_ARG,
                 "osn_spconv_fwd_ws: row counts out of range");
     OSN_REQUIRE(K >= 2 && K <= PL_KMAX && cin >= 4 && (cin & 3) == 0 && cout >= 4 && (cout & 3) == 0, OSN_E_ARG,
@@ -290,14 +152,20 @@ int osn::spconv_fwd_ws_epi(const float* in, int64_t n_in, const void* Wp, const 
     const int chunk = pmax <= 4096 ? 64 : WS_CH;       // (32 / 64 / 128 measured within 5 % of each other)
     const dim3 grid(unsigned(cdiv(pmax, chunk)), unsigned(K), unsigned(gz));
     const bf16x8* wp = static_cast<const bf16x8*>(Wp);
-#define OSN_WS2(NW_, KS_)                                                                                              \
+#define OSN_WS3(KERN_E_, KERN_)                                                                                        \
     do {                                                                                                               \
         if (direct && epi.mean)                                                                                        \
-            hipLaunchKernelGGL((spconv_ws_kernel<NW_, KS_, true>), grid, dim3(256), 0, st, in, wp, gsrc, gdst, v.poff, out, zeros, \
+            hipLaunchKernelGGL((KERN_E_), grid, dim3(256), 0, st, in, wp, gsrc, gdst, v.poff, out, zeros,              \
                                int(n_dst), K, cin, cout, ns, ncb, chunk, direct, epi);                                 \
         else                                                                                                           \
-            hipLaunchKernelGGL((spconv_ws_kernel<NW_, KS_, false>), grid, dim3(256), 0, st, in, wp, gsrc, gdst, v.poff,  \
+            hipLaunchKernelGGL((KERN_), grid, dim3(256), 0, st, in, wp, gsrc, gdst, v.poff,                            \
                                direct ? out : partial, zeros, int(n_dst), K, cin, cout, ns, ncb, chunk, direct, epi_none()); \
+    } while (0)
+#define OSN_WS2(NW_, KS_)                                                                                              \
+    do {                                                                                                               \
+        if (pieces == 3) OSN_WS3((spconv_ws_kernel<NW_, KS_, true>), (spconv_ws_kernel<NW_, KS_, false>));             \
+        else if (pieces == 2) OSN_WS3((spconv_ws_pieces_kernel<2, NW_, KS_, true>), (spconv_ws_pieces_kernel<2, NW_, KS_, false>)); \
+        else OSN_WS3((spconv_ws_pieces_kernel<1, NW_, KS_, true>), (spconv_ws_pieces_kernel<1, NW_, KS_, false>));     \
     } while (0)
 #define OSN_WS(NW_)                                                                                                    \
     do {                                                                                                               \
@@ -316,6 +184,7 @@ int osn::spconv_fwd_ws_epi(const float* in, int64_t n_in, const void* Wp, const 
     }
 #undef OSN_WS
 #undef OSN_WS2
+#undef OSN_WS3
     if (direct) {
         OSN_LAUNCH_CHECK();
         return OSN_OK;
@@ -338,5 +207,12 @@ int osn::spconv_fwd_ws_epi(const float* in, int64_t n_in, const void* Wp, const 
 extern "C" int osn_spconv_fwd_ws(const float* in, int64_t n_in, const void* Wp, const void* pl, int64_t pl_rows,
                                  int swap, int direct, const int32_t* nbr_dst, float* out, int64_t n_dst, int K, int cin, int cout,
                                  void* ws, size_t ws_bytes, osn_stream_t stream) {
-    return spconv_fwd_ws_epi(in, n_in, Wp, pl, pl_rows, swap, direct, nbr_dst, out, n_dst, K, cin, cout, ws, ws_bytes, epi_none(), stream);
+    return spconv_fwd_ws_epi(in, n_in, Wp, pl, pl_rows, swap, direct, nbr_dst, out, n_dst, K, cin, cout, ws, ws_bytes, epi_none(), stream, 3);
+}
+
+extern "C" int osn_spconv_fwd_ws_pieces(const float* in, int64_t n_in, const void* Wp, const void* pl, int64_t pl_rows,
+                                        int swap, int direct, const int32_t* nbr_dst, float* out, int64_t n_dst, int K, int cin, int cout,
+                                        void* ws, size_t ws_bytes, osn_stream_t stream, int pieces) {
+    return spconv_fwd_ws_epi(in, n_in, Wp, pl, pl_rows, swap, direct, nbr_dst, out, n_dst, K, cin, cout, ws, ws_bytes, epi_none(), stream,
+                             pieces);
 }

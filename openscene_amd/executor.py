@@ -18,7 +18,7 @@ import numpy as np
 import torch
 from torch.autograd import Function
 
-from . import _lib, ops
+from . import _lib, ops, precision
 from ._lib import check
 
 ENABLED = os.environ.get("OSN_EXECUTOR", "1") != "0"
@@ -82,6 +82,7 @@ class _Run(ctypes.Structure):
 
 RUN_NO_JOIN = 1                                 # include/openscene_amd.h: OSN_NET_RUN_NO_JOIN
 RUN_NO_BN_EPILOGUE = 2                          # include/openscene_amd.h: OSN_NET_RUN_NO_BN_EPILOGUE
+RUN_PIECES = {3: 0, 2: 4, 1: 8}                 # operand pieces -> OSN_NET_RUN_PIECES_2 / OSN_NET_RUN_PIECES_1 (inference only)
 # Inference: every stage's batch norm (+ residual) (+ ReLU) (+ cat store) runs in the epilogue of the kernel that finishes the stage's
 # convolution (csrc/epilogue.h; bitwise the separate launch, 48 launches fewer per MinkUNet18A pass).  0: the separate launches (A/B, tests)
 BN_EPILOGUE = os.environ.get("OSN_BN_EPILOGUE", "1") != "0"
@@ -190,7 +191,7 @@ class Program:
 
 class _PassState:
     """What a forward pass leaves for its backward pass (kept alive by the autograd node)."""
-    __slots__ = ("rows", "maps", "weights", "bns", "arena", "keep", "training", "feats", "plan_fwd_bytes", "cm")
+    __slots__ = ("rows", "maps", "weights", "bns", "arena", "keep", "training", "feats", "plan_fwd_bytes", "cm", "pieces")
 
 
 class UNetExecutor:
@@ -403,7 +404,8 @@ class UNetExecutor:
         return o["K"] == 1 and o["bn"] < 0 and o["dst"] < 0 and ops.dense_eligible(o["cin"], o["cout"]) and ops.dense_eligible(o["cout"], o["cin"])
 
     def _head_rows(self, st, feat, rows):
-        """output[rows] = feat[rows] @ W_final: a row gather and the 1x1 kernel on len(rows) rows."""
+        """output[rows] = feat[rows] @ W_final: a row gather and the 1x1 kernel on len(rows) rows, in the precision of the pass that
+        made `feat` (st.pieces)."""
         p = self.program
         dev = feat.device
         lib = ops._prep(dev)
@@ -414,7 +416,11 @@ class UNetExecutor:
         image = int(st.weights[len(p.convs) - 1]["tl_fwd"])
         with ops._Dev(dev):
             check(lib.osn_rows_gather(feat.data_ptr(), rows.data_ptr(), n_sel, cin, in_rows.data_ptr(), ops._stream(dev)), "osn_rows_gather")
-            check(lib.osn_dense_fwd(in_rows.data_ptr(), image, out.data_ptr(), n_sel, cin, cout, ops._stream(dev)), "osn_dense_fwd")
+            if st.pieces == 3:
+                check(lib.osn_dense_fwd(in_rows.data_ptr(), image, out.data_ptr(), n_sel, cin, cout, ops._stream(dev)), "osn_dense_fwd")
+            else:
+                check(lib.osn_dense_fwd_pieces(in_rows.data_ptr(), image, out.data_ptr(), n_sel, cin, cout, ops._stream(dev), st.pieces),
+                      "osn_dense_fwd_pieces")
         return out
 
     def _run_forward(self, model, x, features_only=False, grad=False):
@@ -437,6 +443,8 @@ class UNetExecutor:
         self._plan_query(lib, rows, grad or training)
         st = _PassState()
         st.rows, st.training, st.feats, st.cm = rows, training, feats, cm
+        # inference precision (openscene_amd.precision): an evaluation-mode pass that records no graph; everything else is bf16x6
+        st.pieces = precision.inference_pieces(training, grad)
         st.maps, keep_m = self._maps(cm, grad)
         prep_done = None
         if grad and SIDE_STREAM and not _DRY_RUN and K_NAMES[int(self._kf[0])] == "stem":
@@ -467,7 +475,7 @@ class UNetExecutor:
         run = _Run(_ptr(self._rows), _ptr(st.maps), _ptr(st.weights), _ptr(st.bns), feats.data_ptr(),
                    out.data_ptr() if out is not None else None, None, st.arena.data_ptr(), st.arena.numel(), None, 0,
                    ws.data_ptr(), ws.numel(), ops.tl_counters(dev).data_ptr(), int(training), 0, end,
-                   0 if (BN_EPILOGUE and not grad) else RUN_NO_BN_EPILOGUE, self.prof,      # (a pass with a backward pass keeps x)
+                   (0 if (BN_EPILOGUE and not grad) else RUN_NO_BN_EPILOGUE) | RUN_PIECES[st.pieces], self.prof,      # (a pass with a backward pass keeps x)
                    side if events else None, ws2.data_ptr() if (events and ws2 is not None) else None,
                    ws2.numel() if (events and ws2 is not None) else 0, events, None, None, None, 0)
         with ops._Dev(dev):

@@ -7,7 +7,7 @@ import threading
 import torch
 from torch.autograd import Function
 
-from . import ops
+from . import ops, precision
 
 # Kernels / arithmetic of the forward and input-gradient convolutions:
 #   "tl"     (default) second-generation kernels: forward / input gradient from per-tile compacted pair lists
@@ -120,21 +120,23 @@ def _plan_kernels(K, cin, cout, n_in, n_out, transposed, fine_unique, need_dgrad
     return fwd, pick(cout, cin, n_out, n_in, not transposed, have_lists_bwd) if need_dgrad else "none", wgrad
 
 
-def _launch(name, x, w, n_dst, c_dst, K, nbr, tiles, lists, pairs, swap):
+def _launch(name, x, w, n_dst, c_dst, K, nbr, tiles, lists, pairs, swap, pieces=3):
     """Convolution kernel `name` on x -> [n_dst, c_dst] (the Python twin of run_conv in csrc/net.hip).  w: the weight image _IMAGE
     names, else the fp32 weight; nbr / tiles / lists: the destination side's table, tile-ordered table and tile lists; pairs, swap:
-    the map's pair arrays and whether this launch walks them the other way."""
+    the map's pair arrays and whether this launch walks them the other way; pieces: operand pieces of the four split-bf16 families
+    (openscene_amd.precision: below 3 only in a forward pass of an evaluation-mode model that records no graph)."""
     tbl, rows, gm = (tiles[1], tiles[0], tiles[2]) if tiles is not None else (nbr, None, None)
+    kw = {} if pieces == 3 else {"pieces": pieces}          # (the default mode calls the wrappers as it always did)
     if name == "stem":
         return ops.stem_conv_fwd(x, w, nbr, n_dst)
     if name == "dense":
-        return ops.dense_fwd(x, w, c_dst)
+        return ops.dense_fwd(x, w, c_dst, **kw)
     if name in ("ws", "ws_direct"):
-        return ops.spconv_fwd_ws(x, w, pairs, nbr, n_dst, K, c_dst, swap=swap, direct=name == "ws_direct")
+        return ops.spconv_fwd_ws(x, w, pairs, nbr, n_dst, K, c_dst, swap=swap, direct=name == "ws_direct", **kw)
     if name == "tl":
-        return ops.spconv_fwd_tl(x, w, lists, n_dst, K, c_dst)
+        return ops.spconv_fwd_tl(x, w, lists, n_dst, K, c_dst, **kw)
     if name == "rg":
-        return ops.spconv_fwd_rg(x, w, tbl, n_dst, c_dst, out_rows=rows)
+        return ops.spconv_fwd_rg(x, w, tbl, n_dst, c_dst, out_rows=rows, **kw)
     if name == "x6":
         return ops.spconv_fwd_x6(x, w, tbl, n_dst, out_rows=rows, gmask=gm)
     return ops.spconv_fwd(x, w, tbl, n_dst, out_rows=rows, gmask=gm)
@@ -146,7 +148,7 @@ class SparseConvFunction(Function):
 
     @staticmethod
     def forward(ctx, feats, kernel, nbr_fwd, nbr_bwd, flip, n_out, tiles_fwd=None, tiles_bwd=None, counts=None,
-                lists_fwd=None, lists_bwd=None, transposed=False, fine_unique=False):
+                lists_fwd=None, lists_bwd=None, transposed=False, fine_unique=False, pieces=3):
         ctx.save_for_backward(feats, kernel)
         n_in, flip = feats.shape[0], bool(flip)
         K = 1 if kernel.dim() == 2 else kernel.shape[0]
@@ -178,7 +180,7 @@ class SparseConvFunction(Function):
         # direction of the pair arrays and takes the mirrored weight image
         ctx.dgrad = (dgrad, wd, nbr_bwd, tiles_bwd, lists_bwd, pairs, transposed if flip else not transposed)
         ctx.wgrad = (wgrad, nbr_fwd, counts, transposed, flip)
-        return _launch(fwd, feats, wf if wf is not None else kernel, n_out, cout, K, nbr_fwd, tiles_fwd, lists_fwd, pairs, transposed)
+        return _launch(fwd, feats, wf if wf is not None else kernel, n_out, cout, K, nbr_fwd, tiles_fwd, lists_fwd, pairs, transposed, pieces)
 
     @staticmethod
     def backward(ctx, gout):
@@ -219,7 +221,7 @@ class SparseConvFunction(Function):
             gin = _launch(dgrad, gout, wd, n_in, cin, K, nbr_bwd, tiles_bwd, lists_bwd, pairs, swap_b)
         if side is not None:
             main.wait_stream(side)                        # join: later work on this stream sees the weight gradient
-        return gin, gk, None, None, None, None, None, None, None, None, None, None, None
+        return gin, gk, None, None, None, None, None, None, None, None, None, None, None, None
 
 
 class BatchNormActFunction(Function):
@@ -335,15 +337,18 @@ def cat(ts):
     return out
 
 
-def sparse_conv(feats, kernel, maps, n_out, tiles=None, counts=None, lists=None, transposed=False, fine_unique=False):
+def sparse_conv(feats, kernel, maps, n_out, tiles=None, counts=None, lists=None, transposed=False, fine_unique=False, training=True):
     """maps = CoordinateManager.kmap(...); tiles = .kmap_tiles(...) or None; counts = .kmap_counts(...) or None;
     lists = .kmap_lists(...) or None; transposed: the conv is a MinkowskiConvolutionTranspose; fine_unique: the map is a
-    2^3 stride-2 map (every row of its fine side has exactly one pair)."""
+    2^3 stride-2 map (every row of its fine side has exactly one pair); training: the calling module's mode -- an evaluation-mode
+    convolution that records no graph runs in the inference precision in force (openscene_amd.precision), as the executor's pass does."""
     nbr_fwd, nbr_bwd, flip = maps
+    grad = torch.is_grad_enabled() and (feats.requires_grad or kernel.requires_grad)
+    pieces = precision.inference_pieces(training, grad)
     tf, tb = tiles if tiles is not None else (None, None)
     lf, lb = lists if lists is not None else (None, None)
     return SparseConvFunction.apply(feats, kernel, nbr_fwd, nbr_bwd, flip, n_out, tf, tb, counts, lf, lb, bool(transposed),
-                                    bool(fine_unique))
+                                    bool(fine_unique), pieces)
 
 
 _tls = threading.local()

@@ -90,7 +90,7 @@ class MinkowskiConvolutionBase(nn.Module):
                                                                                   self.out_channels):
             lists = cm.kmap_lists(s_in, s_out, self.kernel_size, self.dilation)
         out = F_.sparse_conv(x.F, self.kernel, maps, cm.size(s_out), tiles, counts, lists, transposed=self.TRANSPOSED,
-                             fine_unique=self.kernel_size == 2 and self.stride == 2 and self.dilation == 1)
+                             fine_unique=self.kernel_size == 2 and self.stride == 2 and self.dilation == 1, training=self.training)
         if self.bias is not None:
             out = out + self.bias
         return SparseTensor(out, tensor_stride=s_out, coordinate_manager=cm)

@@ -653,9 +653,19 @@ def tl_counters(dev):
     return c
 
 
-def spconv_fwd_tl(feats, wp, tl, n_out, K, cout, bn_partial=None):
+def _pieces_ok(pieces):
+    """pieces = 3: the six-product arithmetic through the entry it always went through; 2 / 1: the reduced inference modes
+    (openscene_amd.precision, csrc/split.h) through the entry's `_pieces` sibling."""
+    if pieces not in (1, 2, 3):
+        raise ValueError("pieces must be 1, 2 or 3, got %r" % (pieces,))
+    return int(pieces)
+
+
+def spconv_fwd_tl(feats, wp, tl, n_out, K, cout, bn_partial=None, pieces=3):
     """out[o] = sum_k feats[list rows] @ B[k] with B given as a weight_prep_tl image; tl None <=> K == 1 identity.
-    bn_partial: optional float64 [n_tiles, 2, cout] receiving per-tile column sums / sums of squares."""
+    bn_partial: optional float64 [n_tiles, 2, cout] receiving per-tile column sums / sums of squares.
+    pieces: operand pieces (_pieces_ok)."""
+    pieces = _pieces_ok(pieces)
     dev = feats.device
     lib = _prep(dev)
     feats = _f32c(feats, "features")
@@ -677,8 +687,12 @@ def spconv_fwd_tl(feats, wp, tl, n_out, K, cout, bn_partial=None):
     counters = tl_counters(dev)
     with _Dev(dev):
         try:
-            check(lib.osn_spconv_fwd_tl(_p(feats), feats.shape[0], _p(wp), _p(buf), _p(rows), _p(out), _p(bn_partial), n_out,
-                                        K, cin, cout, bm, _p(ws), ws.numel(), _p(counters), _stream(dev)), "osn_spconv_fwd_tl")
+            args = (_p(feats), feats.shape[0], _p(wp), _p(buf), _p(rows), _p(out), _p(bn_partial), n_out, K, cin, cout, bm, _p(ws),
+                    ws.numel(), _p(counters), _stream(dev))
+            if pieces == 3:
+                check(lib.osn_spconv_fwd_tl(*args), "osn_spconv_fwd_tl")
+            else:
+                check(lib.osn_spconv_fwd_tl_pieces(*args, pieces), "osn_spconv_fwd_tl_pieces")
         except Exception:
             _tl_counters.pop((_idx(dev), _stream(dev)), None)   # a failed launch leaves the counters undefined: start from a fresh zero buffer
             raise
@@ -768,8 +782,10 @@ def dense_eligible(cin, cout):
     return bool(_cached("osn_dense_fwd_ok", int(cin), int(cout)))
 
 
-def dense_fwd(feats, wp, cout):
-    """out = feats @ B, B a weight_prep_tl image of a K = 1 weight (forward image, or the input-gradient image)."""
+def dense_fwd(feats, wp, cout, pieces=3):
+    """out = feats @ B, B a weight_prep_tl image of a K = 1 weight (forward image, or the input-gradient image).
+    pieces: operand pieces (_pieces_ok)."""
+    pieces = _pieces_ok(pieces)
     dev = feats.device
     lib = _prep(dev)
     feats = _f32c(feats, "features")
@@ -780,7 +796,10 @@ def dense_fwd(feats, wp, cout):
     out = torch.empty((n, cout), dtype=torch.float32, device=dev)
     tok = _prof_start("dense_fwd", dev, n_in=n, n_out=n, K=1, cin=cin, cout=cout)
     with _Dev(dev):
-        check(lib.osn_dense_fwd(_p(feats), _p(wp), _p(out), n, cin, cout, _stream(dev)), "osn_dense_fwd")
+        if pieces == 3:
+            check(lib.osn_dense_fwd(_p(feats), _p(wp), _p(out), n, cin, cout, _stream(dev)), "osn_dense_fwd")
+        else:
+            check(lib.osn_dense_fwd_pieces(_p(feats), _p(wp), _p(out), n, cin, cout, _stream(dev), pieces), "osn_dense_fwd_pieces")
     if tok is not None:
         _profiler.stop(tok)
     return out
@@ -806,12 +825,13 @@ def stem_conv_wgrad(feats, gout, nbr, K):
     return gw
 
 
-def spconv_fwd_ws(feats, wp, tl, nbr_dst, n_dst, K, cout, swap=False, direct=False):
+def spconv_fwd_ws(feats, wp, tl, nbr_dst, n_dst, K, cout, swap=False, direct=False, pieces=3):
     """Convolution of a small map from the pair arrays of `tl` (weight-stationary workgroups + ordered sum over the
     offsets): out[r] = sum_k feats[src of (k, r)] @ B[k], B a weight_prep_tl image.  nbr_dst int32 [K, n_dst]: the
     neighbour table of the destination side, plain row order.  swap: `tl` belongs to the map's transposed direction.
     direct: every destination row has exactly one pair in the map (fine side of a 2^3 stride-2 map): rows are written
-    straight to the output, nbr_dst may be None."""
+    straight to the output, nbr_dst may be None.  pieces: operand pieces (_pieces_ok)."""
+    pieces = _pieces_ok(pieces)
     dev = feats.device
     lib = _prep(dev)
     feats = _f32c(feats, "features")
@@ -829,9 +849,12 @@ def spconv_fwd_ws(feats, wp, tl, nbr_dst, n_dst, K, cout, swap=False, direct=Fal
     ws = _ws(_cached("osn_spconv_fwd_ws_ws_bytes", n_dst, K, cout, int(bool(direct))), dev)
     tok = _prof_start("spconv_fwd_ws", dev, n_in=n_in, n_out=n_dst, K=K, cin=cin, cout=cout)
     with _Dev(dev):
-        check(lib.osn_spconv_fwd_ws(_p(feats), n_in, _p(wp), _p(pl), table_rows, int(bool(swap)), int(bool(direct)),
-                                    _p(nbr_dst.contiguous() if nbr_dst is not None else None),
-                                    _p(out), n_dst, K, cin, cout, _p(ws), ws.numel(), _stream(dev)), "osn_spconv_fwd_ws")
+        args = (_p(feats), n_in, _p(wp), _p(pl), table_rows, int(bool(swap)), int(bool(direct)),
+                _p(nbr_dst.contiguous() if nbr_dst is not None else None), _p(out), n_dst, K, cin, cout, _p(ws), ws.numel(), _stream(dev))
+        if pieces == 3:
+            check(lib.osn_spconv_fwd_ws(*args), "osn_spconv_fwd_ws")
+        else:
+            check(lib.osn_spconv_fwd_ws_pieces(*args, pieces), "osn_spconv_fwd_ws_pieces")
     if tok is not None:
         _profiler.stop(tok)
     return out
@@ -842,9 +865,10 @@ def rg_eligible(K, cin, cout, n_in):
     return bool(_cached("osn_spconv_fwd_rg_ok", int(max(n_in, 1)), int(K), int(cin), int(cout)))
 
 
-def spconv_fwd_rg(feats, wp, nbr, n_out, cout, out_rows=None):
+def spconv_fwd_rg(feats, wp, nbr, n_out, cout, out_rows=None, pieces=3):
     """out[o] = sum_k feats[nbr[k, o]] @ B[k], B given as a weight_prep_tl image (forward or input-gradient image); nbr plain or
-    tile-ordered (then out_rows = its permutation)."""
+    tile-ordered (then out_rows = its permutation).  pieces: operand pieces (_pieces_ok)."""
+    pieces = _pieces_ok(pieces)
     dev = feats.device
     lib = _prep(dev)
     feats = _f32c(feats, "features")
@@ -854,8 +878,11 @@ def spconv_fwd_rg(feats, wp, nbr, n_out, cout, out_rows=None):
         raise ValueError("table is [%d, %d], conv wants %d output rows" % (K, nbr.shape[1], n_out))
     out = torch.empty((n_out, cout), dtype=torch.float32, device=dev)
     with _Dev(dev):
-        check(lib.osn_spconv_fwd_rg(_p(feats), feats.shape[0], _p(wp), _p(nbr), _p(out_rows), _p(out), n_out, K, feats.shape[1], cout,
-                                    _stream(dev)), "osn_spconv_fwd_rg")
+        args = (_p(feats), feats.shape[0], _p(wp), _p(nbr), _p(out_rows), _p(out), n_out, K, feats.shape[1], cout, _stream(dev))
+        if pieces == 3:
+            check(lib.osn_spconv_fwd_rg(*args), "osn_spconv_fwd_rg")
+        else:
+            check(lib.osn_spconv_fwd_rg_pieces(*args, pieces), "osn_spconv_fwd_rg_pieces")
     return out
 
 
