@@ -1,5 +1,6 @@
 """The arithmetic contract of the convolutions in one place (plain helper module; imported by test_gpu_fullsize.py,
-test_conv_bounds_cpu.py and test_gpu_conv_bounds.py).
+test_conv_bounds_cpu.py, test_gpu_conv_bounds.py, test_gpu_wgrad_batch.py and the instance census conv_census.py): the bounds, the operand
+kinds, the CPU restatements, the CASES, and the Launch that runs a case's kernel on a device.
 
 Contract: every output element lies within  c * sum_k |a_k| |b_k|  of the float64 value, c = 2e-6 for the forward and the input
 gradient, 2e-5 for the weight gradient, whatever the dynamic range of the operands; plus half an ulp of the result itself
@@ -13,6 +14,7 @@ in addition to 2e-5 on every kind: with all-positive operands the only other err
 coherent terms, which test_conv_bounds_cpu.py shows to sit far below 2e-6 for the emulation at every shape used here.
 """
 import collections
+import ctypes
 import functools
 import zlib
 
@@ -198,7 +200,8 @@ def fmaf_chain_wgrad(feats, gout, nbr, rows_per_part=64, max_parts=128):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the cases
-# family: the kernel family; op: "fwd" (features x weight image) or "wgrad"; opt: what the entry point is called with
+# family: the kernel family; op: "fwd" (features x weight image) or "wgrad"; opt: what the entry point is called with (bm: the tile
+# height of the case's tile lists where it is not osn_tile_rows' for the row count)
 Case = collections.namedtuple("Case", "id family op n_in n_out K cin cout occ opt")
 STEM_MFMA_ROWS = 32768 + 17
 
@@ -233,6 +236,59 @@ CASES = [
     _c("dense", "fwd", 257, 257, 1, 8, 20, identity=1, image="fwd"), _c("dense", "fwd", 257, 257, 1, 8, 20, identity=1, image="dgrad"),
     _c("dense", "fwd", 257, 257, 1, 768, 96, identity=1, image="fwd"), _c("dense", "fwd", 257, 257, 1, 768, 96, identity=1, image="dgrad"),
 ]
+
+
+def _both(family, *a, **opt):
+    return [_c(family, "fwd", *a, image="fwd", **opt), _c(family, "fwd", *a, image="dgrad", **opt)]
+
+
+# The instances the shipped networks launch (test_conv_census_cpu.py lists them and fails when one has no case here): per instance
+# the smallest shape that reaches it -- a few hundred rows, split tile-list launches (the persistent launch runs the same instance),
+# the hand-made 30 % tables, the stride-2 map for the K = 8 launches.  In the comments <..> are the template arguments the channel
+# counts select: tile-list <NW, KS> (+ "ragged"), weight-stationary <NW, KS>, pair-array weight gradient <MB, NB>.
+CASES += (
+    # tile-list, K = 27, both weight images: <3,3> 96->96, <3,4> 128->96, <4,3> 96->128 and 192->128 (two chunks), <4,4> 128->128,
+    # 256->256 (two chunks), 384->256 (three)
+    _both("tl", 230, 200, 27, 96, 96, split=1) + _both("tl", 230, 200, 27, 128, 96, split=1) + _both("tl", 230, 200, 27, 96, 128, split=1)
+    + _both("tl", 230, 200, 27, 192, 128, split=1) + _both("tl", 230, 200, 27, 128, 128, split=1)
+    + _both("tl", 230, 200, 27, 256, 256, split=1) + _both("tl", 230, 200, 27, 384, 256, split=1)
+    # ... the narrow decoders of 34A / 34B: <2,2> 64->64, <2,3> 96->64, <2,4> 128->64, <3,2> 64->96; 18D's input gradient 384 -> 416
+    # is <1,4> (13 column groups of 32), here 128->32; its ragged 416-channel contraction <4,4,ragged>
+    + [_c("tl", "fwd", 230, 200, 27, 64, 64, split=1), _c("tl", "fwd", 230, 200, 27, 96, 64, split=1),
+       _c("tl", "fwd", 230, 200, 27, 128, 64, split=1), _c("tl", "fwd", 230, 200, 27, 64, 96, split=1),
+       _c("tl", "fwd", 230, 200, 27, 128, 32, split=1), _c("tl", "fwd", 230, 200, 27, 416, 128, split=1)]
+    # ... K = 8 on the transposed side of the stride-2 map, and the taller tiles: 64 rows (what osn_tile_rows hands out from 86 k
+    # rows on; still three workgroups per CU at 96 columns) and 88 rows, the tallest (two)
+    + [_c("tl", "fwd", 0, 0, 8, 256, 128, split=1, s2="holes"), _c("tl", "fwd", 0, 0, 8, 128, 96, split=1, s2="full"),
+       _c("tl", "fwd", 330, 300, 27, 96, 96, split=1, bm=64), _c("tl", "fwd", 330, 300, 27, 96, 96, split=1, bm=88),
+       _c("tl", "fwd", 330, 300, 27, 128, 96, split=1, bm=88)]
+    # weight-stationary: <1,1> 32->32, <1,2> 64->32, <1,4> 128->32, <2,2> 64->64, <2,3> 96->64, <3,3> 96->96, <3,4> 128->96,
+    # <4,2> 64->128, <4,3> 192->128, <4,4> 256->256; swap and direct launches at K = 8
+    + [_c("ws", "fwd", 350, 300, 27, ci, co, swap=0, direct=0) for ci, co in ((32, 32), (64, 32), (128, 32), (64, 64), (96, 64), (96, 96),
+                                                                              (128, 96), (64, 128), (192, 128), (256, 256))]
+    + [_c("ws", "fwd", 0, 0, 8, 256, 128, swap=1, direct=0, s2="holes"), _c("ws", "fwd", 0, 0, 8, 128, 96, swap=1, direct=1, s2="full"),
+       _c("ws", "fwd", 0, 0, 8, 32, 32, swap=1, direct=1, s2="full")]
+    # register-gather: the 32->32 instance (the only one with three workgroups per CU)
+    + _both("rg", 1000, 257, 27, 32, 32) + [_c("rg", "fwd", 65, 130, 8, 32, 32, image="fwd")]
+    # dense 1x1: KS = 2, KS = 3 (two chunks), KS = 4 (three chunks)
+    + [_c("dense", "fwd", 257, 257, 1, 64, 128, identity=1, image="fwd"), _c("dense", "fwd", 257, 257, 1, 192, 128, identity=1, image="fwd")]
+    + _both("dense", 257, 257, 1, 384, 256, identity=1)
+    # pair-array weight gradient: <1,1> <1,2> <2,2> <2,4> <3,2> <3,3> <4,2> <4,3> <4,4>, wider than one workgroup tile from 192 on
+    + [_c("wgrad_tl", "wgrad", 350, 300, 27, ci, co, swap=0) for ci, co in ((32, 32), (32, 64), (64, 64), (64, 128), (96, 64), (96, 96),
+                                                                           (128, 64), (128, 96), (128, 128), (192, 128), (256, 256), (384, 256))]
+    + [_c("wgrad_tl", "wgrad", 0, 0, 8, 256, 128, swap=1, s2="holes"), _c("wgrad_tl", "wgrad", 0, 0, 8, 32, 32, swap=1, s2="full"),
+       _c("wgrad_tl", "wgrad", 700, 700, 1, 128, 128, identity=1), _c("wgrad_tl", "wgrad", 700, 700, 1, 32, 64, identity=1)]
+    # first-generation weight gradient with 16-byte loads on both operands, 1 - 4 tiles per wave: the heads (32 / 64 / 96 / 128 -> 768)
+    # and 18D's 416 -> 384 shortcut, all identity maps
+    + [_c("wgrad1", "wgrad", 300, 300, 1, ci, co, identity=1, counts=0) for ci, co in ((32, 768), (64, 768), (96, 768), (416, 384))]
+    # first-generation output-stationary kernel (spconv.hip: spconv_fwd_x6_kernel<WM, WN, TN>), which the narrow decoders of 34A / 34B
+    # run between 8192 and 65536 rows: <2,2,1> (33 - 64 columns), <2,2,2> (from 4096 rows, 96 columns), <4,1,2> / <4,1,3> (from 32768
+    # rows, 64 / 96 columns; thin tables keep the float64 reference small)
+    + [_c("x6", "fwd", 350, 300, 27, 128, 64), _c("x6", "fwd", 4300, 4100, 27, 64, 96, 0.05),
+       _c("x6", "fwd", 30000, 32800, 27, 128, 64, 0.03), _c("x6", "fwd", 30000, 32800, 27, 64, 96, 0.03)]
+    # stem from 4096 rows on: four lanes per output row (stem_fwd4_kernel)
+    + [_c("stem_fp32", "fwd", 4300, 4100, 125, 3, 32, 0.12), _c("stem_fp32", "fwd", 4300, 4100, 27, 4, 32)]
+)
 CASE_IDS = [c.id for c in CASES]
 
 
@@ -316,3 +372,139 @@ def reference(case, kind):
     """abs_sum_bounds of a resolved case's operands, computed once per (shape, kind): the forward and the weight-gradient case of one
     shape share it."""
     return _reference(case.n_in, case.n_out, case.K, case.cin, case.cout, case.occ, case.opt.get("s2"), bool(case.opt.get("identity")), kind)
+
+
+# -------------------------------------------------------------------------------------------------------------- the launches
+class Launch:
+    """The kernel of a resolved case, ready to run on features (and an output gradient) that live on `device`: the GPU in
+    test_gpu_conv_bounds.py, the host under the null runtime of the instance census (conv_census.py)."""
+
+    def __init__(self, case, nbr, device):
+        from openscene_amd import ops
+        self.ops, self.case, self.nbr_np = ops, case, nbr
+        d = device
+        self.nbr = torch.from_numpy(np.ascontiguousarray(nbr)).to(d) if nbr is not None else None
+        self.tl = self.rows = self.counts = None
+        f, o = case.family, case.opt
+        if f == "rg" and o.get("perm"):
+            g = torch.Generator().manual_seed(3)
+            perm = torch.randperm(case.n_out, generator=g)
+            self.nbr, self.rows = self.nbr[:, perm.to(d)].contiguous(), perm.int().to(d)
+        if f == "tl" or (f in ("ws", "wgrad_tl") and not o.get("swap") and not o.get("identity")):
+            self.tl = ops.tile_lists(self.nbr, bm=o.get("bm"))   # (bm: a tile height other than osn_tile_rows' for this row count)
+        if o.get("s2") and f != "tl":                        # the lists of the strided convolution this launch mirrors
+            self.tl = ops.tile_lists(torch.from_numpy(stride2_map(o["s2"])[0]).to(d))
+        if f == "wgrad1" and o.get("counts"):
+            self.counts = ops.kmap_count(self.nbr)
+        if f == "tl":                                        # the case is where its name says: a split launch, or one persistent launch
+            wsb = int(ops._cached("osn_spconv_fwd_tl_ws_bytes", case.n_out, case.K, case.cout, self.tl.bm))
+            assert (wsb > 512) == bool(o["split"]) and (o["split"] or self.tl.n_tiles > 1)
+        if f == "rg":
+            assert ops.rg_eligible(case.K, case.cin, case.cout, case.n_in)
+        if f in ("stem_fp32", "stem_mfma"):
+            assert ops.stem_eligible(case.K, case.cin, case.cout) and (case.n_out >= 32768) == (f == "stem_mfma")
+
+    def image(self, w):
+        """The weight image the launch multiplies with: the forward image of w, or the input-gradient image of the transposed weight
+        (the same matrix per offset, through the other preparation path)."""
+        ops = self.ops
+        if self.case.opt.get("image") == "dgrad":
+            return ops.weight_prep_tl(w.transpose(1, 2).contiguous(), flip=False, want_fwd=False)[1]
+        return ops.weight_prep_tl(w, want_dgrad=False)[0]
+
+    def fwd(self, feats, w, bn_partial=None):
+        ops, c, o = self.ops, self.case, self.case.opt
+        if c.family in ("stem_fp32", "stem_mfma"):
+            return ops.stem_conv_fwd(feats, w, self.nbr, c.n_out)
+        if c.family == "x6":
+            assert ops.x6_eligible(c.K, c.cin, c.cout, c.n_out)
+            return ops.spconv_fwd_x6(feats, ops.weight_prep_x6(w), self.nbr, c.n_out)
+        wp = self.image(w)
+        if c.family == "rg":
+            return ops.spconv_fwd_rg(feats, wp, self.nbr, c.n_out, c.cout, out_rows=self.rows)
+        if c.family == "ws":
+            return ops.spconv_fwd_ws(feats, wp, self.tl, None if o["direct"] else self.nbr, c.n_out, c.K, c.cout,
+                                     swap=bool(o["swap"]), direct=bool(o["direct"]))
+        if c.family == "tl":
+            return ops.spconv_fwd_tl(feats, wp, self.tl, c.n_out, c.K, c.cout, bn_partial=bn_partial)
+        assert c.family == "dense" and ops.dense_eligible(c.cin, c.cout)
+        return ops.dense_fwd(feats, wp, c.cout)
+
+    def wgrad(self, feats, gout):
+        ops, c, o = self.ops, self.case, self.case.opt
+        if c.family in ("stem_fp32", "stem_mfma"):
+            return ops.stem_conv_wgrad(feats, gout, self.nbr, c.K)
+        if c.family == "wgrad_tl":
+            return ops.spconv_wgrad_tl(feats, gout, self.tl, c.K, swap=bool(o.get("swap")))
+        assert c.family == "wgrad1"
+        return ops.spconv_wgrad(feats, gout, self.nbr, c.K, self.counts)
+
+
+# ------------------------------------------------------------------------------------------- the batched weight-gradient reduction
+# What every executor backward runs: osn_spconv_wgrad_tl_partial per convolution, then osn_wgrad_tl_reduce_batch over all of them, one
+# launch per 32 jobs.  BATCH_JOBS live jobs reach the second launch with a ragged last batch (one job); one of them is a map without
+# any pair, and one more entry has no rows at all (its job is skipped: gW is zeroed by the first call).
+BATCH_JOBS = 33
+EMPTY_MAP = _c("wgrad_tl", "wgrad", 120, 100, 27, 64, 64, 0.0, swap=0)        # rows on both sides, every table entry -1
+NO_ROWS = _c("wgrad_tl", "wgrad", 0, 0, 1, 64, 32, identity=1)
+
+
+def batch_plan():
+    """[(case, operand kind)]: the pair-array weight-gradient cases in turn (mixed shapes, swap launches, identity maps) with the
+    operand kinds in turn, the map without pairs as the last live job, then the entry without rows."""
+    wg = [c for c in CASES if c.family == "wgrad_tl"]
+    plan = [(wg[i % len(wg)], KINDS[i % len(KINDS)]) for i in range(BATCH_JOBS - 1)]
+    return plan + [(EMPTY_MAP, "row_scales"), (NO_ROWS, "row_scales")]
+
+
+def batch_operands(case, kind):
+    """(features, output gradient) of a resolved case of batch_plan()."""
+    if case.id in (EMPTY_MAP.id, NO_ROWS.id):
+        g = torch.Generator().manual_seed(_seed("batch", case.id))
+        return adversarial(kind, case.n_in, case.cin, g), adversarial(kind, case.n_out, case.cout, g)
+    feats, _w, gout = operands(case, kind)
+    return feats, gout
+
+
+def batch_entries(launch_of, place, zeros=False):
+    """[(Launch, features, output gradient)] of batch_plan(), the input of batched_wgrad.  launch_of(case) -> (resolved case, table,
+    Launch); place(tensor) -> the operand where the launch wants it; zeros: operands of the right shapes only (the instance census)."""
+    entries = []
+    for case, kind in batch_plan():
+        rc, _nbr, run = launch_of(case)
+        if zeros:
+            feats, gout = torch.zeros(rc.n_in, rc.cin), torch.zeros(rc.n_out, rc.cout)
+        else:
+            feats, gout = batch_operands(rc, kind)
+        entries.append((run, place(feats), place(gout)))
+    return entries
+
+
+class WgradJob(ctypes.Structure):                # osn_wgrad_job (include/openscene_amd.h)
+    _fields_ = [("partial", ctypes.c_void_p), ("range", ctypes.c_void_p), ("gW", ctypes.c_void_p), ("K", ctypes.c_int32),
+                ("cin", ctypes.c_int32), ("cout", ctypes.c_int32), ("ident_items", ctypes.c_int32)]
+
+
+def batched_wgrad(entries, device):
+    """entries: [(Launch of a pair-array weight-gradient case, features, output gradient)] on `device` -> ([gW], the job array):
+    one osn_spconv_wgrad_tl_partial per entry, each into a partial buffer of its own, then ONE osn_wgrad_tl_reduce_batch."""
+    from openscene_amd import ops
+    assert ctypes.sizeof(WgradJob) == 40
+    lib = ops._prep(device)
+    jobs = (WgradJob * len(entries))()
+    partials, out = [], []
+    with ops._Dev(device):
+        for i, (run, feats, gout) in enumerate(entries):
+            c = run.case
+            pl = ops.pair_lists(run.tl) if run.tl is not None else None
+            gw = torch.full((c.K, c.cin, c.cout), float("nan"), dtype=torch.float32, device=device)
+            nbytes = int(ops._cached("osn_spconv_wgrad_tl_ws_bytes", c.K, c.cin, c.cout))
+            partial = torch.empty(nbytes, dtype=torch.uint8, device=device)
+            ops.check(lib.osn_spconv_wgrad_tl_partial(ops._p(feats), ops._p(gout), ops._p(pl), int(bool(c.opt.get("swap"))), ops._p(gw),
+                                                      feats.shape[0], gout.shape[0], c.K, c.cin, c.cout, ops._p(partial), nbytes,
+                                                      ctypes.addressof(jobs) + i * ctypes.sizeof(WgradJob), ops._stream(device)),
+                      "osn_spconv_wgrad_tl_partial")
+            partials.append(partial)
+            out.append(gw)
+        ops.check(lib.osn_wgrad_tl_reduce_batch(ctypes.addressof(jobs), len(entries), ops._stream(device)), "osn_wgrad_tl_reduce_batch")
+    return out, jobs

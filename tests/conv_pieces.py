@@ -74,3 +74,20 @@ def distance(a, b, bound):
     """Worst |a - b| in units of FWD_C * abs-sum (+ half an ulp of b + the floor): how far two results sit from each other on the
     scale the first bound is asked on."""
     return cb.worst_ratio(a, b, bound, cb.FWD_C)[0]
+
+
+class PiecesLaunch(cb.Launch):
+    """conv_bounds.Launch whose forward takes the operand-piece count (3: the entry conv_bounds.Launch calls)."""
+
+    def fwd(self, feats, w, pieces=3, bn_partial=None):
+        ops, c, o = self.ops, self.case, self.case.opt
+        wp = self.image(w)
+        if c.family == "rg":
+            return ops.spconv_fwd_rg(feats, wp, self.nbr, c.n_out, c.cout, out_rows=self.rows, pieces=pieces)
+        if c.family == "ws":
+            return ops.spconv_fwd_ws(feats, wp, self.tl, None if o["direct"] else self.nbr, c.n_out, c.K, c.cout,
+                                     swap=bool(o["swap"]), direct=bool(o["direct"]), pieces=pieces)
+        if c.family == "tl":
+            return ops.spconv_fwd_tl(feats, wp, self.tl, c.n_out, c.K, c.cout, bn_partial=bn_partial, pieces=pieces)
+        assert c.family == "dense" and ops.dense_eligible(c.cin, c.cout)
+        return ops.dense_fwd(feats, wp, c.cout, pieces=pieces)

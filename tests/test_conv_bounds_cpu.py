@@ -13,6 +13,8 @@ Stem, small maps (exact fp32 products, one fmaf chain in ascending offset order)
                                   piece_aligned 0.25 | 0.02
     K = 27,  cin = 4, 1000 rows:  row_scales 0.23 | 0.02, cancellation 0.01 | 0.01, gradient_sized 0.10 | 0.00, wide_elements 0.18 | 0.02,
                                   piece_aligned 0.26 | 0.01
+    K = 125, cin = 3, 4100 rows:  row_scales 0.27, cancellation 0.08, gradient_sized 0.11, wide_elements 0.26, piece_aligned 0.31  (forward)
+    K = 27,  cin = 4, 4100 rows:  row_scales 0.24, cancellation 0.01, gradient_sized 0.13, wide_elements 0.24, piece_aligned 0.22  (forward)
 (forward against 2e-6, weight gradient against 2e-5 of the abs-sum.)  No kind exceeds the project's constants, so the stem's fp32 kernels are held to 2e-6 / 2e-5 like every other family
 (STEM_FP32_BOUNDS stays empty)."""
 import pytest

@@ -8,19 +8,28 @@ Bounds: 2e-6 of the abs-sum for a forward / input-gradient launch, 2e-5 for a we
 "piece_aligned" (conv_bounds.PIECE_WGRAD_C: at 2e-5 a lost h2h2 / h1h3 / h3h1 product cannot show).  The stem's exact-fp32 kernels
 take no bound from the CPU chain: the chain meets the project's constants on every kind (figures: test_conv_bounds_cpu.py).
 
+The cases are conv_bounds.CASES: per family the edge shapes, and per kernel INSTANCE a shipped network can launch the smallest shape
+that reaches it (tile-list <NW, KS, ragged, OCC>, weight-stationary <NW, KS>, pair-array weight gradient <MB, NB>, the four
+register-gather and dense instances, the first-generation forward and weight-gradient instances, the three stem forward kernels);
+test_conv_census_cpu.py lists both sets without a GPU and fails when a network's instance has no case.
+
 Worst err / lim per family and kind, measured on an MI355X (the assertion message prints the same figure):
 (worst over the family's cases; forward rows against 2e-6, weight-gradient rows against 2e-5, last column against 2e-6)
-    family          row_scales     cancellation   gradient_sized wide_elements  piece_aligned  piece@2e-6     
-    rg fwd          0.14           0.01           0.06           0.19           0.46           -              
-    stem_fp32 fwd   0.23           0.08           0.12           0.27           0.26           -              
-    stem_fp32 wgrad 0.02           0.01           0.01           0.02           0.02           0.17           
-    stem_mfma fwd   0.18           0.09           0.10           0.20           0.28           -              
-    stem_mfma wgrad 0.01           0.00           0.00           0.01           0.01           0.13           
-    ws fwd          0.10           0.01           0.10           0.24           0.32           -              
-    tl fwd          0.24           0.01           0.14           0.42           0.72           -              
-    wgrad_tl wgrad  0.03           0.03           0.01           0.03           0.05           0.51           
-    wgrad1 wgrad    0.03           0.03           0.01           0.05           0.07           0.64           
-    dense fwd       0.12           0.02           0.09           0.30           0.93           -              
+    family          row_scales     cancellation   gradient_sized wide_elements  piece_aligned  piece@2e-6
+    rg fwd          0.14           0.01           0.06           0.19           0.46           -
+    stem_fp32 fwd   0.23           0.08           0.12           0.27           0.26           -
+    stem_fp32 wgrad 0.02           0.01           0.01           0.02           0.02           0.17
+    stem_mfma fwd   0.18           0.09           0.10           0.20           0.28           -
+    stem_mfma wgrad 0.01           0.00           0.00           0.01           0.01           0.13
+    ws fwd          0.10           0.01           0.12           0.29           0.58           -
+    tl fwd          0.24           0.01           0.14           0.42           0.72           -
+    wgrad_tl wgrad  0.04           0.04           0.01           0.04           0.05           0.51
+    wgrad1 wgrad    0.04           0.04           0.01           0.05           0.08           0.74
+    dense fwd       0.12           0.02           0.12           0.32           0.93           -
+    x6 fwd          0.14           0.01           0.13           0.30           0.65           -
+Where each family's worst sits: rg 64 -> 64 at K = 125; ws 256 -> 128 on the stride-2 map (swap); tl the persistent 32 -> 512 launch
+(the widest shapes: 384 -> 256 0.35, 416 -> 128 0.37); wgrad_tl 64 -> 20; wgrad1 the 64 -> 768 head; dense 768 -> 96 (384 -> 256:
+0.65); x6 128 -> 64 at 32 800 rows.
 """
 import hashlib
 
@@ -37,74 +46,13 @@ def dev():
     return torch.device("cuda", 0)
 
 
-class Launch:
-    """The kernel of a case, ready to run on features (and an output gradient) that live on the device."""
-
-    def __init__(self, case, nbr):
-        from openscene_amd import ops
-        self.ops, self.case, self.nbr_np = ops, case, nbr
-        d = dev()
-        self.nbr = torch.from_numpy(np.ascontiguousarray(nbr)).to(d) if nbr is not None else None
-        self.tl = self.rows = self.counts = None
-        f, o = case.family, case.opt
-        if f == "rg" and o.get("perm"):
-            g = torch.Generator().manual_seed(3)
-            perm = torch.randperm(case.n_out, generator=g)
-            self.nbr, self.rows = self.nbr[:, perm.to(d)].contiguous(), perm.int().to(d)
-        if f == "tl" or (f in ("ws", "wgrad_tl") and not o.get("swap") and not o.get("identity")):
-            self.tl = ops.tile_lists(self.nbr)
-        if o.get("s2"):                                      # the lists of the strided convolution this launch mirrors
-            self.tl = ops.tile_lists(torch.from_numpy(cb.stride2_map(o["s2"])[0]).to(d))
-        if f == "wgrad1" and o.get("counts"):
-            self.counts = ops.kmap_count(self.nbr)
-        if f == "tl":                                        # the case is where its name says: a split launch, or one persistent launch
-            wsb = int(ops._cached("osn_spconv_fwd_tl_ws_bytes", case.n_out, case.K, case.cout, self.tl.bm))
-            assert (wsb > 512) == bool(o["split"]) and (o["split"] or self.tl.n_tiles > 1)
-        if f == "rg":
-            assert ops.rg_eligible(case.K, case.cin, case.cout, case.n_in)
-        if f in ("stem_fp32", "stem_mfma"):
-            assert ops.stem_eligible(case.K, case.cin, case.cout) and (case.n_out >= 32768) == (f == "stem_mfma")
-
-    def image(self, w):
-        """The weight image the launch multiplies with: the forward image of w, or the input-gradient image of the transposed weight
-        (the same matrix per offset, through the other preparation path)."""
-        ops = self.ops
-        if self.case.opt.get("image") == "dgrad":
-            return ops.weight_prep_tl(w.transpose(1, 2).contiguous(), flip=False, want_fwd=False)[1]
-        return ops.weight_prep_tl(w, want_dgrad=False)[0]
-
-    def fwd(self, feats, w, bn_partial=None):
-        ops, c, o = self.ops, self.case, self.case.opt
-        if c.family in ("stem_fp32", "stem_mfma"):
-            return ops.stem_conv_fwd(feats, w, self.nbr, c.n_out)
-        wp = self.image(w)
-        if c.family == "rg":
-            return ops.spconv_fwd_rg(feats, wp, self.nbr, c.n_out, c.cout, out_rows=self.rows)
-        if c.family == "ws":
-            return ops.spconv_fwd_ws(feats, wp, self.tl, None if o["direct"] else self.nbr, c.n_out, c.K, c.cout,
-                                     swap=bool(o["swap"]), direct=bool(o["direct"]))
-        if c.family == "tl":
-            return ops.spconv_fwd_tl(feats, wp, self.tl, c.n_out, c.K, c.cout, bn_partial=bn_partial)
-        assert c.family == "dense" and ops.dense_eligible(c.cin, c.cout)
-        return ops.dense_fwd(feats, wp, c.cout)
-
-    def wgrad(self, feats, gout):
-        ops, c, o = self.ops, self.case, self.case.opt
-        if c.family in ("stem_fp32", "stem_mfma"):
-            return ops.stem_conv_wgrad(feats, gout, self.nbr, c.K)
-        if c.family == "wgrad_tl":
-            return ops.spconv_wgrad_tl(feats, gout, self.tl, c.K, swap=bool(o.get("swap")))
-        assert c.family == "wgrad1"
-        return ops.spconv_wgrad(feats, gout, self.nbr, c.K, self.counts)
-
-
 _LAUNCHES = {}
 
 
 def launch_of(case):
     if case.id not in _LAUNCHES:
         rc, nbr = cb.resolve(case)
-        _LAUNCHES[case.id] = (rc, nbr, Launch(rc, nbr))
+        _LAUNCHES[case.id] = (rc, nbr, cb.Launch(rc, nbr, dev()))
     return _LAUNCHES[case.id]
 
 
