@@ -1299,6 +1299,22 @@ typedef struct osn_map_job {
 int osn_maps_build(const osn_map_level* levels, int n_levels, const osn_map_job* jobs, int n_jobs,
                    const osn_stream_t* streams, void* const* ws, const uint64_t* ws_bytes, int n_streams,
                    osn_events_t* events);
+/* osn_maps_build with block occupancy: occ[l] (nullable, as the array itself) = a buffer of osn_maps_occupancy_bytes(rows of level
+ * l) bytes, 8-byte aligned.  A level that has one gets a second hash table over the 4^3 blocks of its cells (one 64-bit word of cell
+ * bits per block; one launch in front of the level's first probed 3^3 / 5^3 self map, on its stream), and such self maps look up the
+ * block words around a row and probe the coordinate table only where a cell is occupied -- a scene is a surface, most cells of a 5^3
+ * neighbourhood are empty.  The rows of the level must be multiples of the job's `scale` for this to pay (the kernel finds out and
+ * otherwise probes every offset).  Same tables, bit for bit.                                                                   */
+size_t osn_maps_occupancy_bytes(int64_t rows);
+int osn_maps_build_occ(const osn_map_level* levels, int n_levels, const osn_map_job* jobs, int n_jobs,
+                       const osn_stream_t* streams, void* const* ws, const uint64_t* ws_bytes, int n_streams,
+                       osn_events_t* events, void* const* occ);
+/* By default a 3^3 self map that follows a 5^3 self map of the same level and scale in `jobs` is copied out of the finished 5^3
+ * table (27 of its 125 offset rows, and their counts) on the 5^3 job's stream -- no hash probe, no preset -- and
+ * osn_pair_lists_build plans the work items in workgroup 0 of its fill launch.  Tests and A/B only, process-wide: on != 0 runs
+ * the earlier launch sequence (every self map probed at every offset, occ ignored, pair_plan_kernel a launch of its own).  Every
+ * product is bit for bit the same either way.  Returns the previous setting.                                                 */
+int osn_maps_set_legacy(int on);
 
 /* Launch timer for the executor (bench.py's roofline entry): HIP events recorded on the launch stream around the
  * convolution launches of selected stages.  tag = op * 4 + phase (0 forward, 1 input gradient, 2 weight gradient).

@@ -99,6 +99,9 @@ PROTOTYPES = {
     "osn_net_forward": (_i32, [_vp, _vp, _vp]),
     "osn_net_backward": (_i32, [_vp, _vp, _vp]),
     "osn_maps_build": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp]),
+    "osn_maps_occupancy_bytes": (_sz, [_i64]),
+    "osn_maps_build_occ": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _vp, _i32, _vp, _vp]),
+    "osn_maps_set_legacy": (_i32, [_i32]),
     "osn_events_create": (_vp, [_i32]),
     "osn_events_destroy": (None, [_vp]),
     "osn_prof_create": (_vp, [_i32]),

@@ -268,6 +268,138 @@ __global__ void kmap_build_self_kernel(const uint64_t* __restrict__ keys, const 
     }
 }
 
+// ---- block occupancy (coords_impl.h: OccView).  One thread per row: claim the slot of the row's 4^3 block, set the cell's bit.
+// The word is an OR over the rows, so its value does not depend on the order of the threads.
+__global__ void occ_fill_kernel(const int4* __restrict__ coords, int64_t n, int scale, uint64_t* __restrict__ okeys,
+                                unsigned long long* __restrict__ owords, uint32_t omask, int32_t* __restrict__ bad) {
+    const int64_t o = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    if (o >= n) return;
+    const int4 p = coords[o];
+    const int lim = COORD_BIAS - 1;
+    const int xq = floor_div(p.y, scale), yq = floor_div(p.z, scale), zq = floor_div(p.w, scale);
+    if (p.x < 0 || p.x >= 0xFFFF || p.y < -lim || p.y > lim || p.z < -lim || p.z > lim || p.w < -lim || p.w > lim ||
+        xq * scale != p.y || yq * scale != p.z || zq * scale != p.w) {
+        *bad = 1;
+        return;
+    }
+    const uint64_t key = pack_key(p.x, xq >> 2, yq >> 2, zq >> 2);
+    uint32_t slot = hash_key(key) & omask;
+    while (true) {
+        unsigned long long prev = atomicCAS(reinterpret_cast<unsigned long long*>(&okeys[slot]),
+                                            (unsigned long long)KEY_EMPTY, (unsigned long long)key);
+        if (prev == KEY_EMPTY || prev == key) break;
+        slot = (slot + 1) & omask;
+    }
+    atomicOr(&owords[slot], 1ull << ((xq & 3) + 4 * (yq & 3) + 16 * (zq & 3)));
+}
+
+__device__ inline unsigned long long occ_find(const uint64_t* __restrict__ okeys, const unsigned long long* __restrict__ owords,
+                                              uint32_t omask, uint64_t key) {
+    uint32_t slot = hash_key(key) & omask;
+    while (true) {
+        const uint64_t k = okeys[slot];
+        if (k == key) return owords[slot];
+        if (k == KEY_EMPTY) return 0ull;
+        slot = (slot + 1) & omask;
+    }
+}
+
+// kmap_build_self_kernel for KS = 3 / 5 that probes only occupied cells.  blockIdx.y = the kernel's z plane iz <= KS / 2; a thread
+// owns a row and the plane's offsets below the centre (all KS^2 of a plane under the centre's, the first KS^2 / 2 of the centre's):
+// the cells of one plane lie in at most 2 x 2 blocks, whose words give the plane's occupancy mask; table_find runs where a bit is
+// set.  Entries, mirrored entries, the centre's identity and the counts are those of kmap_build_self_kernel; consecutive threads
+// store consecutive entries of a table row.  *bad (occ_fill_kernel): the words do not describe the rows -- every offset is probed.
+template <int KS>
+__global__ __launch_bounds__(256) void kmap_build_self_occ_kernel(const uint64_t* __restrict__ keys, const int32_t* __restrict__ vals,
+                                                                  uint32_t mask, const uint64_t* __restrict__ okeys,
+                                                                  const unsigned long long* __restrict__ owords, uint32_t omask,
+                                                                  const int32_t* __restrict__ bad, const int4* __restrict__ coords,
+                                                                  int64_t n, int scale, int32_t* __restrict__ nbr,
+                                                                  unsigned long long* __restrict__ counts) {
+    constexpr int C = KS / 2, K2 = KS * KS, K = K2 * KS;
+    __shared__ int cnt_s[K2];
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int iz = blockIdx.y;
+    const int nk = iz < C ? K2 : K2 / 2;
+    if (tid < K2) cnt_s[tid] = 0;
+    __syncthreads();
+    const int64_t o = int64_t(blockIdx.x) * blockDim.x + tid;
+    const bool live = o < n;
+    int4 p = make_int4(0, 0, 0, 0);
+    uint32_t m = 0;                                  // bit k2: offset k2 of the plane may have a neighbour
+    if (live) {
+        p = coords[o];
+        if (*bad) {
+            m = 0xFFFFFFFFu;
+        } else {
+            const int xq = p.y / scale, yq = p.z / scale, zq = p.w / scale;        // exact (occ_fill_kernel checked every row)
+            const int zc = zq + iz - C;
+            const int bz = zc >> 2, zb = 16 * (zc & 3);
+            const int bx0 = (xq - C) >> 2, bx1 = (xq + C) >> 2, by0 = (yq - C) >> 2, by1 = (yq + C) >> 2;
+            const unsigned long long w00 = occ_find(okeys, owords, omask, pack_key(p.x, bx0, by0, bz));
+            const unsigned long long w01 = bx1 != bx0 ? occ_find(okeys, owords, omask, pack_key(p.x, bx1, by0, bz)) : w00;
+            const unsigned long long w10 = by1 != by0 ? occ_find(okeys, owords, omask, pack_key(p.x, bx0, by1, bz)) : w00;
+            const unsigned long long w11 = by1 != by0 ? (bx1 != bx0 ? occ_find(okeys, owords, omask, pack_key(p.x, bx1, by1, bz)) : w10) : w01;
+#pragma unroll
+            for (int iy = 0; iy < KS; ++iy) {
+                const int yc = yq + iy - C;
+                const bool jy = (yc >> 2) != by0;
+#pragma unroll
+                for (int ix = 0; ix < KS; ++ix) {
+                    const int xc = xq + ix - C;
+                    const bool jx = (xc >> 2) != bx0;
+                    const unsigned long long w = jy ? (jx ? w11 : w10) : (jx ? w01 : w00);
+                    m |= uint32_t((w >> (zb + 4 * (yc & 3) + (xc & 3))) & 1ull) << (iy * KS + ix);
+                }
+            }
+        }
+    }
+    const int lim = COORD_BIAS - 1;
+    for (int k2 = 0; k2 < nk; ++k2) {
+        int r = -1;
+        if ((m >> k2) & 1u) {
+            const int x = p.y + (k2 % KS - C) * scale, y = p.z + (k2 / KS - C) * scale, z = p.w + (iz - C) * scale;
+            if (x >= -lim && x <= lim && y >= -lim && y <= lim && z >= -lim && z <= lim)
+                r = table_find(keys, vals, mask, pack_key(p.x, x, y, z));
+        }
+        const int k = iz * K2 + k2;
+        if (live) {
+            nbr[int64_t(k) * n + o] = r;
+            if (r >= 0) nbr[int64_t(K - 1 - k) * n + r] = int(o);
+        }
+        const unsigned long long b = __ballot(r >= 0);
+        if (lane == 0 && b) atomicAdd(&cnt_s[k2], __popcll(b));
+    }
+    if (iz == C) {                                   // centre: every row is its own neighbour
+        if (live) nbr[int64_t(K / 2) * n + o] = int(o);
+        if (counts && blockIdx.x == 0 && tid == 0) counts[K / 2] = (unsigned long long)n;
+    }
+    __syncthreads();
+    if (counts && tid < nk) {                        // pairs per offset: one atomic per workgroup, as kmap_build_self_kernel
+        const int c = cnt_s[tid];
+        if (c) {
+            const int k = iz * K2 + tid;
+            atomicAdd(&counts[k], (unsigned long long)c);
+            atomicAdd(&counts[K - 1 - k], (unsigned long long)c);
+        }
+    }
+}
+
+// Self map of the odd kernel `ksize` out of the finished self map of the wider odd kernel `kbig` (same rows, same offset scale):
+// offset (ix, iy, iz) of the small kernel is offset (ix + d, iy + d, iz + d), d = (kbig - ksize) / 2, of the wide one, so row k of
+// the table and counts[k] are copies.  blockIdx.y = offset of the small kernel.
+__global__ void kmap_derive_self_kernel(const int32_t* __restrict__ nbr_big, const unsigned long long* __restrict__ counts_big,
+                                        int kbig, int64_t n, int ksize, int32_t* __restrict__ nbr,
+                                        unsigned long long* __restrict__ counts) {
+    const int64_t o = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
+    const int k = blockIdx.y;
+    const int d = (kbig - ksize) / 2;
+    const int ix = k % ksize, iy = (k / ksize) % ksize, iz = k / (ksize * ksize);
+    const int kb = (ix + d) + kbig * ((iy + d) + kbig * (iz + d));
+    if (o < n) nbr[int64_t(k) * n + o] = nbr_big[int64_t(kb) * n + o];
+    if (counts && blockIdx.x == 0 && threadIdx.x == 0) counts[k] = counts_big[kb];
+}
+
 __global__ void kmap_transpose_kernel(const int32_t* __restrict__ nbr, int64_t n_out, int64_t n_in,
                                       int32_t* __restrict__ tbl) {
     const int64_t o = int64_t(blockIdx.x) * blockDim.x + threadIdx.x;
@@ -542,6 +674,50 @@ int osn::kmap_build_self_impl(const uint64_t* table_keys, const int32_t* table_v
     const int T = 256;
     hipLaunchKernelGGL(kmap_build_self_kernel, dim3(cdiv(n, T), K / 2 + 1), dim3(T), 0, st, table_keys, table_vals,
                        uint32_t(cap - 1), reinterpret_cast<const int4*>(coords4), n, ksize, offset_scale, nbr,
+                       reinterpret_cast<unsigned long long*>(counts));
+    OSN_LAUNCH_CHECK();
+    return OSN_OK;
+}
+
+int osn::occ_fill_impl(const OccView& occ, const int32_t* coords4, int64_t n, int scale, hipStream_t st) {
+    OSN_REQUIRE(n >= 1 && n < (int64_t(1) << 31) && scale >= 1 && coords4 && aligned16(coords4) && occ.bad && occ.cap >= 2 * n &&
+                    (reinterpret_cast<uintptr_t>(occ.bad) & 7u) == 0,
+                OSN_E_ARG, "occ_fill: bad arguments (%lld rows, scale %d)", (long long)n, scale);
+    const int T = 256;
+    hipLaunchKernelGGL(occ_fill_kernel, dim3(cdiv(n, T)), dim3(T), 0, st, reinterpret_cast<const int4*>(coords4), n, scale, occ.keys,
+                       occ.words, uint32_t(occ.cap - 1), occ.bad);
+    OSN_LAUNCH_CHECK();
+    return OSN_OK;
+}
+
+int osn::kmap_build_self_occ_impl(const uint64_t* table_keys, const int32_t* table_vals, int64_t cap, const OccView& occ,
+                                  const int32_t* coords4, int64_t n, int ksize, int offset_scale, int32_t* nbr, int64_t* counts,
+                                  hipStream_t st) {
+    OSN_REQUIRE(ksize == 3 || ksize == 5, OSN_E_ARG, "kmap_build_self_occ: ksize=%d", ksize);
+    OSN_REQUIRE(cap >= 2 && (cap & (cap - 1)) == 0 && n >= 1 && offset_scale >= 1, OSN_E_ARG, "kmap_build_self_occ: cap / rows / scale");
+    OSN_REQUIRE(table_keys && table_vals && coords4 && nbr && occ.bad && aligned16(coords4), OSN_E_ARG, "kmap_build_self_occ: null pointer");
+    const int T = 256;
+    const dim3 grid(cdiv(n, T), ksize / 2 + 1);
+    const int4* c4 = reinterpret_cast<const int4*>(coords4);
+    unsigned long long* cnt = reinterpret_cast<unsigned long long*>(counts);
+    if (ksize == 3)
+        hipLaunchKernelGGL(kmap_build_self_occ_kernel<3>, grid, dim3(T), 0, st, table_keys, table_vals, uint32_t(cap - 1), occ.keys,
+                           occ.words, uint32_t(occ.cap - 1), occ.bad, c4, n, offset_scale, nbr, cnt);
+    else
+        hipLaunchKernelGGL(kmap_build_self_occ_kernel<5>, grid, dim3(T), 0, st, table_keys, table_vals, uint32_t(cap - 1), occ.keys,
+                           occ.words, uint32_t(occ.cap - 1), occ.bad, c4, n, offset_scale, nbr, cnt);
+    OSN_LAUNCH_CHECK();
+    return OSN_OK;
+}
+
+int osn::kmap_derive_self_impl(const int32_t* nbr_big, const int64_t* counts_big, int ksize_big, int64_t n, int ksize, int32_t* nbr,
+                               int64_t* counts, hipStream_t st) {
+    OSN_REQUIRE(ksize >= 1 && (ksize & 1) && (ksize_big & 1) && ksize < ksize_big && ksize_big <= 7, OSN_E_ARG,
+                "kmap_derive_self: kernel %d out of kernel %d", ksize, ksize_big);
+    OSN_REQUIRE(n >= 1 && nbr_big && nbr && (counts_big || !counts), OSN_E_ARG, "kmap_derive_self: null pointer or no rows");
+    const int T = 256;
+    hipLaunchKernelGGL(kmap_derive_self_kernel, dim3(cdiv(n, T), ksize * ksize * ksize), dim3(T), 0, st, nbr_big,
+                       reinterpret_cast<const unsigned long long*>(counts_big), ksize_big, n, ksize, nbr,
                        reinterpret_cast<unsigned long long*>(counts));
     OSN_LAUNCH_CHECK();
     return OSN_OK;

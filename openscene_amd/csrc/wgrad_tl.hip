@@ -22,6 +22,7 @@
 #include "split.h"
 #include <cstdlib>
 #include "pairlist.h"
+#include "coords_impl.h"
 
 namespace osn {
 
@@ -62,12 +63,17 @@ __global__ __launch_bounds__(256) void pair_prefix_kernel(const int32_t* __restr
     if (tid == 0) total[k] = carry_s;
 }
 
-// pin / pout of every offset, in (tile, local row) order; workgroup 0 also publishes poff.
+__device__ inline void pair_plan(const int32_t* __restrict__ total, int K, int4* __restrict__ items, int2* __restrict__ range,
+                                 int items_max);
+
+// pin / pout of every offset, in (tile, local row) order; workgroup 0 also publishes poff and, with items (non-null), plans the
+// work items: it has read total[] anyway, and the plan was a one-workgroup launch of 512 items in front of this one.
 __global__ __launch_bounds__(256) void pair_fill_kernel(const int32_t* __restrict__ cnt, const int2* __restrict__ lst,
                                                         const int32_t* __restrict__ out_rows,
                                                         const int32_t* __restrict__ pref, const int32_t* __restrict__ total,
                                                         int n_tiles, int K, int bm, int32_t* __restrict__ pin,
-                                                        int32_t* __restrict__ pout, int32_t* __restrict__ poff) {
+                                                        int32_t* __restrict__ pout, int32_t* __restrict__ poff, int4* __restrict__ items,
+                                                        int2* __restrict__ range, int items_max) {
     __shared__ int poff_s[PL_KMAX + 1];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t tile = blockIdx.x;
@@ -96,12 +102,13 @@ __global__ __launch_bounds__(256) void pair_fill_kernel(const int32_t* __restric
             pout[base + p] = out_rows ? out_rows[r] : int(r);
         }
     }
+    if (tile == 0 && items) pair_plan(total, K, items, range, items_max);      // (uniform in the workgroup: its barriers are safe)
 }
 
 // Work items: every offset's pairs cut into ranges of `quota` pairs (quota: whole 32-pair steps, at least
-// PL_MIN_QUOTA, such that at most PL_ITEMS items exist).  One workgroup.
-__global__ __launch_bounds__(256) void pair_plan_kernel(const int32_t* __restrict__ total, int K, int4* __restrict__ items,
-                                                        int2* __restrict__ range, int items_max) {
+// PL_MIN_QUOTA, such that at most PL_ITEMS items exist).  One workgroup of 256 threads; writes every items[t] and range[k < K].
+__device__ inline void pair_plan(const int32_t* __restrict__ total, int K, int4* __restrict__ items, int2* __restrict__ range,
+                                 int items_max) {
     __shared__ int nk[PL_KMAX];
     __shared__ int start[PL_KMAX + 1];
     __shared__ int quota_s;
@@ -137,6 +144,12 @@ __global__ __launch_bounds__(256) void pair_plan_kernel(const int32_t* __restric
         }
         items[t] = it;
     }
+}
+
+// (a launch of its own: osn_maps_set_legacy)
+__global__ __launch_bounds__(256) void pair_plan_kernel(const int32_t* __restrict__ total, int K, int4* __restrict__ items,
+                                                        int2* __restrict__ range, int items_max) {
+    pair_plan(total, K, items, range, items_max);
 }
 
 // ------------------------------------------------------------------------------------- the kernel
@@ -427,9 +440,10 @@ extern "C" int osn_pair_lists_build(const void* tl, const int32_t* out_rows, int
     // items per map: PL_ITEMS (one round of two workgroups per CU).  Fewer, longer items (less partial-sum traffic for the reduction,
     // less parallelism for the kernel) were measured per step: 256 items +0.02 .. +0.13 ms, 384 equal (profiles/r05_s1_knobs_ab.txt)
     const int items_max = PL_ITEMS;
-    hipLaunchKernelGGL(pair_plan_kernel, dim3(1), dim3(256), 0, st, v.total, K, v.items, v.range, items_max);
+    const bool own_plan = maps_legacy();
+    if (own_plan) hipLaunchKernelGGL(pair_plan_kernel, dim3(1), dim3(256), 0, st, v.total, K, v.items, v.range, items_max);
     hipLaunchKernelGGL(pair_fill_kernel, dim3(unsigned(nt)), dim3(256), 0, st, cnt, lst, out_rows, v.pref, v.total, int(nt), K,
-                       bm, v.pin, v.pout, v.poff);
+                       bm, v.pin, v.pout, v.poff, own_plan ? nullptr : v.items, v.range, items_max);
     OSN_LAUNCH_CHECK();
     return OSN_OK;
 }

@@ -346,10 +346,12 @@ def _addr(v):
     return 0 if v is None else (int(v) if isinstance(v, int) else v.data_ptr())
 
 
-def maps_build(levels, jobs, dev, sort_rows, streams=None):
+def maps_build(levels, jobs, dev, sort_rows, streams=None, occ=None):
     """levels: [(coords4, HashTable, rows)]; jobs: list of dicts with the fields of osn_map_job (tensors, device addresses
     or None for the pointers, `stream` = 0 .. MAPS_STREAMS - 1); sort_rows: rows of the largest table that gets tile-ordered (scratch
-    size).  One C call; the maps of different levels run side by side on MAPS_STREAMS streams (fork / join inside)."""
+    size).  One C call; the maps of different levels run side by side on MAPS_STREAMS streams (fork / join inside).
+    occ: per level a buffer of maps_occupancy_bytes(rows) bytes (tensor, device address) or None -- the level's 3^3 / 5^3 self maps
+    then probe occupied cells only (osn_maps_build_occ)."""
     import numpy as np
     lib = _prep(dev)
     ldt, jdt = _map_dtypes()
@@ -381,9 +383,21 @@ def maps_build(levels, jobs, dev, sort_rows, streams=None):
     st_arr = (ctypes.c_void_p * ns)(*raws)
     ws_arr = (ctypes.c_void_p * ns)(*[w.data_ptr() for w in wss])
     wb_arr = (ctypes.c_uint64 * ns)(*[w.numel() for w in wss])
+    occ_arr = (ctypes.c_void_p * len(levels))(*[_addr(o) or None for o in occ]) if occ is not None else None
     with _Dev(dev):
-        check(lib.osn_maps_build(la.ctypes.data, len(levels), ja.ctypes.data, len(jobs), st_arr, ws_arr, wb_arr, ns, ev),
+        check(lib.osn_maps_build_occ(la.ctypes.data, len(levels), ja.ctypes.data, len(jobs), st_arr, ws_arr, wb_arr, ns, ev, occ_arr),
               "osn_maps_build")
+
+
+def maps_occupancy_bytes(rows):
+    """Bytes of a level's block-occupancy buffer (maps_build's occ)."""
+    return int(_cached("osn_maps_occupancy_bytes", int(rows)))
+
+
+def maps_set_legacy(on):
+    """Tests and A/B: run the kernel-map launches of the earlier rounds (every self map probed, the pair lists' work items planned
+    by a launch of their own), process-wide; every product is bitwise the same.  Returns the previous setting."""
+    return bool(_lib.load().osn_maps_set_legacy(int(bool(on))))
 
 
 # ----------------------------------------------------------------- convolution

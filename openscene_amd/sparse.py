@@ -190,6 +190,11 @@ class CoordinateManager:
             plan.append(e)
         if not plan:
             return
+        # block occupancy for the levels whose first self map has enough probes to repay the table's launch (ops.maps_build)
+        occ = {}
+        for e in plan:
+            if e["own"] and e["ksize"] in (3, 5) and e["lvl_in"] not in occ:
+                occ[e["lvl_in"]] = take(ops.maps_occupancy_bytes(e["n_in"])) if e["n_in"] * (e["K"] // 2) >= self.OCC_MIN_PROBES else None
         arena = torch.empty(total, dtype=torch.uint8, device=dev)
         base = arena.data_ptr()
         ptr_fields = ("nbr_fwd", "nbr_bwd", "counts", "order_fwd", "sorted_fwd", "gmask_fwd", "order_bwd", "sorted_bwd", "gmask_bwd",
@@ -202,7 +207,8 @@ class CoordinateManager:
                 if f in e:
                     q[f] = base + e[f][0]
             jobs.append(q)
-        ops.maps_build([(self._coords[s], self._tables[s], self.size(s)) for s in levels], jobs, dev, sort_rows, streams)
+        ops.maps_build([(self._coords[s], self._tables[s], self.size(s)) for s in levels], jobs, dev, sort_rows, streams,
+                       occ=[base + occ[i][0] if occ.get(i) else None for i in range(len(levels))])
 
         # ---- the launches are queued; now the views the rest of the library works with
         def view(e, f, dtype, shape):
@@ -260,6 +266,9 @@ class CoordinateManager:
     # 2^3 (strided / transposed) maps are never tile-ordered: measured per-step kernel time 14.81 ms with, 14.42 ms without
     # (tools/ab_kernel_time.sh): their eight sorts cost more than the convs of those maps gain
     SORT_MIN_ROWS_K8 = 10 ** 9
+    # a level gets a block-occupancy table (its self maps probe occupied cells only) from this many probes, rows x offsets below
+    # the centre, of its first self map: below it the table's own launch costs what the skipped probes save
+    OCC_MIN_PROBES = 400000
 
     def kmap_tiles(self, in_stride, out_stride, ksize, dilation=1):
         """Tile-ordered variants of kmap(): ((order, table) for the forward conv or None,

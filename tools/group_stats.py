@@ -16,7 +16,7 @@ def group(n):
     if 'weight_prep' in n: return 'weight prep'
     if 'bn_' in n or 'col_reduce' in n: return 'BN'
     if 'pair_' in n or 'tile_lists' in n: return 'maps: tile/pair lists'
-    if 'kmap' in n or 'rocprim' in n or 'hash_insert' in n or 'unique' in n or 'scan_' in n or 'table_renumber' in n: return 'maps: coords + tables + sort'
+    if 'kmap' in n or 'occ_fill' in n or 'rocprim' in n or 'hash_insert' in n or 'unique' in n or 'scan_' in n or 'table_renumber' in n: return 'maps: coords + tables + sort'
     if 'fillBuffer' in n or 'copyBuffer' in n: return 'memset/memcpy'
     if n.startswith('_ZN2at') or 'at::' in n: return 'torch'
     return 'other:' + n[:40]
