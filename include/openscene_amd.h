@@ -322,6 +322,25 @@ int osn_spconv_wgrad_tl_partial(const float* in, const float* gout, const void* 
                                 osn_wgrad_job* job_host, osn_stream_t stream);
 int osn_wgrad_tl_reduce_batch(const osn_wgrad_job* jobs_host, int n_jobs, osn_stream_t stream);
 
+/* ---- reduced-precision training: the `_pieces` siblings of the two weight-gradient entries -------------------------------- *
+ * The arguments of the base entry plus a trailing `int pieces`, with the meaning of the `_pieces` forward entries above: both
+ * operands (gathered input rows, gathered output-gradient rows) are split into `pieces` bf16 pieces and "ij" is kept iff
+ * i + j <= pieces + 1, in the same accumulation order; the per-item partial sums stay fp32 and are reduced in item order by the
+ * same launches (osn_wgrad_tl_reduce_batch takes the jobs of every mode), so the result is bitwise repeatable in every mode and
+ * partial + batched reduction is bitwise the one-call entry.  pieces == 3 is bitwise the base entry.  Error per element of gW, in
+ * units of the sum over the offset's pairs of |in||gout|: fp32-class (pieces 3), 2^-15 more (pieces 2), 2^-7 more (pieces 1);
+ * against the float64 sum of the kept products of the exact pieces fp32-class in every mode (tests/train_pieces.py).
+ * pieces outside {1, 2, 3}: OSN_E_ARG before anything else is looked at.  Every shape of the base entries has reduced instances
+ * (all <MB, NB> blockings, identity maps, swap, strided items, both addressing modes): none falls back to three pieces.  Workspace
+ * and job layout are those of the base entries (osn_spconv_wgrad_tl_ws_bytes).  The first-generation osn_spconv_wgrad and the
+ * stem's weight gradient have no reduced mode.                                                                              */
+int osn_spconv_wgrad_tl_pieces(const float* in, const float* gout, const void* pl, int swap, float* gW, int64_t n_in,
+                               int64_t n_out, int K, int cin, int cout, void* ws, size_t ws_bytes, osn_stream_t stream,
+                               int pieces);
+int osn_spconv_wgrad_tl_partial_pieces(const float* in, const float* gout, const void* pl, int swap, float* gW, int64_t n_in,
+                                       int64_t n_out, int K, int cin, int cout, void* partial, size_t partial_bytes,
+                                       osn_wgrad_job* job_host, osn_stream_t stream, int pieces);
+
 /* 1x1 convolution = row-wise matrix product ([ME] MinkowskiConvolution(kernel_size=1): the head `final`,
  * models/mink_unet.py:108-113, and the BasicBlock shortcuts, models/resnet_base.py:101-107; with the input-gradient image
  * their backward):  out[n, cout] = in[n, cin] @ B,  B given as an osn_weight_prep_tl image with K = 1 (forward image:
@@ -1227,6 +1246,17 @@ typedef struct osn_events osn_events_t;       /* pool of HIP events for the fork
  * launch.  osn_net_plan_query does not know the mode: arenas and workspaces are those of the exact pass.                       */
 #define OSN_NET_RUN_PIECES_2 4
 #define OSN_NET_RUN_PIECES_1 8
+/* Reduced-precision TRAINING: accepted by osn_net_forward (any run.training) and by osn_net_backward.  With one of them set every
+ * launch of the same four families in that call -- forward launches; in osn_net_backward their input-gradient launches (the head's
+ * row-compacted one included) and every OSN_NET_K_WGRAD_TL weight gradient (osn_spconv_wgrad_tl_partial_pieces) -- runs with two /
+ * one pieces.  The stem (forward and weight gradient), the first-generation kernels (osn_spconv_fwd_x6, osn_spconv_wgrad), batch
+ * norm and everything else stay exact; parameters, gradients and partial sums stay fp32.  A pass's forward and backward calls
+ * (every segment of a segmented backward pass) should carry the same bit.  With a bit set osn_net_backward adds the three gradient
+ * sources of a tensor with three consumers last consumer first (autograd's order: the module-by-module path then gives the same bits;
+ * without a bit the order is first consumer first, as it always was).  Both bits, or one of them together with
+ * OSN_NET_RUN_PIECES_2 / _1: OSN_E_ARG before the first launch.  osn_net_plan_query does not know the mode.                     */
+#define OSN_NET_RUN_TRAIN_PIECES_2 16
+#define OSN_NET_RUN_TRAIN_PIECES_1 32
 typedef struct osn_net_run {
     const int64_t* level_rows;   /* [n_levels] rows of every pyramid level                                        */
     const osn_net_map* maps;

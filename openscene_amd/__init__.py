@@ -22,6 +22,8 @@ Python surface (mirrors the reference's own, file:line in each module):
     install_minkowski_alias()      make `import MinkowskiEngine` resolve to openscene_amd.minkowski
     conv_precision(name)           context: the convolutions of inference passes in "bf16x6" (default), "bf16x3" or "bf16x1"
                                    (openscene_amd.precision; set_conv_precision for the process, OSN_INFER_PRECISION at start)
+    train_precision(name)          context: the same three modes for TRAINING passes, forward and backward (set_train_precision,
+                                   OSN_TRAIN_PRECISION); independent of conv_precision
 
 There is no CPU fallback: every op raises if libopenscene_amd.so is missing or
 the tensors are not on a gfx950 device.
@@ -31,6 +33,7 @@ import sys
 import types
 
 from .precision import conv_precision, get_conv_precision, set_conv_precision  # noqa: F401  (inference arithmetic: bf16x6 / x3 / x1)
+from .precision import train_precision, get_train_precision, set_train_precision  # noqa: F401  (training arithmetic, independent)
 
 __version__ = "0.1.0"
 

@@ -83,6 +83,8 @@ PROTOTYPES = {
     "osn_spconv_fwd_ws": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i32, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _sz, _vp]),
     "osn_spconv_wgrad_tl_partial": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _sz, _vp, _vp]),
     "osn_wgrad_tl_reduce_batch": (_i32, [_vp, _i32, _vp]),
+    "osn_spconv_wgrad_tl_pieces": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _sz, _vp, _i32]),
+    "osn_spconv_wgrad_tl_partial_pieces": (_i32, [_vp, _vp, _vp, _i32, _vp, _i64, _i64, _i32, _i32, _i32, _vp, _sz, _vp, _vp, _i32]),
     "osn_stem_conv_fwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp]),
     "osn_bn_ws_bytes": (_sz, [_i64, _i32]),
     "osn_bn_stats": (_i32, [_vp, _i64, _i32, _vp, _vp, _vp, _vp, _f32, _vp, _sz, _vp]),

@@ -314,12 +314,16 @@ static int run_conv(int kernel, const float* in, int64_t n_in, float* out, int64
     return OSN_OK;
 }
 
-// the piece count the flags of an evaluation-mode forward pass select (split.h); 0: a combination that is an error
+// the piece count the flags of a pass select (split.h); 0: a combination that is an error.  OSN_NET_RUN_PIECES_*: an evaluation-mode
+// forward pass only; OSN_NET_RUN_TRAIN_PIECES_*: any forward pass and the backward pass; at most one of the four bits.
 static int run_pieces(const osn_net_run* run, bool backward) {
-    const int bits = run->flags & (OSN_NET_RUN_PIECES_2 | OSN_NET_RUN_PIECES_1);
-    if (!bits) return 3;
-    if (backward || run->training || bits == (OSN_NET_RUN_PIECES_2 | OSN_NET_RUN_PIECES_1)) return 0;
-    return bits == OSN_NET_RUN_PIECES_2 ? 2 : 1;
+    const int infer = run->flags & (OSN_NET_RUN_PIECES_2 | OSN_NET_RUN_PIECES_1);
+    const int train = run->flags & (OSN_NET_RUN_TRAIN_PIECES_2 | OSN_NET_RUN_TRAIN_PIECES_1);
+    if (!infer && !train) return 3;
+    if (infer && train) return 0;
+    if (train) return train == OSN_NET_RUN_TRAIN_PIECES_2 ? 2 : train == OSN_NET_RUN_TRAIN_PIECES_1 ? 1 : 0;
+    if (backward || run->training || infer == (OSN_NET_RUN_PIECES_2 | OSN_NET_RUN_PIECES_1)) return 0;
+    return infer == OSN_NET_RUN_PIECES_2 ? 2 : 1;
 }
 
 static int check_run(const osn_net_desc* net, const osn_net_run* run, const Layout& L, bool backward) {
@@ -364,8 +368,8 @@ extern "C" int osn_net_plan_query(const osn_net_desc* net, const int64_t* level_
 extern "C" int osn_net_forward(const osn_net_desc* net, const osn_net_run* run, osn_stream_t stream) {
     OSN_REQUIRE(net && run, OSN_E_ARG, "osn_net_forward: null argument");
     const int pieces = run_pieces(run, false);
-    OSN_REQUIRE(pieces, OSN_E_ARG, "osn_net_forward: flags %d: OSN_NET_RUN_PIECES_2 and OSN_NET_RUN_PIECES_1 exclude each other and "
-                "need run.training == 0 (reduced precision is for inference)", run->flags);
+    OSN_REQUIRE(pieces, OSN_E_ARG, "osn_net_forward: flags %d: at most one of the four piece bits; OSN_NET_RUN_PIECES_2 and "
+                "OSN_NET_RUN_PIECES_1 need run.training == 0 (a training pass takes OSN_NET_RUN_TRAIN_PIECES_*)", run->flags);
     Layout L;
     int rc = make_layout(net, run->level_rows, run->training, L);
     if (rc) return rc;
@@ -486,7 +490,9 @@ extern "C" int osn_net_forward(const osn_net_desc* net, const osn_net_run* run, 
 
 extern "C" int osn_net_backward(const osn_net_desc* net, const osn_net_run* run, osn_stream_t stream) {
     OSN_REQUIRE(net && run, OSN_E_ARG, "osn_net_backward: null argument");
-    OSN_REQUIRE(run_pieces(run, true), OSN_E_ARG, "osn_net_backward: flags %d: a backward pass has no reduced-precision mode", run->flags);
+    const int pieces = run_pieces(run, true);       // input gradients and pair-array weight gradients; everything else stays exact
+    OSN_REQUIRE(pieces, OSN_E_ARG, "osn_net_backward: flags %d: a backward pass takes at most one of OSN_NET_RUN_TRAIN_PIECES_2 and "
+                "OSN_NET_RUN_TRAIN_PIECES_1, and neither inference bit", run->flags);
     Layout L;
     int rc = make_layout(net, run->level_rows, 1, L);
     if (rc) return rc;
@@ -534,6 +540,14 @@ extern "C" int osn_net_backward(const osn_net_desc* net, const osn_net_run* run,
             }
             OSN_REQUIRE(ng >= 1 && ng <= 3, OSN_E_ARG, "osn_net_backward: the output of op %d has %s consumers inside the executed range (1 .. 3 supported)",
                         i, ng == 0 ? "no" : "more than three");
+            // Reduced modes: the sources are added last consumer first, the order in which autograd meets them on the module path.
+            // In bf16x6 the two associations differ by an ulp and stay there (tests/test_gpu_unet.py: 2e-6); in a reduced mode every
+            // later convolution rounds its operands to bf16 pieces, and an ulp that moves one rounding grows from layer to layer
+            // to the mode's own rounding (measured: 1e-5 at two pieces, 5e-3 at one) -- so the two host paths add in ONE order there.
+            if (pieces < 3 && ng == 3) {
+                const float* tp = gsrc[0]; gsrc[0] = gsrc[2]; gsrc[2] = tp;
+                const int64_t tl_ = gld[0]; gld[0] = gld[2]; gld[2] = tl_;
+            }
         }
         // Round 4: a shortcut stage's batch-norm backward and input gradient stay on the MAIN stream.  Queued on the side stream they
         // sat behind its backlog of weight gradients, and the main stream stalled 24 - 112 us at each of the pass's joins waiting for
@@ -609,8 +623,9 @@ extern "C" int osn_net_backward(const osn_net_desc* net, const osn_net_run* run,
                 // pair arrays of the map's forward table; a transposed conv uses the strided conv's arrays, roles swapped
                 OSN_REQUIRE(o.K == 1 || (m && m->pl_fwd), OSN_E_ARG, "osn_net_backward: op %d: pair lists missing", i);
                 osn_wgrad_job job;
-                rc = osn_spconv_wgrad_tl_partial(in, gx, m ? m->pl_fwd : nullptr, o.transposed ? 1 : 0, w.gW, n_in, n_out, o.K, o.cin, o.cout,
-                                                 B + L.gpart_off[i], osn_spconv_wgrad_tl_ws_bytes(o.K, o.cin, o.cout), &job, wstream);
+                rc = osn_spconv_wgrad_tl_partial_pieces(in, gx, m ? m->pl_fwd : nullptr, o.transposed ? 1 : 0, w.gW, n_in, n_out, o.K, o.cin,
+                                                        o.cout, B + L.gpart_off[i], osn_spconv_wgrad_tl_ws_bytes(o.K, o.cin, o.cout), &job,
+                                                        wstream, pieces);
                 if (!rc) jobs.push_back(job);
                 // reduce in batches ON the stream the partial sums were computed on (stream order is all the ordering it needs):
                 // only the last, small batch is left for the tail of the pass
@@ -638,12 +653,12 @@ extern "C" int osn_net_backward(const osn_net_desc* net, const osn_net_run* run,
                 const int swap_f = o.transposed ? 1 : 0;
                 if (sparse_rows) {
                     float* gin_rows = reinterpret_cast<float*>(B + L.rows_gin_off);
-                    rc = osn_dense_fwd(run->goutput_rows, w.tl_dgrad, gin_rows, run->n_grows, o.cout, o.cin, sstream);
+                    rc = dense_fwd_epi(run->goutput_rows, w.tl_dgrad, gin_rows, run->n_grows, o.cout, o.cin, epi_none(), sstream, pieces);
                     if (!rc) rc = osn_rows_scatter_zero(gin_rows, run->grows_pos, n_in, o.cin, gin, sstream);
                 } else
                 rc = run_conv(L.dgrad_k[i], gx, n_out, gin, n_in, o.K, o.cout, o.cin, nullptr, w.x6_dgrad, w.tl_dgrad, v.nbr_b, v.tb_rows,
                               v.tb_tbl, v.tb_g, v.tl_b, v.tl_b_rows, v.tl_b_bm, m ? m->pl_fwd : nullptr, o.transposed ? n_in : n_out,
-                              (m && m->flip) ? swap_f : 1 - swap_f, r, sstream, i);
+                              (m && m->flip) ? swap_f : 1 - swap_f, r, sstream, i, epi_none(), pieces);
             }
             if (rc) return rc;
         }

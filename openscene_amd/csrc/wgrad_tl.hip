@@ -17,7 +17,9 @@
 //     ds_read_b64_tr_b16 (lane i of a 16-lane group receives channel i of four consecutive pairs; semantics
 //     measured in round 1, tools/probes/probe_gfx950.hip), 2 reads per 16 x 32 operand fragment;
 //   * 4 waves as 2 x 2 over the (input channel, output channel) block, MB x NB accumulator blocks of 16 x 16
-//     per wave, six MFMAs per block and step (split_products in split.h, fp32 accumulate).
+//     per wave, six MFMAs per block and step (split_products in split.h, fp32 accumulate);
+//   * the reduced training modes (wgrad_tl_pieces_kernel<NP, ...>, osn_spconv_wgrad_tl_pieces): the same kernel text with two or one
+//     pieces per operand -- NP planes staged and read back, three or one MFMAs per block and step.
 #include "common.h"
 #include "split.h"
 #include <cstdlib>
@@ -159,194 +161,27 @@ __global__ __launch_bounds__(256) void pair_plan_kernel(const int32_t* __restric
 // profiles/r05_s1_knobs_ab.txt): both operands' rows come through buffer resources -- 32-bit offset
 // row * (4 c) + 4 (block's first channel + quad) from one v_mad_u32_u24 -- instead of a 64-bit multiply-add and two 64-bit adds per
 // quad; needs < 2^24 rows and < 2 GB per operand (the launch checks).  A padded pair reads row 0 (the split zeroes its quad as before).
-template <int MB, int NB, bool BUFG = false>
-__global__ __launch_bounds__(256, 2) void wgrad_tl_kernel(const float* __restrict__ rows_a, const float* __restrict__ rows_g,
-                                                          const int32_t* __restrict__ idx_a, const int32_t* __restrict__ idx_g,
-                                                          const int32_t* __restrict__ poff, const int4* __restrict__ items,
-                                                          float* __restrict__ partial, int ca, int cg, int n_cgb,
-                                                          int ident_rows, int ident_quota, unsigned a_bytes, unsigned g_bytes) {
-    constexpr int CA_T = 32 * MB, CG_T = 32 * NB;
-    constexpr int LDA = CA_T + 8, LDG = CG_T + 8;        // bf16 row pitch (16-byte aligned rows)
-    constexpr int QA = CA_T / 4, QG = CG_T / 4;          // quads per staged row
-    __shared__ __attribute__((aligned(16))) __bf16 Ap[3][32][LDA];
-    __shared__ __attribute__((aligned(16))) __bf16 Gp[3][32][LDG];
-    __shared__ int idxbuf[2][32];
-
-    const int tid = threadIdx.x, lane = tid & 63;
-    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-    const int wi = wave >> 1, wj = wave & 1;
-    const int a0 = (blockIdx.x / n_cgb) * CA_T;          // first input channel of the workgroup's block
-    const int g0 = (blockIdx.x % n_cgb) * CG_T;
-    int k, p0, p1, base;
-    int pstep = 32;                                      // pairs between this item's consecutive 32-pair steps
-    if (idx_a) {
-        const int4 it = items[blockIdx.y];
-        k = it.x; p0 = it.y; p1 = it.z;
-        if (k < 0) return;
-        base = poff[k];
-        // item.w = j | n << 16 (0 = the whole range): the item takes the steps j, j + n, ... of [p0, p1) -- strided items of one row
-        // region walk its rows together (round 6: Z-ordered pair arrays, tools/micro_crowd.py)
-        const int n_it = it.w >> 16;
-        if (n_it > 1) { p0 += 32 * (it.w & 0xFFFF); pstep = 32 * n_it; }
-        if (p0 >= p1) p1 = p0;                           // (an item past the range's last step: nothing to add, zeros are stored)
-    } else {
-        k = 0; base = 0;
-        p0 = blockIdx.y * ident_quota;
-        p1 = min(p0 + ident_quota, ident_rows);
-        if (p0 >= p1) return;
-    }
-    (void)k;
-
-    f32x4 acc[MB][NB];
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-    // staging coordinates of this thread's quads (MB of the A rows, NB of the G rows)
-    int ar[MB], ac[MB], gr[NB], gc[NB];
-#pragma unroll
-    for (int j = 0; j < MB; ++j) { const int idx = tid + 256 * j; ar[j] = idx / QA; ac[j] = (idx - ar[j] * QA) * 4; }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) { const int idx = tid + 256 * j; gr[j] = idx / QG; gc[j] = (idx - gr[j] * QG) * 4; }
-
-    const __amdgpu_buffer_rsrc_t arsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rows_a), 0, int(BUFG ? a_bytes : 0u), 0x00020000);
-    const __amdgpu_buffer_rsrc_t grsrc = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(rows_g), 0, int(BUFG ? g_bytes : 0u), 0x00020000);
-    const unsigned ca4 = unsigned(ca) * 4u, cg4 = unsigned(cg) * 4u;
-    float4 pa[MB], pg[NB];
-    // the (input row, output row) of pair p0 + s * 32 + (tid & 31): threads 0..31 hold the A index, 32..63 the G index
-    auto load_idx = [&](int p) -> int {
-        const int q = p + (tid & 31);
-        if (tid >= 64) return -1;
-        if (q >= p1) return -1;
-        if (!idx_a) return q;
-        return tid < 32 ? idx_a[base + q] : idx_g[base + q];
-    };
-    auto fetch = [&](int par) {
-#pragma unroll
-        for (int j = 0; j < MB; ++j) {
-            const int r = idxbuf[0][ar[j]];
-            const int ch = a0 + ac[j];
-            if constexpr (BUFG) {       // (channels past the operand: inside the matrix or past its end, where the resource returns zeros)
-                pa[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                       arsrc, __umul24(unsigned(max(r, 0)), ca4) + 4u * unsigned(ch), 0, 0));
-                continue;
-            }
-            const bool ok = r >= 0 && ch < ca;
-            const unsigned ru = ok ? unsigned(r) : 0u, cu = ok ? unsigned(ch) : 0u;
-            pa[j] = *reinterpret_cast<const float4*>(rows_a + (uint64_t(ru) * unsigned(ca) + cu));
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const int r = idxbuf[1][gr[j]];
-            const int ch = g0 + gc[j];
-            if constexpr (BUFG) {
-                pg[j] = __builtin_bit_cast(float4, __builtin_amdgcn_raw_buffer_load_b128(
-                                                       grsrc, __umul24(unsigned(max(r, 0)), cg4) + 4u * unsigned(ch), 0, 0));
-                continue;
-            }
-            const bool ok = r >= 0 && ch < cg;
-            const unsigned ru = ok ? unsigned(r) : 0u, cu = ok ? unsigned(ch) : 0u;
-            pg[j] = *reinterpret_cast<const float4*>(rows_g + (uint64_t(ru) * unsigned(cg) + cu));
-        }
-        (void)par;
-    };
-    // three bf16 pieces per element, two elements per conversion (split.h); rows of padded pairs and channels past the
-    // operand are zeroed first
-    auto split4 = [&](const float4& v, bool ok, bf16x4& h1, bf16x4& h2, bf16x4& h3) {
-        tl_split4(ok ? v : make_float4(0.f, 0.f, 0.f, 0.f), h1, h2, h3);
-    };
-
-    // prologue: indices of step 0 -> LDS -> rows of step 0 in flight, indices of step 1 in registers
-    int ireg = load_idx(p0);
-    if (tid < 64) idxbuf[tid >> 5][tid & 31] = ireg;
-    __syncthreads();
-    bool ok_a[MB], ok_g[NB];
-    auto valid_now = [&]() {
-#pragma unroll
-        for (int j = 0; j < MB; ++j) ok_a[j] = idxbuf[0][ar[j]] >= 0 && a0 + ac[j] < ca;
-#pragma unroll
-        for (int j = 0; j < NB; ++j) ok_g[j] = idxbuf[1][gr[j]] >= 0 && g0 + gc[j] < cg;
-    };
-    valid_now();
-    fetch(0);
-    ireg = load_idx(p0 + pstep);
-
-    for (int p = p0; p < p1; p += pstep) {
-        // ---- split the rows of this step (registers)
-        bf16x4 a1[MB], a2[MB], a3[MB], g1[NB], g2[NB], g3[NB];
-#pragma unroll
-        for (int j = 0; j < MB; ++j) split4(pa[j], ok_a[j], a1[j], a2[j], a3[j]);
-#pragma unroll
-        for (int j = 0; j < NB; ++j) split4(pg[j], ok_g[j], g1[j], g2[j], g3[j]);
-        __syncthreads();                                   // the previous step's fragments have been read
-#pragma unroll
-        for (int j = 0; j < MB; ++j) {
-            *reinterpret_cast<bf16x4*>(&Ap[0][ar[j]][ac[j]]) = a1[j];
-            *reinterpret_cast<bf16x4*>(&Ap[1][ar[j]][ac[j]]) = a2[j];
-            *reinterpret_cast<bf16x4*>(&Ap[2][ar[j]][ac[j]]) = a3[j];
-        }
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            *reinterpret_cast<bf16x4*>(&Gp[0][gr[j]][gc[j]]) = g1[j];
-            *reinterpret_cast<bf16x4*>(&Gp[1][gr[j]][gc[j]]) = g2[j];
-            *reinterpret_cast<bf16x4*>(&Gp[2][gr[j]][gc[j]]) = g3[j];
-        }
-        if (tid < 64) idxbuf[tid >> 5][tid & 31] = ireg;  // indices of the next step
-        __syncthreads();
-        if (p + pstep < p1) {
-            valid_now();
-            fetch(0);                                      // rows of the next step: in flight during the MFMAs
-            ireg = load_idx(p + 2 * pstep);
-        }
-        // ---- fragments by transpose reads: lane i of a 16-lane group points at (pair 8 g + (i >> 2), channels
-        // 4 (i & 3) .. + 3) of a 16-channel block and receives channel i of pairs 8 g .. 8 g + 3 (then + 4)
-        const int li = lane & 15, lg = lane >> 4;
-        auto frag = [&](const __bf16* plane, int pitch, int c16) -> bf16x8 {
-            const __bf16* q = plane + (8 * lg + (li >> 2)) * pitch + c16 + 4 * (li & 3);
-            const s16x4 lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (__attribute__((address_space(3))) s16x4*)(q));
-            const s16x4 hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16(
-                (__attribute__((address_space(3))) s16x4*)(q + 4 * pitch));
-            union { s16x4 h[2]; bf16x8 v; } u;
-            u.h[0] = lo; u.h[1] = hi;
-            return u.v;
-        };
-        bf16x8 fa[MB][3], fg[NB][3];
-#pragma unroll
-        for (int i = 0; i < MB; ++i)
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) fa[i][pl] = frag(&Ap[pl][0][0], LDA, (wi * MB + i) * 16);
-#pragma unroll
-        for (int j = 0; j < NB; ++j)
-#pragma unroll
-            for (int pl = 0; pl < 3; ++pl) fg[j][pl] = frag(&Gp[pl][0][0], LDG, (wj * NB + j) * 16);
-#pragma unroll
-        for (int i = 0; i < MB; ++i)
-#pragma unroll
-            for (int j = 0; j < NB; ++j) {
-                f32x4 t = acc[i][j];
-                split_products([&](auto ap, auto gp) {
-                    t = __builtin_amdgcn_mfma_f32_16x16x32_bf16(fa[i][ap], fg[j][gp], t, 0, 0, 0);
-                });
-                acc[i][j] = t;
-            }
-    }
-
-    // ---- partial[item][ca][cg]: C row = 4 (lane >> 4) + r (input channel), col = lane & 15 (output channel)
-    float* d = partial + int64_t(blockIdx.y) * ca * cg;
-#pragma unroll
-    for (int i = 0; i < MB; ++i)
-#pragma unroll
-        for (int j = 0; j < NB; ++j) {
-            const int co = g0 + (wj * NB + j) * 16 + (lane & 15);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int ci = a0 + (wi * MB + i) * 16 + 4 * (lane >> 4) + r;
-                if (ci < ca && co < cg) d[int64_t(ci) * cg + co] = acc[i][j][r];
-            }
-        }
-}
+// The kernel's text is wgrad_tl_kernel.h, included once per kernel template; per accumulator its products and their order are those of
+// split_products() in split.h, for the template's piece count.
+// the three-piece kernel, under the name and template parameters it always had ...
+#define OSN_WG_TEMPLATE template <int MB, int NB, bool BUFG = false>
+#define OSN_WG_NAME wgrad_tl_kernel
+#define OSN_WG_NP 3
+#include "wgrad_tl_kernel.h"
+#undef OSN_WG_TEMPLATE
+#undef OSN_WG_NAME
+#undef OSN_WG_NP
+// ... and the reduced training modes: the same text with NP_ = 2 or 1 pieces.  LDS per workgroup is NP_ / 3 of the three-piece
+// instance's (NP_ planes per operand), the fragment registers likewise.  Two workgroups per CU as the three-piece kernel: a map's
+// PL_ITEMS work items are one round of two workgroups per CU, so a third resident workgroup would find nothing to run, and the
+// compiler's report shows no reduced instance near the 256-register limit of that bound.
+#define OSN_WG_TEMPLATE template <int NP_, int MB, int NB, bool BUFG = false>
+#define OSN_WG_NAME wgrad_tl_pieces_kernel
+#define OSN_WG_NP NP_
+#include "wgrad_tl_kernel.h"
+#undef OSN_WG_TEMPLATE
+#undef OSN_WG_NAME
+#undef OSN_WG_NP
 
 // gW[k] = sum of the partials of offset k's items, in item order (offsets without pairs: zero).
 // transpose: the kernel ran with the operand roles swapped (partials are [cout][cin]).
@@ -475,18 +310,25 @@ extern "C" size_t osn_spconv_wgrad_tl_ws_bytes(int K, int cin, int cout) {
 }
 
 template <int MB>
-static void launch_wg_tl_nb(int nb, dim3 grid, hipStream_t st, const float* ra, const float* rg, const int32_t* ia,
+static void launch_wg_tl_nb(int pieces, int nb, dim3 grid, hipStream_t st, const float* ra, const float* rg, const int32_t* ia,
                             const int32_t* ig, const int32_t* poff, const int4* items, float* partial, int ca, int cg,
                             int n_gb, int irows, int iquota, unsigned a_bytes, unsigned g_bytes) {
     const bool bufg = a_bytes != 0u && g_bytes != 0u;
-#define OSN_WGTL(NB_)                                                                                              \
-    do {                                                                                                           \
-        if (bufg)                                                                                                  \
-            hipLaunchKernelGGL((wgrad_tl_kernel<MB, NB_, true>), grid, dim3(256), 0, st, ra, rg, ia, ig, poff, items, partial, ca, \
-                               cg, n_gb, irows, iquota, a_bytes, g_bytes);                                         \
-        else                                                                                                       \
-            hipLaunchKernelGGL((wgrad_tl_kernel<MB, NB_, false>), grid, dim3(256), 0, st, ra, rg, ia, ig, poff, items, partial, ca, \
-                               cg, n_gb, irows, iquota, 0u, 0u);                                                   \
+#define OSN_WGTL_L(...)                                                                                                        \
+    do {                                                                                                                       \
+        if (bufg)                                                                                                              \
+            hipLaunchKernelGGL((__VA_ARGS__, true>), grid, dim3(256), 0, st, ra, rg, ia, ig, poff, items, partial, ca, cg, n_gb, irows, \
+                               iquota, a_bytes, g_bytes);                                                                      \
+        else                                                                                                                   \
+            hipLaunchKernelGGL((__VA_ARGS__, false>), grid, dim3(256), 0, st, ra, rg, ia, ig, poff, items, partial, ca, cg, n_gb, irows, \
+                               iquota, 0u, 0u);                                                                                \
+    } while (0)
+    // every <MB, NB> and BUFG of the three-piece kernel has its two reduced instances: no shape falls back to three pieces
+#define OSN_WGTL(NB_)                                                                                                          \
+    do {                                                                                                                       \
+        if (pieces == 3) OSN_WGTL_L(wgrad_tl_kernel<MB, NB_);                                                                  \
+        else if (pieces == 2) OSN_WGTL_L(wgrad_tl_pieces_kernel<2, MB, NB_);                                                   \
+        else OSN_WGTL_L(wgrad_tl_pieces_kernel<1, MB, NB_);                                                                    \
     } while (0)
     switch (nb) {
         case 1: OSN_WGTL(1); break;
@@ -495,14 +337,16 @@ static void launch_wg_tl_nb(int nb, dim3 grid, hipStream_t st, const float* ra, 
         default: OSN_WGTL(4); break;
     }
 #undef OSN_WGTL
+#undef OSN_WGTL_L
 }
 
 // kernel launch only: partial[item][cin][cout] + the job describing its reduction (job->gW = gW); gW itself is written only
 // when the map is empty (zeros).  Returns through *launched whether a reduction is pending.
 static int wgrad_tl_partial(const float* in, const float* gout, const void* pl, int swap, float* gW, int64_t n_in,
                             int64_t n_out, int K, int cin, int cout, void* ws, size_t ws_bytes, osn_wgrad_job* job,
-                            int* launched, osn_stream_t stream) {
+                            int* launched, osn_stream_t stream, int pieces) {
     hipStream_t st = static_cast<hipStream_t>(stream);
+    OSN_REQUIRE(pieces >= 1 && pieces <= 3, OSN_E_ARG, "osn_spconv_wgrad_tl: pieces=%d (1, 2 or 3)", pieces);
     OSN_REQUIRE(K >= 1 && K <= PL_KMAX && cin >= 4 && (cin & 3) == 0 && cout >= 4 && (cout & 3) == 0 && gW, OSN_E_ARG,
                 "osn_spconv_wgrad_tl: needs cin %% 4 == 0 and cout %% 4 == 0 (K=%d cin=%d cout=%d)", K, cin, cout);
     OSN_REQUIRE(n_in >= 0 && n_out >= 0 && n_in < (int64_t(1) << 31) && n_out < (int64_t(1) << 31), OSN_E_ARG,
@@ -550,10 +394,10 @@ static int wgrad_tl_partial(const float* in, const float* gout, const void* pl, 
                       gb64 < (uint64_t(1) << 31);
     const unsigned a_bytes = bufg ? unsigned(ab64) : 0u, g_bytes = bufg ? unsigned(gb64) : 0u;
     switch (p.mb) {
-        case 1: launch_wg_tl_nb<1>(p.nb, grid, st, ra, rg, ia, ig, poff, items, partial, ca, cg, p.n_gb, irows, iquota, a_bytes, g_bytes); break;
-        case 2: launch_wg_tl_nb<2>(p.nb, grid, st, ra, rg, ia, ig, poff, items, partial, ca, cg, p.n_gb, irows, iquota, a_bytes, g_bytes); break;
-        case 3: launch_wg_tl_nb<3>(p.nb, grid, st, ra, rg, ia, ig, poff, items, partial, ca, cg, p.n_gb, irows, iquota, a_bytes, g_bytes); break;
-        default: launch_wg_tl_nb<4>(p.nb, grid, st, ra, rg, ia, ig, poff, items, partial, ca, cg, p.n_gb, irows, iquota, a_bytes, g_bytes); break;
+        case 1: launch_wg_tl_nb<1>(pieces, p.nb, grid, st, ra, rg, ia, ig, poff, items, partial, ca, cg, p.n_gb, irows, iquota, a_bytes, g_bytes); break;
+        case 2: launch_wg_tl_nb<2>(pieces, p.nb, grid, st, ra, rg, ia, ig, poff, items, partial, ca, cg, p.n_gb, irows, iquota, a_bytes, g_bytes); break;
+        case 3: launch_wg_tl_nb<3>(pieces, p.nb, grid, st, ra, rg, ia, ig, poff, items, partial, ca, cg, p.n_gb, irows, iquota, a_bytes, g_bytes); break;
+        default: launch_wg_tl_nb<4>(pieces, p.nb, grid, st, ra, rg, ia, ig, poff, items, partial, ca, cg, p.n_gb, irows, iquota, a_bytes, g_bytes); break;
     }
     OSN_LAUNCH_CHECK();
     job->partial = partial;
@@ -564,13 +408,12 @@ static int wgrad_tl_partial(const float* in, const float* gout, const void* pl, 
     return OSN_OK;
 }
 
-extern "C" int osn_spconv_wgrad_tl(const float* in, const float* gout, const void* pl, int swap, float* gW, int64_t n_in,
-                                   int64_t n_out, int K, int cin, int cout, void* ws, size_t ws_bytes,
-                                   osn_stream_t stream) {
+static int wgrad_tl_whole(const float* in, const float* gout, const void* pl, int swap, float* gW, int64_t n_in, int64_t n_out, int K,
+                          int cin, int cout, void* ws, size_t ws_bytes, osn_stream_t stream, int pieces) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     osn_wgrad_job job;
     int launched = 0;
-    int rc = wgrad_tl_partial(in, gout, pl, swap, gW, n_in, n_out, K, cin, cout, ws, ws_bytes, &job, &launched, stream);
+    int rc = wgrad_tl_partial(in, gout, pl, swap, gW, n_in, n_out, K, cin, cout, ws, ws_bytes, &job, &launched, stream, pieces);
     if (rc || !launched) return rc;
     const int64_t wtotal = int64_t(K) * cin * cout;
     int g = int(cdiv(wtotal, 256));
@@ -581,14 +424,41 @@ extern "C" int osn_spconv_wgrad_tl(const float* in, const float* gout, const voi
     return OSN_OK;
 }
 
-extern "C" int osn_spconv_wgrad_tl_partial(const float* in, const float* gout, const void* pl, int swap, float* gW, int64_t n_in,
-                                           int64_t n_out, int K, int cin, int cout, void* partial, size_t partial_bytes,
-                                           osn_wgrad_job* job, osn_stream_t stream) {
+extern "C" int osn_spconv_wgrad_tl(const float* in, const float* gout, const void* pl, int swap, float* gW, int64_t n_in,
+                                   int64_t n_out, int K, int cin, int cout, void* ws, size_t ws_bytes,
+                                   osn_stream_t stream) {
+    return wgrad_tl_whole(in, gout, pl, swap, gW, n_in, n_out, K, cin, cout, ws, ws_bytes, stream, 3);
+}
+
+// the reduced training modes (split.h): the same launches and the same item-order fp32 reduction with `pieces` pieces per operand
+extern "C" int osn_spconv_wgrad_tl_pieces(const float* in, const float* gout, const void* pl, int swap, float* gW, int64_t n_in,
+                                          int64_t n_out, int K, int cin, int cout, void* ws, size_t ws_bytes,
+                                          osn_stream_t stream, int pieces) {
+    OSN_REQUIRE(pieces >= 1 && pieces <= 3, OSN_E_ARG, "osn_spconv_wgrad_tl_pieces: pieces=%d (1, 2 or 3)", pieces);
+    return wgrad_tl_whole(in, gout, pl, swap, gW, n_in, n_out, K, cin, cout, ws, ws_bytes, stream, pieces);
+}
+
+static int wgrad_tl_partial_job(const float* in, const float* gout, const void* pl, int swap, float* gW, int64_t n_in, int64_t n_out,
+                                int K, int cin, int cout, void* partial, size_t partial_bytes, osn_wgrad_job* job, osn_stream_t stream,
+                                int pieces) {
     OSN_REQUIRE(job, OSN_E_ARG, "osn_spconv_wgrad_tl_partial: null job");
     int launched = 0;
     job->partial = nullptr; job->range = nullptr; job->gW = nullptr;
     job->K = 0; job->cin = 0; job->cout = 0; job->ident_items = 0;
-    return wgrad_tl_partial(in, gout, pl, swap, gW, n_in, n_out, K, cin, cout, partial, partial_bytes, job, &launched, stream);
+    return wgrad_tl_partial(in, gout, pl, swap, gW, n_in, n_out, K, cin, cout, partial, partial_bytes, job, &launched, stream, pieces);
+}
+
+extern "C" int osn_spconv_wgrad_tl_partial(const float* in, const float* gout, const void* pl, int swap, float* gW, int64_t n_in,
+                                           int64_t n_out, int K, int cin, int cout, void* partial, size_t partial_bytes,
+                                           osn_wgrad_job* job, osn_stream_t stream) {
+    return wgrad_tl_partial_job(in, gout, pl, swap, gW, n_in, n_out, K, cin, cout, partial, partial_bytes, job, stream, 3);
+}
+
+extern "C" int osn_spconv_wgrad_tl_partial_pieces(const float* in, const float* gout, const void* pl, int swap, float* gW,
+                                                  int64_t n_in, int64_t n_out, int K, int cin, int cout, void* partial,
+                                                  size_t partial_bytes, osn_wgrad_job* job, osn_stream_t stream, int pieces) {
+    OSN_REQUIRE(pieces >= 1 && pieces <= 3, OSN_E_ARG, "osn_spconv_wgrad_tl_partial_pieces: pieces=%d (1, 2 or 3)", pieces);
+    return wgrad_tl_partial_job(in, gout, pl, swap, gW, n_in, n_out, K, cin, cout, partial, partial_bytes, job, stream, pieces);
 }
 
 extern "C" int osn_wgrad_tl_reduce_batch(const osn_wgrad_job* jobs, int n_jobs, osn_stream_t stream) {

@@ -83,6 +83,7 @@ class _Run(ctypes.Structure):
 RUN_NO_JOIN = 1                                 # include/openscene_amd.h: OSN_NET_RUN_NO_JOIN
 RUN_NO_BN_EPILOGUE = 2                          # include/openscene_amd.h: OSN_NET_RUN_NO_BN_EPILOGUE
 RUN_PIECES = {3: 0, 2: 4, 1: 8}                 # operand pieces -> OSN_NET_RUN_PIECES_2 / OSN_NET_RUN_PIECES_1 (inference only)
+RUN_TRAIN_PIECES = {3: 0, 2: 16, 1: 32}         # ... -> OSN_NET_RUN_TRAIN_PIECES_2 / _1: a training pass, forward and every backward segment
 # Inference: every stage's batch norm (+ residual) (+ ReLU) (+ cat store) runs in the epilogue of the kernel that finishes the stage's
 # convolution (csrc/epilogue.h; bitwise the separate launch, 48 launches fewer per MinkUNet18A pass).  0: the separate launches (A/B, tests)
 BN_EPILOGUE = os.environ.get("OSN_BN_EPILOGUE", "1") != "0"
@@ -191,7 +192,7 @@ class Program:
 
 class _PassState:
     """What a forward pass leaves for its backward pass (kept alive by the autograd node)."""
-    __slots__ = ("rows", "maps", "weights", "bns", "arena", "keep", "training", "feats", "plan_fwd_bytes", "cm", "pieces")
+    __slots__ = ("rows", "maps", "weights", "bns", "arena", "keep", "training", "feats", "plan_fwd_bytes", "cm", "pieces", "train_mode")
 
 
 class UNetExecutor:
@@ -443,8 +444,10 @@ class UNetExecutor:
         self._plan_query(lib, rows, grad or training)
         st = _PassState()
         st.rows, st.training, st.feats, st.cm = rows, training, feats, cm
-        # inference precision (openscene_amd.precision): an evaluation-mode pass that records no graph; everything else is bf16x6
-        st.pieces = precision.inference_pieces(training, grad)
+        # openscene_amd.precision: the inference mode for an evaluation-mode pass that records no graph, the training mode for every
+        # other pass -- kept on the state, so the backward pass runs in the mode its forward ran in
+        st.pieces = precision.pass_pieces(training, grad)
+        st.train_mode = training or grad
         st.maps, keep_m = self._maps(cm, grad)
         prep_done = None
         if grad and SIDE_STREAM and not _DRY_RUN and K_NAMES[int(self._kf[0])] == "stem":
@@ -475,7 +478,8 @@ class UNetExecutor:
         run = _Run(_ptr(self._rows), _ptr(st.maps), _ptr(st.weights), _ptr(st.bns), feats.data_ptr(),
                    out.data_ptr() if out is not None else None, None, st.arena.data_ptr(), st.arena.numel(), None, 0,
                    ws.data_ptr(), ws.numel(), ops.tl_counters(dev).data_ptr(), int(training), 0, end,
-                   (0 if (BN_EPILOGUE and not grad) else RUN_NO_BN_EPILOGUE) | RUN_PIECES[st.pieces], self.prof,      # (a pass with a backward pass keeps x)
+                   (0 if (BN_EPILOGUE and not grad) else RUN_NO_BN_EPILOGUE) | (RUN_TRAIN_PIECES if st.train_mode else RUN_PIECES)[st.pieces],
+                   self.prof,                                            # (a pass with a backward pass keeps x)
                    side if events else None, ws2.data_ptr() if (events and ws2 is not None) else None,
                    ws2.numel() if (events and ws2 is not None) else 0, events, None, None, None, 0)
         with ops._Dev(dev):
@@ -556,7 +560,7 @@ class UNetExecutor:
         run = _Run(_ptr(self._rows), _ptr(st.maps), _ptr(st.weights), _ptr(st.bns), st.feats.data_ptr(), None,
                    gout.data_ptr() if gout is not None else None,
                    st.arena.data_ptr(), st.arena.numel(), barena.data_ptr(), barena.numel(), ws.data_ptr(), ws.numel(),
-                   ops.tl_counters(dev).data_ptr(), int(st.training), 0, len(p.ops), 0, self.prof,
+                   ops.tl_counters(dev).data_ptr(), int(st.training), 0, len(p.ops), RUN_TRAIN_PIECES[st.pieces], self.prof,
                    side if events else None, ws2.data_ptr() if (events and ws2 is not None) else None,
                    ws2.numel() if (events and ws2 is not None) else 0, events, rows_pos, rows_idx, rows_g, n_rows)
         hook = self.grad_ready_hook
@@ -574,7 +578,7 @@ class UNetExecutor:
                 for lo in self.backward_cuts():
                     run.first_op, run.end_op = lo, hi
                     inner = forked and lo > 0
-                    run.flags = RUN_NO_JOIN if inner else 0
+                    run.flags = (RUN_NO_JOIN if inner else 0) | RUN_TRAIN_PIECES[st.pieces]
                     check(lib.osn_net_backward(ctypes.addressof(self.desc), ctypes.addressof(run), ops._stream(dev)), "osn_net_backward")
                     lo_f, hi_f = self.grad_off[lo], self.grad_off[hi] if hi < nc else self.conv_grad_end
                     if inner:
@@ -583,7 +587,7 @@ class UNetExecutor:
                     else:
                         hook(grads, lo_f, hi_f, lo == 0)
                     hi = lo
-                run.flags = 0
+                run.flags = RUN_TRAIN_PIECES[st.pieces]
         return [grads[o:o + q.numel()].view_as(q) for o, q in zip(self.grad_off, p.params)]
 
     def backward_cuts(self):

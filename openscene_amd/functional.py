@@ -124,7 +124,7 @@ def _launch(name, x, w, n_dst, c_dst, K, nbr, tiles, lists, pairs, swap, pieces=
     """Convolution kernel `name` on x -> [n_dst, c_dst] (the Python twin of run_conv in csrc/net.hip).  w: the weight image _IMAGE
     names, else the fp32 weight; nbr / tiles / lists: the destination side's table, tile-ordered table and tile lists; pairs, swap:
     the map's pair arrays and whether this launch walks them the other way; pieces: operand pieces of the four split-bf16 families
-    (openscene_amd.precision: below 3 only in a forward pass of an evaluation-mode model that records no graph)."""
+    (openscene_amd.precision.pass_pieces: the inference mode of an evaluation-mode pass that records no graph, else the training mode)."""
     tbl, rows, gm = (tiles[1], tiles[0], tiles[2]) if tiles is not None else (nbr, None, None)
     kw = {} if pieces == 3 else {"pieces": pieces}          # (the default mode calls the wrappers as it always did)
     if name == "stem":
@@ -180,6 +180,7 @@ class SparseConvFunction(Function):
         # direction of the pair arrays and takes the mirrored weight image
         ctx.dgrad = (dgrad, wd, nbr_bwd, tiles_bwd, lists_bwd, pairs, transposed if flip else not transposed)
         ctx.wgrad = (wgrad, nbr_fwd, counts, transposed, flip)
+        ctx.pieces = pieces                    # the backward pass runs in the forward's mode, wherever backward() is called
         return _launch(fwd, feats, wf if wf is not None else kernel, n_out, cout, K, nbr_fwd, tiles_fwd, lists_fwd, pairs, transposed, pieces)
 
     @staticmethod
@@ -189,6 +190,8 @@ class SparseConvFunction(Function):
         wgrad, nbr_fwd, counts, swap, flip = ctx.wgrad
         gout = gout.contiguous()
         gin = gk = None
+        pieces = ctx.pieces
+        kw = {} if pieces == 3 else {"pieces": pieces}          # (the default mode calls the wrappers as it always did)
         K = 1 if kernel.dim() == 2 else kernel.shape[0]
         n_in, cin = feats.shape
         if wd is not None and ctx.kver != (kernel._version, kernel.data_ptr()):
@@ -199,7 +202,7 @@ class SparseConvFunction(Function):
             if wgrad == "wgrad_stem":
                 gw = ops.stem_conv_wgrad(feats, gout, nbr_fwd, K)
             elif wgrad == "wgrad_tl":
-                gw = ops.spconv_wgrad_tl(feats, gout, pairs, K, swap=swap) if K > 1 else ops.spconv_wgrad_tl(feats, gout, None, 1)
+                gw = ops.spconv_wgrad_tl(feats, gout, pairs, K, swap=swap, **kw) if K > 1 else ops.spconv_wgrad_tl(feats, gout, None, 1, **kw)
             else:
                 gw = ops.spconv_wgrad(feats, gout, nbr_fwd, K, counts)
             return gw.reshape(kernel.shape)
@@ -218,7 +221,7 @@ class SparseConvFunction(Function):
         if ctx.needs_input_grad[0]:
             if wd is None:
                 wd = ops.weight_image(kernel, flip, True, ops.PREP_X6) if dgrad == "x6" else ops.weight_transpose(kernel, flip)
-            gin = _launch(dgrad, gout, wd, n_in, cin, K, nbr_bwd, tiles_bwd, lists_bwd, pairs, swap_b)
+            gin = _launch(dgrad, gout, wd, n_in, cin, K, nbr_bwd, tiles_bwd, lists_bwd, pairs, swap_b, pieces)
         if side is not None:
             main.wait_stream(side)                        # join: later work on this stream sees the weight gradient
         return gin, gk, None, None, None, None, None, None, None, None, None, None, None, None
@@ -341,10 +344,11 @@ def sparse_conv(feats, kernel, maps, n_out, tiles=None, counts=None, lists=None,
     """maps = CoordinateManager.kmap(...); tiles = .kmap_tiles(...) or None; counts = .kmap_counts(...) or None;
     lists = .kmap_lists(...) or None; transposed: the conv is a MinkowskiConvolutionTranspose; fine_unique: the map is a
     2^3 stride-2 map (every row of its fine side has exactly one pair); training: the calling module's mode -- an evaluation-mode
-    convolution that records no graph runs in the inference precision in force (openscene_amd.precision), as the executor's pass does."""
+    convolution that records no graph runs in the inference precision in force, every other one in the training precision
+    (openscene_amd.precision.pass_pieces), as the executor's pass does."""
     nbr_fwd, nbr_bwd, flip = maps
     grad = torch.is_grad_enabled() and (feats.requires_grad or kernel.requires_grad)
-    pieces = precision.inference_pieces(training, grad)
+    pieces = precision.pass_pieces(training, grad)
     tf, tb = tiles if tiles is not None else (None, None)
     lf, lb = lists if lists is not None else (None, None)
     return SparseConvFunction.apply(feats, kernel, nbr_fwd, nbr_bwd, flip, n_out, tf, tb, counts, lf, lb, bool(transposed),

@@ -740,9 +740,10 @@ def pair_arrays(tl):
     return poff, pin, pout
 
 
-def spconv_wgrad_tl(feats, gout, tl, K, swap=False):
+def spconv_wgrad_tl(feats, gout, tl, K, swap=False, pieces=3):
     """gW [K, cin, cout] from the pair arrays of `tl` (None <=> K == 1 identity).  swap: `tl` belongs to the strided
-    convolution that this transposed convolution mirrors."""
+    convolution that this transposed convolution mirrors.  pieces: operand pieces (_pieces_ok; below 3: the reduced training modes)."""
+    pieces = _pieces_ok(pieces)
     dev = feats.device
     lib = _prep(dev)
     feats = _f32c(feats, "features")
@@ -764,8 +765,11 @@ def spconv_wgrad_tl(feats, gout, tl, K, swap=False):
     ws = _ws(wsb, dev)
     tok = _prof_start("spconv_wgrad_tl", dev, n_in=n_in, n_out=n_out, K=K, cin=cin, cout=cout)
     with _Dev(dev):
-        check(lib.osn_spconv_wgrad_tl(_p(feats), _p(gout), _p(pl), int(bool(swap)), _p(gw), n_in, n_out, K, cin, cout,
-                                      _p(ws), ws.numel(), _stream(dev)), "osn_spconv_wgrad_tl")
+        args = (_p(feats), _p(gout), _p(pl), int(bool(swap)), _p(gw), n_in, n_out, K, cin, cout, _p(ws), ws.numel(), _stream(dev))
+        if pieces == 3:
+            check(lib.osn_spconv_wgrad_tl(*args), "osn_spconv_wgrad_tl")
+        else:
+            check(lib.osn_spconv_wgrad_tl_pieces(*args, pieces), "osn_spconv_wgrad_tl_pieces")
     if tok is not None:
         _profiler.stop(tok)
     return gw

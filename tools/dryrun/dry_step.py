@@ -67,7 +67,7 @@ def install(so, setattr_=setattr):
 
 
 def conv_launches(log):
-    return [l for l in log.split("\n") if re.search(r"spconv|wgrad_tl_kernel|stem_fwd", l)]
+    return [l for l in log.split("\n") if re.search(r"spconv|wgrad_tl_kernel|wgrad_tl_pieces_kernel|stem_fwd", l)]
 
 
 def bn_launches(log):

@@ -7,7 +7,9 @@ ONLY=pieces: the inference precision modes (openscene_amd.precision: pieces 3 / 
 forward shapes of S100k / MinkUNet18A, one per kernel family -- tile-list 3^3 96 -> 96 at 100 999 rows, register-gather 3^3 32 -> 64 on
 the 13 k-row level, weight-stationary 3^3 256 -> 256 on the level-3 map, the 96 -> 768 head -- the three modes interleaved in one process
 (ROUNDS rounds of REPS launches each, median round).  One JSON line per (shape, mode): time, the bf16 MFMA work it issued
-(pairs x cin x cout x 2 x products) as a fraction of the 2.5 PFLOP/s dense bf16 roof, and the fp32-equivalent rate.  OUT=file appends."""
+(pairs x cin x cout x 2 x products) as a fraction of the 2.5 PFLOP/s dense bf16 roof, and the fp32-equivalent rate.  OUT=file appends.
+Then the same for the pair-array weight gradient in the training modes (family "wgrad_tl"): 3^3 96 -> 96 at 100 999 rows, the 2^3
+256 -> 128 transposed convolution between the two deepest levels (a swap launch) and a 1x1 128 -> 128 shortcut (identity map)."""
 import json
 import os
 import statistics
@@ -65,6 +67,19 @@ def pieces_modes(cm, dev, reps):
                 else:
                     run = lambda p, x=x, wf=wf, tl=tl, nbr=nbr, n=n, K=K, cout=cout: ops.spconv_fwd_ws(x, wf, tl, nbr, n, K, cout, pieces=p)
         cases.append((fam, "s%d k%d %d->%d" % (stride, ks, cin, cout), n, pairs, cin, cout, run))
+    # the pair-array weight gradient: (stride of the input rows, stride of the output-gradient rows, kernel size, cin, cout)
+    for s_in, s_out, ks, cin, cout in ((1, 1, 3, 96, 96), (16, 8, 2, 256, 128), (2, 2, 1, 128, 128)):
+        n_in, n = cm.size(s_in), cm.size(s_out)
+        x, g = torch.randn(n_in, cin, device=dev), torch.randn(n, cout, device=dev)
+        K = ks ** 3
+        if ks == 1:
+            pairs, tl, swap = n, None, False
+        elif s_in > s_out:            # transposed: the arrays of the strided convolution it mirrors, walked the other way
+            pairs, tl, swap = int(ops.kmap_count(cm.kmap(s_out, s_in, ks)[0]).sum()), cm.kmap_lists(s_out, s_in, ks)[0], True
+        else:
+            pairs, tl, swap = int(ops.kmap_count(cm.kmap(s_in, s_out, ks)[0]).sum()), cm.kmap_lists(s_in, s_out, ks)[0], False
+        run = lambda p, x=x, g=g, tl=tl, K=K, swap=swap: ops.spconv_wgrad_tl(x, g, tl, K, swap=swap, pieces=p)
+        cases.append(("wgrad_tl", "s%d->s%d k%d %d->%d" % (s_in, s_out, ks, cin, cout), n, pairs, cin, cout, run))
     for fam, shape, n, pairs, cin, cout, run in cases:
         us = {p: [] for p in (3, 2, 1)}
         ref = run(3)
