@@ -1092,6 +1092,37 @@ int osn_knn_blend(const void* values, int value_bytes, int64_t n, int64_t n_cols
 int osn_knn_vote(const int64_t* labels, int64_t n, const int32_t* idx, const int32_t* count, int64_t m, int k, int64_t fill,
                  int64_t* out, int32_t* err, osn_stream_t stream);
 
+/* ---- nearest sources at any range: exact distance fields on the voxel grid (csrc/reach.hip) ---------------------- *
+ * osn_knn_grid stops one voxel from the query.  This entry finds, for every query cell, the nearest source cell of the
+ * same scene inside a Euclidean ball of `reach` cells (1 .. 4096), exactly: cells are integers, so is
+ * d2 = dx dx + dy dy + dz dz, and the result is the minimum of ONE 64-bit key,  uint32(d2) << 32 | uint32(id),  over the
+ * candidates -- the sources of the query's scene with |dx|, |dy|, |dz| <= reach and d2 <= reach^2.  A tie in d2 goes to
+ * the lowest id; a query that is itself a source gets d2 = 0.  No floating point, no atomics across workgroups: a pure
+ * function of the inputs whatever the schedule, two calls give the same bits.  Cells lie in the packable range
+ * |c| < 32767; a difference reaches 65 532 and its square does not fit 32 bits, so an axis is rejected by |d| > reach
+ * before any square is formed and no wrapped value is compared.
+ *
+ * osn_reach_nearest takes SORTED data (openscene_amd.ops.reach_nearest does the sorting in torch); block = cell >> 3 per
+ * axis (arithmetic shift: a floor division), ids >= 0:
+ *   q_cells int32 [n_queries, 4] rows (scene, x, y, z) sorted by (scene, block); order int32 [n_queries] (null: identity):
+ *     the result of sorted query i goes to row order[i] of the outputs;
+ *   src int32 [n_src, 4] rows (x, y, z, id) sorted by (scene, block); blocks int32 [n_blocks, 4] rows (scene, bx, by, bz):
+ *     the occupied blocks in that order; block_start int32 [n_blocks + 1]: block b holds src[block_start[b] ..
+ *     block_start[b + 1]): 512 entries for 8^3 distinct cells (repeated cells are allowed; LDS holds 512 at a time);
+ *   items int32 [n_items, 4] rows (q_start, q_end, block_start, block_end): at most 256 consecutive sorted queries of ONE
+ *     scene and the range of that scene's rows in `blocks`.  One workgroup per item, one query per lane: it walks the
+ *     range, first the blocks that touch the bounding box of its queries, then the others; it skips a block whose gap to
+ *     the box exceeds reach on an axis, or whose squared gap exceeds the largest best d2 of its lanes so far (a block at
+ *     exactly that bound is visited: it may hold a lower id); it stages a visited block in LDS and every lane scans it.
+ *   q_cells, items, src and blocks are 16-byte aligned.
+ * -> dist2 int32 [n_queries] and nearest int32 [n_queries] (the id), both -1 without a candidate; a query no item names
+ * is not written.  The err word (device int32, OR-ed into, never cleared here): 1 = an item's ranges out of range, 2 = a
+ * block's entry range or coordinates out of range, 4 = a cell outside the packable range, 8 = an order entry outside
+ * [0, n_queries).  Such entries are skipped, never dereferenced.  Asynchronous on `stream`, no workspace.              */
+int osn_reach_nearest(const int32_t* q_cells, const int32_t* order, int64_t n_queries, const int32_t* items, int64_t n_items,
+                      const int32_t* src, int64_t n_src, const int32_t* blocks, const int32_t* block_start, int64_t n_blocks,
+                      int reach, int32_t* dist2, int32_t* nearest, int32_t* err, osn_stream_t stream);
+
 /* ---- two scans in one frame: rigid RANSAC over correspondences, moments for Kabsch / ICP (csrc/align.hip) --------- *
  * Pairs are src, dst float32 [n_pairs, 3] on the device: pair p says "point src[p] of one scan is point dst[p] of the
  * other" (openscene_amd.match.mutual gives the rows).  A transform is 12 float32: R row-major, then t; it takes src onto

@@ -18,6 +18,7 @@ Python surface (mirrors the reference's own, file:line in each module):
     openscene_amd.merge            ... and merged again by mean feature: region adjacency, star contraction of adjacent regions
     openscene_amd.render           views of a scene on the GPU: point-splat z-buffer -> heat-map / label / colour pictures, depth for fusion
     openscene_amd.neighbors        results on other points: k-nearest search on the voxel grid, transfer, fill of unseen rows, smoothing
+    openscene_amd.reach            nearest sources at any range: exact distance fields on the voxel grid, "A near B", wide holes
     openscene_amd.align            two scans in one frame: rigid RANSAC over feature matches, ICP on the voxel index, overlap
     install_minkowski_alias()      make `import MinkowskiEngine` resolve to openscene_amd.minkowski
     conv_precision(name)           context: the convolutions of inference passes in "bf16x6" (default), "bf16x3" or "bf16x1"

@@ -173,6 +173,7 @@ PROTOTYPES = {
     "osn_knn_grid": (_i32, [_vp, _i64, _vp, _vp, _i64, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "osn_knn_blend": (_i32, [_vp, _i32, _i64, _i64, _vp, _vp, _vp, _i64, _i32, _i32, _f32, _f32, _vp, _vp, _vp, _vp]),
     "osn_knn_vote": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _i64, _vp, _vp, _vp]),
+    "osn_reach_nearest": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
     "osn_rigid_from_triplets": (_i32, [_vp, _vp, _i64, _vp, _i32, _f32, _c.c_double, _vp, _vp, _vp]),
     "osn_rigid_score": (_i32, [_vp, _vp, _i64, _vp, _vp, _i32, _f32, _vp, _vp]),
     "osn_rigid_best": (_i32, [_vp, _i32, _vp, _vp]),

@@ -243,7 +243,7 @@ def align_scenes(bank_a, xyz_a, bank_b, xyz_b, threshold, rows_a=None, rows_b=No
     return Alignment(fit, pairs, scores)
 
 
-def refine_icp(index_b, xyz_a, transform, iterations=10, radius=None, scene=0):
+def refine_icp(index_b, xyz_a, transform, iterations=10, radius=None, scene=0, reach=None):
     """Point-to-point ICP of xyz_a (float [M, 3], A's frame) onto the points of index_b (a PointIndex of scan B), starting
     from `transform` -> RigidFit (.neighbors int32 [M]: the final partner of every point, -1 without one; .iterations: the
     Kabsch steps taken).
@@ -251,7 +251,11 @@ def refine_icp(index_b, xyz_a, transform, iterations=10, radius=None, scene=0):
     A round: index_b.knn(transform.apply(xyz_a), 1, radius, scene); the moments of the pairs (a, its neighbour) under the
     float32 transform with tau2 = float32(radius)^2, straight from the neighbour list (no gathered copy of B); Kabsch on the
     host.  It stops when the neighbour list repeats, after `iterations` steps, or with fewer than 3 pairs.  radius: at most
-    (and by default) the grid's voxel size."""
+    (and by default) the grid's voxel size.
+
+    reach (cells): every round's knn runs its second stage (PointIndex.knn), so a point whose 27 cells are empty is paired
+    with a point around the nearest occupied cell within `reach` cells -- the nearest of a stated candidate set, not the exact
+    metric nearest neighbour; radius, and with it tau2, is then at most and by default (reach + 1) voxel sizes."""
     if not isinstance(index_b, PointIndex):
         raise TypeError("index_b must be a PointIndex")
     if not isinstance(transform, RigidTransform):
@@ -261,11 +265,16 @@ def refine_icp(index_b, xyz_a, transform, iterations=10, radius=None, scene=0):
     iterations = int(iterations)
     if iterations < 0:
         raise ValueError("iterations must be >= 0 (got %d)" % iterations)
-    tau2 = _tau2(grid.voxel_size if radius is None else radius)
+    if reach is None:
+        tau2 = _tau2(grid.voxel_size if radius is None else radius)
+        search = dict(radius=radius, scene=scene)
+    else:
+        tau2 = _tau2((ops.reach_value(reach) + 1) * grid.voxel_size if radius is None else radius)
+        search = dict(radius=radius, scene=scene, reach=reach)
     cur = transform.float32()
     prev = None
     for it in range(iterations + 1):
-        idx = index_b.knn(RigidTransform.from_float32(cur).apply(src), 1, radius=radius, scene=scene).idx[:, 0].contiguous()
+        idx = index_b.knn(RigidTransform.from_float32(cur).apply(src), 1, **search).idx[:, 0].contiguous()
         inl, r2, mom = ops.rigid_moments(src, grid.xyz, cur, tau2, dst_idx=idx)
         m = mom.cpu().numpy()
         if it == iterations or m[0] < 3 or (prev is not None and torch.equal(idx, prev)):

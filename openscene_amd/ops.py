@@ -2589,6 +2589,125 @@ def knn_vote(labels, idx, count, fill=-1, err=None):
     return out
 
 
+# ------------------------------------------------------- nearest sources at any range (csrc/reach.hip)
+REACH_MAX = 4096
+REACH_ITEM = 256                     # queries per work item: one workgroup, one query per lane
+REACH_E_ITEM, REACH_E_BLOCK, REACH_E_CELL, REACH_E_ORDER = 1, 2, 4, 8      # the bits of the err word (csrc/reach.hip)
+
+
+def reach_check(err):
+    """Raise if ops.reach_nearest recorded an entry out of range in `err` (int32 [1]); zeroes the word.  Synchronises."""
+    bits = int(err.item())
+    if bits == 0:
+        return
+    err.zero_()
+    what = [text for bit, text in ((REACH_E_ITEM, "a work item's ranges out of range"),
+                                   (REACH_E_BLOCK, "a block's entry range or coordinates out of range"),
+                                   (REACH_E_CELL, "a cell outside the packable range |c| < 32767"),
+                                   (REACH_E_ORDER, "an order entry outside [0, C)")) if bits & bit]
+    raise _lib.OpenSceneAmdError("reach: %s (err bits %d); such entries were skipped" % ("; ".join(what) or "unknown error", bits))
+
+
+def reach_value(reach):
+    if isinstance(reach, bool) or not hasattr(reach, "__index__") or isinstance(reach, torch.Tensor):
+        raise TypeError("reach must be an int (got %s)" % type(reach).__name__)
+    reach = int(reach)
+    if not 1 <= reach <= REACH_MAX:
+        raise ValueError("reach must be in 1 .. %d cells (got %d)" % (REACH_MAX, reach))
+    return reach
+
+
+def _reach_block_key(cells):
+    """int64 [R]: (scene, bx, by, bz) of int32 [R, 4] rows as one ascending key; block = cell >> 3, an arithmetic shift."""
+    c = cells.long()
+    b = (c[:, 1:] >> 3) + 4096                               # 13 bits per axis for |cell| < 32767
+    return ((c[:, 0] * 8192 + b[:, 0]) * 8192 + b[:, 1]) * 8192 + b[:, 2]
+
+
+def reach_plan(query_cells, source_cells, source_ids):
+    """The sorted arrays osn_reach_nearest takes (include/openscene_amd.h), in torch: (q_sorted int32 [C, 4], order int32 [C],
+    items int32 [W, 4], src int32 [S, 4] rows (x, y, z, id), blocks int32 [B, 4], block_start int32 [B + 1]).  Queries and
+    sources are sorted by (scene, block); the items are runs of at most REACH_ITEM sorted queries cut at scene boundaries,
+    each with the range of its scene's blocks."""
+    dev = query_cells.device
+    i32 = dict(dtype=torch.int32, device=dev)
+    order = torch.sort(_reach_block_key(query_cells), stable=True)[1]
+    q_sorted = query_cells[order].contiguous()
+    s_key, s_perm = torch.sort(_reach_block_key(source_cells), stable=True)
+    s_cells = source_cells[s_perm]
+    src = torch.cat([s_cells[:, 1:], source_ids[s_perm][:, None]], 1).contiguous()
+    _keys, per_block = torch.unique_consecutive(s_key, return_counts=True)
+    block_start = torch.zeros(per_block.shape[0] + 1, dtype=torch.int64, device=dev)
+    block_start[1:] = torch.cumsum(per_block, 0)
+    first = s_cells[block_start[:-1]]
+    blocks = torch.cat([first[:, :1], first[:, 1:] >> 3], 1).contiguous()
+    scenes, per_scene = torch.unique_consecutive(q_sorted[:, 0], return_counts=True)
+    scene_end = torch.cumsum(per_scene, 0)
+    scene_start = scene_end - per_scene
+    per_scene_items = (per_scene + REACH_ITEM - 1) // REACH_ITEM
+    item_first = torch.cumsum(per_scene_items, 0) - per_scene_items
+    seg = torch.repeat_interleave(torch.arange(scenes.shape[0], device=dev), per_scene_items)
+    q_start = scene_start[seg] + (torch.arange(seg.shape[0], device=dev) - item_first[seg]) * REACH_ITEM
+    q_end = torch.minimum(q_start + REACH_ITEM, scene_end[seg])
+    block_scene = blocks[:, 0].contiguous()
+    item_scene = scenes[seg].contiguous()
+    b_start = torch.searchsorted(block_scene, item_scene, right=False)
+    b_end = torch.searchsorted(block_scene, item_scene, right=True)
+    items = torch.stack([q_start, q_end, b_start, b_end], 1).to(torch.int32).contiguous()
+    return q_sorted, order.to(torch.int32).contiguous(), items, src, blocks, block_start.to(torch.int32).contiguous()
+
+
+def reach_nearest(query_cells, source_cells, source_ids, reach, err=None):
+    """For every query cell the nearest source cell of the same scene inside a Euclidean ball of `reach` cells, exactly.
+    query_cells int32 [C, 4] rows (scene, x, y, z); source_cells int32 [S, 4]; source_ids int32 [S] (>= 0); reach an int in
+    1 .. 4096.  The candidates of a query are the sources of its scene with |dx|, |dy|, |dz| <= reach and
+    d2 = dx^2 + dy^2 + dz^2 <= reach^2; the result is the minimum of the key uint32(d2) << 32 | uint32(id) over them.
+    -> (nearest int32 [C]: the id, dist2 int32 [C]: its d2), both -1 without a candidate; a tie in d2 goes to the lowest id.
+    Integers only: exact, and two calls give the same bits.  Cells lie in |c| < 32767; one outside is skipped and recorded
+    in `err` when one is given (reach_check raises), and checked here otherwise.  The sort by (scene, 8^3 block) and the
+    work items are torch (reach_plan); the search is csrc/reach.hip."""
+    for t, name in ((query_cells, "query_cells"), (source_cells, "source_cells")):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32:
+            raise TypeError("%s must be an int32 tensor" % name)
+        if t.dim() != 2 or t.shape[1] != 4:
+            raise ValueError("%s must be int32 [R, 4] rows (scene, x, y, z) (got %s)" % (name, tuple(t.shape)))
+    dev = query_cells.device
+    if source_cells.device != dev:
+        raise ValueError("source_cells must be on the queries' device (%s, got %s)" % (dev, source_cells.device))
+    if not isinstance(source_ids, torch.Tensor) or source_ids.dtype != torch.int32:
+        raise TypeError("source_ids must be an int32 tensor")
+    c, s = query_cells.shape[0], source_cells.shape[0]
+    if tuple(source_ids.shape) != (s,) or source_ids.device != dev:
+        raise ValueError("source_ids must be an int32 [%d] vector on the queries' device" % s)
+    if c >= 1 << 31 or s >= 1 << 31:
+        raise ValueError("fewer than 2^31 cells per call")
+    reach = reach_value(reach)
+    err, own = _regions_err(err, dev)
+    _prep(dev)                                    # (after the checks: they hold without a device)
+    if c == 0 or s == 0:
+        none = torch.full((c,), -1, dtype=torch.int32, device=dev)
+        return none, none.clone()
+    nearest, dist2 = reach_run(reach_plan(query_cells, source_cells, source_ids), reach, err)
+    if own:
+        reach_check(err)
+    return nearest, dist2
+
+
+def reach_run(plan, reach, err):
+    """The search over a reach_plan (the kernel alone: what tools/micro_reach.py times) -> (nearest, dist2); `err` is required
+    and not read here."""
+    q_sorted, order, items, src, blocks, block_start = plan
+    dev, c = q_sorted.device, q_sorted.shape[0]
+    lib = _prep(dev)
+    dist2 = torch.full((c,), -1, dtype=torch.int32, device=dev)           # (a query no item names keeps -1)
+    nearest = torch.full((c,), -1, dtype=torch.int32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_reach_nearest(_p(q_sorted), _p(order), c, _p(items), items.shape[0], _p(src), src.shape[0], _p(blocks),
+                                    _p(block_start), blocks.shape[0], reach_value(reach), _p(dist2), _p(nearest), _p(err), _stream(dev)),
+              "osn_reach_nearest")
+    return nearest, dist2
+
+
 # ------------------------------------------------------- two scans in one frame: rigid RANSAC, moments (csrc/align.hip)
 RIGID_MAX_HYPOTHESES = 1 << 20       # OSN_RIGID_MAX_HYPOTHESES
 RIGID_MOMENTS_CHUNK = 1024           # OSN_RIGID_MOMENTS_CHUNK: the pairs that are reduced into one float64 partial

@@ -318,6 +318,15 @@ class SearchResult:
         kw.setdefault("names", self.names)
         return find_objects(grid, self.heat, thresholds, **kw)
 
+    def near(self, grid, target, anchor, anchor_threshold, distance, reach=None):
+        """"target near anchor": fp16 [N, 1], column `target` of this search's heat-map where the point's voxel lies within
+        `distance` of a voxel holding a hit of column `anchor` (score >= anchor_threshold), -inf elsewhere
+        (openscene_amd.reach.near over `grid`, a VoxelGrid of the bank's points).  Needs a search with return_heat."""
+        if self.heat is None:
+            raise ValueError("the search was run without return_heat")
+        from .reach import near
+        return near(grid, self.heat, target, anchor, anchor_threshold, distance, reach=reach)
+
     def render(self, raster, scene, q, lo=None, hi=None, base=None, **kw):
         """uint8 [V, H, W, 3]: the views of `raster` (openscene_amd.render.rasterize of that scene's points) shaded with
         column q of the scene's heat-map, read in place through the row stride.  After a search with negatives the
