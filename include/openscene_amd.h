@@ -712,6 +712,39 @@ int osn_bank_search_contrast_fp8(const uint8_t* codes, const int8_t* exps, int64
                                  int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream,
                                  const void* negatives_f16, int m, float temperature);
 
+/* Two banks searched as one: the 2D-3D ensemble of run/evaluate.py:302-324 at query time.  A = bank_f16 / (codes, exps), in
+ * the reference the distilled features; B = other_f16 / (other_codes, other_exps), the fused ones: the same kind, n and d,
+ * row p of both the same point.  The choice of a source depends on the text rows (mask_ of :319 is a function of
+ * text_features), so it is made here, in the pass that reads the two banks, and not stored.
+ *   s_X(p, j)   the fp16 score osn_bank_search[_fp8] writes for row p of bank X and query j under the caller's normalize
+ *   n_X(p, j)   the same with normalize = 1
+ *   r_X(p, j)   with negatives, the relevancy osn_bank_search_contrast[_fp8] writes for bank X
+ * all three pure functions of one stored row and the query rows, formed here by the same code, bit for bit.
+ *   x_X = s_X, or r_X with negatives (m >= 1; m = 0 with null negatives_f16 means plain scores).
+ * mode 0, "vocabulary" (:318-321):  source(p) = max_j n_A(p, j) < max_j n_B(p, j).  The maximum propagates NaN; the
+ *   comparison is IEEE, so equal values, -0 against +0 and a NaN on either side give 0 (A).  The pick is always taken on the
+ *   normalised scores, whatever normalize is; negatives take no part in it.  Row p of heat is x_B(p, :) where source(p), else
+ *   x_A(p, :): a query's column depends on the other queries of the call.  source uint8 [n], required.
+ * mode 1, "query" (the commented variant, :312-316):  source(p, j) = x_A(p, j) < x_B(p, j), IEEE;  heat(p, j) = x_B(p, j)
+ *   where source(p, j), else x_A(p, j): column j depends on query j alone.  source uint8 [n, q] row-major, nullable.
+ * Everything after the heat-map -- heatT, topk_*, thresholds, counts, padding, NaN order, err bits, repeatability, the workspace
+ * osn_bank_search_ws_bytes(n, n_scenes, q, ...) -- is osn_bank_search's, on that heat-map.  q, m <= 1024, k <= 128.
+ * One launch, 128 rows per workgroup.  Vocabulary: the queries' column groups over A's rows, then over B's, keeping only each
+ * row's maximum; the pick; then the walk of the plain (or contrast) search, every row fetched from its chosen source.  Query:
+ * every column group over A, then over B, A's fp16 values held in registers.  Each bank comes from HBM once; the further
+ * walks read the workgroup's rows from cache.                                                                             */
+int osn_bank_search_ensemble(const void* bank_f16, const void* other_f16, int64_t n, int d, const int64_t* scene_offsets,
+                             int n_scenes, int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
+                             const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
+                             int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream,
+                             const void* negatives_f16, int m, float temperature, int mode, uint8_t* source);
+int osn_bank_search_ensemble_fp8(const uint8_t* codes, const int8_t* exps, const uint8_t* other_codes, const int8_t* other_exps,
+                                 int64_t n, int d, const int64_t* scene_offsets, int n_scenes, int64_t max_scene_rows,
+                                 const void* queries_f16, int q, int normalize, int k, const float* thresholds, void* heat_f16,
+                                 void* topk_scores_f16, int64_t* topk_points, int64_t* counts, int32_t* err, void* ws,
+                                 size_t ws_bytes, osn_stream_t stream, const void* negatives_f16, int m, float temperature,
+                                 int mode, uint8_t* source);
+
 /* ---- descriptors of point sets over the bank (csrc/pool.hip) ----------------------------------------------------- *
  * The way back from points to a feature vector (README "Applications": "retrieve examples based on similarities", room
  * type, labelling a found object): the sum of the normalised stored rows of every group of a list of bank rows; the mean

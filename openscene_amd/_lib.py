@@ -132,6 +132,10 @@ PROTOTYPES = {
                                         _vp, _i32, _f32]),
     "osn_bank_search_contrast_fp8": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
                                             _vp, _vp, _i32, _f32]),
+    "osn_bank_search_ensemble": (_i32, [_vp, _vp, _i64, _i32, _vp, _i32, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _sz,
+                                        _vp, _vp, _i32, _f32, _i32, _vp]),
+    "osn_bank_search_ensemble_fp8": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, _vp, _i32, _i64, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp,
+                                            _vp, _vp, _sz, _vp, _vp, _i32, _f32, _i32, _vp]),
     "osn_bank_pool_ws_bytes": (_sz, [_i64, _i64, _i32]),
     "osn_bank_pool": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),
     "osn_bank_pool_fp8": (_i32, [_vp, _vp, _i64, _i32, _vp, _i64, _vp, _i64, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _sz, _vp]),

@@ -37,6 +37,8 @@
 // Negative queries (osn_bank_search_contrast / _fp8): the heat kernels' CONTRAST instances walk the negatives' column groups
 // first -- same loop, each score rounded to fp16, only the row's maximum kept (rneg, LDS) -- and then write, for the queries,
 // fp16(1 / (1 + expf(-(s - rneg) / temperature))) in place of the fp16 score s.  Pass 2 selects on that relevancy unchanged.
+#include <type_traits>
+
 #include "bank.h"
 
 namespace osn {
@@ -47,6 +49,7 @@ constexpr int S_BM = 128;          // bank rows per workgroup (4 waves x 32)
 constexpr int S_DK = 128;          // feature chunk (halfs): 256 bytes of a row, 32 KB per workgroup in flight
 constexpr int S_LD = S_DK + 8;     // padded LDS row (272 B: 16-byte aligned, conflict-free 16-byte reads)
 static_assert(S_LD >= S_BM + 8, "the score tile [column][row] reuses the row tile");
+enum { ENS_NONE = 0, ENS_VOCABULARY = 1, ENS_QUERY = 2 };  // two banks searched as one (osn_bank_search_ensemble): mode + 1
 
 constexpr int SEL_T = 256;         // threads of a select workgroup
 constexpr int SEL_IT = 2;          // 8 scores per thread and iteration
@@ -166,12 +169,18 @@ __device__ __forceinline__ void row_norms(float* rden, const float (&ss)[S_BM * 
 // CONTRAST (osn_bank_search_contrast): a group of negatives (`neg`, q = their number) is stored nowhere -- the largest fp16
 // score of a row, NaN if one of them is, is kept in rneg[row]; a group of queries writes, in place of the fp16 score s,
 // fp16(1 / (1 + expf(-(s - rneg[row]) / temperature))), the relevancy against the best negative.
-template <int CT, bool SCALED, bool CONTRAST>
+// ENS_VOCABULARY: the pick's two walks over the queries are such maxima groups (neg, rneg = the source's row maxima), with or
+// without CONTRAST.  ENS_QUERY: a group of queries runs twice; side 0 (source A) keeps its fp16 values in `held` and writes
+// nothing, side 1 (source B) writes the larger of the two where A < B (IEEE), A's otherwise, and the choice into `source`
+// (nullable, [n, q] bytes).
+template <int CT, bool SCALED, bool CONTRAST, int ENS = ENS_NONE>
 __device__ __forceinline__ void scores_out(const f32x16 (&acc)[CT], _Float16 (*Sc)[S_LD], const float* rden, const float* rscale,
                                            float* rneg, bool neg, float temperature, _Float16* __restrict__ heat,
                                            _Float16* __restrict__ heatT, int64_t ldT, int64_t row0, int64_t n, int q, int cg0,
-                                           int normalize, int tid) {
+                                           int normalize, int tid, int side = 0, half2 (*held)[8] = nullptr,
+                                           uint8_t* __restrict__ source = nullptr) {
     const int lane = tid & 63, wave = tid >> 6;
+    constexpr bool MAXIMA = CONTRAST || ENS == ENS_VOCABULARY;      // groups that leave a row maximum and nothing else exist
 #pragma unroll
     for (int t = 0; t < CT; ++t) {
 #pragma unroll
@@ -185,11 +194,28 @@ __device__ __forceinline__ void scores_out(const f32x16 (&acc)[CT], _Float16 (*S
                 const float z = ((float)h - rneg[lrow]) / temperature;
                 h = (_Float16)(1.0f / (1.0f + expf(-z)));
             }
+            if constexpr (ENS == ENS_QUERY) {
+                if (!neg) {
+                    if (side == 0) {                        // (uniform) A's value waits in registers for B's
+                        held[t][r >> 1][r & 1] = h;
+                        continue;
+                    }
+                    const _Float16 a = held[t][r >> 1][r & 1];
+                    const bool from_b = (float)a < (float)h;        // IEEE: a tie, -0 against +0, a NaN on either side -> A
+                    h = from_b ? h : a;
+                    const int64_t row = row0 + lrow;
+                    const int col = cg0 + t * 32 + (lane & 31);
+                    if (source && row < n && col < q) source[row * q + col] = from_b ? 1 : 0;
+                }
+            }
             Sc[t * 32 + (lane & 31)][lrow] = h;
         }
     }
+    if constexpr (ENS == ENS_QUERY) {
+        if (!neg && side == 0) return;                      // nothing was written to the tile
+    }
     __syncthreads();
-    if (CONTRAST && neg) {                                  // (uniform over the workgroup)
+    if (MAXIMA && neg) {                                    // (uniform over the workgroup)
         if (tid < S_BM) {
             const int qn = (q - cg0) < 32 * CT ? (q - cg0) : 32 * CT;
             float nm = rneg[tid];
@@ -235,15 +261,27 @@ struct ColumnGroups {
     __device__ __forceinline__ int col0(int cg) const { return neg(cg) ? cg - first : cg; }       // first column inside its matrix
 };
 
-template <int CT, int WGS, bool CONTRAST>
+// Two banks as one (ENS, osn_bank_search_ensemble): B2 holds the second source's rows; bit ps of `from2` sends the fetch of this
+// thread's row ps of a sweep to B2.  A walk is one column group over the workgroup's rows, the plain kernel's loop body.
+//   ENS_VOCABULARY  the queries' groups over A, then over B, normalised, each keeping only the row maxima (rneg, rneg2), as the
+//                   negatives of CONTRAST do; source(row) = max A < max B goes to LDS (over rneg2) and to `source`; then the plain
+//                   kernel's walks, every row fetched from its chosen source, the sum of squares taken again on the way (the same
+//                   chunks in the same order: the chosen source's denominator, bit for bit).  LDS: 512 bytes more than CONTRAST.
+//   ENS_QUERY       A's negatives (rneg) and first group of queries, then B's (rneg2), then every further group over A and over B;
+//                   A's fp16 values of a group wait in registers for B's (scores_out), across B's negatives for the first group.
+//                   Denominators of both sources stay in LDS (rden, rden2).
+template <int CT, int WGS, bool CONTRAST, int ENS = ENS_NONE>
 __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restrict__ B, const _Float16* __restrict__ T,
                                                         _Float16* __restrict__ heat, _Float16* __restrict__ heatT, int64_t ldT,
                                                         int64_t n, int d, int q, int normalize, const _Float16* __restrict__ Tn,
-                                                        int m, float temperature) {
+                                                        int m, float temperature, const _Float16* __restrict__ B2,
+                                                        uint8_t* __restrict__ source) {
     __shared__ __attribute__((aligned(16))) _Float16 Xs[S_BM][S_LD];
     __shared__ __attribute__((aligned(16))) _Float16 Ts[CT * 32][S_LD];
     __shared__ float rden[S_BM];
     __shared__ float rneg[S_BM];                            // CONTRAST: the row's best negative score
+    __shared__ float rden2[S_BM];                           // ENS_QUERY: B's denominators
+    __shared__ float rneg2[S_BM];                           // ENS: B's row maxima, then the pick | B's best negative score
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t row0 = int64_t(blockIdx.x) * S_BM;
@@ -252,19 +290,23 @@ __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restri
 #pragma unroll
     for (int ps = 0; ps < S_BM / 16; ++ps) ss[ps] = 0.f;
     if (CONTRAST && tid < S_BM) rneg[tid] = -INFINITY;      // (read after the barriers of the first group)
+    uint32_t from2 = 0;
+    half2 held[ENS == ENS_QUERY ? CT : 1][8];
 
-    const ColumnGroups<CT, CONTRAST> groups(m);
-    for (int cg = groups.first; cg < q; cg += 32 * CT) {
-        const bool neg = groups.neg(cg);
-        const int cg0 = groups.col0(cg);
-        const _Float16* __restrict__ Tg = neg ? Tn : T;
-        const int qg = neg ? m : q;
-        const bool sumsq = normalize && cg == groups.first;
+    // one column group: columns cg0 .. of Tg [qg, d]; sumsq: the row norms are taken on the way, into den
+    auto walk = [&](const _Float16* __restrict__ Tg, int qg, int cg0, bool neg, bool sumsq, int nrm, float* den, float* rn,
+                    int side) {
         f32x16 acc[CT];
 #pragma unroll
         for (int t = 0; t < CT; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+        if constexpr (ENS != ENS_NONE) {
+            if (sumsq) {
+#pragma unroll
+                for (int ps = 0; ps < S_BM / 16; ++ps) ss[ps] = 0.f;
+            }
+        }
         // one chunk in flight in registers while the MFMAs of the previous one run from LDS (rows fetched as the queries are)
         uint4 px[S_BM / 16];
         uint4 pt[2 * CT];
@@ -274,7 +316,9 @@ __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restri
             for (int ps = 0; ps < S_BM / 16; ++ps) {
                 const int64_t row = row0 + ps * 16 + xr;
                 const bool ok = row < n && d0 + xq * 8 < d;
-                px[ps] = *reinterpret_cast<const uint4*>(ok ? B + row * d + d0 + xq * 8 : B);
+                const _Float16* __restrict__ Bs = B;
+                if constexpr (ENS != ENS_NONE) Bs = (from2 >> ps) & 1u ? B2 : B;
+                px[ps] = *reinterpret_cast<const uint4*>(ok ? Bs + row * d + d0 + xq * 8 : B);
             }
         };
         auto stash = [&](int d0) {
@@ -307,9 +351,52 @@ __global__ __launch_bounds__(256, WGS) void heat_kernel(const _Float16* __restri
             if (d0 + S_DK < d) stash(d0 + S_DK);
             __syncthreads();
         }
-        if (sumsq) row_norms<16, false>(rden, ss, nullptr, tid);
-        scores_out<CT, false, CONTRAST>(acc, Xs, rden, nullptr, rneg, neg, temperature, heat, heatT, ldT, row0, n, qg, cg0,
-                                        normalize, tid);
+        if (sumsq) row_norms<16, false>(den, ss, nullptr, tid);
+        scores_out<CT, false, CONTRAST, ENS>(acc, Xs, den, nullptr, rn, neg, temperature, heat, heatT, ldT, row0, n, qg, cg0, nrm,
+                                             tid, side, held, source);
+    };
+
+    const ColumnGroups<CT, CONTRAST> groups(m);
+    if constexpr (ENS == ENS_VOCABULARY) {
+        for (int side = 0; side < 2; ++side) {
+            float* rmax = side ? rneg2 : rneg;
+            from2 = side ? ~0u : 0u;
+            if (tid < S_BM) rmax[tid] = -INFINITY;          // (read after the barriers of the first group)
+            for (int cg = 0; cg < q; cg += 32 * CT) walk(T, q, cg, true, cg == 0, 1, rden, rmax, 0);
+        }
+        if (tid < S_BM) {                                   // (the last walk ended with a barrier)
+            const bool from_b = rneg[tid] < rneg2[tid];     // IEEE: a tie or a NaN on either side -> A
+            if (row0 + tid < n) source[row0 + tid] = from_b ? 1 : 0;
+            rneg2[tid] = from_b ? 1.f : 0.f;
+            if (CONTRAST) rneg[tid] = -INFINITY;
+        }
+        __syncthreads();
+        from2 = 0;
+#pragma unroll
+        for (int ps = 0; ps < S_BM / 16; ++ps) from2 |= (rneg2[ps * 16 + xr] != 0.f ? 1u : 0u) << ps;
+    }
+    if constexpr (ENS == ENS_QUERY) {
+        if (CONTRAST && tid < S_BM) rneg2[tid] = -INFINITY;
+        // a source's negatives and its first group of queries back to back (its rows are still in cache), then the further groups
+        for (int side = 0; side < 2; ++side) {
+            from2 = side ? ~0u : 0u;
+            for (int cg = groups.first; cg <= 0; cg += 32 * CT) {
+                const bool neg = groups.neg(cg);
+                walk(neg ? Tn : T, neg ? m : q, groups.col0(cg), neg, normalize && cg == groups.first, normalize,
+                     side ? rden2 : rden, side ? rneg2 : rneg, side);
+            }
+        }
+        for (int cg = 32 * CT; cg < q; cg += 32 * CT) {
+            for (int side = 0; side < 2; ++side) {
+                from2 = side ? ~0u : 0u;
+                walk(T, q, cg, false, false, normalize, side ? rden2 : rden, side ? rneg2 : rneg, side);
+            }
+        }
+    } else {
+        for (int cg = groups.first; cg < q; cg += 32 * CT) {
+            const bool neg = groups.neg(cg);
+            walk(neg ? Tn : T, neg ? m : q, groups.col0(cg), neg, normalize && cg == groups.first, normalize, rden, rneg, 0);
+        }
     }
 }
 
@@ -419,17 +506,23 @@ __global__ __launch_bounds__(256) void bank_append_fp8_kernel(const void* __rest
 // Two workgroups per CU: the second register stage and the conversion need 194 / 250 VGPRs (one / two column tiles); held to
 // the 168 of three workgroups the kernel spills inside the loop and measured 0.81x of the fp16 pass at 8 x 150 k x 768 x 32
 // where this shape measured 0.67x.
-template <int CT, int WGS, bool CONTRAST>
+// ENS: as heat_kernel; the second source is (B2, E2).  ENS_VOCABULARY loads rscale anew for each of its three parts (row_norms
+// leaves 1 there), the last from the exponent of each row's chosen source; ENS_QUERY keeps rscale2 / rden2 for B.
+template <int CT, int WGS, bool CONTRAST, int ENS = ENS_NONE>
 __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __restrict__ B, const int8_t* __restrict__ E,
                                                             const _Float16* __restrict__ T, _Float16* __restrict__ heat,
                                                             _Float16* __restrict__ heatT, int64_t ldT, int64_t n, int d, int q,
                                                             int normalize, const _Float16* __restrict__ Tn, int m,
-                                                            float temperature) {
+                                                            float temperature, const uint8_t* __restrict__ B2,
+                                                            const int8_t* __restrict__ E2, uint8_t* __restrict__ source) {
     __shared__ __attribute__((aligned(16))) _Float16 Xs[S_BM][S_LD];
     __shared__ __attribute__((aligned(16))) _Float16 Ts[CT * 32][S_LD];
     __shared__ float rden[S_BM];
     __shared__ float rscale[S_BM];                          // 2^e of the row
     __shared__ float rneg[S_BM];                            // CONTRAST: the row's best negative score
+    __shared__ float rden2[S_BM];                           // ENS_QUERY: B's denominators
+    __shared__ float rscale2[S_BM];                         // ENS_QUERY: B's 2^e
+    __shared__ float rneg2[S_BM];                           // ENS: B's row maxima, then the pick | B's best negative score
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int64_t row0 = int64_t(blockIdx.x) * S_BM;
@@ -441,21 +534,26 @@ __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __res
     if (tid < S_BM) {
         const int64_t row = row0 + tid < n ? row0 + tid : n - 1;
         rscale[tid] = __uint_as_float(uint32_t(127 + int(E[row])) << 23);
+        if (ENS == ENS_QUERY) rscale2[tid] = __uint_as_float(uint32_t(127 + int(E2[row])) << 23);
         if (CONTRAST) rneg[tid] = -INFINITY;
     }
+    uint32_t from2 = 0;
+    half2 held[ENS == ENS_QUERY ? CT : 1][8];
 
-    const ColumnGroups<CT, CONTRAST> groups(m);
-    for (int cg = groups.first; cg < q; cg += 32 * CT) {
-        const bool neg = groups.neg(cg);
-        const int cg0 = groups.col0(cg);
-        const _Float16* __restrict__ Tg = neg ? Tn : T;
-        const int qg = neg ? m : q;
-        const bool sumsq = normalize && cg == groups.first;
+    // one column group: columns cg0 .. of Tg [qg, d]; sumsq: the row norms are taken on the way, into den (and rs becomes 1)
+    auto walk = [&](const _Float16* __restrict__ Tg, int qg, int cg0, bool neg, bool sumsq, int nrm, float* den, float* rs,
+                    float* rn, int side) {
         f32x16 acc[CT];
 #pragma unroll
         for (int t = 0; t < CT; ++t)
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;
+        if constexpr (ENS != ENS_NONE) {
+            if (sumsq) {
+#pragma unroll
+                for (int ps = 0; ps < NPS; ++ps) ss[ps] = 0.f;
+            }
+        }
         uint4 pxa[NPS], pxb[NPS];                           // code chunks c + 1 and c + 2 while the MFMAs of chunk c run
         uint4 pt[2 * CT];                                   // the query chunk c + 1 (from L2)
         auto fetch_x = [&](uint4(&px)[NPS], int d0) {       // (unconditional from clamped addresses, as the queries)
@@ -463,7 +561,9 @@ __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __res
             for (int ps = 0; ps < NPS; ++ps) {
                 const int64_t row = row0 + ps * 32 + xr;
                 const bool ok = row < n && d0 + xq * 16 < d;
-                px[ps] = *reinterpret_cast<const uint4*>(ok ? B + row * d + d0 + xq * 16 : B);
+                const uint8_t* __restrict__ Bs = B;
+                if constexpr (ENS != ENS_NONE) Bs = (from2 >> ps) & 1u ? B2 : B;
+                px[ps] = *reinterpret_cast<const uint4*>(ok ? Bs + row * d + d0 + xq * 16 : B);
             }
         };
         auto stash = [&](const uint4(&px)[NPS], int d0) {
@@ -515,9 +615,57 @@ __global__ __launch_bounds__(256, WGS) void heat_fp8_kernel(const uint8_t* __res
             if (d0 + 2 * S_DK < d) stash(pxa, d0 + 2 * S_DK);
             __syncthreads();
         }
-        if (sumsq) row_norms<8, true>(rden, ss, rscale, tid);       // ||c|| + 1e-5 / 2^e
-        scores_out<CT, true, CONTRAST>(acc, Xs, rden, rscale, rneg, neg, temperature, heat, heatT, ldT, row0, n, qg, cg0,
-                                       normalize, tid);
+        if (sumsq) row_norms<8, true>(den, ss, rs, tid);            // ||c|| + 1e-5 / 2^e
+        scores_out<CT, true, CONTRAST, ENS>(acc, Xs, den, rs, rn, neg, temperature, heat, heatT, ldT, row0, n, qg, cg0, nrm, tid,
+                                            side, held, source);
+    };
+
+    const ColumnGroups<CT, CONTRAST> groups(m);
+    if constexpr (ENS == ENS_VOCABULARY) {
+        const int64_t erow = row0 + tid < n ? row0 + tid : n - 1;          // (tid < S_BM)
+        for (int side = 0; side < 2; ++side) {
+            float* rmax = side ? rneg2 : rneg;
+            from2 = side ? ~0u : 0u;
+            if (tid < S_BM) {                               // (read after the barriers of the first group)
+                rmax[tid] = -INFINITY;
+                if (side) rscale[tid] = __uint_as_float(uint32_t(127 + int(E2[erow])) << 23);
+            }
+            for (int cg = 0; cg < q; cg += 32 * CT) walk(T, q, cg, true, cg == 0, 1, rden, rscale, rmax, 0);
+        }
+        if (tid < S_BM) {                                   // (the last walk ended with a barrier)
+            const bool from_b = rneg[tid] < rneg2[tid];     // IEEE: a tie or a NaN on either side -> A
+            if (row0 + tid < n) source[row0 + tid] = from_b ? 1 : 0;
+            rneg2[tid] = from_b ? 1.f : 0.f;
+            rscale[tid] = __uint_as_float(uint32_t(127 + int(from_b ? E2[erow] : E[erow])) << 23);
+            if (CONTRAST) rneg[tid] = -INFINITY;
+        }
+        __syncthreads();
+        from2 = 0;
+#pragma unroll
+        for (int ps = 0; ps < NPS; ++ps) from2 |= (rneg2[ps * 32 + xr] != 0.f ? 1u : 0u) << ps;
+    }
+    if constexpr (ENS == ENS_QUERY) {
+        if (CONTRAST && tid < S_BM) rneg2[tid] = -INFINITY;
+        // a source's negatives and its first group of queries back to back (its rows are still in cache), then the further groups
+        for (int side = 0; side < 2; ++side) {
+            from2 = side ? ~0u : 0u;
+            for (int cg = groups.first; cg <= 0; cg += 32 * CT) {
+                const bool neg = groups.neg(cg);
+                walk(neg ? Tn : T, neg ? m : q, groups.col0(cg), neg, normalize && cg == groups.first, normalize,
+                     side ? rden2 : rden, side ? rscale2 : rscale, side ? rneg2 : rneg, side);
+            }
+        }
+        for (int cg = 32 * CT; cg < q; cg += 32 * CT) {
+            for (int side = 0; side < 2; ++side) {
+                from2 = side ? ~0u : 0u;
+                walk(T, q, cg, false, false, normalize, side ? rden2 : rden, side ? rscale2 : rscale, side ? rneg2 : rneg, side);
+            }
+        }
+    } else {
+        for (int cg = groups.first; cg < q; cg += 32 * CT) {
+            const bool neg = groups.neg(cg);
+            walk(neg ? Tn : T, neg ? m : q, groups.col0(cg), neg, normalize && cg == groups.first, normalize, rden, rscale, rneg, 0);
+        }
     }
 }
 
@@ -899,23 +1047,39 @@ extern "C" size_t osn_bank_search_ws_bytes(int64_t n, int n_scenes, int q, int k
     return search_ws(n, n_scenes, q, k, max_scene_rows).total;
 }
 
+// the second source of an ensemble search (osn_bank_search_ensemble): null for every other entry
+struct Ensemble {
+    const void* rows;      // fp16 rows, or codes
+    const int8_t* exps;    // the codes' row exponents
+    int mode;              // 0 vocabulary, 1 query
+    uint8_t* source;       // [n] (mode 0) | [n, q], nullable (mode 1)
+};
+
 // pass 1 of every search: one or two column tiles (32 or 64 columns a group); three workgroups per CU over fp16 rows, two over
 // codes (heat_fp8_kernel).  The CONTRAST instances keep these bounds: the relevancy adds no register that lives across the
 // chunk loop and 512 bytes of LDS (3 x 53248 B with two column tiles, of 160 KB).
-template <bool CONTRAST>
+// The ensemble instances over fp16 rows run TWO workgroups per CU.  Their LDS fits three (ENS_VOCABULARY adds 512 bytes to
+// CONTRAST's, 3 x 53760 B; ENS_QUERY 1024, 3 x 54272 B = 162816 of 163840), but held to the 168 VGPRs
+// of three they spill 64 .. 436 bytes a lane inside the walk; measured at 8 x 150 k x 768 x 32 (heat pass, us, three | two per CU):
+// vocabulary 1042 | 997, with 4 negatives 1158 | 1183; query 864 | 805, with 4 negatives 1727 | 1318 (the last pair with both
+// sources' negatives ahead of the queries; a source's negatives next to its first group of queries: 1180 at two per CU).
+constexpr int ENS_WGS16 = 2;
+template <bool CONTRAST, int ENS>
 static void heat_launch(bool fp8, const void* rows, const int8_t* exps, const _Float16* T, _Float16* heat, _Float16* heatT,
                         int64_t ldT, int64_t n, int d, int q, int normalize, const _Float16* Tn, int m, float temperature,
-                        hipStream_t st) {
+                        const void* rows2, const int8_t* exps2, uint8_t* source, hipStream_t st) {
     const dim3 grid(unsigned(cdiv(n, S_BM))), block(256);
     const bool one = q <= 32 && m <= 32;                    // (m = 0 without negatives)
     if (fp8) {
         const uint8_t* B = static_cast<const uint8_t*>(rows);
-        if (one) hipLaunchKernelGGL((heat_fp8_kernel<1, 2, CONTRAST>), grid, block, 0, st, B, exps, T, heat, heatT, ldT, n, d, q, normalize, Tn, m, temperature);
-        else hipLaunchKernelGGL((heat_fp8_kernel<2, 2, CONTRAST>), grid, block, 0, st, B, exps, T, heat, heatT, ldT, n, d, q, normalize, Tn, m, temperature);
+        const uint8_t* B2 = static_cast<const uint8_t*>(rows2);
+        if (one) hipLaunchKernelGGL((heat_fp8_kernel<1, 2, CONTRAST, ENS>), grid, block, 0, st, B, exps, T, heat, heatT, ldT, n, d, q, normalize, Tn, m, temperature, B2, exps2, source);
+        else hipLaunchKernelGGL((heat_fp8_kernel<2, 2, CONTRAST, ENS>), grid, block, 0, st, B, exps, T, heat, heatT, ldT, n, d, q, normalize, Tn, m, temperature, B2, exps2, source);
     } else {
         const _Float16* B = static_cast<const _Float16*>(rows);
-        if (one) hipLaunchKernelGGL((heat_kernel<1, 3, CONTRAST>), grid, block, 0, st, B, T, heat, heatT, ldT, n, d, q, normalize, Tn, m, temperature);
-        else hipLaunchKernelGGL((heat_kernel<2, 3, CONTRAST>), grid, block, 0, st, B, T, heat, heatT, ldT, n, d, q, normalize, Tn, m, temperature);
+        const _Float16* B2 = static_cast<const _Float16*>(rows2);
+        if (one) hipLaunchKernelGGL((heat_kernel<1, ENS == ENS_NONE ? 3 : ENS_WGS16, CONTRAST, ENS>), grid, block, 0, st, B, T, heat, heatT, ldT, n, d, q, normalize, Tn, m, temperature, B2, source);
+        else hipLaunchKernelGGL((heat_kernel<2, ENS == ENS_NONE ? 3 : ENS_WGS16, CONTRAST, ENS>), grid, block, 0, st, B, T, heat, heatT, ldT, n, d, q, normalize, Tn, m, temperature, B2, source);
     }
 }
 
@@ -927,11 +1091,12 @@ struct Contrast {
 };
 
 // every search: `rows` are fp16 rows or, with `fp8`, e4m3 codes that go with the row exponents `exps`; `who` names the entry
-// in the messages; `contrast` (nullable) turns the scores into relevancies
+// in the messages; `contrast` (nullable) turns the scores into relevancies; `ens` (nullable) is the second source
 static int bank_search_impl(const char* who, bool fp8, const void* rows, const int8_t* exps, int64_t n, int d, const int64_t* scene_offsets,
                             int n_scenes, int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
                             const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points, int64_t* counts,
-                            int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream, const Contrast* contrast = nullptr) {
+                            int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream, const Contrast* contrast = nullptr,
+                            const Ensemble* ens = nullptr) {
     hipStream_t st = static_cast<hipStream_t>(stream);
     const int dm = fp8 ? 16 : 8;
     OSN_REQUIRE(n >= 0 && d >= dm && d % dm == 0 && q >= 1 && q <= 1024, OSN_E_ARG,
@@ -952,6 +1117,12 @@ static int bank_search_impl(const char* who, bool fp8, const void* rows, const i
         OSN_REQUIRE(contrast->negatives_f16 && aligned16(contrast->negatives_f16), OSN_E_ARG,
                     "%s: negatives must be non-null and 16-byte aligned", who);
     }
+    if (ens) {
+        OSN_REQUIRE(ens->mode == 0 || ens->mode == 1, OSN_E_ARG, "%s: mode=%d (0 vocabulary, 1 query)", who, ens->mode);
+        OSN_REQUIRE(n == 0 || (ens->rows && aligned16(ens->rows) && (ens->exps || !fp8)), OSN_E_ARG,
+                    "%s: the other bank's rows%s must be non-null, the rows 16-byte aligned", who, fp8 ? " and exponents" : "");
+        OSN_REQUIRE(n == 0 || ens->mode == 1 || ens->source, OSN_E_ARG, "%s: vocabulary mode needs source [n]", who);
+    }
     const SearchWs w = search_ws(n, n_scenes, q, k, max_scene_rows);
     OSN_REQUIRE(ws && aligned16(ws) && ws_bytes >= w.total, OSN_E_WS, "%s: workspace too small (%zu < %zu)", who, ws_bytes, w.total);
     char* p = static_cast<char*>(ws);
@@ -959,10 +1130,20 @@ static int bank_search_impl(const char* who, bool fp8, const void* rows, const i
     if (n > 0) {
         const _Float16* T = static_cast<const _Float16*>(queries_f16);
         _Float16* heat = static_cast<_Float16*>(heat_f16);
-        if (contrast)
-            heat_launch<true>(fp8, rows, exps, T, heat, heatT, w.ldT, n, d, q, normalize,
-                              static_cast<const _Float16*>(contrast->negatives_f16), contrast->m, contrast->temperature, st);
-        else heat_launch<false>(fp8, rows, exps, T, heat, heatT, w.ldT, n, d, q, normalize, nullptr, 0, 0.f, st);
+        const _Float16* Tn = contrast ? static_cast<const _Float16*>(contrast->negatives_f16) : nullptr;
+        const int m = contrast ? contrast->m : 0;
+        const float tau = contrast ? contrast->temperature : 0.f;
+        const void* rows2 = ens ? ens->rows : nullptr;
+        const int8_t* exps2 = ens ? ens->exps : nullptr;
+        uint8_t* source = ens ? ens->source : nullptr;
+        auto launch = [&](auto has_negatives) {
+            constexpr bool C = decltype(has_negatives)::value;
+            if (!ens) heat_launch<C, ENS_NONE>(fp8, rows, exps, T, heat, heatT, w.ldT, n, d, q, normalize, Tn, m, tau, rows2, exps2, source, st);
+            else if (ens->mode == 0) heat_launch<C, ENS_VOCABULARY>(fp8, rows, exps, T, heat, heatT, w.ldT, n, d, q, normalize, Tn, m, tau, rows2, exps2, source, st);
+            else heat_launch<C, ENS_QUERY>(fp8, rows, exps, T, heat, heatT, w.ldT, n, d, q, normalize, Tn, m, tau, rows2, exps2, source, st);
+        };
+        if (contrast) launch(std::true_type());
+        else launch(std::false_type());
         OSN_LAUNCH_CHECK();
     }
     if (n_scenes == 0) return OSN_OK;
@@ -1006,4 +1187,40 @@ extern "C" int osn_bank_search_contrast_fp8(const uint8_t* codes, const int8_t* 
     return bank_search_impl("osn_bank_search_contrast_fp8", true, codes, exps, n, d, scene_offsets, n_scenes, max_scene_rows,
                             queries_f16, q, normalize, k, thresholds, heat_f16, topk_scores_f16, topk_points, counts, err, ws,
                             ws_bytes, stream, &c);
+}
+
+// two banks as one (include/openscene_amd.h): m = 0 with null negatives means plain scores
+static int bank_search_ensemble_impl(const char* who, bool fp8, const void* rows, const int8_t* exps, const void* rows2,
+                                     const int8_t* exps2, int64_t n, int d, const int64_t* scene_offsets, int n_scenes,
+                                     int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
+                                     const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
+                                     int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream,
+                                     const void* negatives_f16, int m, float temperature, int mode, uint8_t* source) {
+    const Contrast c = {negatives_f16, m, temperature};
+    const Ensemble e = {rows2, exps2, mode, source};
+    const bool plain = m == 0 && !negatives_f16;
+    return bank_search_impl(who, fp8, rows, exps, n, d, scene_offsets, n_scenes, max_scene_rows, queries_f16, q, normalize, k,
+                            thresholds, heat_f16, topk_scores_f16, topk_points, counts, err, ws, ws_bytes, stream,
+                            plain ? nullptr : &c, &e);
+}
+
+extern "C" int osn_bank_search_ensemble(const void* bank_f16, const void* other_f16, int64_t n, int d, const int64_t* scene_offsets,
+                                        int n_scenes, int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
+                                        const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
+                                        int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream,
+                                        const void* negatives_f16, int m, float temperature, int mode, uint8_t* source) {
+    return bank_search_ensemble_impl("osn_bank_search_ensemble", false, bank_f16, nullptr, other_f16, nullptr, n, d, scene_offsets,
+                                     n_scenes, max_scene_rows, queries_f16, q, normalize, k, thresholds, heat_f16, topk_scores_f16,
+                                     topk_points, counts, err, ws, ws_bytes, stream, negatives_f16, m, temperature, mode, source);
+}
+
+extern "C" int osn_bank_search_ensemble_fp8(const uint8_t* codes, const int8_t* exps, const uint8_t* other_codes,
+                                            const int8_t* other_exps, int64_t n, int d, const int64_t* scene_offsets, int n_scenes,
+                                            int64_t max_scene_rows, const void* queries_f16, int q, int normalize, int k,
+                                            const float* thresholds, void* heat_f16, void* topk_scores_f16, int64_t* topk_points,
+                                            int64_t* counts, int32_t* err, void* ws, size_t ws_bytes, osn_stream_t stream,
+                                            const void* negatives_f16, int m, float temperature, int mode, uint8_t* source) {
+    return bank_search_ensemble_impl("osn_bank_search_ensemble_fp8", true, codes, exps, other_codes, other_exps, n, d, scene_offsets,
+                                     n_scenes, max_scene_rows, queries_f16, q, normalize, k, thresholds, heat_f16, topk_scores_f16,
+                                     topk_points, counts, err, ws, ws_bytes, stream, negatives_f16, m, temperature, mode, source);
 }

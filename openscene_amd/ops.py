@@ -1371,6 +1371,7 @@ def eval_check(err):
 # ---------------------------------------------------------------------- search
 BANK_MAX_K = 128
 BANK_MAX_Q = 1024
+BANK_ENSEMBLE_MODES = ("vocabulary", "query")    # the `mode` word of osn_bank_search_ensemble: the position in this tuple
 
 
 def _bank_append_args(feats, rows, row0, err, gather):
@@ -1417,11 +1418,14 @@ def bank_check(err):
 
 
 def _bank_search(entries, bank_ptrs, n, d, d_multiple, dev, scene_offsets, queries, k, thresholds, normalize, want_heat,
-                 max_scene_rows, err, negatives=None, temperature=0.1):
+                 max_scene_rows, err, negatives=None, temperature=0.1, ensemble_mode=None, want_source=True):
     """bank_search and bank_search_fp8 behind their own checks of the bank: `entries` are the C entries (plain, contrast)
     that take `bank_ptrs` (the fp16 rows, or the codes and the exponents) ahead of the arguments the two share; the
-    contrast entry is called when `negatives` are given."""
+    contrast entry is called when `negatives` are given.  ensemble_mode ("vocabulary" / "query"): `entries` is the one
+    ensemble entry, `bank_ptrs` hold both banks, and the choice of source is returned after the four results."""
     entry, tail = entries[0], ()
+    if ensemble_mode is not None and ensemble_mode not in BANK_ENSEMBLE_MODES:
+        raise ValueError('ensemble_mode must be "vocabulary" or "query" (got %r)' % (ensemble_mode,))
     if negatives is not None:
         if not isinstance(negatives, torch.Tensor) or negatives.dtype != torch.float16:
             raise TypeError("negatives must be a float16 tensor")
@@ -1435,7 +1439,9 @@ def _bank_search(entries, bank_ptrs, n, d, d_multiple, dev, scene_offsets, queri
         if not 0.0 < temperature < float("inf"):
             raise ValueError("the temperature must be finite and > 0 (got %r)" % (temperature,))
         negatives = negatives.contiguous()
-        entry, tail = entries[1], (_p(negatives), negatives.shape[0], temperature)
+        entry, tail = entries[-1], (_p(negatives), negatives.shape[0], temperature)
+    elif ensemble_mode is not None:
+        tail = (None, 0, 0.0)                               # m = 0 with null negatives: plain scores
     if queries.dtype != torch.float16:
         raise TypeError("queries must be float16 (util/util.py:41-44 produces fp16)")
     if queries.dim() != 2 or queries.shape[1] != d:
@@ -1472,6 +1478,14 @@ def _bank_search(entries, bank_ptrs, n, d, d_multiple, dev, scene_offsets, queri
     top_s = torch.empty((s, q, k), dtype=torch.float16, device=dev)
     top_p = torch.empty((s, q, k), dtype=torch.int64, device=dev)
     counts = torch.empty((s, q), dtype=torch.int64, device=dev) if thresholds is not None else None
+    source = None
+    if ensemble_mode is not None:
+        mode = BANK_ENSEMBLE_MODES.index(ensemble_mode)
+        if mode == 0:
+            source = torch.empty((n,), dtype=torch.bool, device=dev)
+        elif want_source:
+            source = torch.empty((n, q), dtype=torch.bool, device=dev)
+        tail = tail + (mode, _p(source))
     wsb = _cached("osn_bank_search_ws_bytes", n, s, q, k, max_scene_rows)
     ws = _ws(wsb, dev)
     with _Dev(dev):
@@ -1479,6 +1493,8 @@ def _bank_search(entries, bank_ptrs, n, d, d_multiple, dev, scene_offsets, queri
                     _p(heat), _p(top_s), _p(top_p), _p(counts), _p(err), _p(ws), ws.numel(), _stream(dev), *tail), entry.__name__)
     if own_err and s > 0:
         bank_check(err)
+    if ensemble_mode is not None:
+        return heat, top_s, top_p, counts, source
     return heat, top_s, top_p, counts
 
 
@@ -1548,6 +1564,53 @@ def bank_search_fp8(codes, exps, scene_offsets, queries, k=16, thresholds=None, 
     n, d = codes.shape
     return _bank_search((lib.osn_bank_search_fp8, lib.osn_bank_search_contrast_fp8), (_p(codes), _p(exps)), n, d, 16, dev,
                         scene_offsets, queries, k, thresholds, normalize, want_heat, max_scene_rows, err, negatives, temperature)
+
+
+def _same_bank(what, a, b):
+    if b.dtype != a.dtype or tuple(b.shape) != tuple(a.shape) or b.device != a.device or not b.is_contiguous():
+        raise ValueError("the other bank's %s must be a contiguous %s %s tensor on the bank's device (got %s %s on %s)"
+                         % (what, a.dtype, tuple(a.shape), b.dtype, tuple(b.shape), b.device))
+
+
+def bank_search_ensemble(bank, other, scene_offsets, queries, k=16, thresholds=None, normalize=True, want_heat=False,
+                         max_scene_rows=None, err=None, negatives=None, temperature=0.1, mode="vocabulary", want_source=True):
+    """bank_search over two fp16 banks of the same shape as one (osn_bank_search_ensemble; run/evaluate.py:302-324): row p
+    of the heat-map is that of `other` where the pick says so, of `bank` elsewhere.  mode "vocabulary": the source whose best
+    normalised score over the call's queries is larger (other only if strictly larger); "query": per element, the larger of
+    the two scores (relevancies with negatives).  -> bank_search's four results and source: bool [N] ("vocabulary"), bool
+    [N, Q] or, without want_source, None ("query").  The selection and the counts are taken on the combined heat-map."""
+    lib = _prep(bank.device)
+    if bank.dtype != torch.float16:
+        raise TypeError("the bank must be float16 (got %s)" % bank.dtype)
+    if bank.dim() != 2 or not bank.is_contiguous():
+        raise ValueError("the bank must be a contiguous [rows, dim] matrix")
+    _same_bank("rows", bank, other)
+    n, d = bank.shape
+    return _bank_search((lib.osn_bank_search_ensemble,), (_p(bank), _p(other)), n, d, 8, bank.device, scene_offsets, queries, k,
+                        thresholds, normalize, want_heat, max_scene_rows, err, negatives, temperature, mode, want_source)
+
+
+def bank_search_ensemble_fp8(codes, exps, other_codes, other_exps, scene_offsets, queries, k=16, thresholds=None, normalize=True,
+                             want_heat=False, max_scene_rows=None, err=None, negatives=None, temperature=0.1, mode="vocabulary",
+                             want_source=True):
+    """bank_search_ensemble over two fp8 banks (osn_bank_search_ensemble_fp8): (codes, exps) and (other_codes, other_exps) as
+    bank_search_fp8 takes them; everything else is bank_search_ensemble's."""
+    dev = codes.device
+    lib = _prep(dev)
+    if codes.dtype != torch.uint8:
+        raise TypeError("codes must be uint8 (got %s)" % codes.dtype)
+    if exps.dtype != torch.int8:
+        raise TypeError("exponents must be int8 (got %s)" % exps.dtype)
+    if codes.dim() != 2 or not codes.is_contiguous():
+        raise ValueError("codes must be a contiguous [rows, dim] matrix")
+    if exps.dim() != 1 or exps.shape[0] != codes.shape[0] or exps.device != dev or not exps.is_contiguous():
+        raise ValueError("exponents must be a contiguous [%d] vector on the codes' device" % codes.shape[0])
+    _same_bank("codes", codes, other_codes)
+    _same_bank("exponents", exps, other_exps)
+    n, d = codes.shape
+    return _bank_search((lib.osn_bank_search_ensemble_fp8,), (_p(codes), _p(exps), _p(other_codes), _p(other_exps)), n, d, 16, dev,
+                        scene_offsets, queries, k, thresholds, normalize, want_heat, max_scene_rows, err, negatives, temperature,
+                        mode, want_source)
 
 
 # ------------------------------------------------------------------------ pool

@@ -15,7 +15,7 @@ against CLIP text embeddings (``:291``, ``:305,310``) and can save them per scen
                      over rendered views of the scene (openscene_amd.render)
 
 Kernels: csrc/search.hip through ops.bank_append / ops.bank_search and their _fp8 twins (osn_bank_search_contrast[_fp8]
-when negatives are given); no CPU path.
+when negatives are given, osn_bank_search_ensemble[_fp8] when a second bank is); no CPU path.
 """
 import numpy as np
 import torch
@@ -231,6 +231,23 @@ class FeatureBank:
         bank.names = list(self.names)
         return bank
 
+    def select(self, other, source):
+        """A new bank of the same kind and scenes whose row p is `other`'s where ``source[p]`` is true and this bank's
+        elsewhere: the reference's ``feat_ensemble`` (``run/evaluate.py:318-324``, "if we need to save the features") for the
+        label set `source` was chosen with -- ``search(..., ensemble=other).source`` in vocabulary mode.  fp16 rows are
+        copied; fp8 rows copy codes and exponent byte.  Ready for save, io.save_point_features, pool and pca."""
+        _same_banks(self, other)
+        if not isinstance(source, torch.Tensor) or source.dtype != torch.bool or tuple(source.shape) != (self.rows,):
+            raise ValueError("source must be a bool [%d] tensor (the .source of a vocabulary-mode search)" % self.rows)
+        source = source.to(self.device)
+        bank = FeatureBank(self.dim, self.device, capacity_rows=max(self.rows, 1), dtype=self.dtype)
+        for dst, mine, theirs in zip(bank._store, self._store, other._store):
+            pick = source[:, None] if mine.dim() == 2 else source
+            dst[:self.rows].copy_(torch.where(pick, theirs[:self.rows], mine[:self.rows]))
+        bank.offsets = list(self.offsets)
+        bank.names = list(self.names)
+        return bank
+
     # ---- persistence
     def save(self, path):
         """One file: the filled rows (fp16, or codes and exponents), the offsets and the names."""
@@ -257,14 +274,34 @@ class FeatureBank:
         return bank
 
 
+def _same_banks(a, b):
+    """Two banks that can be searched as one: raises ValueError naming the first difference."""
+    if not isinstance(b, FeatureBank):
+        raise TypeError("ensemble must be a FeatureBank")
+    if b.dtype != a.dtype:
+        raise ValueError("the two banks differ in kind: %s and %s (mixed kinds are not supported)" % (a.dtype, b.dtype))
+    if b.dim != a.dim:
+        raise ValueError("the two banks differ in dim: %d and %d" % (a.dim, b.dim))
+    if b.device != a.device:
+        raise ValueError("the two banks differ in device: %s and %s" % (a.device, b.device))
+    if b.names != a.names:
+        raise ValueError("the two banks differ in scene names: %r and %r"
+                         % next(((x, y) for x, y in zip(a.names, b.names) if x != y), (len(a.names), len(b.names))))
+    if b.offsets != a.offsets:
+        raise ValueError("the two banks differ in scene offsets: %r and %r" % (a.offsets, b.offsets))
+
+
 class SearchResult:
     """topk_scores fp16 [S, Q, k], topk_points int64 [S, Q, k] (row inside its scene; -1 with score -inf pads a scene
     of fewer than k points), counts int64 [S, Q] or None (points with score >= the query's threshold), heat fp16 [N, Q]
     or None, names (the bank's scene names), offsets.  relevancy: the search was given negatives -- every score (heat,
     topk_scores, what thresholds and counts compare) is then the relevancy in [0, 1] against the best negative at
-    `temperature` (None for a plain search), and 0.5 means "as likely as the best negative"."""
+    `temperature` (None for a plain search), and 0.5 means "as likely as the best negative".  source / ensemble_mode: the
+    search was given a second bank (``ensemble=``) -- source is bool [N] in "vocabulary" mode (the point's row comes from the
+    second bank), bool [N, Q] in "query" mode with return_heat (the element does); both None for every other search."""
 
-    def __init__(self, names, offsets, topk_scores, topk_points, counts, heat, relevancy=False, temperature=None):
+    def __init__(self, names, offsets, topk_scores, topk_points, counts, heat, relevancy=False, temperature=None, source=None,
+                 ensemble_mode=None):
         self.names = list(names)
         self.offsets = list(offsets)
         self.topk_scores = topk_scores
@@ -273,6 +310,8 @@ class SearchResult:
         self.heat = heat
         self.relevancy = bool(relevancy)
         self.temperature = temperature
+        self.source = source
+        self.ensemble_mode = ensemble_mode
 
     def scene_heat(self, which):
         """fp16 [n, Q] view of one scene's rows of the heat-map."""
@@ -358,7 +397,8 @@ def _queries(queries, dim, device, what="queries", letter="Q"):
     return queries.to(device)
 
 
-def search(bank, queries, k=16, thresholds=None, normalize=True, return_heat=False, negatives=None, temperature=0.1):
+def search(bank, queries, k=16, thresholds=None, normalize=True, return_heat=False, negatives=None, temperature=0.1,
+           ensemble=None, ensemble_mode="vocabulary"):
     """Score every point of the bank against every query and select per scene.
 
     queries fp16 [Q, dim], L2-normalised (``util/util.py:41-44``); the score is ``run/evaluate.py:305,310`` (normalize:
@@ -371,9 +411,24 @@ def search(bank, queries, k=16, thresholds=None, normalize=True, return_heat=Fal
     smallest pairwise softmax of the query against a negative -- in the same pass over the bank; the heat-map, the
     top-k, thresholds and counts are all taken on it, and a threshold of 0.5 means "as likely as the best negative"
     for every query.  The negatives get no column of their own.  temperature: finite and > 0; the default 0.1 is an
-    interface default, not a tuned value."""
+    interface default, not a tuned value.
+
+    ensemble: a second FeatureBank of the same kind, dim, device and scenes (equal names and offsets) -- in the reference
+    `bank` holds the distilled features and `ensemble` the fused ones -- searched with `bank` as one, the 2D-3D ensemble of
+    ``run/evaluate.py:302-324`` at query time, in the pass that reads the two banks:
+      ensemble_mode="vocabulary" (``:318-321``)  a point takes its whole row from the source whose best normalised score over
+        THIS CALL'S queries is larger (the second bank only if strictly larger; always on normalised scores, whatever
+        `normalize`; negatives take no part).  A query's column therefore depends on the other queries of the call.
+      ensemble_mode="query" (the commented variant, ``:312-316``)  every element is the larger of the two sources' scores
+        (relevancies with negatives); column q depends on query q alone.
+    The result's .source says which (bool [N], or bool [N, Q] with return_heat); top-k, thresholds and counts are taken on the
+    combined heat-map.  bank.select(ensemble, source) stores the vocabulary-mode choice as a bank of its own."""
     if not isinstance(bank, FeatureBank):
         raise TypeError("bank must be a FeatureBank")
+    if ensemble is not None:
+        _same_banks(bank, ensemble)
+        if ensemble_mode not in ops.BANK_ENSEMBLE_MODES:
+            raise ValueError('ensemble_mode must be "vocabulary" or "query" (got %r)' % (ensemble_mode,))
     queries = _queries(queries, bank.dim, bank.device)
     contrast = {}
     if negatives is not None:
@@ -395,16 +450,42 @@ def search(bank, queries, k=16, thresholds=None, normalize=True, return_heat=Fal
     rows = bank.scene_rows()
     kw = dict(k=k, thresholds=thresholds, normalize=bool(normalize), want_heat=bool(return_heat),
               max_scene_rows=max(rows) if rows else 0, err=bank._err_word())       # (the bank owns its offsets: nothing to check)
-    if bank.dtype == "fp8":
+    source = None
+    if ensemble is not None:
+        kw.update(mode=ensemble_mode, want_source=bool(return_heat))
+        if bank.dtype == "fp8":
+            heat, top_s, top_p, counts, source = ops.bank_search_ensemble_fp8(
+                bank.codes, bank.exponents, ensemble.codes, ensemble.exponents, bank.offsets_tensor(), queries, **kw, **contrast)
+        else:
+            heat, top_s, top_p, counts, source = ops.bank_search_ensemble(bank.features, ensemble.features, bank.offsets_tensor(),
+                                                                          queries, **kw, **contrast)
+    elif bank.dtype == "fp8":
         heat, top_s, top_p, counts = ops.bank_search_fp8(bank.codes, bank.exponents, bank.offsets_tensor(), queries, **kw, **contrast)
     else:
         heat, top_s, top_p, counts = ops.bank_search(bank.features, bank.offsets_tensor(), queries, **kw, **contrast)
     return SearchResult(bank.names, bank.offsets, top_s, top_p, counts, heat, relevancy=bool(contrast),
-                        temperature=contrast.get("temperature"))
+                        temperature=contrast.get("temperature"), source=source,
+                        ensemble_mode=ensemble_mode if ensemble is not None else None)
 
 
-def heat_map(features, queries, inds_reverse=None, normalize=True, negatives=None, temperature=0.1):
-    """fp16 [points, Q]: one scene's similarity heat-map (a bank of one scene); with negatives, its relevancy map (search)."""
-    bank = FeatureBank(features.shape[1], features.device, capacity_rows=(inds_reverse if inds_reverse is not None else features).shape[0])
+def heat_map(features, queries, inds_reverse=None, normalize=True, negatives=None, temperature=0.1, ensemble=None,
+             ensemble_mode="vocabulary"):
+    """fp16 [points, Q]: one scene's similarity heat-map (a bank of one scene); with negatives, its relevancy map (search).
+    ensemble: a second feature matrix per voxel, like `features` (same rows, width and device; it goes through the same
+    `inds_reverse`, ``run/evaluate.py:303,308``): the heat-map of the two as one (search's `ensemble`)."""
+    rows = (inds_reverse if inds_reverse is not None else features).shape[0]
+    bank = FeatureBank(features.shape[1], features.device, capacity_rows=rows)
     bank.add_scene("scene", features, inds_reverse)
-    return search(bank, queries, k=1, normalize=normalize, return_heat=True, negatives=negatives, temperature=temperature).heat
+    other = None
+    if ensemble is not None:
+        if isinstance(ensemble, np.ndarray):
+            ensemble = torch.from_numpy(ensemble)
+        if not isinstance(ensemble, torch.Tensor) or ensemble.dim() != 2:
+            raise TypeError("ensemble must be a [rows, dim] feature matrix")
+        if tuple(ensemble.shape) != tuple(features.shape) or ensemble.device != features.device:
+            raise ValueError("ensemble must be %s on %s, like features (got %s on %s)"
+                             % (tuple(features.shape), features.device, tuple(ensemble.shape), ensemble.device))
+        other = FeatureBank(features.shape[1], features.device, capacity_rows=rows)
+        other.add_scene("scene", ensemble, inds_reverse)
+    return search(bank, queries, k=1, normalize=normalize, return_heat=True, negatives=negatives, temperature=temperature,
+                  ensemble=other, ensemble_mode=ensemble_mode).heat

@@ -3,6 +3,7 @@ the fp16 bank widened to float32, ops.cosine_query(want_scores=True), the norm a
 scene and query.  HIP events around back-to-back calls after a warm-up.
 
     python tools/micro_search.py [iters] [--no-composed] [--contrast-only]
+    python tools/micro_search.py [iters] --ensemble-only          (the default run does not time the ensemble)
 
 Prints one JSON object per line:
   kind=search   per shape (scenes x rows x d x Q, k = 16): us of the whole search, of the heat pass alone (a call without
@@ -20,7 +21,15 @@ Prints one JSON object per line:
                 torch_route = that plain search, then the relevancy formula in torch on the [N, 36] heat-map and torch.topk
                 per scene.  Per route every round's us, the minimum and the spread (max - min) / min; the ratios of the
                 minima.  Before timing, the relevancy map is held to 1 fp16 ulp of the float64 formula on the plain36
-                heat-map (or the tool stops)."""
+                heat-map (or the tool stops).
+  kind=ensemble (--ensemble-only) two banks searched as one (8 scenes x 150 k x 768, 32 queries, without and with 4 negatives,
+                k = 16, heat returned; fp16 and fp8 banks; both modes) against two routes on the same build, timed in turn for
+                ROUNDS rounds: composed = two searches with return_heat (two more, normalised and plain, where the vocabulary
+                pick is not taken on the maps themselves), torch max / compare / where, torch.topk per scene; plain = the
+                search of one bank, the floor on half the ensemble's bytes.  Whole call and heat pass alone (a call without
+                scenes).  Per route every round's us, the minimum and the spread; composed / ensemble and ensemble / (2 x
+                plain).  Before timing, the ensemble's heat-map and source are held to the composed ones bit for bit (or the
+                tool stops)."""
 import json
 import os
 import sys
@@ -217,7 +226,78 @@ def contrast():
              parity_max_ulp=int(ulps.max()), parity_share_differing=float((ulps != 0).mean()))
 
 
+def ensemble():
+    scenes, n, d, q, m, tau = 8, 150_000, 768, 32, 4, 0.1
+    gen = torch.Generator(device=dev).manual_seed(4)
+    a16, b16 = make_bank(scenes, n, d, gen), make_bank(scenes, n, d, gen)
+    rows = torch.nn.functional.normalize(torch.randn(q + m, d, generator=gen, device=dev), dim=1).half()
+    text, negs = rows[:q].contiguous(), rows[q:].contiguous()
+    empty = torch.zeros(1, dtype=torch.int64, device=dev)
+    for kind, a, b in (("fp16", a16, b16), ("fp8", a16.to_fp8(), b16.to_fp8())):
+        for neg in (None, negs):
+            kw = dict(k=K, return_heat=True, negatives=neg, temperature=tau)
+            if kind == "fp16":
+                def plain_heat():
+                    return ops.bank_search(a.features, empty, text, k=K, want_heat=True, max_scene_rows=0, negatives=neg, temperature=tau)
+            else:
+                def plain_heat():
+                    return ops.bank_search_fp8(a.codes, a.exponents, empty, text, k=K, want_heat=True, max_scene_rows=0, negatives=neg,
+                                               temperature=tau)
+            for mode in ops.BANK_ENSEMBLE_MODES:
+                def ours():
+                    return search(a, text, ensemble=b, ensemble_mode=mode, **kw)
+
+                if kind == "fp16":
+                    def ours_heat():
+                        return ops.bank_search_ensemble(a.features, b.features, empty, text, k=K, want_heat=True, max_scene_rows=0,
+                                                        negatives=neg, temperature=tau, mode=mode)
+                else:
+                    def ours_heat():
+                        return ops.bank_search_ensemble_fp8(a.codes, a.exponents, b.codes, b.exponents, empty, text, k=K, want_heat=True,
+                                                            max_scene_rows=0, negatives=neg, temperature=tau, mode=mode)
+
+                def composed_heat():
+                    xa, xb = search(a, text, **kw).heat, search(b, text, **kw).heat
+                    if mode == "query":
+                        source = xa.float() < xb.float()
+                        return torch.where(source, xb, xa), source
+                    na, nb = (xa, xb) if neg is None else (search(a, text, k=K, return_heat=True).heat, search(b, text, k=K, return_heat=True).heat)
+                    source = na.float().max(dim=1)[0] < nb.float().max(dim=1)[0]
+                    return torch.where(source[:, None], xb, xa), source
+
+                def composed_route():
+                    heat, source = composed_heat()
+                    return heat, source, [torch.topk(heat[o:e].t().float(), min(K, e - o), dim=1) for o, e in zip(a.offsets[:-1], a.offsets[1:])]
+
+                def plain():
+                    return search(a, text, **kw)
+                got, (want_heat, want_source) = ours(), composed_heat()
+                if not (torch.equal(got.heat.view(torch.int16), want_heat.view(torch.int16)) and torch.equal(got.source, want_source)):
+                    raise SystemExit("the ensemble's heat-map or source is not the composed one (%s %s)" % (kind, mode))
+                share = want_source.double().mean().item()
+                del got, want_heat, want_source
+                us = {"ensemble": [], "ensemble_heat": [], "composed": [], "composed_heat": [], "plain": [], "plain_heat": []}
+                for _ in range(ROUNDS):                        # A B C A B C: shows the spread
+                    us["ensemble"].append(timed(ours))
+                    us["ensemble_heat"].append(timed(ours_heat))
+                    us["plain"].append(timed(plain))
+                    us["plain_heat"].append(timed(plain_heat))
+                    us["composed"].append(timed(composed_route, iters=max(3, ITERS // 4), warmup=1))
+                    us["composed_heat"].append(timed(composed_heat, iters=max(3, ITERS // 4), warmup=1))
+                lo = {k_: min(v) for k_, v in us.items()}
+                emit(kind="ensemble", bank=kind, mode=mode, scenes=scenes, rows_per_scene=n, d=d, q=q, m=0 if neg is None else m, k=K,
+                     temperature=tau, iters=ITERS, share_from_second=share, us=us, us_min=lo,
+                     spread={k_: (max(v) - min(v)) / min(v) for k_, v in us.items()},
+                     composed_over_ensemble=lo["composed"] / lo["ensemble"],
+                     composed_heat_over_ensemble_heat=lo["composed_heat"] / lo["ensemble_heat"],
+                     ensemble_over_two_plain=lo["ensemble"] / (2 * lo["plain"]),
+                     ensemble_heat_over_two_plain_heat=lo["ensemble_heat"] / (2 * lo["plain_heat"]))
+
+
 if __name__ == "__main__":
+    if "--ensemble-only" in sys.argv:
+        ensemble()
+        sys.exit(0)
     if not CONTRAST_ONLY:
         shapes()
         append()
