@@ -1419,6 +1419,56 @@ void osn_prof_destroy(osn_prof_t* p);
 int osn_prof_filter(osn_prof_t* p, const int32_t* tags, int n_tags);
 int osn_prof_read(osn_prof_t* p, int32_t* tags, float* ms, int capacity, int reset);
 
+/* ---- sparse pooling layers ---------------------------------------------------------------------------- *
+ * [ME] MinkowskiSumPooling / MinkowskiAvgPooling / MinkowskiMaxPooling, MinkowskiGlobal{Sum,Avg,Max}Pooling and
+ * MinkowskiBroadcast{Addition,Multiplication}: the layers models/resnet_base.py:54,69,71 builds next to its convolutions
+ * (glob_avg = ME.MinkowskiGlobalMaxPooling(), MinkowskiAvgPooling, final = ME.MinkowskiLinear).  Semantics recalled from ME
+ * v0.5.4.  Features are float32 [rows, c], any c >= 1: 16-byte accesses when c % 4 == 0 and every
+ * matrix is 16-byte aligned, one element per thread otherwise.  No floating-point atomics anywhere: every result is a pure
+ * function of the arguments, bit for bit repeatable.  Every refused argument of this family -- a null pointer, K or mode out of
+ * range, a workspace below osn_gpool_ws_bytes -- returns OSN_E_ARG before anything is launched, the entry's name first in the text. */
+#define OSN_POOL_SUM 0
+#define OSN_POOL_AVG 1
+#define OSN_POOL_MAX 2
+#define OSN_GPOOL_CHUNK 512      /* rows of a batch that are reduced into one fp32 partial                              */
+#define OSN_BROADCAST_ADD 0
+#define OSN_BROADCAST_MUL 1
+/* Local pooling over a kernel map (models/resnet_base.py:54,69,71; the table of osn_kmap_build: nbr[k, o] = input row or -1,
+ * an entry outside [0, n_in) counts as absent), K = 8 (a 2^3 kernel) or 27 (3^3).
+ *   osn_pool_count  cnt[o] = present neighbours of output row o (the divisor of avg; kept next to the map).
+ *   osn_pool_fwd    sum: y[o] = fp32 sum of x[nbr[k, o]] over the present k, added one by one in ascending k from +0;
+ *                   avg: that sum / float(cnt[o]) (IEEE division; no neighbour: 0);
+ *                   max: the maximum, arg[o, c] = its input row (int32; -1 and y = 0 without a neighbour); ties to the lowest k
+ *                   (+0 == -0), a NaN wins and the first NaN in k order stays.  `arg` is read for max only.
+ *   osn_pool_bwd    gx[i] = sum over the forward offsets k = 0 .. K - 1, in that order, of the term of the output row
+ *                   o = nbr_bwd[k, i] (the table of osn_kmap_transpose; flip = 1: the forward table of an odd stride-1 kernel
+ *                   itself, forward offset k at row K - 1 - k):  gy[o]  |  gy[o] / float(cnt[o])  |  arg[o, c] == i ? gy[o, c] : 0. */
+int osn_pool_count(const int32_t* nbr, int64_t n_in, int64_t n_out, int K, int32_t* cnt, osn_stream_t stream);
+int osn_pool_fwd(const float* x, int64_t n_in, const int32_t* nbr, int64_t n_out, int K, int c, int mode, float* y, int32_t* arg,
+                 osn_stream_t stream);
+int osn_pool_bwd(const float* gy, int64_t n_out, const int32_t* nbr_bwd, int64_t n_in, int K, int flip, int c, int mode,
+                 const int32_t* cnt, const int32_t* arg, float* gx, osn_stream_t stream);
+/* Global pooling (models/resnet_base.py:54,69,71: glob_avg): y[b] = reduce over the rows order[offsets[b] .. offsets[b + 1]) of x,
+ * `order` the rows of every batch in ascending row index (int32 [n]), `offsets` int64 [n_batches + 1].  A batch's list is cut into
+ * chunks of OSN_GPOOL_CHUNK entries; a chunk is reduced in an order that depends on c alone, the partials are added in chunk
+ * order, avg then divides once by float(n_b): a batch's bits depend on its own rows only.  max: exact, arg[b, c] = the lowest
+ * row among equals (+0 == -0), a NaN wins and arg is the lowest NaN row; an empty batch gives 0 (sum, avg) or -inf and arg -1.
+ * osn_gpool_bwd: rank[i] = batch position of row i (int32 [n]);  gx[i] = gy[rank[i]]  |  gy[rank[i]] / float(n_b)  |
+ * arg[rank[i], c] == i ? gy[rank[i], c] : 0; every element of gx is written.                                              */
+size_t osn_gpool_ws_bytes(int64_t n, int64_t n_batches, int c);
+int osn_gpool_fwd(const float* x, int64_t n, int c, const int32_t* order, const int64_t* offsets, int64_t n_batches, int mode,
+                  float* y, int32_t* arg, void* ws, size_t ws_bytes, osn_stream_t stream);
+int osn_gpool_bwd(const float* gy, const int32_t* rank, const int64_t* offsets, const int32_t* arg, int64_t n, int64_t n_batches,
+                  int c, int mode, float* gx, osn_stream_t stream);
+/* Broadcast of a pooled tensor over the rows of its batches (the squeeze-excite gate on a models/resnet_base.py:54,69,71 trunk):
+ * y[i] = x[i] + g[rank[i]]  (op 1: *), one streaming pass; the input gradient of a multiplication is the same call on gy.
+ * osn_broadcast_bwd_pooled: gg[b] = sum over the batch's rows of gy[i]  (x != null: gy[i] * x[i], formed where the row is read),
+ * through the chunked reduction of osn_gpool_fwd (workspace: osn_gpool_ws_bytes).                                           */
+int osn_broadcast_fwd(const float* x, const float* g, const int32_t* rank, int64_t n, int64_t n_batches, int c, int op, float* y,
+                      osn_stream_t stream);
+int osn_broadcast_bwd_pooled(const float* gy, const float* x, int64_t n, int c, const int32_t* order, const int64_t* offsets,
+                             int64_t n_batches, float* gg, void* ws, size_t ws_bytes, osn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -144,8 +144,9 @@ def install_minkowski_alias(force=False, accelerate=True):
     me.__openscene_amd__ = True
     me.__version__ = mk.__version__
     for name in ("SparseTensor", "CoordinateManager", "cat", "MinkowskiConvolution", "MinkowskiConvolutionTranspose",
-                 "MinkowskiBatchNorm", "MinkowskiReLU", "MinkowskiAvgPooling", "MinkowskiGlobalMaxPooling",
-                 "MinkowskiLinear"):
+                 "MinkowskiBatchNorm", "MinkowskiReLU", "MinkowskiSumPooling", "MinkowskiAvgPooling", "MinkowskiMaxPooling",
+                 "MinkowskiGlobalSumPooling", "MinkowskiGlobalAvgPooling", "MinkowskiGlobalMaxPooling",
+                 "MinkowskiBroadcastAddition", "MinkowskiBroadcastMultiplication", "MinkowskiLinear"):
         setattr(me, name, getattr(mk, name))
     modules = types.ModuleType("MinkowskiEngine.modules")
     resnet_block = types.ModuleType("MinkowskiEngine.modules.resnet_block")

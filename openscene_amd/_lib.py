@@ -189,6 +189,14 @@ PROTOTYPES = {
     "osn_elastic_blur": (_i32, [_vp, _i32, _i32, _i32, _vp, _sz, _vp]),
     "osn_elastic_apply_ws_bytes": (_sz, [_i64]),
     "osn_elastic_apply": (_i32, [_vp, _i64, _vp, _i32, _i32, _i32, _vp, _c.c_double, _vp, _vp, _vp, _sz, _vp]),
+    "osn_pool_count": (_i32, [_vp, _i64, _i64, _i32, _vp, _vp]),
+    "osn_pool_fwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _vp, _vp, _vp]),
+    "osn_pool_bwd": (_i32, [_vp, _i64, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp]),
+    "osn_gpool_ws_bytes": (_sz, [_i64, _i64, _i32]),
+    "osn_gpool_fwd": (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _sz, _vp]),
+    "osn_gpool_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
+    "osn_broadcast_fwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
+    "osn_broadcast_bwd_pooled": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
 }
 
 _lock = threading.Lock()

@@ -299,6 +299,83 @@ class Cat2Function(Function):
         return ops.cat2_bwd(g, ca, cb)
 
 
+class LocalPoolFunction(Function):
+    """[ME] MinkowskiSumPooling / AvgPooling / MaxPooling over a kernel map: one launch forward, one backward (a gather through
+    the inverse table in ascending forward offset: no atomics).  `cnt` (avg) and `arg` (max) are kept for the backward pass."""
+
+    @staticmethod
+    def forward(ctx, x, nbr_fwd, nbr_bwd, flip, mode, cnt):
+        y, arg = ops.pool_fwd(x, nbr_fwd, mode)
+        ctx.cfg = (nbr_bwd, bool(flip), mode, cnt)
+        ctx.save_for_backward(arg)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        nbr_bwd, flip, mode, cnt = ctx.cfg
+        (arg,) = ctx.saved_tensors
+        return ops.pool_bwd(gy, nbr_bwd, flip, mode, cnt=cnt, arg=arg), None, None, None, None, None
+
+
+class GlobalPoolFunction(Function):
+    """[ME] MinkowskiGlobalSumPooling / AvgPooling / MaxPooling: one row per batch of a CoordinateManager.batch_index."""
+
+    @staticmethod
+    def forward(ctx, x, index, mode):
+        y, arg = ops.gpool_fwd(x, index.order, index.offsets, mode)
+        ctx.cfg = (index, mode, x.shape[0])
+        ctx.save_for_backward(arg)
+        return y
+
+    @staticmethod
+    def backward(ctx, gy):
+        index, mode, n = ctx.cfg
+        (arg,) = ctx.saved_tensors
+        return ops.gpool_bwd(gy, index.rank, index.offsets, n, mode, arg=arg), None, None
+
+
+class BroadcastFunction(Function):
+    """[ME] MinkowskiBroadcastAddition / Multiplication: y[i] = x[i] (+ | *) pooled[batch(i)]."""
+
+    @staticmethod
+    def forward(ctx, x, pooled, index, op):
+        ctx.cfg = (index, op)
+        ctx.save_for_backward(x if op == "mul" else None, pooled if op == "mul" else None)
+        return ops.broadcast_fwd(x, pooled, index.rank, op)
+
+    @staticmethod
+    def backward(ctx, gy):
+        index, op = ctx.cfg
+        x, pooled = ctx.saved_tensors
+        gx = gg = None
+        if ctx.needs_input_grad[0]:
+            gx = gy if op == "add" else ops.broadcast_fwd(gy, pooled, index.rank, "mul")
+        if ctx.needs_input_grad[1]:
+            gg = ops.broadcast_bwd_pooled(gy, x, index.order, index.offsets)
+        return gx, gg, None, None
+
+
+def local_pool(x, maps, mode, cnt=None):
+    """maps = CoordinateManager.kmap(...); mode "sum" / "avg" / "max"; cnt = .pool_counts(...) for "avg"."""
+    nbr_fwd, nbr_bwd, flip = maps
+    if nbr_fwd is None:
+        raise ValueError("local pooling needs a kernel map (kernel_size 1 pools nothing)")
+    return LocalPoolFunction.apply(x, nbr_fwd, nbr_bwd, flip, mode, cnt)
+
+
+def global_pool(x, index, mode):
+    """index = CoordinateManager.batch_index(stride) of x's rows."""
+    return GlobalPoolFunction.apply(x, index, mode)
+
+
+def broadcast(x, pooled, index, op):
+    """op "add" / "mul"; pooled [B, C] on the batches of index."""
+    if pooled.dim() != 2 or pooled.shape[0] != index.ids.shape[0] or pooled.shape[1] != x.shape[1]:
+        raise ValueError("broadcast: pooled features %s do not match %d batches of %d columns"
+                         % (tuple(pooled.shape), index.ids.shape[0], x.shape[1]))
+    return BroadcastFunction.apply(x, pooled, index, op)
+
+
 def _hip_eligible(*ts):
     """The elementwise HIP kernels take contiguous float32 device matrices on 16-byte boundaries.  Anything else ON A DEVICE
     (another dtype, a strided view, an odd storage offset) goes to the torch operator of the same name -- MinkowskiEngine

@@ -18,7 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as F_
-from .sparse import CoordinateManager, SparseTensor, cat  # noqa: F401  (re-exported ME names)
+from .sparse import ORIGIN_STRIDE, CoordinateManager, SparseTensor, cat  # noqa: F401  (re-exported ME names)
 
 __version__ = "0.5.4+openscene_amd"
 
@@ -131,20 +131,117 @@ class MinkowskiReLU(nn.Module):
         return x._like(F_.relu(x.F))
 
 
-def _outside_path(name):
-    class _Stub(nn.Module):
-        def __init__(self, *a, **kw):
-            super().__init__()
-            raise NotImplementedError(
-                "%s is only referenced by dead code of the reference (models/resnet_base.py:45-71, never "
-                "constructed by MinkUNetBase) and is outside the accelerated path" % name)
-    _Stub.__name__ = name
-    return _Stub
+# ---- pooling, broadcast, linear (models/resnet_base.py:54,69,71; semantics recalled from ME v0.5.4) ----
+class MinkowskiPoolingBase(nn.Module):
+    """Parameter-free reduction over the kernel map of a convolution of the same geometry (the two share the cached map)."""
+    MODE = None
+
+    def __init__(self, kernel_size, stride=1, dilation=1, kernel_generator=None, expand_coordinates=False, dimension=None):
+        super().__init__()
+        if dimension is not None and dimension != 3:
+            raise NotImplementedError("only 3-D sparse tensors are supported (dimension=%r)" % (dimension,))
+        if kernel_generator is not None or expand_coordinates:
+            raise NotImplementedError("custom kernel generators / coordinate expansion are outside the reference path")
+        self.kernel_size = _triple_ok(kernel_size, "kernel_size")
+        self.stride = _triple_ok(stride, "stride")
+        self.dilation = _triple_ok(dilation, "dilation")
+        if self.kernel_size not in (2, 3):
+            raise NotImplementedError("pooling kernel_size %d: kernel sizes 2 and 3 are supported" % self.kernel_size)
+        if self.stride not in (1, 2):
+            raise NotImplementedError("stride %d: the reference only uses strides 1 and 2" % self.stride)
+        self.dimension = 3
+        self.kernel_volume = self.kernel_size ** 3
+
+    def forward(self, x):
+        cm, s_in = x.coordinate_manager, x.tensor_stride
+        s_out = s_in * self.stride
+        maps = cm.kmap(s_in, s_out, self.kernel_size, self.dilation)          # (ValueError on a globally pooled tensor)
+        cnt = cm.pool_counts(s_in, s_out, self.kernel_size, self.dilation) if self.MODE == "avg" else None
+        return SparseTensor(F_.local_pool(x.F, maps, self.MODE, cnt), tensor_stride=s_out, coordinate_manager=cm)
+
+    def extra_repr(self):
+        return "kernel_size=%d, stride=%d, dilation=%d" % (self.kernel_size, self.stride, self.dilation)
 
 
-MinkowskiAvgPooling = _outside_path("MinkowskiAvgPooling")
-MinkowskiGlobalMaxPooling = _outside_path("MinkowskiGlobalMaxPooling")
-MinkowskiLinear = _outside_path("MinkowskiLinear")
+class MinkowskiSumPooling(MinkowskiPoolingBase):
+    MODE = "sum"
+
+
+class MinkowskiAvgPooling(MinkowskiPoolingBase):
+    """Divides by the number of PRESENT inputs of an output voxel, not by the kernel volume."""
+    MODE = "avg"
+
+
+class MinkowskiMaxPooling(MinkowskiPoolingBase):
+    MODE = "max"
+
+
+class MinkowskiGlobalPoolingBase(nn.Module):
+    """One output row per batch index present, in ascending batch index, on the input's coordinate manager; the result's
+    tensor stride is sparse.ORIGIN_STRIDE and its coordinates are [[b, 0, 0, 0]]."""
+    MODE = None
+
+    def __init__(self, mode=None, dimension=None):
+        super().__init__()
+        if dimension is not None and dimension != 3:
+            raise NotImplementedError("only 3-D sparse tensors are supported (dimension=%r)" % (dimension,))
+
+    def forward(self, x):
+        cm = x.coordinate_manager
+        index = cm.batch_index(x.tensor_stride)
+        return SparseTensor(F_.global_pool(x.F, index, self.MODE), tensor_stride=ORIGIN_STRIDE, coordinate_manager=cm)
+
+
+class MinkowskiGlobalSumPooling(MinkowskiGlobalPoolingBase):
+    MODE = "sum"
+
+
+class MinkowskiGlobalAvgPooling(MinkowskiGlobalPoolingBase):
+    MODE = "avg"
+
+
+class MinkowskiGlobalMaxPooling(MinkowskiGlobalPoolingBase):
+    MODE = "max"
+
+
+class MinkowskiBroadcastBase(nn.Module):
+    """forward(x, pooled): the pooled tensor's row of every row's batch, added to / multiplied with the row."""
+    OP = None
+
+    def forward(self, x, pooled):
+        if pooled.coordinate_manager is not x.coordinate_manager or pooled.tensor_stride != ORIGIN_STRIDE:
+            raise ValueError("broadcast: the second argument must be a globally pooled tensor of the first one's coordinate manager")
+        index = x.coordinate_manager.batch_index(x.tensor_stride)
+        return x._like(F_.broadcast(x.F, pooled.F, index, self.OP))
+
+
+class MinkowskiBroadcastAddition(MinkowskiBroadcastBase):
+    OP = "add"
+
+
+class MinkowskiBroadcastMultiplication(MinkowskiBroadcastBase):
+    OP = "mul"
+
+
+class MinkowskiLinear(nn.Module):
+    """Holds ``self.linear = nn.Linear`` exactly like ME (checkpoint keys ``linear.weight`` / ``linear.bias``).  Shapes the 1x1
+    convolution kernel takes run on it (the K = 1 path of the convolutions, on ``linear.weight.t()``); every other shape runs
+    torch.nn.functional.linear.  The bias is a row add."""
+
+    def __init__(self, in_features, out_features, bias=True):
+        super().__init__()
+        self.linear = nn.Linear(in_features, out_features, bias=bias)
+
+    def forward(self, x):
+        lin, f = self.linear, x.F
+        if (f.dtype == torch.float32 and lin.weight.dtype == torch.float32
+                and F_.ops.dense_eligible(lin.in_features, lin.out_features)):
+            out = F_.sparse_conv(f, lin.weight.t(), (None, None, False), f.shape[0], training=self.training)
+            if lin.bias is not None:
+                out = out + lin.bias
+        else:
+            out = nn.functional.linear(f, lin.weight, lin.bias)
+        return x._like(out)
 
 
 # ---- ME.modules.resnet_block ------------------------------------------------

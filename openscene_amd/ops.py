@@ -3056,3 +3056,164 @@ def elastic_distort(xyz, granularity, magnitude, bbox6=None, return_bbox=False):
     grid = elastic_blur(torch.from_numpy(noise).to(dev))
     out, box = elastic_apply(xyz, grid, axes, magnitude)
     return (out, box) if return_bbox else out
+
+
+# ------------------------------------------------------------ pooling layers
+GPOOL_CHUNK = 512                # OSN_GPOOL_CHUNK: the rows of a batch that are reduced into one fp32 partial
+POOL_MODES = ("sum", "avg", "max")          # the `mode` word of osn_pool_* / osn_gpool_*: the position in this tuple
+BROADCAST_OPS = ("add", "mul")              # the `op` word of osn_broadcast_fwd
+
+
+def _pool_mode(mode):
+    if mode not in POOL_MODES:
+        raise ValueError("pooling mode %r (one of %s)" % (mode, ", ".join(POOL_MODES)))
+    return POOL_MODES.index(mode)
+
+
+def _pool_table(nbr, rows, name):
+    if nbr.dtype != torch.int32 or nbr.dim() != 2 or (rows is not None and nbr.shape[1] != rows):
+        raise TypeError("%s must be an int32 [K, %s] neighbour table" % (name, "rows" if rows is None else rows))
+    if nbr.shape[0] not in (8, 27):
+        raise ValueError("%s has %d offsets; pooling takes the 8 of a 2^3 kernel or the 27 of a 3^3 kernel" % (name, nbr.shape[0]))
+    return nbr if nbr.is_contiguous() else nbr.contiguous()
+
+
+def _pool_vec(t, name, dtype, n, dev):
+    if t.dtype != dtype or t.dim() != 1 or t.shape[0] != n or t.device != dev:
+        raise TypeError("%s must be %s [%d] on %s" % (name, dtype, n, dev))
+    return t if t.is_contiguous() else t.contiguous()
+
+
+def _pool_feats(t, name, rows=None):
+    if t.dim() != 2 or t.shape[1] < 1 or (rows is not None and t.shape[0] != rows):
+        raise ValueError("%s must be a [%s, c >= 1] matrix (got %s)" % (name, "rows" if rows is None else rows, tuple(t.shape)))
+    return _f32c(t, name)
+
+
+def pool_count(nbr, n_in):
+    """int32 [n_out]: the present neighbours of every output row of the table nbr [K, n_out] over n_in input rows."""
+    dev = nbr.device
+    lib = _prep(dev)
+    nbr = _pool_table(nbr, None, "nbr")
+    K, n_out = nbr.shape
+    cnt = torch.empty(n_out, dtype=torch.int32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_pool_count(_p(nbr), int(n_in), n_out, K, _p(cnt), _stream(dev)), "osn_pool_count")
+    return cnt
+
+
+def pool_fwd(x, nbr, mode):
+    """Local pooling of x [n_in, c] over nbr [K, n_out] -> (y [n_out, c], arg int32 [n_out, c] for "max", else None)."""
+    m = _pool_mode(mode)
+    dev = x.device
+    lib = _prep(dev)
+    x = _pool_feats(x, "x")
+    nbr = _pool_table(nbr, None, "nbr")
+    (n_in, c), (K, n_out) = x.shape, nbr.shape
+    y = torch.empty((n_out, c), dtype=torch.float32, device=dev)
+    arg = torch.empty((n_out, c), dtype=torch.int32, device=dev) if mode == "max" else None
+    with _Dev(dev):
+        check(lib.osn_pool_fwd(_p(x), n_in, _p(nbr), n_out, K, c, m, _p(y), _p(arg), _stream(dev)), "osn_pool_fwd")
+    return y, arg
+
+
+def pool_bwd(gy, nbr_bwd, flip, mode, cnt=None, arg=None):
+    """Input gradient [n_in, c] of pool_fwd from gy [n_out, c] through the inverse table nbr_bwd [K, n_in] (flip: the forward table
+    of an odd stride-1 kernel, read mirrored); cnt int32 [n_out] for "avg", arg int32 [n_out, c] for "max"."""
+    m = _pool_mode(mode)
+    dev = gy.device
+    lib = _prep(dev)
+    gy = _pool_feats(gy, "grad_output")
+    nbr_bwd = _pool_table(nbr_bwd, None, "nbr_bwd")
+    (n_out, c), (K, n_in) = gy.shape, nbr_bwd.shape
+    if mode == "avg":
+        cnt = _pool_vec(cnt, "cnt", torch.int32, n_out, dev)
+    if mode == "max":
+        if arg is None or arg.dtype != torch.int32 or arg.shape != gy.shape:
+            raise TypeError("arg must be the int32 %s matrix of the forward pass" % (tuple(gy.shape),))
+        arg = arg.contiguous()
+    gx = torch.empty((n_in, c), dtype=torch.float32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_pool_bwd(_p(gy), n_out, _p(nbr_bwd), n_in, K, int(bool(flip)), c, m, _p(cnt) if mode == "avg" else None,
+                               _p(arg) if mode == "max" else None, _p(gx), _stream(dev)), "osn_pool_bwd")
+    return gx
+
+
+def _gpool_lists(order, offsets, n, dev):
+    order = _pool_vec(order, "order", torch.int32, n, dev)
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 1 or offsets.device != dev:
+        raise TypeError("offsets must be int64 [n_batches + 1] on %s" % (dev,))
+    return order, offsets.contiguous(), offsets.shape[0] - 1
+
+
+def _gpool_reduce(entry, x, x2, order, offsets, m, want_arg):
+    dev = x.device
+    lib = _prep(dev)
+    n, c = x.shape
+    order, offsets, B = _gpool_lists(order, offsets, n, dev)
+    y = torch.empty((B, c), dtype=torch.float32, device=dev)
+    arg = torch.empty((B, c), dtype=torch.int32, device=dev) if want_arg else None
+    ws = _ws(_cached("osn_gpool_ws_bytes", n, B, c), dev)
+    with _Dev(dev):
+        if entry == "osn_gpool_fwd":
+            rc = lib.osn_gpool_fwd(_p(x), n, c, _p(order), _p(offsets), B, m, _p(y), _p(arg), _p(ws), ws.numel(), _stream(dev))
+        else:
+            rc = lib.osn_broadcast_bwd_pooled(_p(x), _p(x2), n, c, _p(order), _p(offsets), B, _p(y), _p(ws), ws.numel(), _stream(dev))
+        check(rc, entry)
+    return y, arg
+
+
+def gpool_fwd(x, order, offsets, mode):
+    """Global pooling of x [n, c]: one row per batch, the batches' rows as CSR (order int32 [n], offsets int64 [B + 1]) ->
+    (y [B, c], arg int32 [B, c] for "max", else None)."""
+    m = _pool_mode(mode)
+    return _gpool_reduce("osn_gpool_fwd", _pool_feats(x, "x"), None, order, offsets, m, mode == "max")
+
+
+def gpool_bwd(gy, rank, offsets, n, mode, arg=None):
+    """Input gradient [n, c] of gpool_fwd: rank int32 [n] = every row's batch position."""
+    m = _pool_mode(mode)
+    dev = gy.device
+    lib = _prep(dev)
+    gy = _pool_feats(gy, "grad_output")
+    B, c = gy.shape
+    rank = _pool_vec(rank, "rank", torch.int32, n, dev)
+    if offsets.dtype != torch.int64 or offsets.shape != (B + 1,):
+        raise TypeError("offsets must be int64 [%d]" % (B + 1))
+    if mode == "max":
+        if arg is None or arg.dtype != torch.int32 or arg.shape != gy.shape:
+            raise TypeError("arg must be the int32 %s matrix of the forward pass" % (tuple(gy.shape),))
+        arg = arg.contiguous()
+    gx = torch.empty((n, c), dtype=torch.float32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_gpool_bwd(_p(gy), _p(rank), _p(offsets.contiguous()), _p(arg) if mode == "max" else None, n, B, c, m, _p(gx),
+                                _stream(dev)), "osn_gpool_bwd")
+    return gx
+
+
+def broadcast_fwd(x, g, rank, op):
+    """y[i] = x[i] + g[rank[i]] ("add") or x[i] * g[rank[i]] ("mul"): x [n, c], g [B, c], rank int32 [n]."""
+    if op not in BROADCAST_OPS:
+        raise ValueError("broadcast op %r (one of %s)" % (op, ", ".join(BROADCAST_OPS)))
+    dev = x.device
+    lib = _prep(dev)
+    x, g = _pool_feats(x, "x"), _pool_feats(g, "pooled")
+    n, c = x.shape
+    if g.shape[1] != c:
+        raise ValueError("broadcast: %d feature columns against %d pooled columns" % (c, g.shape[1]))
+    rank = _pool_vec(rank, "rank", torch.int32, n, dev)
+    y = torch.empty_like(x)
+    with _Dev(dev):
+        check(lib.osn_broadcast_fwd(_p(x), _p(g), _p(rank), n, g.shape[0], c, BROADCAST_OPS.index(op), _p(y), _stream(dev)),
+              "osn_broadcast_fwd")
+    return y
+
+
+def broadcast_bwd_pooled(gy, x, order, offsets):
+    """Gradient [B, c] of the pooled operand of a broadcast: the per-batch sum of gy (x None: addition) or of gy * x."""
+    gy = _pool_feats(gy, "grad_output")
+    if x is not None:
+        x = _pool_feats(x, "x", gy.shape[0])
+        if x.shape != gy.shape:
+            raise ValueError("broadcast_bwd_pooled: shapes %s and %s differ" % (tuple(gy.shape), tuple(x.shape)))
+    return _gpool_reduce("osn_broadcast_bwd_pooled", gy, x, order, offsets, 0, False)[0]

@@ -11,6 +11,8 @@ and ``+=``).  Semantics restated in SURVEY.md appendix C items 1-4:
   * transposed convs land on the cached finer map, so decoder outputs are
     row-aligned with encoder skips.
 """
+import collections
+
 import torch
 
 from . import ops
@@ -19,6 +21,15 @@ from . import ops
 def _F_mod():
     from . import functional       # late: functional imports ops, which this module imports too
     return functional
+
+
+# tensor_stride of a globally pooled tensor: one row per batch at the origin, coordinates [[b, 0, 0, 0]].  No spatial map has
+# stride 0, so every convolution or local pooling that asks for a kernel map of it is refused by CoordinateManager.kmap.
+ORIGIN_STRIDE = 0
+
+# CoordinateManager.batch_index: ids int32 [B] the distinct batch indices, ascending; rank int32 [N] the position of every row's
+# batch in ids; order int32 [N] / offsets int64 [B + 1] the rows of every batch in ascending row index (CSR)
+BatchIndex = collections.namedtuple("BatchIndex", "ids rank order offsets")
 
 
 class CoordinateManager:
@@ -50,6 +61,13 @@ class CoordinateManager:
     # -- coordinate maps ----------------------------------------------------
     def coords(self, stride):
         if stride not in self._coords:
+            if stride == ORIGIN_STRIDE:               # a globally pooled tensor: one row per batch, at the origin
+                built = [v for k, v in self._kmaps.items() if k[0] == "batch"]       # (every stride has the same batches)
+                ids = (built[0] if built else self.batch_index(1)).ids
+                origin = torch.zeros((ids.shape[0], 4), dtype=torch.int32, device=ids.device)
+                origin[:, 0] = ids
+                self._coords[stride] = origin
+                return origin
             if stride < 2 or stride % 2:
                 raise ValueError("tensor stride %r was never created on this manager" % (stride,))
             fine = self.coords(stride // 2)
@@ -70,11 +88,46 @@ class CoordinateManager:
     def has(self, stride):
         return stride in self._coords
 
+    # -- batches ---------------------------------------------------------------
+    def batch_index(self, stride):
+        """BatchIndex of the stride's rows (cached): what the global pooling and broadcast layers reduce and expand over.  Torch
+        operators on coords[:, 0]; the one host read is the number of batches (the size of torch.unique's result).  Batch
+        indices may have gaps (0, 2, 5: three batches) and a batch's rows may lie anywhere."""
+        key = ("batch", stride)
+        hit = self._kmaps.get(key)
+        if hit is not None:
+            return hit
+        if stride == ORIGIN_STRIDE:
+            raise ValueError("a globally pooled tensor has one row per batch already: there is nothing to pool or broadcast over")
+        b = self.coords(stride)[:, 0]
+        if b.shape[0] == 0:
+            empty = torch.zeros(0, dtype=torch.int32, device=b.device)
+            res = BatchIndex(empty, empty, empty, torch.zeros(1, dtype=torch.int64, device=b.device))
+        else:
+            ids, rank, counts = torch.unique(b, sorted=True, return_inverse=True, return_counts=True)
+            order = torch.argsort(rank, stable=True).int()          # per batch: ascending row index
+            offsets = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).long()
+            res = BatchIndex(ids.int(), rank.int(), order, offsets)
+        self._kmaps[key] = res
+        return res
+
     # -- kernel maps ---------------------------------------------------------
+    def pool_counts(self, in_stride, out_stride, ksize, dilation=1):
+        """int32 [N_out]: the present neighbours of every output row of kmap(...)'s forward table (the divisor of an average
+        pooling), kept next to the map it belongs to."""
+        key = ("pool_cnt", in_stride, out_stride, ksize, dilation)
+        if key not in self._kmaps:
+            fwd = self.kmap(in_stride, out_stride, ksize, dilation)[0]
+            self._kmaps[key] = ops.pool_count(fwd, self.size(in_stride))
+        return self._kmaps[key]
+
     def kmap(self, in_stride, out_stride, ksize, dilation=1):
         """(nbr_fwd, nbr_bwd, flip).  nbr_fwd [K, N_out] feeds the forward conv;
         the input gradient is a forward conv of grad_out over nbr_bwd with the
         kernel transposed (and mirrored in k if flip)."""
+        if in_stride == ORIGIN_STRIDE or out_stride == ORIGIN_STRIDE:
+            raise ValueError("a globally pooled tensor (tensor stride %d: one row per batch at the origin) has no kernel maps: "
+                             "convolutions and local poolings need a spatial tensor" % ORIGIN_STRIDE)
         key = (in_stride, out_stride, ksize, dilation)
         hit = self._kmaps.get(key)
         if hit is not None:
