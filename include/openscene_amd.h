@@ -1469,6 +1469,41 @@ int osn_broadcast_fwd(const float* x, const float* g, const int32_t* rank, int64
 int osn_broadcast_bwd_pooled(const float* gy, const float* x, int64_t n, int c, const int32_t* order, const int64_t* offsets,
                              int64_t n_batches, float* gg, void* ws, size_t ws_bytes, osn_stream_t stream);
 
+/* ---- points in and out of the voxel grid (csrc/field.hip) ------------------------------------------------ *
+ * [ME] TensorField / .sparse(), SparseTensor.slice(), SparseTensor.interpolate(), MinkowskiInterpolation and
+ * features_at_coordinates, where run/evaluate.py:283-292 hands a point the row of its voxel (predictions[inds_reverse]).
+ * Semantics recalled from ME v0.5.4.  Features are float32 [rows, c], any c >= 1: 16-byte accesses when
+ * c % 4 == 0 and the matrices are 16-byte aligned, one element per thread otherwise.  Every float32 operation rounds on its own
+ * (no FMA contraction) and there are no floating-point atomics: every result is a pure function of the arguments, bit for bit
+ * repeatable.  Every refused argument -- a null pointer, c < 1, a stride below 1, a negative size, 8 m past the int32 pair index --
+ * returns OSN_E_ARG before anything is launched, the entry's name first in the text.  Zero rows launch nothing (osn_interp_bwd
+ * and osn_segment_reduce still write their whole output).
+ *
+ * osn_field_map: coords4f float32 [m, 4] rows (batch, x, y, z) in lattice units, any positions; the table is the stride's
+ * (osn_coords_unique).  Per axis q = p / float(stride), f = floorf(q), base = int(f) * stride, t = q - f, a[0] = 1 - t,
+ * a[1] = t.  Corner k = dx + 2 dy + 4 dz (the offset order of osn_kmap_build for ksize 2, x fastest) sits at
+ * base + stride * (dx, dy, dz) in the row's batch: nbr[k, i] = its row in the table or -1, w[k, i] = (ax[dx] * ay[dy]) * az[dz],
+ * both k-major [8, m].  A row with a non-finite coordinate, a batch outside [0, 65535) or a base with base or base + stride
+ * outside (-32767, 32767) is invalid: eight -1, eight +0, and `bad` (int32, device, zeroed by the caller) is incremented with
+ * an integer atomic.  The range test comes before the key is packed, so an invalid row never aliases a packed key.
+ * osn_interp_fwd: y[i] = sum over the present k (nbr[k, i] in [0, n_in)), ascending, from +0, of w[k, i] * x[nbr[k, i]]; no
+ * renormalisation over absent corners, a present corner of weight 0 is still multiplied (0 * inf = NaN stays).
+ * osn_interp_bwd: `pair` int32 [n_pair] holds the indices e = k * m + i of the present corners sorted by (nbr[e], e), `offsets`
+ * int64 [n_in + 1] the range of every voxel row in it:  gx[v] = sum over the row's pairs, in list order, from +0, of
+ * w[e] * gy[e % m].  Every element of gx is written; an entry outside [0, 8 m) is skipped.
+ * osn_segment_reduce: y[u] = the rows order[offsets[u] .. offsets[u + 1]) of x (order int32 [n], offsets int64 [n_seg + 1]) added
+ * one by one in list order from +0; OSN_SEGMENT_AVG divides the sum once by float(length) (IEEE; an empty segment gives 0).  One
+ * thread per segment and column group walks the list: a segment of hundreds of rows is correct and slow.                      */
+#define OSN_SEGMENT_SUM 0
+#define OSN_SEGMENT_AVG 1
+int osn_field_map(const uint64_t* table_keys, const int32_t* table_vals, int64_t cap, const float* coords4f, int64_t m, int stride,
+                  int32_t* nbr, float* w, int32_t* bad, osn_stream_t stream);
+int osn_interp_fwd(const float* x, int64_t n_in, const int32_t* nbr, const float* w, int64_t m, int c, float* y, osn_stream_t stream);
+int osn_interp_bwd(const float* gy, int64_t m, int c, const int32_t* pair, int64_t n_pair, const int64_t* offsets, const float* w,
+                   int64_t n_in, float* gx, osn_stream_t stream);
+int osn_segment_reduce(const float* x, int64_t n, int c, const int32_t* order, const int64_t* offsets, int64_t n_seg, int mode, float* y,
+                       osn_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -5,6 +5,8 @@ query, as hand-written HIP kernels behind a C ABI (include/openscene_amd.h).
 
 Python surface (mirrors the reference's own, file:line in each module):
     openscene_amd.minkowski        the MinkowskiEngine symbols the reference imports
+    openscene_amd.field            points in and out: TensorField, .sparse(), SparseTensor.slice / .interpolate (also exported here:
+                                   TensorField, SparseTensorQuantizationMode, InterpolationMap, MinkowskiInterpolation)
     openscene_amd.mink_unet        models/mink_unet.py  (MinkUNet14A..34C, `mink_unet` factory)
     openscene_amd.disnet           models/disnet.py     (DisNet)
     openscene_amd.voxelizer        dataset/voxelizer.py (Voxelizer)
@@ -121,6 +123,18 @@ def merge_regions(bank, grid, regions, similarity=0.8, min_contact=1, max_rounds
     return f(bank, grid, regions, similarity=similarity, min_contact=min_contact, max_rounds=max_rounds)
 
 
+_FIELD_NAMES = {"TensorField": "field", "SparseTensorQuantizationMode": "field", "InterpolationMap": "field",
+                "MinkowskiInterpolation": "minkowski"}
+
+
+def __getattr__(name):
+    """The field names, resolved on first use (importing the package stays light: torch is not imported for them)."""
+    if name in _FIELD_NAMES:
+        import importlib
+        return getattr(importlib.import_module("." + _FIELD_NAMES[name], __name__), name)
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))
+
+
 def install_minkowski_alias(force=False, accelerate=True):
     """Register ``MinkowskiEngine`` (+ ``.modules.resnet_block``, ``.utils``) in
     ``sys.modules`` so the reference's imports (models/mink_unet.py:25-26,
@@ -146,7 +160,8 @@ def install_minkowski_alias(force=False, accelerate=True):
     for name in ("SparseTensor", "CoordinateManager", "cat", "MinkowskiConvolution", "MinkowskiConvolutionTranspose",
                  "MinkowskiBatchNorm", "MinkowskiReLU", "MinkowskiSumPooling", "MinkowskiAvgPooling", "MinkowskiMaxPooling",
                  "MinkowskiGlobalSumPooling", "MinkowskiGlobalAvgPooling", "MinkowskiGlobalMaxPooling",
-                 "MinkowskiBroadcastAddition", "MinkowskiBroadcastMultiplication", "MinkowskiLinear"):
+                 "MinkowskiBroadcastAddition", "MinkowskiBroadcastMultiplication", "MinkowskiLinear", "MinkowskiInterpolation",
+                 "TensorField", "SparseTensorQuantizationMode"):
         setattr(me, name, getattr(mk, name))
     modules = types.ModuleType("MinkowskiEngine.modules")
     resnet_block = types.ModuleType("MinkowskiEngine.modules.resnet_block")
@@ -155,6 +170,8 @@ def install_minkowski_alias(force=False, accelerate=True):
     modules.resnet_block = resnet_block
     utils = types.ModuleType("MinkowskiEngine.utils")
     utils.kaiming_normal_ = mk.kaiming_normal_
+    utils.batched_coordinates = mk.batched_coordinates
+    utils.sparse_collate = mk.sparse_collate
     me.modules = modules
     me.utils = utils
     sys.modules["MinkowskiEngine"] = me

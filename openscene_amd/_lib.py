@@ -197,6 +197,10 @@ PROTOTYPES = {
     "osn_gpool_bwd": (_i32, [_vp, _vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "osn_broadcast_fwd": (_i32, [_vp, _vp, _vp, _i64, _i64, _i32, _i32, _vp, _vp]),
     "osn_broadcast_bwd_pooled": (_i32, [_vp, _vp, _i64, _i32, _vp, _vp, _i64, _vp, _vp, _sz, _vp]),
+    "osn_field_map": (_i32, [_vp, _vp, _i64, _vp, _i64, _i32, _vp, _vp, _vp, _vp]),
+    "osn_interp_fwd": (_i32, [_vp, _i64, _vp, _vp, _i64, _i32, _vp, _vp]),
+    "osn_interp_bwd": (_i32, [_vp, _i64, _i32, _vp, _i64, _vp, _vp, _i64, _vp, _vp]),
+    "osn_segment_reduce": (_i32, [_vp, _i64, _i32, _vp, _vp, _i64, _i32, _vp, _vp]),
 }
 
 _lock = threading.Lock()

@@ -376,6 +376,84 @@ def broadcast(x, pooled, index, op):
     return BroadcastFunction.apply(x, pooled, index, op)
 
 
+# ---- points in and out of the grid (field.py; DESIGN.md section 4).  `index` is a field.FieldIndex: rank int32 [N] the voxel row
+# of every point, order / offsets the points of every voxel in ascending point index (CSR), first int64 [U] each voxel's first point
+class QuantizeFunction(Function):
+    """[ME] TensorField.sparse(), SparseTensor(quantization_mode=): the sum or the average of the points of every voxel in ascending
+    point index; the backward pass is the gather osn_gpool_bwd performs, with a voxel in the place of a batch."""
+
+    @staticmethod
+    def forward(ctx, x, index, mode):
+        ctx.cfg = (index, mode)
+        return ops.segment_reduce(x, index.order, index.offsets, mode)
+
+    @staticmethod
+    def backward(ctx, gy):
+        index, mode = ctx.cfg
+        return ops.segment_expand(gy, index.rank, index.offsets, mode), None, None
+
+
+class SubsampleFunction(Function):
+    """RANDOM_SUBSAMPLE: the first point's row of every voxel (row indexing, what SparseTensor always did); the gradient goes to
+    that point, +0 to the others."""
+
+    @staticmethod
+    def forward(ctx, x, first):
+        ctx.cfg = (first, x.shape[0])
+        return x[first]
+
+    @staticmethod
+    def backward(ctx, gy):
+        first, n = ctx.cfg
+        return gy.new_zeros((n,) + tuple(gy.shape[1:])).index_copy_(0, first, gy), None
+
+
+class SliceFunction(Function):
+    """[ME] SparseTensor.slice: F[i] = x[rank[i]]; the backward pass is the quantisation's ordered sum."""
+
+    @staticmethod
+    def forward(ctx, x, index):
+        ctx.index = index
+        return ops.segment_expand(x, index.rank)
+
+    @staticmethod
+    def backward(ctx, gy):
+        index = ctx.index
+        return ops.segment_reduce(gy, index.order, index.offsets, "sum"), None
+
+
+class InterpolateFunction(Function):
+    """[ME] MinkowskiInterpolation: trilinear interpolation over a field.InterpolationMap; the backward pass walks the map's plan
+    (built on the first backward pass, kept on the map).  No gradient with respect to the positions."""
+
+    @staticmethod
+    def forward(ctx, x, imap):
+        ctx.imap = imap
+        return ops.interp_fwd(x, imap.nbr, imap.w)
+
+    @staticmethod
+    def backward(ctx, gy):
+        imap = ctx.imap
+        return ops.interp_bwd(gy, imap.plan(), imap.w, imap.n_in), None
+
+
+def quantize(x, index, mode):
+    """mode "sum" / "avg" / "first" over a field.FieldIndex."""
+    if mode == "first":
+        return SubsampleFunction.apply(x, index.first)
+    return QuantizeFunction.apply(x, index, mode)
+
+
+def slice_rows(x, index):
+    return SliceFunction.apply(x, index)
+
+
+def interpolate(x, imap):
+    if x.dim() != 2 or x.shape[0] != imap.n_in:
+        raise ValueError("interpolate: features %s against a map over %d voxel rows" % (tuple(x.shape), imap.n_in))
+    return InterpolateFunction.apply(x, imap)
+
+
 def _hip_eligible(*ts):
     """The elementwise HIP kernels take contiguous float32 device matrices on 16-byte boundaries.  Anything else ON A DEVICE
     (another dtype, a strided view, an odd storage offset) goes to the torch operator of the same name -- MinkowskiEngine

@@ -18,6 +18,7 @@ import torch
 import torch.nn as nn
 
 from . import functional as F_
+from .field import InterpolationMap, SparseTensorQuantizationMode, TensorField  # noqa: F401  (re-exported ME names)
 from .sparse import ORIGIN_STRIDE, CoordinateManager, SparseTensor, cat  # noqa: F401  (re-exported ME names)
 
 __version__ = "0.5.4+openscene_amd"
@@ -244,6 +245,24 @@ class MinkowskiLinear(nn.Module):
         return x._like(out)
 
 
+class MinkowskiInterpolation(nn.Module):
+    """forward(input, positions): the features of `input` interpolated trilinearly at `positions` float [M, 4] (batch, x, y, z)
+    in lattice units, a plain float32 [M, C] tensor -- SparseTensor.features_at_coordinates as a layer.  return_kernel_map /
+    return_weights append this engine's own tables to the result: nbr int32 [8, M] (-1: absent) and w float32 [8, M], corner
+    k = dx + 2 dy + 4 dz (ME returns its in / out map pair instead)."""
+
+    def __init__(self, return_kernel_map=False, return_weights=False):
+        super().__init__()
+        self.return_kernel_map, self.return_weights = bool(return_kernel_map), bool(return_weights)
+
+    def forward(self, input, positions):
+        imap = InterpolationMap(input.coordinate_manager, input.tensor_stride, positions)
+        out = F_.interpolate(input.F, imap)
+        if not (self.return_kernel_map or self.return_weights):
+            return out
+        return (out,) + ((imap.nbr,) if self.return_kernel_map else ()) + ((imap.w,) if self.return_weights else ())
+
+
 # ---- ME.modules.resnet_block ------------------------------------------------
 class BasicBlock(nn.Module):
     """conv3-bn-relu-conv3-bn-(+residual)-relu, expansion 1 ([ME] modules/resnet_block.py;
@@ -319,3 +338,28 @@ def kaiming_normal_(tensor, a=0, mode="fan_in", nonlinearity="leaky_relu"):
     std = gain / math.sqrt(fan)
     with torch.no_grad():
         return tensor.normal_(0, std)
+
+
+def batched_coordinates(coords, dtype=torch.int32, device=None):
+    """ME.utils.batched_coordinates: a list of [N_i, 3] coordinate arrays or tensors -> [sum N_i, 4] rows (batch, x, y, z), the
+    batch index = the position in the list.  dtype torch.int32 (voxels) or a floating dtype (a TensorField's positions)."""
+    rows = []
+    for b, c in enumerate(coords):
+        c = torch.as_tensor(c)
+        if c.dim() != 2 or c.shape[1] != 3:
+            raise ValueError("batched_coordinates: entry %d has shape %s, expected [N, 3]" % (b, tuple(c.shape)))
+        c = (torch.floor(c) if c.dtype.is_floating_point and not dtype.is_floating_point else c).to(dtype)
+        rows.append(torch.cat([torch.full((c.shape[0], 1), b, dtype=dtype, device=c.device), c], 1))
+    out = torch.cat(rows, 0) if rows else torch.zeros((0, 4), dtype=dtype)
+    return out if device is None else out.to(device)
+
+
+def sparse_collate(coords, feats, dtype=torch.int32, device=None):
+    """ME.utils.sparse_collate without labels: (batched_coordinates(coords), the feature matrices stacked in the same order)."""
+    if len(coords) != len(feats):
+        raise ValueError("sparse_collate: %d coordinate lists vs %d feature matrices" % (len(coords), len(feats)))
+    for b, (c, f) in enumerate(zip(coords, feats)):
+        if len(c) != len(f):
+            raise ValueError("sparse_collate: entry %d has %d coordinates and %d feature rows" % (b, len(c), len(f)))
+    f = torch.cat([torch.as_tensor(v) for v in feats], 0) if len(feats) else torch.zeros((0, 0))
+    return batched_coordinates(coords, dtype=dtype, device=device), (f if device is None else f.to(device))

@@ -1,6 +1,7 @@
 """Tensor-level wrappers over the C ABI: allocate outputs / scratch with torch,
 pass raw device pointers and the current HIP stream.  No autograd here (see
 functional.py) and no CPU fallback."""
+import collections
 import ctypes
 import os
 import threading
@@ -3217,3 +3218,142 @@ def broadcast_bwd_pooled(gy, x, order, offsets):
         if x.shape != gy.shape:
             raise ValueError("broadcast_bwd_pooled: shapes %s and %s differ" % (tuple(gy.shape), tuple(x.shape)))
     return _gpool_reduce("osn_broadcast_bwd_pooled", gy, x, order, offsets, 0, False)[0]
+
+
+# ------------------------------------------------------------ points in and out of the grid (csrc/field.hip)
+SEGMENT_MODES = ("sum", "avg")              # the `mode` word of osn_segment_reduce: the position in this tuple
+FIELD_MAX_POINTS = ((1 << 31) - 1) // 8     # 8 m is an int32 pair index
+
+InterpPlan = collections.namedtuple("InterpPlan", "pair offsets")
+
+
+def _segment_mode(mode):
+    if mode not in SEGMENT_MODES:
+        raise ValueError("segment mode %r (one of %s)" % (mode, ", ".join(SEGMENT_MODES)))
+    return SEGMENT_MODES.index(mode)
+
+
+def _csr_offsets(offsets, dev):
+    if offsets.dtype != torch.int64 or offsets.dim() != 1 or offsets.shape[0] < 1 or offsets.device != dev:
+        raise TypeError("offsets must be int64 [segments + 1] on %s" % (dev,))
+    return offsets.contiguous()
+
+
+def _positions(positions):
+    if positions.dim() != 2 or positions.shape[1] != 4 or not positions.dtype.is_floating_point:
+        raise TypeError("positions must be floating-point [M, 4] rows (batch, x, y, z) in lattice units")
+    return _f32c(positions.float(), "positions")
+
+
+def field_map(table, positions, stride):
+    """The eight corners of every position's cell in the stride's coordinate table and their trilinear weights ->
+    (nbr int32 [8, M], w float32 [8, M], bad int32 [1]: the invalid rows, counted on the device; reading it synchronises)."""
+    positions = _positions(positions)
+    dev = positions.device
+    lib = _prep(dev)
+    m = positions.shape[0]
+    nbr = torch.empty((8, m), dtype=torch.int32, device=dev)
+    w = torch.empty((8, m), dtype=torch.float32, device=dev)
+    bad = torch.zeros(1, dtype=torch.int32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_field_map(_p(table.keys), _p(table.vals), table.cap, _p(positions), m, int(stride), _p(nbr), _p(w), _p(bad),
+                                _stream(dev)), "osn_field_map")
+    return nbr, w, bad
+
+
+def _interp_tables(nbr, w, dev):
+    if nbr.dtype != torch.int32 or nbr.dim() != 2 or nbr.shape[0] != 8 or nbr.device != dev:
+        raise TypeError("nbr must be the int32 [8, M] corner table of field_map on %s" % (dev,))
+    if w.dtype != torch.float32 or w.shape != nbr.shape or w.device != dev:
+        raise TypeError("w must be the float32 %s weight table of field_map on %s" % (tuple(nbr.shape), dev))
+    return nbr.contiguous(), w.contiguous()
+
+
+def interp_fwd(x, nbr, w):
+    """y [M, c] = the trilinear interpolation of x [n_in, c] over field_map's tables."""
+    dev = x.device
+    lib = _prep(dev)
+    x = _pool_feats(x, "x")
+    nbr, w = _interp_tables(nbr, w, dev)
+    (n_in, c), m = x.shape, nbr.shape[1]
+    y = torch.empty((m, c), dtype=torch.float32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_interp_fwd(_p(x), n_in, _p(nbr), _p(w), m, c, _p(y), _stream(dev)), "osn_interp_fwd")
+    return y
+
+
+def interp_plan(nbr, n_in):
+    """The backward plan of an interpolation: the flat indices e = k M + m of the present corners sorted by (voxel row, e)
+    (a stable torch sort of the flattened table) and every voxel row's range in that list.  Built once per map."""
+    m = nbr.shape[1]
+    if m > FIELD_MAX_POINTS:
+        raise ValueError("interp_plan: %d positions (8 M must stay below 2^31)" % m)
+    flat = nbr.reshape(-1).long()
+    e = torch.nonzero((flat >= 0) & (flat < int(n_in))).reshape(-1)
+    rows = flat[e]
+    perm = torch.sort(rows, stable=True)[1]
+    counts = torch.bincount(rows, minlength=int(n_in))
+    offsets = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).long()
+    return InterpPlan(e[perm].int(), offsets)
+
+
+def interp_bwd(gy, plan, w, n_in, out=None):
+    """gx [n_in, c] of interp_fwd from gy [M, c] through interp_plan's lists; every element is written (out: the caller's own
+    contiguous float32 [n_in, c] destination)."""
+    dev = gy.device
+    lib = _prep(dev)
+    gy = _pool_feats(gy, "grad_output")
+    m, c = gy.shape
+    if w.dtype != torch.float32 or w.shape != (8, m) or w.device != dev:
+        raise TypeError("w must be the float32 [8, %d] weight table of field_map on %s" % (m, dev))
+    pair = plan.pair
+    if pair.dtype != torch.int32 or pair.dim() != 1 or pair.device != dev:
+        raise TypeError("plan.pair must be int32 [pairs] on %s" % (dev,))
+    offsets = _csr_offsets(plan.offsets, dev)
+    if offsets.shape[0] != int(n_in) + 1:
+        raise TypeError("plan.offsets must be int64 [%d]" % (int(n_in) + 1))
+    if out is not None and (out.dtype != torch.float32 or out.shape != (int(n_in), c) or out.device != dev or not out.is_contiguous()):
+        raise TypeError("out must be a contiguous float32 [%d, %d] matrix on %s" % (int(n_in), c, dev))
+    gx = torch.empty((int(n_in), c), dtype=torch.float32, device=dev) if out is None else out
+    with _Dev(dev):
+        check(lib.osn_interp_bwd(_p(gy), m, c, _p(pair.contiguous()), pair.shape[0], _p(offsets), _p(w.contiguous()), int(n_in), _p(gx),
+                                 _stream(dev)), "osn_interp_bwd")
+    return gx
+
+
+def segment_reduce(x, order, offsets, mode):
+    """y [segments, c]: the rows order[offsets[u] .. offsets[u + 1]) of x [n, c] added in list order ("avg": divided once by the
+    length).  order int32 [n], offsets int64 [segments + 1]."""
+    md = _segment_mode(mode)
+    dev = x.device
+    lib = _prep(dev)
+    x = _pool_feats(x, "x")
+    n, c = x.shape
+    order = _pool_vec(order, "order", torch.int32, n, dev)
+    offsets = _csr_offsets(offsets, dev)
+    n_seg = offsets.shape[0] - 1
+    y = torch.empty((n_seg, c), dtype=torch.float32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_segment_reduce(_p(x), n, c, _p(order), _p(offsets), n_seg, md, _p(y), _stream(dev)), "osn_segment_reduce")
+    return y
+
+
+def segment_expand(g, rank, offsets=None, mode="sum"):
+    """y [n, c] = g[rank[i]] ("avg": divided by the length of segment rank[i], from offsets): the gather osn_gpool_bwd performs,
+    with a segment in the place of a batch.  rank int32 [n]."""
+    md = _segment_mode(mode)
+    dev = g.device
+    lib = _prep(dev)
+    g = _pool_feats(g, "g")
+    n_seg, c = g.shape
+    n = rank.shape[0]
+    rank = _pool_vec(rank, "rank", torch.int32, n, dev)
+    if mode == "avg":
+        offsets = _csr_offsets(offsets, dev)
+        if offsets.shape[0] != n_seg + 1:
+            raise TypeError("offsets must be int64 [%d]" % (n_seg + 1))
+    y = torch.empty((n, c), dtype=torch.float32, device=dev)
+    with _Dev(dev):
+        check(lib.osn_gpool_bwd(_p(g), _p(rank), _p(offsets) if mode == "avg" else None, None, n, n_seg, c, md, _p(y), _stream(dev)),
+              "osn_gpool_bwd")
+    return y

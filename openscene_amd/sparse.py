@@ -31,6 +31,11 @@ ORIGIN_STRIDE = 0
 # batch in ids; order int32 [N] / offsets int64 [B + 1] the rows of every batch in ascending row index (CSR)
 BatchIndex = collections.namedtuple("BatchIndex", "ids rank order offsets")
 
+# CoordinateManager.point_index: the caller's input rows (a field's points) over the rows of one stride.  rank int32 [N] the row of
+# the voxel holding every point; order int32 [N] / offsets int64 [U + 1] the points of every voxel in ascending point index (CSR);
+# cnt int32 [U] their number; first int64 [U] every voxel's first point (stride 1 only, else None)
+PointIndex = collections.namedtuple("PointIndex", "rank order offsets cnt first")
+
 
 class CoordinateManager:
     """Caches, per tensor stride, the coordinate rows + hash table, and per
@@ -108,6 +113,31 @@ class CoordinateManager:
             order = torch.argsort(rank, stable=True).int()          # per batch: ascending row index
             offsets = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).long()
             res = BatchIndex(ids.int(), rank.int(), order, offsets)
+        self._kmaps[key] = res
+        return res
+
+    # -- the input rows over the voxels ------------------------------------------
+    def point_index(self, stride=1):
+        """PointIndex of the rows this manager was built from over the rows of `stride` (cached): what the sum / average
+        quantisation reduces over and a slice expands over.  Torch operators on the inverse map composed with the parent maps
+        (a stable sort, a bincount, a cumsum); no host read beyond the maps' own."""
+        key = ("points", stride)
+        hit = self._kmaps.get(key)
+        if hit is not None:
+            return hit
+        if stride == 1:
+            if self.inverse_mapping is not None:
+                rank, first = self.inverse_mapping.int(), self.unique_index
+            else:
+                rank = torch.arange(self.n_input, dtype=torch.int32, device=self.device)
+                first = rank.long()
+        else:
+            if stride == ORIGIN_STRIDE or not self.has(stride):
+                raise ValueError("tensor stride %r was never created on this manager" % (stride,))
+            rank, first = self.parent(stride)[self.point_index(stride // 2).rank.long()], None
+        counts = torch.bincount(rank.long(), minlength=self.size(stride))
+        offsets = torch.cat([counts.new_zeros(1), torch.cumsum(counts, 0)]).long()
+        res = PointIndex(rank, torch.argsort(rank, stable=True).int(), offsets, counts.int(), first)
         self._kmaps[key] = res
         return res
 
@@ -449,7 +479,13 @@ class MapPrefetcher:
 class SparseTensor:
     """features float32 [N, C] + int32 coordinates [N, 4] (batch, x, y, z) on one device."""
 
-    def __init__(self, features, coordinates=None, tensor_stride=1, coordinate_manager=None, **unused):
+    def __init__(self, features, coordinates=None, tensor_stride=1, coordinate_manager=None, quantization_mode=None, **unused):
+        """quantization_mode (a field.SparseTensorQuantizationMode; default RANDOM_SUBSAMPLE): the row of a coordinate that
+        several rows share -- the first of them, their ordered fp32 sum, or that sum divided by their number."""
+        word = "first"
+        if quantization_mode is not None:
+            from . import field                   # late: field imports this module
+            word = field.mode_word(quantization_mode, None)
         if coordinate_manager is None:
             if coordinates is None:
                 raise ValueError("SparseTensor needs coordinates or a coordinate_manager")
@@ -461,14 +497,20 @@ class SparseTensor:
                 raise ValueError("%d feature rows vs %d coordinate rows" % (features.shape[0], coordinates.shape[0]))
             coordinate_manager = CoordinateManager(coordinates)
             if coordinate_manager.unique_index is not None:
-                features = features[coordinate_manager.unique_index]
+                features = self._merge_rows(features, coordinate_manager, word)
         elif (tensor_stride == 1 and coordinate_manager.unique_index is not None
               and features.shape[0] == coordinate_manager.n_input):
             # a prefetched manager built from the raw (duplicated) coordinates of these feature rows
-            features = features[coordinate_manager.unique_index]
+            features = self._merge_rows(features, coordinate_manager, word)
         self._F = features
         self.tensor_stride = tensor_stride
         self.coordinate_manager = coordinate_manager
+
+    @staticmethod
+    def _merge_rows(features, manager, word):
+        if word == "first":
+            return features[manager.unique_index]
+        return _F_mod().quantize(features, manager.point_index(1), word)
 
     # ME names
     @property
@@ -522,6 +564,26 @@ class SparseTensor:
         else:
             self._F = self._F + other
         return self
+
+    # -- back to the points (field.py; DESIGN.md section 4) ---------------------------------------------------
+    def slice(self, field):
+        """[ME] A TensorField on `field`'s points with F[i] = the row of the voxel of this tensor that holds point i: works for
+        every stride of the manager `field.sparse()` created, and for no other manager (ValueError)."""
+        return field._like(_F_mod().slice_rows(self._F, field.point_index(self)))
+
+    def cat_slice(self, field):
+        """[ME] slice(field) with the field's own features to its right: columns [slice, field.F]."""
+        return field._like(_F_mod().cat([self.slice(field).F, field.F]))
+
+    def interpolate(self, field):
+        """[ME] A TensorField on `field`'s points with the trilinear interpolation of this tensor's rows at every point."""
+        return field._like(_F_mod().interpolate(self._F, field.interpolation_map(self)))
+
+    def features_at_coordinates(self, positions):
+        """[ME] float32 [M, C]: this tensor interpolated at `positions` float [M, 4] (batch, x, y, z) in lattice units -- any
+        positions.  A voxel's feature sits AT its integer coordinate; absent corners are not renormalised away."""
+        from . import field
+        return _F_mod().interpolate(self._F, field.InterpolationMap(self.coordinate_manager, self.tensor_stride, positions))
 
     def __repr__(self):
         return "SparseTensor(N=%d, C=%d, tensor_stride=%d, device=%s)" % (
